@@ -10,7 +10,13 @@ Workload (BASELINE.json configs[1], "C2" in SURVEY.md §8(d)):
 One step = one round: GP fit + propose + hash + dedup + encode + GP score +
 top-k (+ all-gather merge of the local top-k over RCCL when N > 1).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K rounds, writes the last timed
+round's outputs (--dump-outputs) and prints the result line.  Everything else
+this file measures or checks -- the secondary ell = 2 line, the oracle parity
+checker, the CPU baselines -- runs only under --full (and there
+--no-secondary / --no-parity / --no-cpu-baseline drop one leg each).
 
 N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set)
 each process is one rank; run directly with --gpus N, the script starts the N
@@ -35,8 +41,14 @@ f16x3 dense lines), K* where it carries more work (C4), and in a pruned line
 contraction only (in categorical mode the one-hot blocks' int8 code product
 beside it is not counted), timed without the wait for the fit (`fit_wait`).
 
-After the timed rounds (outside the timed region) rank 0 checks the last
-round's selections against the oracle (`parity`: DE trials, hash_config
+--dump-outputs DIR: after the timed rounds rank 0 writes what the last timed
+round returned to its caller -- the merged top-k -- as DIR/indices.npy [k],
+DIR/scores.npy [k] and DIR/digests.npy [k][8] (the 32-bit digest words), all
+float64 (exact for the indices and the digest words).  The inputs are seeded,
+so two runs with the same arguments are comparable output for output.
+
+Under --full, after the timed rounds (outside the timed region) rank 0 checks
+the last round's selections against the oracle (`parity`: DE trials, hash_config
 digests, EI) and runs one extra round at a lengthscale whose EI top-k is
 score-determined, checking it against the oracle EI of a random sample of the
 other candidates.  Prints ONE JSON line on rank 0.
@@ -80,6 +92,17 @@ def selection_sha(idx, dig):
     import hashlib
     return hashlib.sha256(idx.detach().cpu().numpy().astype("<i8").tobytes() +
                           dig.detach().cpu().numpy().view(np.uint32).astype(">u4").tobytes()).hexdigest()
+
+
+def dump_outputs(path, idx, top, dig):
+    """--dump-outputs: what the last timed round returned to its caller, the
+    merged top-k (global indices [k], scores [k], digests [k][8] as 32-bit
+    words), one float64 .npy each (indices < 2^53 and 32-bit words are exact)"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "indices.npy"), idx.detach().cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), top.detach().cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "digests.npy"),
+            np.ascontiguousarray(dig.detach().cpu().numpy()).view(np.uint32).astype(np.float64))
 
 
 def host_info():
@@ -422,7 +445,19 @@ def main():
     ap.add_argument("--prune-pass", type=int, default=32, choices=(32, 64),
                     help="--prune's bound pass over every candidate: 32 = K* past the bound rows on the f32 MFMA "
                          "with v_exp_f32, every rounding bounded (ut_gp_set_prune_pass; the default), 64 = fp64")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed round's outputs (the merged top-k: indices, scores, digests) as "
+                         "DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the secondary ell = 2 line, the oracle "
+                         "parity checker and the CPU baselines (each still dropped by its --no-... option)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.secondary = False
+        args.no_parity = True
+        args.no_cpu_baseline = True
     if args.precision is None:
         args.precision = 64 if args.prune else 8
     if args.prune and args.precision != 64:
@@ -613,6 +648,8 @@ def main():
         step(w)
     torch.cuda.synchronize()
     elapsed, stages, i8_timed, (idx, top, sdig) = timed_rounds(args.warmup, args.steps, ell)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx, top, sdig)
 
     # the secondary C2 line: the same round timed at ell = 2,
     # where k* spans (1e-3, 1), every K* digit plane carries data, EI values

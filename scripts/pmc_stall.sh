@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=${PROF_OUT:-gpurun_out/stall}
 mkdir -p $OUT
-ARGS=${BENCH_ARGS:---steps 3 --warmup 1 --no-cpu-baseline --no-parity}
+ARGS=${BENCH_ARGS:---full --steps 3 --warmup 1 --no-cpu-baseline --no-parity}
 timeout -k 10 -s KILL 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
   SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES -d $OUT -o run --output-format csv -- \
   python3 bench.py $ARGS > $OUT/log 2>&1 || { echo "pmc rc=$?"; tail -5 $OUT/log; exit 1; }

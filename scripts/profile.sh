@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=${PROF_OUT:-gpurun_out/prof}
 mkdir -p $OUT
-ARGS=${BENCH_ARGS:---steps 3 --warmup 1 --no-cpu-baseline}
+ARGS=${BENCH_ARGS:---full --steps 3 --warmup 1 --no-cpu-baseline}
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
   python3 bench.py $ARGS > $OUT/trace.log 2>&1 || { echo "trace rc=$?"; exit 1; }
 echo trace ok

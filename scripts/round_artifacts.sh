@@ -13,10 +13,10 @@ bash scripts/profile.sh > $O/profile.log 2>&1 || { echo "profile failed"; tail -
 echo profile ok
 bash scripts/pmc_clock.sh > $O/clock.log 2>&1 || { echo "clock failed"; tail -5 $O/clock.log; exit 1; }
 echo clock ok
-run 400 bench_c2_f64 python bench.py --steps 10 --warmup 3
-run 300 bench_c2_f32 python bench.py --steps 10 --warmup 3 --precision 32 --no-cpu-baseline
-run 400 bench_c3_f64 python bench.py --config c3 --steps 3 --warmup 1 --no-cpu-baseline
-run 400 bench_c3_f32 python bench.py --config c3 --steps 3 --warmup 1 --precision 32 --no-cpu-baseline
-run 400 bench_c4_f64 python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline
+run 400 bench_c2_f64 python bench.py --full --steps 10 --warmup 3
+run 300 bench_c2_f32 python bench.py --full --steps 10 --warmup 3 --precision 32 --no-cpu-baseline
+run 400 bench_c3_f64 python bench.py --full --config c3 --steps 3 --warmup 1 --no-cpu-baseline
+run 400 bench_c3_f32 python bench.py --full --config c3 --steps 3 --warmup 1 --precision 32 --no-cpu-baseline
+run 400 bench_c4_f64 python bench.py --full --config c4 --steps 3 --warmup 1 --no-cpu-baseline
 run 300 c5_bandit python scripts/c5_bandit.py --generations 100
 run 300 microbench python scripts/microbench.py all

@@ -2,18 +2,17 @@
 the C-ABI header and the integration notes points inside the cited file
 (citations past the end of pso.py / globalGA.py).
 
-The reference tree is read as text (line counts only); the test is skipped
-where it is absent (the GPU box).  A citation resolves to the reference files
-of that basename, narrowed by its path when it has one (`OT/` =
-python/uptune/opentuner/, `PY/` = python/uptune/); names no reference file
+The reference's line counts are the fixture
+tests/golden/reference_line_counts.json (relative path -> lines, written by
+tests/golden/make_golden.py), so the test needs nothing outside the
+repository.  A citation resolves to the reference files of that basename,
+narrowed by its path when it has one (`OT/` = python/uptune/opentuner/, `PY/` = python/uptune/); names no reference file
 carries (this repository's own files, CPython's stdlib) are not checked.
 """
+import json
 import os
 import re
 
-import pytest
-
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CITE = re.compile(r"((?:[\w.]+/)*\w+\.py):(\d+)(?:-(\d+))?")
 SCOPE = ("oracle", "include", "uptune_amd")
@@ -21,15 +20,11 @@ DOCS = ("INTEGRATION.md", "DESIGN.md")
 
 
 def _ref_files():
+    with open(os.path.join(ROOT, "tests", "golden", "reference_line_counts.json")) as fh:
+        lines = json.load(fh)["lines"]
     out = {}
-    for dp, dn, fn in os.walk(REF):
-        dn[:] = [d for d in dn if d != ".git"]
-        for f in fn:
-            if f.endswith(".py"):
-                p = os.path.join(dp, f)
-                with open(p, errors="replace") as fh:
-                    n = sum(1 for _ in fh)
-                out.setdefault(f, []).append((os.path.relpath(p, REF), n))
+    for rel, n in lines.items():
+        out.setdefault(os.path.basename(rel), []).append((rel, n))
     return out
 
 
@@ -44,7 +39,6 @@ def _sources():
         yield os.path.join(ROOT, f)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not present here")
 def test_reference_citations_in_range():
     ref = _ref_files()
     checked, bad = 0, []

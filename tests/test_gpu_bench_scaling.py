@@ -30,13 +30,46 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(*args, timeout=420):
     env = dict(os.environ, UT_DIST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--parity-sample", "2048", *args]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--parity-sample", "2048", *args]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (cmd, r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def test_plain_run_times_only_and_dumps_the_last_round(tmp_path):
+    """without --full: no secondary line, parity block or CPU baseline; --steps
+    is the number of timed rounds; --dump-outputs writes the last timed
+    round's merged top-k as float64 arrays, equal to the --full run's"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    M, k = 1 << 15, 256
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+            "--m", str(M)]
+    r = subprocess.run(base + ["--dump-outputs", str(tmp_path / "plain")], cwd=ROOT, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(M / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["parity"] is None and line["cpu_baseline"] is None and "secondary_ell2" not in line
+    assert "cpu_baseline_1thread" not in line and "host" not in line
+    got = {n: np.load(tmp_path / "plain" / (n + ".npy")) for n in ("indices", "scores", "digests")}
+    assert sorted(os.listdir(tmp_path / "plain")) == ["digests.npy", "indices.npy", "scores.npy"]
+    assert got["indices"].shape == (k,) and got["scores"].shape == (k,) and got["digests"].shape == (k, 8)
+    assert all(a.dtype == np.float64 for a in got.values())
+    sel = got["indices"][got["indices"] >= 0]
+    assert len(sel) > 0 and np.all(sel < M) and len(np.unique(sel)) == len(sel)
+    full = _bench("--gpus", "1", "--m", str(M), "--steps", "3", "--dump-outputs", str(tmp_path / "full"))
+    assert full["parity"]["all_ok"] and "secondary_ell2" in full
+    assert full["selection_sha"] == line["selection_sha"]
+    for n, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "full" / (n + ".npy"))), n
 
 
 @pytest.mark.timeout(900)
