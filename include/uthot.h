@@ -233,7 +233,14 @@ int ut_hash_de(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, int64_t
  * Replaces the per-child hash_config of evolutionarytechniques.py:38-49. */
 int ut_hash_parent(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, const double* parent,
                    uint32_t* out_digest);
+/* Empty history sized for `capacity` digests.  If the new table cannot be
+ * allocated (UT_ENOMEM) the history is left empty and valid: ut_dedup then
+ * reports in-batch repeats only, and ut_history_add may be called again. */
 int ut_history_reset(ut_ctx* ctx, int64_t capacity);
+/* Add n digests (a digest may be given more than once, in one call or over
+ * several).  The table grows as needed; if a growth fails (UT_ENOMEM, UT_EHIP)
+ * the history is exactly what it was before the call: none of the call's
+ * digests is added and every earlier one is still found. */
 int ut_history_add(ut_ctx* ctx, const uint32_t* digests, int64_t n);   /* device [n][8] */
 int ut_history_add_host(ut_ctx* ctx, const uint32_t* digests_host, int64_t n);
 /* out_dup[i] = 1 if digest i is in the history or repeats an earlier
@@ -415,10 +422,16 @@ typedef struct ut_tree_node {
   double threshold;
   double value;          /* leaf value */
 } ut_tree_node;
+/* An ensemble with no tree, a root or child index outside [0, n_nodes), an
+ * unknown rule or div == 0 is UT_EINVAL, and the ensemble loaded before stays
+ * loaded.  The largest feature index of the splits is recorded. */
 int ut_forest_set(ut_ctx* ctx, int32_t n_trees, const int32_t* roots_host, int64_t n_nodes,
                   const ut_tree_node* nodes_host, int32_t rule, double base, double scale, double div);
 /* features [n_features][ld] (the layout ut_encode_features writes); pred and
- * score [m] may be NULL; score = sign * pred (sign -1: minimise), -inf where dup[i] */
+ * score [m] may be NULL; score = sign * pred (sign -1: minimise), -inf where dup[i].
+ * n_features must exceed the largest feature index the loaded ensemble splits
+ * on: fewer columns than the model was trained on is UT_EINVAL (the message
+ * names both numbers), never an answer read from another column. */
 int ut_forest_predict(ut_ctx* ctx, const double* features, int64_t ld, int64_t m, int32_t n_features,
                       const uint8_t* dup, double sign, double* pred, double* score);
 
@@ -477,9 +490,17 @@ enum { UT_RED_SUM = 0, UT_RED_MAX = 1, UT_RED_MIN = 2 };
 int ut_comm_allreduce_f64(ut_ctx* ctx, double* buf, int64_t n, int32_t op);
 /* every rank's stream reaches this point (an all-reduce, then a stream sync) */
 int ut_comm_barrier(ut_ctx* ctx);
-/* Fault injection for tests: the next `count` device allocations of the
- * context that would grow a buffer fail with UT_ENOMEM (0 clears it). */
+/* Fault injection for tests: the next `count` counted device allocations of
+ * the context all fail with UT_ENOMEM (0 clears it).  Counted are the growths
+ * of the context's scratch buffers and every array of the history table
+ * (ut_history_reset and a growing ut_history_add allocate two: the keys, then
+ * the slot states) and of ut_dedup's batch table.  A call stops at its first
+ * failed allocation, so any count >= 1 fails the first array it needs. */
 int ut_debug_fail_alloc(ut_ctx* ctx, int32_t count);
+/* The same, after `skip` counted allocations have gone through: skip = 1,
+ * count = 1 lets a history call obtain its keys array and fails the slot
+ * states.  Replaces any injection set before; count = 0 clears it. */
+int ut_debug_fail_alloc_after(ut_ctx* ctx, int32_t skip, int32_t count);
 
 /* per-kernel device time (ms) of the ut_score_round_* calls since timing was
  * enabled with ut_set_timing(ctx, 1), averaged over those rounds.  Events are

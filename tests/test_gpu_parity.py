@@ -296,10 +296,11 @@ def test_dedup_matches_oracle():
     e.history_add(hist)
     got = e.dedup(d).cpu().numpy().tolist()
     assert got == osel.dedup(hx, set(hist))
-    # growth path of the history table keeps earlier entries
-    e.history_add(hexes(e.hash(dev(ode.population_init(space, 3000, seed=99)))))
-    got2 = e.dedup(d).cpu().numpy()
-    assert got2.sum() >= sum(got)
+    # growth path of the history table keeps earlier entries and adds exactly the new ones
+    hist2 = hexes(e.hash(dev(ode.population_init(space, 3000, seed=99))))
+    e.history_add(hist2)
+    got2 = e.dedup(d).cpu().numpy().tolist()
+    assert got2 == osel.dedup(hx, set(hist) | set(hist2))
 
 
 def test_dedup_unique_large():

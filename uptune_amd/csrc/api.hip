@@ -192,16 +192,33 @@ static int compile_hash_layout(ut_ctx* c, const std::vector<std::string>& names,
 static int history_alloc(ut_ctx* c, int64_t cap) {
   int64_t p2 = 1024;
   while (p2 < cap) p2 <<= 1;
-  if (c->hist_keys) {
+  if (c->hist_keys || c->hist_state) {
     UT_HIP(c, ut::sync_all(c));
     ut::dfree(c->hist_keys);
     ut::dfree(c->hist_state);
   }
-  UT_HIP(c, ut::dmalloc((void**)&c->hist_keys, sizeof(uint32_t) * 8 * p2));
-  UT_HIP(c, ut::dmalloc((void**)&c->hist_state, sizeof(uint32_t) * p2));
-  UT_HIP(c, hipMemsetAsync(c->hist_state, 0, sizeof(uint32_t) * p2, c->stream));
-  c->hist_cap = p2;
+  // from here on the history is empty and valid (hist_cap == 0: ut_dedup
+  // skips the table) until both arrays of the new one exist
+  c->hist_keys = nullptr;
+  c->hist_state = nullptr;
+  c->hist_cap = 0;
   c->hist_count = 0;
+  uint32_t* keys = nullptr;
+  uint32_t* state = nullptr;
+  if (int rc = ut::dalloc(c, (void**)&keys, sizeof(uint32_t) * 8 * p2)) return rc;
+  if (int rc = ut::dalloc(c, (void**)&state, sizeof(uint32_t) * p2)) {
+    ut::dfree(keys);
+    return rc;
+  }
+  const hipError_t e = hipMemsetAsync(state, 0, sizeof(uint32_t) * p2, c->stream);
+  if (e != hipSuccess) {
+    ut::dfree(keys);
+    ut::dfree(state);
+    return set_err(c, UT_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+  }
+  c->hist_keys = keys;
+  c->hist_state = state;
+  c->hist_cap = p2;
   return 0;
 }
 
@@ -700,30 +717,36 @@ int ut_history_add(ut_ctx* c, const uint32_t* dig, int64_t n) {
   if (n <= 0) return 0;
   UT_CHECK(c, dig != nullptr, UT_EINVAL, "history_add: NULL digests");
   if (!c->hist_keys || (c->hist_count + n) * 2 > c->hist_cap) {
-    // grow: rebuild is not needed for correctness of membership if we keep
-    // the old entries, so re-insert by copying old keys
-    const int64_t old_cap = c->hist_cap;
-    uint32_t* old_keys = c->hist_keys;
-    uint32_t* old_state = c->hist_state;
-    const int64_t old_count = c->hist_count;
-    c->hist_keys = nullptr;
-    c->hist_state = nullptr;
-    int64_t want = (old_count + n) * 4;
+    // grow: build the larger table beside the old one, re-insert the old
+    // entries, then swap.  Any failure before the swap frees what was obtained
+    // and leaves the old table (and hist_count) as it was.
+    int64_t want = (c->hist_count + n) * 4;
     int64_t p2 = 1024;
     while (p2 < want) p2 <<= 1;
-    UT_HIP(c, ut::dmalloc((void**)&c->hist_keys, sizeof(uint32_t) * 8 * p2));
-    UT_HIP(c, ut::dmalloc((void**)&c->hist_state, sizeof(uint32_t) * p2));
-    UT_HIP(c, hipMemsetAsync(c->hist_state, 0, sizeof(uint32_t) * p2, c->stream));
-    c->hist_cap = p2;
-    c->hist_count = 0;
-    if (old_keys) {
-      int rc = launch_hist_rehash(c, old_keys, old_state, old_cap);
-      UT_HIP(c, ut::sync_all(c));
-      ut::dfree(old_keys);
-      ut::dfree(old_state);
-      if (rc) return rc;
-      c->hist_count = old_count;
+    uint32_t* keys = nullptr;
+    uint32_t* state = nullptr;
+    if (int rc = ut::dalloc(c, (void**)&keys, sizeof(uint32_t) * 8 * p2)) return rc;
+    if (int rc = ut::dalloc(c, (void**)&state, sizeof(uint32_t) * p2)) {
+      ut::dfree(keys);
+      return rc;
     }
+    int rc = 0;
+    hipError_t e = hipMemsetAsync(state, 0, sizeof(uint32_t) * p2, c->stream);
+    if (e == hipSuccess && c->hist_keys) {
+      rc = launch_hist_rehash(c, c->hist_keys, c->hist_state, c->hist_cap, keys, state, p2);
+      // the old table is read by the rehash, and maybe by a dedup on another stream of the context
+      if (rc == 0) e = ut::sync_all(c);
+    }
+    if (e != hipSuccess || rc) {
+      ut::dfree(keys);
+      ut::dfree(state);
+      return rc ? rc : set_err(c, UT_EHIP, std::string("history_add (grow): ") + hipGetErrorString(e));
+    }
+    ut::dfree(c->hist_keys);
+    ut::dfree(c->hist_state);
+    c->hist_keys = keys;
+    c->hist_state = state;
+    c->hist_cap = p2;
   }
   int rc = launch_hist_insert(c, dig, n);
   if (rc) return rc;

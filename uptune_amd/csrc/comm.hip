@@ -407,6 +407,15 @@ int ut_debug_fail_alloc(ut_ctx* c, int32_t count) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, count >= 0, UT_EINVAL, "debug_fail_alloc: count < 0");
   c->dbg_fail_alloc = count;
+  c->dbg_fail_skip = 0;
+  return 0;
+}
+
+int ut_debug_fail_alloc_after(ut_ctx* c, int32_t skip, int32_t count) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, skip >= 0 && count >= 0, UT_EINVAL, "debug_fail_alloc_after: skip or count < 0");
+  c->dbg_fail_alloc = count;
+  c->dbg_fail_skip = count > 0 ? skip : 0;
   return 0;
 }
 

@@ -106,10 +106,11 @@ __global__ void k_hist_rehash(const uint32_t* __restrict__ okeys, const uint32_t
   }
 }
 
-int launch_hist_rehash(ut_ctx* c, const uint32_t* okeys, const uint32_t* ostate, int64_t ocap) {
+int launch_hist_rehash(ut_ctx* c, const uint32_t* okeys, const uint32_t* ostate, int64_t ocap, uint32_t* keys,
+                       uint32_t* state, int64_t cap) {
   if (ocap <= 0) return 0;
-  hipLaunchKernelGGL(k_hist_rehash, dim3(grid1(ocap, 256)), dim3(256), 0, c->stream, okeys, ostate, ocap,
-                     c->hist_keys, c->hist_state, c->hist_cap);
+  hipLaunchKernelGGL(k_hist_rehash, dim3(grid1(ocap, 256)), dim3(256), 0, c->stream, okeys, ostate, ocap, keys,
+                     state, cap);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -145,7 +146,13 @@ int launch_dedup(ut_ctx* c, const uint32_t* dig, int64_t m, uint8_t* dup) {
       UT_HIP(c, ut::sync_all(c));
       ut::dfree(c->batch_slots);
     }
-    UT_HIP(c, ut::dmalloc((void**)&c->batch_slots, cap * sizeof(int32_t)));
+    // no table until the new one exists: a failed growth leaves batch_cap == 0,
+    // so the next call allocates again instead of using the freed array
+    c->batch_slots = nullptr;
+    c->batch_cap = 0;
+    int32_t* slots = nullptr;
+    if (int rc = ut::dalloc(c, (void**)&slots, cap * sizeof(int32_t))) return rc;
+    c->batch_slots = slots;
     c->batch_cap = cap;
   }
   UT_HIP(c, hipMemsetAsync(c->batch_slots, 0xFF, cap * sizeof(int32_t), c->stream));

@@ -62,11 +62,14 @@ extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_ho
   // validate on the host: every child / root index in range (a bad index would fault on the device)
   for (int32_t t = 0; t < n_trees; ++t)
     UT_CHECK(c, roots_host[t] >= 0 && roots_host[t] < n_nodes, UT_EINVAL, "forest_set: root out of range");
+  int32_t max_feat = -1;   // largest feature column any split tests (ut_forest_predict needs more columns)
   for (int64_t k = 0; k < n_nodes; ++k) {
     const ut_tree_node& q = nodes_host[k];
-    if (q.feature >= 0)
+    if (q.feature >= 0) {
       UT_CHECK(c, q.left >= 0 && q.left < n_nodes && q.right >= 0 && q.right < n_nodes, UT_EINVAL,
                "forest_set: child out of range");
+      max_feat = std::max(max_feat, q.feature);
+    }
   }
   UT_HIP(c, hipSetDevice(c->device));
   UT_HIP(c, ut::sync_all(c));
@@ -81,6 +84,7 @@ extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_ho
   UT_HIP(c, hipMemcpy(c->forest_roots, roots_host, sizeof(int32_t) * n_trees, hipMemcpyHostToDevice));
   c->forest_trees = n_trees;
   c->forest_rule = rule;
+  c->forest_max_feat = max_feat;
   c->forest_base = base;
   c->forest_scale = scale;
   c->forest_div = div;
@@ -92,6 +96,9 @@ extern "C" int ut_forest_predict(ut_ctx* c, const double* features, int64_t ld, 
   if (!c) return UT_EINVAL;
   UT_CHECK(c, c->forest_trees > 0, UT_EINVAL, "forest_predict: call ut_forest_set first");
   UT_CHECK(c, features && n_features >= 1 && ld >= m && m >= 0, UT_EINVAL, "forest_predict: bad arguments");
+  UT_CHECK(c, n_features > c->forest_max_feat, UT_EINVAL,
+           "forest_predict: the ensemble splits on feature " + std::to_string(c->forest_max_feat) +
+               " but n_features is " + std::to_string(n_features));
   if (m == 0) return 0;
   hipLaunchKernelGGL(ut::k_forest, dim3(ut::grid1(m, 256)), dim3(256), 0, c->stream, c->forest_nodes,
                      c->forest_roots, c->forest_trees, c->forest_rule, c->forest_base, c->forest_scale,

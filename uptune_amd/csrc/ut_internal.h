@@ -359,6 +359,7 @@ struct ut_ctx {
   ut_tree_node* forest_nodes = nullptr;
   int32_t* forest_roots = nullptr;
   int32_t forest_trees = 0, forest_rule = 0;
+  int32_t forest_max_feat = -1;   // largest feature index of the loaded ensemble's splits
   double forest_base = 0.0, forest_scale = 1.0, forest_div = 1.0;
 
   // multi-GPU exchange (comm.hip): the RCCL communicator of this context's
@@ -372,7 +373,8 @@ struct ut_ctx {
   // record capacity (uint64 words of cm_send / cm_recv) every rank agreed it
   // holds: the all-gather votes only when a call needs more (comm.hip)
   size_t cm_agreed_send = 0, cm_agreed_recv = 0;
-  int32_t dbg_fail_alloc = 0;              // ut_debug_fail_alloc: the next N growing ensure() calls fail
+  int32_t dbg_fail_alloc = 0;              // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
+  int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
   ut::Timing timing;
 };
@@ -428,13 +430,23 @@ struct StreamScope {
 // feature rows of the K* operands (Xs^T, U'): d rounded up to the f64 MFMA's k = 4
 inline int32_t kstar_dpad(int32_t d) { return ((d + 3) / 4) * 4; }
 
+// fault injection (tests): true when this counted allocation is to fail as
+// hipMalloc would -- after dbg_fail_skip counted allocations went through, the
+// next dbg_fail_alloc fail
+inline bool inject_alloc_failure(ut_ctx* c) {
+  if (c->dbg_fail_alloc <= 0) return false;
+  if (c->dbg_fail_skip > 0) {
+    --c->dbg_fail_skip;
+    return false;
+  }
+  --c->dbg_fail_alloc;
+  return true;
+}
+
 template <class T>
 int ensure(ut_ctx* c, DevBuf<T>& b, size_t n) {
   if (b.n >= n && b.p) return 0;
-  if (c->dbg_fail_alloc > 0) {   // fault injection (tests): this growth fails as hipMalloc would
-    --c->dbg_fail_alloc;
-    return set_err(c, UT_ENOMEM, "hipMalloc: injected failure (ut_debug_fail_alloc)");
-  }
+  if (inject_alloc_failure(c)) return set_err(c, UT_ENOMEM, "hipMalloc: injected failure (ut_debug_fail_alloc)");
   // a buffer that has to grow again (sizes that follow a growing training
   // set) gets headroom, up to 2 GiB: every regrowth costs a device-wide sync
   size_t want = n;
@@ -454,6 +466,21 @@ int ensure(ut_ctx* c, DevBuf<T>& b, size_t n) {
   }
   if (e != hipSuccess) return set_err(c, UT_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
   b.n = want;
+  return 0;
+}
+
+// a plain device array outside a DevBuf (the history and batch dedup tables):
+// dmalloc under the same fault injection as ensure().  *p is written only on
+// success, so a caller allocates into locals and commits them once it has all.
+inline int dalloc(ut_ctx* c, void** p, size_t bytes) {
+  if (inject_alloc_failure(c)) return set_err(c, UT_ENOMEM, "hipMalloc: injected failure (ut_debug_fail_alloc)");
+  void* q = nullptr;
+  const hipError_t e = ut::dmalloc(&q, bytes ? bytes : 1);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(c, UT_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  }
+  *p = q;
   return 0;
 }
 
@@ -500,7 +527,9 @@ int launch_pop_aos_rows(ut_ctx* c, const double* trial, int64_t ld, const int64_
 int launch_aos_row(ut_ctx* c, const double* src, int64_t row);
 inline int64_t pop_aos_ld(const ut_ctx* c) { return ((int64_t)c->space.ncols + 15) / 16 * 16; }
 int launch_hist_insert(ut_ctx* c, const uint32_t* dig, int64_t n);
-int launch_hist_rehash(ut_ctx* c, const uint32_t* okeys, const uint32_t* ostate, int64_t ocap);
+// re-insert the occupied slots of the table (okeys, ostate, ocap) into (keys, state, cap)
+int launch_hist_rehash(ut_ctx* c, const uint32_t* okeys, const uint32_t* ostate, int64_t ocap, uint32_t* keys,
+                       uint32_t* state, int64_t cap);
 int launch_dedup(ut_ctx* c, const uint32_t* dig, int64_t m, uint8_t* dup);
 int launch_mask_or(ut_ctx* c, uint8_t* dst, const uint8_t* src, int64_t m);
 // feat == nullptr: the candidates' scaled features and norms are already in

@@ -56,7 +56,11 @@ def _append_sklearn_tree(tree, out: List[np.ndarray], offset: int) -> int:
     a["feature"] = np.where(leaf, -1, t.feature)
     a["left"] = np.where(leaf, 0, t.children_left + offset)
     a["right"] = np.where(leaf, 0, t.children_right + offset)
-    a["default_left"] = 1
+    # sklearn >= 1.3 routes NaN by the split's missing_go_to_left (a split that saw
+    # no missing value in training sends it to the child with more samples);
+    # older trees reject NaN altogether
+    mgl = getattr(t, "missing_go_to_left", None)
+    a["default_left"] = 1 if mgl is None else np.asarray(mgl, np.int32)
     a["threshold"] = t.threshold
     a["value"] = t.value[:, 0, 0]
     out.append(a)
