@@ -369,6 +369,27 @@ int ut_gp_fit_status(ut_ctx* ctx, int32_t* ok);
 int ut_gp_kstar_mode(ut_ctx* ctx, int32_t* categorical);
 /* f_best (min standardised y), y mean/std used for standardisation */
 int ut_gp_stats(ut_ctx* ctx, double* f_best, double* y_mean, double* y_std);
+/* Log marginal likelihood of the standardised targets,
+ *   lml = -1/2 |L^-1 ys|^2 - sum_{i<n} log L_ii - (n/2) log 2 pi,  L = chol(K + (sigma_n2 + jitter) I):
+ * the measure by which a lengthscale is chosen (the reference has no GP and so
+ * none to choose).
+ * LML of the current fit (standardised y); waits for an in-flight fit like
+ * ut_gp_fit_status; UT_ENOTPD if that fit was not positive definite */
+int ut_gp_lml(ut_ctx* ctx, double* lml_host);
+/* LML at g hyperparameter points for the training set (X_host [n][d], y_host [n]):
+ * point j uses lengthscale scale_host[j] * hyper->lengthscale_host[k] (the ARD
+ * shape is kept), hyper->sigma_f2, and noise noise_host[j] (NULL: hyper->sigma_n2)
+ * + hyper->jitter.  lml_host[j] = NaN where K is not positive definite.
+ * *best_host = argmax over the finite values (ties: smallest j), -1 if none.
+ * Synchronous.  Leaves the context's current fit, a staged asynchronous fit
+ * and every scoring result untouched.  The g factorisations run batched, in
+ * chunks of as many points as fit 1 GiB of kernel matrices (UT_LML_BATCH
+ * overrides the chunk size; the results do not depend on it), in scratch
+ * buffers of their own.  n < 1, d < 1, g < 1, a NULL pointer (noise_host
+ * excepted) or a scale that is not finite and > 0 is UT_EINVAL. */
+int ut_gp_lml_grid(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
+                   const ut_gp_hyper* hyper, int32_t g, const double* scale_host,
+                   const double* noise_host, double* lml_host, int32_t* best_host);
 
 /* ---- selection ---------------------------------------------------------- */
 /* k largest scores, ties -> smallest global index; entries with dup[i]!=0 or

@@ -288,6 +288,7 @@ int ut_ctx_create(int device, uint64_t seed, ut_ctx** out) {
   if (const char* e = getenv("UT_CAT_KSTAR")) c->cat_enable = atoi(e) != 0;
   if (const char* e = getenv("UT_FIT_DEFER")) c->fit_defer = atoi(e) != 0;
   if (const char* e = getenv("UT_KSTAR_Q")) c->kstar_q = atoi(e) != 0;
+  if (const char* e = getenv("UT_LML_BATCH")) c->lml_batch = atoi(e);
   *out = c;
   return 0;
 }
@@ -318,6 +319,7 @@ int ut_ctx_destroy(ut_ctx* c) {
   fr(c->gp_XsT_num.p); fr(c->gp_xnorm_num.p); fr(c->gp_acat.p); fr(c->bcat.p); fr(c->pr_bcat.p);
   fr(c->gp_i8a.p); fr(c->gp_i8rs.p);
   fr(c->gp_x8.p); fr(c->u8.p); fr(c->gp_q8.p); fr(c->scol.p);
+  fr(c->lml_in.p); fr(c->lml_d2.p); fr(c->lml_k.p); fr(c->lml_li.p); fr(c->lml_rhs.p); fr(c->lml_flag.p);
   fr(c->kst.p); fr(c->mu_part.p); fr(c->var_part.p); fr(c->cnorm.p);
   fr(c->r_values.p); fr(c->r_feat.p); fr(c->r_mu.p); fr(c->r_var.p); fr(c->r_score.p); fr(c->r_digest.p);
   fr(c->r_dup.p); fr(c->tk_score[0].p); fr(c->tk_score[1].p); fr(c->tk_idx[0].p); fr(c->tk_idx[1].p);
@@ -329,6 +331,7 @@ int ut_ctx_destroy(ut_ctx* c) {
     if (e) hipEventDestroy(e);
   if (c->fit_host) hipHostFree(c->fit_host);
   if (c->flag_host) hipHostFree(c->flag_host);
+  if (c->lml_host) hipHostFree(c->lml_host);
   for (hipStream_t st : {c->own_stream, c->side, c->fit_stream})
     if (st) hipStreamDestroy(st);
   delete c;
@@ -903,6 +906,19 @@ int ut_gp_fit_status(ut_ctx* c, int32_t* ok) {
   if (rc != 0 && rc != UT_ENOTPD) return rc;
   *ok = rc == 0 ? 1 : 0;
   return 0;
+}
+
+int ut_gp_lml(ut_ctx* c, double* lml_host) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_lml_impl(c, lml_host);
+}
+
+int ut_gp_lml_grid(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
+                   int32_t g, const double* scale, const double* noise, double* lml_host, int32_t* best_host) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_lml_grid_impl(c, X, y, n, d, h, g, scale, noise, lml_host, best_host);
 }
 
 int ut_gp_kstar_mode(ut_ctx* c, int32_t* categorical) {

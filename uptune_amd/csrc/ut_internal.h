@@ -373,6 +373,17 @@ struct ut_ctx {
   // record capacity (uint64 words of cm_send / cm_recv) every rank agreed it
   // holds: the all-gather votes only when a call needs more (comm.hip)
   size_t cm_agreed_send = 0, cm_agreed_recv = 0;
+  // log marginal likelihood (gp_lml.hip).  The grid's scratch, apart from
+  // everything the fit and the scoring own:
+  ut::DevBuf<double> lml_in;      // staged X [n][d] | y [n] | 1/ell [d] | scaled rows [npad][d] | norms [npad] |
+                                  // ys [npad] | stats [4] | per point: 0.5 / scale^2, diagonal, lml [3 g]
+  ut::DevBuf<double> lml_d2;      // [npad][npad] |xs_i - xs_j|^2 (lower 64 x 64 tiles)
+  ut::DevBuf<double> lml_k;       // [B][npad][npad] K_z, then L_z
+  ut::DevBuf<double> lml_li;      // [B][64][npad]: inv(L_kk) of the current panel in columns 0 .. 63
+  ut::DevBuf<double> lml_rhs;     // [B][npad] ys, then beta_z = L_z^-1 ys
+  ut::DevBuf<int32_t> lml_flag;   // [g] point z is not positive definite
+  int32_t lml_batch = 0;          // grid points per chunk; 0 = what fits LML_BUDGET (UT_LML_BATCH)
+  double* lml_host = nullptr;     // pinned: ut_gp_lml's result, written by its kernel
   int32_t dbg_fail_alloc = 0;              // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
@@ -490,6 +501,14 @@ int gp_wait_fit(ut_ctx* c);
 int gp_fit_flush(ut_ctx* c);
 int gp_ensure_linvt(ut_ctx* c);
 int gp_fit_prefit(ut_ctx* c);
+// gp.hip's staging kernels on any buffers: scaled rows + norms, standardised y + stats
+int launch_gp_prep_train(ut_ctx* c, const double* X, int32_t n, int32_t npad, int32_t d, const double* inv_ell,
+                         double* Xs, double* xnorm);
+int launch_gp_ystats(ut_ctx* c, const double* y, int32_t n, int32_t npad, double* ys, double* stats);
+// gp_lml.hip: the log marginal likelihood of the fit in place / at g hyperparameter points
+int gp_lml_impl(ut_ctx* c, double* lml_host);
+int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
+                     int32_t g, const double* scale, const double* noise, double* lml_host, int32_t* best_host);
 
 // kernel launchers implemented in the .hip translation units
 int launch_population_init(ut_ctx* c, uint32_t round_);

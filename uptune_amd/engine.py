@@ -349,6 +349,40 @@ class BatchEngine:
         L.check(self.ctx, self.lib.ut_gp_kstar_mode(self.ctx, C.byref(v)), "ut_gp_kstar_mode")
         return "categorical" if v.value else "dense"
 
+    def gp_lml(self) -> float:
+        """ut_gp_lml: log marginal likelihood of the current fit (standardised y);
+        waits for an in-flight fit, raises UT_ENOTPD if it was not positive definite"""
+        v = C.c_double()
+        L.check(self.ctx, self.lib.ut_gp_lml(self.ctx, C.byref(v)), "ut_gp_lml")
+        return float(v.value)
+
+    def gp_lml_grid(self, X: np.ndarray, y: np.ndarray, lengthscale, scales, noises=None, sigma_f2: float = 1.0,
+                    sigma_n2: float = 1e-6, jitter: float = 0.0) -> Tuple[np.ndarray, int]:
+        """ut_gp_lml_grid: the log marginal likelihood of (X, y) at the points
+        (scales[j] * lengthscale, noises[j] or sigma_n2), all factorised in one
+        batched chain on the device.  Returns (lml [g], NaN where not positive
+        definite; the argmax over the finite values, -1 if none).  The current
+        fit and a fit in flight are left as they are."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        n, d = X.shape
+        ell = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscale, dtype=np.float64), (d,)))
+        sc = np.ascontiguousarray(np.atleast_1d(np.asarray(scales, dtype=np.float64)))
+        g = int(sc.shape[0])
+        nz = None
+        if noises is not None:
+            nz = np.ascontiguousarray(np.atleast_1d(np.asarray(noises, dtype=np.float64)))
+            if nz.shape != sc.shape:
+                raise ValueError("gp_lml_grid: noises must have one entry per scale")
+        h = L.GpHyper(sigma_f2=float(sigma_f2), sigma_n2=float(sigma_n2), jitter=float(jitter),
+                      lengthscale_host=ell.ctypes.data)
+        out = np.empty(max(g, 1), dtype=np.float64)
+        best = C.c_int32(-1)
+        L.check(self.ctx, self.lib.ut_gp_lml_grid(self.ctx, X.ctypes.data, y.ctypes.data, n, d, C.byref(h), g,
+                                                  sc.ctypes.data, None if nz is None else nz.ctypes.data,
+                                                  out.ctypes.data, C.byref(best)), "ut_gp_lml_grid")
+        return out[:g], int(best.value)
+
     def gp_stats(self) -> Tuple[float, float, float]:
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         L.check(self.ctx, self.lib.ut_gp_stats(self.ctx, C.byref(a), C.byref(b), C.byref(c)), "ut_gp_stats")

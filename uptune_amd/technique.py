@@ -27,7 +27,7 @@ import logging
 import math
 import random
 from collections import deque
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
 
@@ -271,11 +271,24 @@ class SharedModel:
     requests_query() (every requested configuration's hash -> the dedup set),
     results_query() (Configuration.data + time -> the training set)."""
 
-    def __init__(self, device: int = 0, seed: int = 0, lengthscale: float = 0.3, min_train: int = 4,
+    def __init__(self, device: int = 0, seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4,
                  precision: int = 64, sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 1e-8,
-                 engine_factory=None, y_transform: Optional[str] = None):
+                 engine_factory=None, y_transform: Optional[str] = None, ell_grid=None):
+        if isinstance(lengthscale, str) and lengthscale != "auto":
+            raise ValueError("lengthscale: a number (or one per feature) or 'auto'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
         self.precision = precision
+        # lengthscale="auto": the lengthscale is the candidate of ell_grid
+        # (isotropic; default sqrt(n_features) * geomspace(0.05, 4, 16)) with the
+        # largest log marginal likelihood on the fit's own rows and targets
+        # (engine.gp_lml_grid: one batched factorisation chain).  Chosen at the
+        # first fit and wherever the padded size changes -- where the device
+        # refactors anyway -- so the incremental fits in between keep identical
+        # hyperparameters.  lengthscale_ is the value in use, ell_history one
+        # (n, ell, lml) per selection.
+        self.ell_grid = None if ell_grid is None else np.asarray(ell_grid, dtype=np.float64).ravel()
+        self.lengthscale_ = None if isinstance(lengthscale, str) else lengthscale
+        self.ell_history: List[Any] = []
         # y_transform: what the GP is fitted on.  None = the objective as
         # measured; "rank" = its normal scores, Phi^-1((rank + 1/2) / n) (order
         # preserving, so the incumbent stays the minimum): an objective spanning
@@ -309,6 +322,7 @@ class SharedModel:
         self._yf = np.zeros(0)
         self._nf = 0
         self._perm_npad = 0
+        self._ell_npad = 0          # padded size of the fit the lengthscale was last selected at ("auto")
         # features of the rounds' selections, encoded on the device beside
         # them (GpuBatchTechnique._round), by hash_config digest: a result of a
         # selected configuration needs no second encode round trip
@@ -443,11 +457,32 @@ class SharedModel:
             # whatever their row order
             r = rankdata(y, method="average") - 1.0
             y = ndtri((r + 0.5) / n)
-        self.engine.gp_fit(self._Xf[:n], y, lengthscale=self.lengthscale, wait=False, **self.hyper)
+        ell = self.lengthscale
+        if isinstance(ell, str):   # "auto"
+            if npad != self._ell_npad:
+                self._select_lengthscale(self._Xf[:n], y)
+                self._ell_npad = npad
+            ell = self.lengthscale_
+        self.engine.gp_fit(self._Xf[:n], y, lengthscale=ell, wait=False, **self.hyper)
         self._fit_key = key
         self._fit_unverified = True
         self.fits += 1
         return True
+
+    def _select_lengthscale(self, X, y) -> None:
+        """lengthscale_ := the grid candidate with the largest log marginal
+        likelihood of (X, y); when no candidate is positive definite the previous
+        choice stays (the grid's median on the first fit) and the fit's jitter
+        retry takes it from there"""
+        grid = self.ell_grid
+        if grid is None:
+            grid = math.sqrt(X.shape[1]) * np.geomspace(0.05, 4.0, 16)
+        lml, best = self.engine.gp_lml_grid(X, y, 1.0, grid, **self.hyper)
+        if best >= 0:
+            self.lengthscale_ = float(grid[best])
+        elif self.lengthscale_ is None:
+            self.lengthscale_ = float(np.median(grid))
+        self.ell_history.append((len(y), self.lengthscale_, float(lml[best]) if best >= 0 else float("nan")))
 
     def note_selections(self, hexes) -> None:
         """a round's selections are requests the driver has not made yet: they
@@ -508,7 +543,7 @@ class GpuBatchTechnique(SearchTechnique):
     sharded = True
 
     def __init__(self, pool: int = 1 << 14, batch: int = 8, population: int = 1024, device: int = 0,
-                 seed: int = 0, lengthscale: float = 0.3, min_train: int = 4, acq: str = "ei",
+                 seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4, acq: str = "ei",
                  group=None, surrogate=None, shared: Optional[SharedModel] = None, engine_factory=None,
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)

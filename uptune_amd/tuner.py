@@ -13,7 +13,7 @@ the reference's batch dispatch + api.sync (api.py:428-482, :547-553).
 """
 from __future__ import annotations
 
-from typing import Any, Callable, Dict, Optional
+from typing import Any, Callable, Dict, Optional, Union
 
 from .driver import DistributedSearchDriver, SearchDriver
 from .technique import pso_ga_de_bandit
@@ -36,7 +36,7 @@ def random_configs(manipulator, n: int, seed: int, device: int = 0, with_keys: b
 
 def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], generations: int = 100,
                 parallelism: int = 4, n_init: int = 0, pool: int = 1 << 16, batch: int = 8, population: int = 1024,
-                seed: int = 0, lengthscale: float = 0.3, device: int = 0, group=None,
+                seed: int = 0, lengthscale: Union[float, str] = 0.3, device: int = 0, group=None,
                 precision: int = 64, prune_rows: int = 0) -> SearchDriver:
     """Run the bandit for `generations` generations; returns the driver (results,
     best_result, bandit statistics).  With torch.distributed initialised and
