@@ -112,26 +112,18 @@ static int timing_collect(ut_ctx* c, bool keep) {
   return 0;
 }
 
-static void free_space(Space& s) {
-  if (s.d_params) ut::dfree(s.d_params);
-  if (s.d_order) ut::dfree(s.d_order);
-  if (s.d_words) ut::dfree(s.d_words);
-  if (s.d_block_last) ut::dfree(s.d_block_last);
-  if (s.d_lut) ut::dfree(s.d_lut);
-  if (s.d_vtab) ut::dfree(s.d_vtab);
-  for (void* q : {(void*)s.d_order_col, (void*)s.d_perm_params, (void*)s.d_perm_bytes, (void*)s.d_perm_off,
-                  (void*)s.d_perm_offbase, (void*)s.d_perm_len, (void*)s.d_comp,
-                  (void*)s.d_col_param, (void*)s.d_cat_ccol, (void*)s.d_num_feat, (void*)s.d_feat_num})
-    if (q) ut::dfree(q);
-  s = Space();
+// a host vector as a new device array (the space's tables, synchronous)
+template <class T>
+static hipError_t upload(DevBuf<T>& b, const std::vector<T>& v) {
+  const hipError_t e = b.alloc(v.size());
+  return e != hipSuccess ? e : hipMemcpy(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
 }
 
 // Build the fixed outer message of hash_config (manipulator.py:233-243):
 //   for i, p in enumerate(sorted params): name ++ hash_value ++ str(i) ++ "|"
 // with hash_value = "b'" hex "'" (py3, primitive) or hex.
-static int compile_hash_layout(ut_ctx* c, const std::vector<std::string>& names,
+static int compile_hash_layout(ut_ctx* c, Space& s, const std::vector<std::string>& names,
                                const std::vector<bool>& primitive) {
-  Space& s = c->space;
   const int32_t P = s.P;
   std::vector<uint8_t> msg;
   std::vector<int64_t> hole_start(P);
@@ -182,42 +174,33 @@ static int compile_hash_layout(ut_ctx* c, const std::vector<std::string>& names,
   }
   s.outer_len = L;
   s.outer_blocks = NBLK;
-  UT_HIP(c, ut::dmalloc((void**)&s.d_words, sizeof(HashWord) * words.size()));
-  UT_HIP(c, hipMemcpy(s.d_words, words.data(), sizeof(HashWord) * words.size(), hipMemcpyHostToDevice));
-  UT_HIP(c, ut::dmalloc((void**)&s.d_block_last, sizeof(int32_t) * block_last.size()));
-  UT_HIP(c, hipMemcpy(s.d_block_last, block_last.data(), sizeof(int32_t) * block_last.size(), hipMemcpyHostToDevice));
+  UT_HIP(c, upload(s.d_words, words));
+  UT_HIP(c, upload(s.d_block_last, block_last));
+  return 0;
+}
+
+// a new, empty table of p2 slots in (keys, state), which are written only if both exist
+static int history_table(ut_ctx* c, int64_t p2, DevBuf<uint32_t>& keys, DevBuf<uint32_t>& state) {
+  DevBuf<uint32_t> k, st;
+  if (int rc = ut::dalloc(c, k, (size_t)8 * p2)) return rc;
+  if (int rc = ut::dalloc(c, st, (size_t)p2)) return rc;
+  UT_HIP(c, hipMemsetAsync(st.p, 0, sizeof(uint32_t) * p2, c->stream));
+  keys.swap(k);
+  state.swap(st);
   return 0;
 }
 
 static int history_alloc(ut_ctx* c, int64_t cap) {
   int64_t p2 = 1024;
   while (p2 < cap) p2 <<= 1;
-  if (c->hist_keys || c->hist_state) {
-    UT_HIP(c, ut::sync_all(c));
-    ut::dfree(c->hist_keys);
-    ut::dfree(c->hist_state);
-  }
+  if (c->hist_keys.p || c->hist_state.p) UT_HIP(c, ut::sync_all(c));
   // from here on the history is empty and valid (hist_cap == 0: ut_dedup
   // skips the table) until both arrays of the new one exist
-  c->hist_keys = nullptr;
-  c->hist_state = nullptr;
+  c->hist_keys.reset();
+  c->hist_state.reset();
   c->hist_cap = 0;
   c->hist_count = 0;
-  uint32_t* keys = nullptr;
-  uint32_t* state = nullptr;
-  if (int rc = ut::dalloc(c, (void**)&keys, sizeof(uint32_t) * 8 * p2)) return rc;
-  if (int rc = ut::dalloc(c, (void**)&state, sizeof(uint32_t) * p2)) {
-    ut::dfree(keys);
-    return rc;
-  }
-  const hipError_t e = hipMemsetAsync(state, 0, sizeof(uint32_t) * p2, c->stream);
-  if (e != hipSuccess) {
-    ut::dfree(keys);
-    ut::dfree(state);
-    return set_err(c, UT_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-  }
-  c->hist_keys = keys;
-  c->hist_state = state;
+  if (int rc = history_table(c, p2, c->hist_keys, c->hist_state)) return rc;
   c->hist_cap = p2;
   return 0;
 }
@@ -298,34 +281,6 @@ int ut_ctx_destroy(ut_ctx* c) {
   hipSetDevice(c->device);
   if (c->stream) ut::sync_all(c);
   ut::comm_release(c);
-  free_space(c->space);
-  auto fr = [](void* p) { if (p) ut::dfree(p); };
-  fr(c->pop); fr(c->pso_vel); fr(c->pso_best);
-  fr(c->pop_dig); fr(c->pop_aos);
-  for (size_t s = 0; s < c->pop_slots.size(); ++s) {
-    if ((int32_t)s == c->pop_slot) continue;   // the selected slot's buffers are the fields above
-    fr(c->pop_slots[s].pop); fr(c->pop_slots[s].pso_vel); fr(c->pop_slots[s].pso_best); fr(c->pop_slots[s].pop_dig);
-    fr(c->pop_slots[s].pop_aos);
-  }
-  fr(c->r_mask.p); fr(c->r_fresh.p); fr(c->r_pairs.p); fr(c->r_npairs.p); fr(c->de_xbits.p); fr(c->par_dig.p);
-  fr(c->hs_mask.p); fr(c->hs_fresh.p);
-  fr(c->pr_mu.p); fr(c->pr_ub.p); fr(c->pr_score.p); fr(c->pr_mpart.p); fr(c->pr_kst.p); fr(c->pr_vpart.p);
-  fr(c->pr_idx.p); fr(c->pr_count.p); fr(c->pr_ucand.p); fr(c->pr_cnorm.p);
-  fr(c->pr_k2.p); fr(c->pr_f2.p); fr(c->pr_exact.p); fr(c->app_ws.p); fr(c->var_vbuf.p);
-  fr(c->hist_keys); fr(c->hist_state); fr(c->batch_slots);
-  fr(c->gp_Xs); fr(c->gp_xnorm); fr(c->gp_K); fr(c->gp_Linv); fr(c->gp_y); fr(c->gp_tmp);
-  fr(c->gp_alpha); fr(c->gp_beta); fr(c->gp_inv_ell); fr(c->gp_stats); fr(c->gp_flag); fr(c->gp_Xs_f); fr(c->gp_T);
-  fr(c->gp_LinvT); fr(c->gp_LinvT_f); fr(c->gp_ctr); fr(c->gp_XsT); fr(c->ucand.p);
-  fr(c->gp_XsT_num.p); fr(c->gp_xnorm_num.p); fr(c->gp_acat.p); fr(c->bcat.p); fr(c->pr_bcat.p);
-  fr(c->gp_i8a.p); fr(c->gp_i8rs.p);
-  fr(c->gp_x8.p); fr(c->u8.p); fr(c->gp_q8.p); fr(c->scol.p);
-  fr(c->lml_in.p); fr(c->lml_d2.p); fr(c->lml_k.p); fr(c->lml_li.p); fr(c->lml_rhs.p); fr(c->lml_flag.p);
-  fr(c->kst.p); fr(c->mu_part.p); fr(c->var_part.p); fr(c->cnorm.p);
-  fr(c->r_values.p); fr(c->r_feat.p); fr(c->r_mu.p); fr(c->r_var.p); fr(c->r_score.p); fr(c->r_digest.p);
-  fr(c->r_dup.p); fr(c->tk_score[0].p); fr(c->tk_score[1].p); fr(c->tk_idx[0].p); fr(c->tk_idx[1].p);
-  fr(c->r_topk_idx.p); fr(c->r_topk_score.p); fr(c->perm_ws.p); fr(c->perm_dig.p);
-  fr(c->forest_nodes); fr(c->forest_roots); fr(c->r_topk_vals.p);
-  fr(c->cm_send.p); fr(c->cm_recv.p); fr(c->cm_keep.p); fr(c->cm_pay.p); fr(c->cm_cnt.p);
   for (auto& m : c->timing.marks) hipEventDestroy(m.ev);
   for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_fit, c->ev_prefit, c->ev_fit_x})
     if (e) hipEventDestroy(e);
@@ -334,7 +289,7 @@ int ut_ctx_destroy(ut_ctx* c) {
   if (c->lml_host) hipHostFree(c->lml_host);
   for (hipStream_t st : {c->own_stream, c->side, c->fit_stream})
     if (st) hipStreamDestroy(st);
-  delete c;
+  delete c;   // (the device is still current: the DevBuf members free on it)
   return 0;
 }
 
@@ -360,9 +315,9 @@ int ut_space_define(ut_ctx* c, int32_t P, const ut_param_desc* params, int32_t p
   UT_HIP(c, hipSetDevice(c->device));
   if (int rc = gp_fit_flush(c)) return rc;   // a staged fit reads the space's categorical layout
   UT_HIP(c, ut::sync_all(c));
-  free_space(c->space);
+  c->space = Space();
   c->has_space = false;
-  Space& s = c->space;
+  Space s;   // moved into the context once every table is on the device
   s.P = P;
   s.py2 = py2_layout ? 1 : 0;
   s.host_params.resize(P);
@@ -477,49 +432,35 @@ int ut_space_define(ut_ctx* c, int32_t P, const ut_param_desc* params, int32_t p
   }
   s.n_feat = feat;
   s.ncols = col;
-  UT_HIP(c, ut::dmalloc((void**)&s.d_params, sizeof(DevParam) * P));
-  UT_HIP(c, hipMemcpy(s.d_params, s.host_params.data(), sizeof(DevParam) * P, hipMemcpyHostToDevice));
-  UT_HIP(c, ut::dmalloc((void**)&s.d_order, sizeof(int32_t) * P));
-  UT_HIP(c, hipMemcpy(s.d_order, s.host_order.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice));
+  UT_HIP(c, upload(s.d_params, s.host_params));
+  UT_HIP(c, upload(s.d_order, s.host_order));
   if (lut.empty()) lut.resize(8, 0u);
   {  // the device LUT holds each digest as its 64 hex characters (16 big-endian
      // words, what the outer message holds): k_hash copies them into its hex slot
     std::vector<uint32_t> luthex(lut.size() * 2);
     for (size_t e = 0; e < lut.size() / 8; ++e) ut::digest_hex(&lut[8 * e], &luthex[16 * e]);
-    UT_HIP(c, ut::dmalloc((void**)&s.d_lut, sizeof(uint32_t) * luthex.size()));
-    UT_HIP(c, hipMemcpy(s.d_lut, luthex.data(), sizeof(uint32_t) * luthex.size(), hipMemcpyHostToDevice));
+    UT_HIP(c, upload(s.d_lut, luthex));
   }
   if (vtab.empty()) vtab.resize(1, 0.0);
-  UT_HIP(c, ut::dmalloc((void**)&s.d_vtab, sizeof(double) * vtab.size()));
-  UT_HIP(c, hipMemcpy(s.d_vtab, vtab.data(), sizeof(double) * vtab.size(), hipMemcpyHostToDevice));
+  UT_HIP(c, upload(s.d_vtab, vtab));
   {
     std::vector<int32_t> order_col(P);
     for (int32_t j = 0; j < P; ++j) order_col[j] = s.host_params[s.host_order[j]].col;
-    UT_HIP(c, ut::dmalloc((void**)&s.d_order_col, sizeof(int32_t) * P));
-    UT_HIP(c, hipMemcpy(s.d_order_col, order_col.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice));
+    UT_HIP(c, upload(s.d_order_col, order_col));
   }
   if (s.n_perm > 0) {
-    auto up = [&](auto*& dst, const auto& v) -> hipError_t {
-      hipError_t e = ut::dmalloc((void**)&dst, sizeof(v[0]) * v.size());
-      if (e != hipSuccess) return e;
-      return hipMemcpy(dst, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice);
-    };
-    UT_HIP(c, up(s.d_perm_params, perm_params));
-    UT_HIP(c, up(s.d_perm_bytes, perm_bytes));
-    UT_HIP(c, up(s.d_perm_off, perm_off));
-    UT_HIP(c, up(s.d_perm_offbase, perm_offbase));
-    UT_HIP(c, up(s.d_perm_len, perm_len));
+    UT_HIP(c, upload(s.d_perm_params, perm_params));
+    UT_HIP(c, upload(s.d_perm_bytes, perm_bytes));
+    UT_HIP(c, upload(s.d_perm_off, perm_off));
+    UT_HIP(c, upload(s.d_perm_offbase, perm_offbase));
+    UT_HIP(c, upload(s.d_perm_len, perm_len));
   }
-  if (s.n_comp > 0) {
-    UT_HIP(c, ut::dmalloc((void**)&s.d_comp, sizeof(int32_t) * comp.size()));
-    UT_HIP(c, hipMemcpy(s.d_comp, comp.data(), sizeof(int32_t) * comp.size(), hipMemcpyHostToDevice));
-  }
+  if (s.n_comp > 0) UT_HIP(c, upload(s.d_comp, comp));
   {
     std::vector<int32_t> col_param(s.ncols > 0 ? s.ncols : 1, -1);
     for (int32_t j = 0; j < P; ++j)
       if (s.host_params[j].kind != UT_PERM) col_param[s.host_params[j].col] = j;
-    UT_HIP(c, ut::dmalloc((void**)&s.d_col_param, sizeof(int32_t) * col_param.size()));
-    UT_HIP(c, hipMemcpy(s.d_col_param, col_param.data(), sizeof(int32_t) * col_param.size(), hipMemcpyHostToDevice));
+    UT_HIP(c, upload(s.d_col_param, col_param));
   }
   {  // categorical K*: ENUM / BOOL code columns, numeric features (gp_gemm.hip)
     std::vector<int32_t> ccol(P, -1), feat_num(s.n_feat > 0 ? s.n_feat : 1, -1);
@@ -542,25 +483,19 @@ int ut_space_define(ut_ctx* c, int32_t P, const ut_param_desc* params, int32_t p
     s.cat_k = (kc + 127) / 128 * 128;
     std::vector<int32_t> num_feat = s.host_num_feat;
     if (num_feat.empty()) num_feat.push_back(0);
-    UT_HIP(c, ut::dmalloc((void**)&s.d_cat_ccol, sizeof(int32_t) * P));
-    UT_HIP(c, hipMemcpy(s.d_cat_ccol, ccol.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice));
-    UT_HIP(c, ut::dmalloc((void**)&s.d_num_feat, sizeof(int32_t) * num_feat.size()));
-    UT_HIP(c, hipMemcpy(s.d_num_feat, num_feat.data(), sizeof(int32_t) * num_feat.size(), hipMemcpyHostToDevice));
-    UT_HIP(c, ut::dmalloc((void**)&s.d_feat_num, sizeof(int32_t) * feat_num.size()));
-    UT_HIP(c, hipMemcpy(s.d_feat_num, feat_num.data(), sizeof(int32_t) * feat_num.size(), hipMemcpyHostToDevice));
+    UT_HIP(c, upload(s.d_cat_ccol, ccol));
+    UT_HIP(c, upload(s.d_num_feat, num_feat));
+    UT_HIP(c, upload(s.d_feat_num, feat_num));
   }
-  int rc = compile_hash_layout(c, names, primitive);
+  int rc = compile_hash_layout(c, s, names, primitive);
   if (rc) return rc;
+  c->space = std::move(s);
   c->has_space = true;
   // a new space invalidates the population (and its digest cache)
-  if (c->pop) {
-    ut::dfree(c->pop);
-    c->pop = nullptr;
-    c->npop = 0;
-    c->pop_cap = 0;
-  }
-  c->pop_dig_valid = false;
-  c->pop_aos_valid = false;
+  c->cur.pop.reset();
+  c->cur.npop = 0;
+  c->cur.pop_dig_valid = false;
+  c->cur.pop_aos_valid = false;
   for (auto& ps : c->pop_slots) ps.pop_dig_valid = ps.pop_aos_valid = false;
   return 0;
 }
@@ -583,17 +518,11 @@ int ut_space_columns(ut_ctx* c, int32_t* n_columns) {
 
 static int pop_alloc(ut_ctx* c, int64_t npop) {
   const int64_t need = npop * c->space.ncols;
-  if (c->pop && c->pop_cap >= need) {
-    c->npop = npop;
-    return 0;
+  if (!c->cur.pop.p || (int64_t)c->cur.pop.n < need) {
+    if (c->cur.pop.p) UT_HIP(c, ut::sync_all(c));
+    UT_HIP(c, c->cur.pop.alloc((size_t)need));
   }
-  if (c->pop) {
-    UT_HIP(c, ut::sync_all(c));
-    ut::dfree(c->pop);
-  }
-  UT_HIP(c, ut::dmalloc((void**)&c->pop, sizeof(double) * need));
-  c->pop_cap = need;
-  c->npop = npop;
+  c->cur.npop = npop;
   return 0;
 }
 
@@ -603,8 +532,8 @@ int ut_population_init(ut_ctx* c, int64_t npop, uint32_t round_) {
   UT_CHECK(c, npop >= 4 && npop < (int64_t)0xFFFFFFFF, UT_EINVAL, "population size must be in [4, 2^32)");
   int rc = pop_alloc(c, npop);
   if (rc) return rc;
-  c->pop_dig_valid = false;
-  c->pop_aos_valid = false;
+  c->cur.pop_dig_valid = false;
+  c->cur.pop_aos_valid = false;
   return launch_population_init(c, round_);
 }
 
@@ -615,9 +544,9 @@ int ut_population_set(ut_ctx* c, int64_t npop, const double* values, int64_t ld)
            "population_set: bad arguments");
   int rc = pop_alloc(c, npop);
   if (rc) return rc;
-  c->pop_dig_valid = false;
-  c->pop_aos_valid = false;
-  UT_HIP(c, hipMemcpy2DAsync(c->pop, sizeof(double) * npop, values, sizeof(double) * ld, sizeof(double) * npop,
+  c->cur.pop_dig_valid = false;
+  c->cur.pop_aos_valid = false;
+  UT_HIP(c, hipMemcpy2DAsync(c->cur.pop.p, sizeof(double) * npop, values, sizeof(double) * ld, sizeof(double) * npop,
                              c->space.ncols, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
@@ -628,39 +557,30 @@ int ut_population_select(ut_ctx* c, int32_t slot) {
   if (slot == c->pop_slot) return 0;
   if ((int32_t)c->pop_slots.size() <= std::max(slot, c->pop_slot))
     c->pop_slots.resize(std::max(slot, c->pop_slot) + 1);
-  // park the current slot, load the requested one (host-side pointer swap:
-  // launches already enqueued keep the pointers they were given)
-  ut_ctx::PopSlot& cur = c->pop_slots[c->pop_slot];
-  cur.pop = c->pop; cur.npop = c->npop; cur.pop_cap = c->pop_cap;
-  cur.pso_vel = c->pso_vel; cur.pso_best = c->pso_best; cur.pso_cap = c->pso_cap;
-  cur.pop_dig = c->pop_dig; cur.pop_dig_cap = c->pop_dig_cap; cur.pop_dig_valid = c->pop_dig_valid;
-  cur.pop_dig_lo = c->pop_dig_lo; cur.pop_dig_n = c->pop_dig_n;
-  cur.pop_aos = c->pop_aos; cur.pop_aos_cap = c->pop_aos_cap; cur.pop_aos_valid = c->pop_aos_valid;
-  const ut_ctx::PopSlot& nx = c->pop_slots[slot];
-  c->pop = nx.pop; c->npop = nx.npop; c->pop_cap = nx.pop_cap;
-  c->pso_vel = nx.pso_vel; c->pso_best = nx.pso_best; c->pso_cap = nx.pso_cap;
-  c->pop_dig = nx.pop_dig; c->pop_dig_cap = nx.pop_dig_cap; c->pop_dig_valid = nx.pop_dig_valid;
-  c->pop_dig_lo = nx.pop_dig_lo; c->pop_dig_n = nx.pop_dig_n;
-  c->pop_aos = nx.pop_aos; c->pop_aos_cap = nx.pop_aos_cap; c->pop_aos_valid = nx.pop_aos_valid;
+  // park the current slot (its entry is empty while it is selected), load the
+  // requested one: a host-side pointer swap, launches already enqueued keep
+  // the pointers they were given
+  std::swap(c->cur, c->pop_slots[c->pop_slot]);
+  std::swap(c->cur, c->pop_slots[slot]);
   c->pop_slot = slot;
   return 0;
 }
 
 int ut_population_get(ut_ctx* c, double* values, int64_t ld) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->pop != nullptr && values && ld >= c->npop, UT_EINVAL, "population_get: bad arguments");
-  UT_HIP(c, hipMemcpy2DAsync(values, sizeof(double) * ld, c->pop, sizeof(double) * c->npop,
-                             sizeof(double) * c->npop, c->space.ncols, hipMemcpyDeviceToDevice, c->stream));
+  UT_CHECK(c, c->cur.pop.p != nullptr && values && ld >= c->cur.npop, UT_EINVAL, "population_get: bad arguments");
+  UT_HIP(c, hipMemcpy2DAsync(values, sizeof(double) * ld, c->cur.pop.p, sizeof(double) * c->cur.npop,
+                             sizeof(double) * c->cur.npop, c->space.ncols, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
 static int check_de_params(ut_ctx* c, const ut_de_params* p, int64_t m, int64_t cand_base) {
   UT_CHECK(c, c->has_space, UT_ENOSPACE, "space not defined");
-  UT_CHECK(c, c->pop != nullptr, UT_EINVAL, "propose_de: population not initialised");
+  UT_CHECK(c, c->cur.pop.p != nullptr, UT_EINVAL, "propose_de: population not initialised");
   UT_CHECK(c, p && p->n_cross >= 0 && p->n_cross <= 4, UT_EINVAL, "propose_de: n_cross must be in [0, 4]");
   UT_CHECK(c, p->information_sharing >= 0 && p->information_sharing <= (1 << 20), UT_EINVAL,
            "propose_de: information_sharing must be in [0, 2^20]");
-  UT_CHECK(c, c->npop - 1 + (p->best ? (int64_t)p->information_sharing : 0) >= 3, UT_EINVAL,
+  UT_CHECK(c, c->cur.npop - 1 + (p->best ? (int64_t)p->information_sharing : 0) >= 3, UT_EINVAL,
            "propose_de: the donor pool (population - target + best copies) needs >= 3 entries");
   UT_CHECK(c, m >= 0 && cand_base >= 0, UT_EINVAL, "propose_de: bad arguments");
   return 0;
@@ -697,7 +617,7 @@ int ut_hash(ut_ctx* c, const double* values, int64_t ld, int64_t m, uint32_t* ou
 int ut_hash_de(ut_ctx* c, const double* values, int64_t ld, int64_t m, int64_t cand_base, uint32_t* out) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, c->has_space, UT_ENOSPACE, "space not defined");
-  UT_CHECK(c, c->pop != nullptr, UT_EINVAL, "hash_de: population not initialised");
+  UT_CHECK(c, c->cur.pop.p != nullptr, UT_EINVAL, "hash_de: population not initialised");
   UT_CHECK(c, m >= 0 && cand_base >= 0 && ((values && out) || m == 0) && ld >= m, UT_EINVAL, "hash_de: bad arguments");
   return launch_hash_de(c, values, ld, m, cand_base, out);
 }
@@ -719,36 +639,23 @@ int ut_history_add(ut_ctx* c, const uint32_t* dig, int64_t n) {
   if (!c) return UT_EINVAL;
   if (n <= 0) return 0;
   UT_CHECK(c, dig != nullptr, UT_EINVAL, "history_add: NULL digests");
-  if (!c->hist_keys || (c->hist_count + n) * 2 > c->hist_cap) {
+  if (!c->hist_keys.p || (c->hist_count + n) * 2 > c->hist_cap) {
     // grow: build the larger table beside the old one, re-insert the old
-    // entries, then swap.  Any failure before the swap frees what was obtained
-    // and leaves the old table (and hist_count) as it was.
+    // entries, then swap.  A failure before the swap leaves the old table (and
+    // hist_count) as it was; the locals free what was obtained.
     int64_t want = (c->hist_count + n) * 4;
     int64_t p2 = 1024;
     while (p2 < want) p2 <<= 1;
-    uint32_t* keys = nullptr;
-    uint32_t* state = nullptr;
-    if (int rc = ut::dalloc(c, (void**)&keys, sizeof(uint32_t) * 8 * p2)) return rc;
-    if (int rc = ut::dalloc(c, (void**)&state, sizeof(uint32_t) * p2)) {
-      ut::dfree(keys);
-      return rc;
-    }
-    int rc = 0;
-    hipError_t e = hipMemsetAsync(state, 0, sizeof(uint32_t) * p2, c->stream);
-    if (e == hipSuccess && c->hist_keys) {
-      rc = launch_hist_rehash(c, c->hist_keys, c->hist_state, c->hist_cap, keys, state, p2);
+    DevBuf<uint32_t> keys, state;
+    if (int rc = history_table(c, p2, keys, state)) return rc;
+    if (c->hist_keys.p) {
+      if (int rc = launch_hist_rehash(c, c->hist_keys.p, c->hist_state.p, c->hist_cap, keys.p, state.p, p2)) return rc;
       // the old table is read by the rehash, and maybe by a dedup on another stream of the context
-      if (rc == 0) e = ut::sync_all(c);
+      const hipError_t e = ut::sync_all(c);
+      if (e != hipSuccess) return set_err(c, UT_EHIP, std::string("history_add (grow): ") + hipGetErrorString(e));
     }
-    if (e != hipSuccess || rc) {
-      ut::dfree(keys);
-      ut::dfree(state);
-      return rc ? rc : set_err(c, UT_EHIP, std::string("history_add (grow): ") + hipGetErrorString(e));
-    }
-    ut::dfree(c->hist_keys);
-    ut::dfree(c->hist_state);
-    c->hist_keys = keys;
-    c->hist_state = state;
+    c->hist_keys.swap(keys);   // the old table goes with the locals
+    c->hist_state.swap(state);
     c->hist_cap = p2;
   }
   int rc = launch_hist_insert(c, dig, n);
@@ -761,12 +668,11 @@ int ut_history_add_host(ut_ctx* c, const uint32_t* dig, int64_t n) {
   if (!c) return UT_EINVAL;
   if (n <= 0) return 0;
   UT_CHECK(c, dig != nullptr, UT_EINVAL, "history_add_host: NULL digests");
-  uint32_t* tmp = nullptr;
-  UT_HIP(c, ut::dmalloc((void**)&tmp, sizeof(uint32_t) * 8 * n));
-  UT_HIP(c, hipMemcpyAsync(tmp, dig, sizeof(uint32_t) * 8 * n, hipMemcpyHostToDevice, c->stream));
-  int rc = ut_history_add(c, tmp, n);
-  UT_HIP(c, ut::sync_all(c));
-  ut::dfree(tmp);
+  DevBuf<uint32_t> tmp;
+  UT_HIP(c, tmp.alloc((size_t)8 * n));
+  UT_HIP(c, hipMemcpyAsync(tmp.p, dig, sizeof(uint32_t) * 8 * n, hipMemcpyHostToDevice, c->stream));
+  int rc = ut_history_add(c, tmp.p, n);
+  UT_HIP(c, ut::sync_all(c));   // the insert reads tmp
   return rc;
 }
 
@@ -933,7 +839,7 @@ int ut_gp_stats(ut_ctx* c, double* f_best, double* y_mean, double* y_std) {
   int rc = gp_wait_fit(c);
   if (rc) return rc;
   double st[4];
-  UT_HIP(c, hipMemcpyAsync(st, c->gp_stats, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+  UT_HIP(c, hipMemcpyAsync(st, c->gp_stats.p, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
   UT_HIP(c, ut::sync_all(c));
   if (f_best) *f_best = st[0];
   if (y_mean) *y_mean = st[1];
@@ -971,7 +877,7 @@ static int score_round_de_impl(ut_ctx* c, const ut_de_params* de, const ut_acq* 
                                ut_prune_stats* stats) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, c->has_space, UT_ENOSPACE, "space not defined");
-  UT_CHECK(c, c->pop != nullptr, UT_EINVAL, "score_round: population not initialised");
+  UT_CHECK(c, c->cur.pop.p != nullptr, UT_EINVAL, "score_round: population not initialised");
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "score_round: call ut_gp_fit first");
   UT_CHECK(c, c->gp_d == c->space.n_feat, UT_EINVAL, "score_round: GP feature width != space feature width");
   UT_CHECK(c, m >= 1 && de && acq, UT_EINVAL, "score_round: bad arguments");

@@ -117,7 +117,7 @@ int launch_hist_rehash(ut_ctx* c, const uint32_t* okeys, const uint32_t* ostate,
 
 int launch_hist_insert(ut_ctx* c, const uint32_t* dig, int64_t n) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_hist_insert, dim3(grid1(n, 256)), dim3(256), 0, c->stream, c->hist_keys, c->hist_state,
+  hipLaunchKernelGGL(k_hist_insert, dim3(grid1(n, 256)), dim3(256), 0, c->stream, c->hist_keys.p, c->hist_state.p,
                      c->hist_cap, dig, n);
   UT_LAUNCH_CHECK(c);
   return 0;
@@ -141,25 +141,18 @@ int launch_dedup(ut_ctx* c, const uint32_t* dig, int64_t m, uint8_t* dup) {
   int64_t cap = 1024;
   while (cap < 2 * m) cap <<= 1;
   UT_CHECK(c, m < (int64_t)0x7FFFFFFF, UT_EINVAL, "dedup batch must be < 2^31 candidates");
-  if (c->batch_cap < cap) {
-    if (c->batch_slots) {
-      UT_HIP(c, ut::sync_all(c));
-      ut::dfree(c->batch_slots);
-    }
-    // no table until the new one exists: a failed growth leaves batch_cap == 0,
-    // so the next call allocates again instead of using the freed array
-    c->batch_slots = nullptr;
-    c->batch_cap = 0;
-    int32_t* slots = nullptr;
-    if (int rc = ut::dalloc(c, (void**)&slots, cap * sizeof(int32_t))) return rc;
-    c->batch_slots = slots;
-    c->batch_cap = cap;
+  if ((int64_t)c->batch_slots.n < cap) {
+    if (c->batch_slots.p) UT_HIP(c, ut::sync_all(c));
+    // no table until the new one exists: a failed growth leaves none, so the
+    // next call allocates again
+    c->batch_slots.reset();
+    if (int rc = ut::dalloc(c, c->batch_slots, (size_t)cap)) return rc;
   }
-  UT_HIP(c, hipMemsetAsync(c->batch_slots, 0xFF, cap * sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(k_batch_insert, dim3(grid1(m, 256)), dim3(256), 0, c->stream, dig, m, c->batch_slots, cap);
+  UT_HIP(c, hipMemsetAsync(c->batch_slots.p, 0xFF, cap * sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_batch_insert, dim3(grid1(m, 256)), dim3(256), 0, c->stream, dig, m, c->batch_slots.p, cap);
   UT_LAUNCH_CHECK(c);
-  hipLaunchKernelGGL(k_dedup_mark, dim3(grid1(m, 256)), dim3(256), 0, c->stream, dig, m, c->batch_slots, cap,
-                     c->hist_keys, c->hist_state, c->hist_cap, dup);
+  hipLaunchKernelGGL(k_dedup_mark, dim3(grid1(m, 256)), dim3(256), 0, c->stream, dig, m, c->batch_slots.p, cap,
+                     c->hist_keys.p, c->hist_state.p, c->hist_cap, dup);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

@@ -73,15 +73,11 @@ extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_ho
   }
   UT_HIP(c, hipSetDevice(c->device));
   UT_HIP(c, ut::sync_all(c));
-  if (c->forest_nodes) ut::dfree(c->forest_nodes);
-  if (c->forest_roots) ut::dfree(c->forest_roots);
-  c->forest_nodes = nullptr;
-  c->forest_roots = nullptr;
   c->forest_trees = 0;
-  UT_HIP(c, ut::dmalloc((void**)&c->forest_nodes, sizeof(ut_tree_node) * n_nodes));
-  UT_HIP(c, ut::dmalloc((void**)&c->forest_roots, sizeof(int32_t) * n_trees));
-  UT_HIP(c, hipMemcpy(c->forest_nodes, nodes_host, sizeof(ut_tree_node) * n_nodes, hipMemcpyHostToDevice));
-  UT_HIP(c, hipMemcpy(c->forest_roots, roots_host, sizeof(int32_t) * n_trees, hipMemcpyHostToDevice));
+  UT_HIP(c, c->forest_nodes.alloc((size_t)n_nodes));
+  UT_HIP(c, c->forest_roots.alloc((size_t)n_trees));
+  UT_HIP(c, hipMemcpy(c->forest_nodes.p, nodes_host, sizeof(ut_tree_node) * n_nodes, hipMemcpyHostToDevice));
+  UT_HIP(c, hipMemcpy(c->forest_roots.p, roots_host, sizeof(int32_t) * n_trees, hipMemcpyHostToDevice));
   c->forest_trees = n_trees;
   c->forest_rule = rule;
   c->forest_max_feat = max_feat;
@@ -100,8 +96,8 @@ extern "C" int ut_forest_predict(ut_ctx* c, const double* features, int64_t ld, 
            "forest_predict: the ensemble splits on feature " + std::to_string(c->forest_max_feat) +
                " but n_features is " + std::to_string(n_features));
   if (m == 0) return 0;
-  hipLaunchKernelGGL(ut::k_forest, dim3(ut::grid1(m, 256)), dim3(256), 0, c->stream, c->forest_nodes,
-                     c->forest_roots, c->forest_trees, c->forest_rule, c->forest_base, c->forest_scale,
+  hipLaunchKernelGGL(ut::k_forest, dim3(ut::grid1(m, 256)), dim3(256), 0, c->stream, c->forest_nodes.p,
+                     c->forest_roots.p, c->forest_trees, c->forest_rule, c->forest_base, c->forest_scale,
                      c->forest_div, n_features, features, ld, m, dup, sign, pred, score);
   UT_LAUNCH_CHECK(c);
   return 0;

@@ -806,48 +806,39 @@ __global__ void k_gp_fix_i8(int64_t nf, const int64_t* __restrict__ idx, int32_t
 // ---------------------------------------------------------------------------
 static void launch_chol_diag(ut_ctx* c, int32_t npad, int32_t kb) {
   hipLaunchKernelGGL(c->chol_merged ? k_chol_diag<true> : k_chol_diag<false>, dim3(1), dim3(256), 0, c->stream,
-                     c->gp_K, c->gp_Linv, npad, kb, c->gp_flag);
+                     c->gp_K.p, c->gp_Linv.p, npad, kb, c->gp_flag.p);
 }
 
 static int gp_alloc(ut_ctx* c, int32_t npad_need, int32_t d) {
-  if (c->gp_cap_n >= npad_need && c->gp_d == d && c->gp_Xs) return 0;
+  if (c->gp_cap_n >= npad_need && c->gp_d == d) return 0;
   // room for a growing training set (the tuning loop adds a few rows per fit):
   // a new padded size then reuses the buffers instead of freeing and
   // allocating ~5 n^2 doubles behind a device-wide sync (2.5-10 ms per 128
   // rows in the C5 loop).  Every kernel indexes with the fit's own npad.
-  const int64_t npad = ((npad_need + npad_need / 4 + NPAD - 1) / NPAD) * NPAD;
-  if (c->gp_Xs_f) {
-    UT_HIP(c, ut::sync_all(c));
-    ut::dfree(c->gp_Xs_f); ut::dfree(c->gp_LinvT); ut::dfree(c->gp_LinvT_f); ut::dfree(c->gp_T); ut::dfree(c->gp_ctr);
-    ut::dfree(c->gp_XsT);
-    c->gp_Xs_f = nullptr; c->gp_LinvT = nullptr; c->gp_LinvT_f = nullptr; c->gp_T = nullptr; c->gp_ctr = nullptr;
-    c->gp_XsT = nullptr;
-  }
-  if (c->gp_Xs) {
-    UT_HIP(c, ut::sync_all(c));
-    ut::dfree(c->gp_Xs); ut::dfree(c->gp_xnorm); ut::dfree(c->gp_K); ut::dfree(c->gp_Linv);
-    ut::dfree(c->gp_y); ut::dfree(c->gp_tmp); ut::dfree(c->gp_alpha); ut::dfree(c->gp_beta); ut::dfree(c->gp_inv_ell);
-    ut::dfree(c->gp_stats); ut::dfree(c->gp_flag);
-  }
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_Xs, sizeof(double) * npad * d));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_xnorm, sizeof(double) * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_K, sizeof(double) * npad * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_Linv, sizeof(double) * npad * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_y, sizeof(double) * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_tmp, sizeof(double) * npad * (d + 1)));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_alpha, sizeof(double) * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_beta, sizeof(double) * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_inv_ell, sizeof(double) * d));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_stats, sizeof(double) * 4));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_flag, sizeof(int32_t)));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_T, sizeof(double) * npad * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_Xs_f, sizeof(float) * npad * d));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_LinvT, sizeof(double) * npad * npad));
+  const size_t npad = (size_t)((npad_need + npad_need / 4 + NPAD - 1) / NPAD) * NPAD;
+  UT_HIP(c, ut::sync_all(c));   // earlier rounds may still read the buffers replaced here
+  // no capacity until every buffer exists: after a failure part-way the next
+  // call allocates them all again
+  c->gp_cap_n = 0;
+  UT_HIP(c, c->gp_Xs.alloc(npad * d));
+  UT_HIP(c, c->gp_xnorm.alloc(npad));
+  UT_HIP(c, c->gp_K.alloc(npad * npad));
+  UT_HIP(c, c->gp_Linv.alloc(npad * npad));
+  UT_HIP(c, c->gp_y.alloc(npad));
+  UT_HIP(c, c->gp_tmp.alloc(npad * (d + 1)));
+  UT_HIP(c, c->gp_alpha.alloc(npad));
+  UT_HIP(c, c->gp_beta.alloc(npad));
+  UT_HIP(c, c->gp_inv_ell.alloc(d));
+  UT_HIP(c, c->gp_stats.alloc(4));
+  UT_HIP(c, c->gp_flag.alloc(1));
+  UT_HIP(c, c->gp_T.alloc(npad * npad));
+  UT_HIP(c, c->gp_Xs_f.alloc(npad * d));
+  UT_HIP(c, c->gp_LinvT.alloc(npad * npad));
   // fp32: (L^-1)^T; h3: the blocked fp16 hi / lo planes, rows padded to 256
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_LinvT_f, sizeof(float) * (((npad + 255) / 256) * 256) * npad));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_ctr, sizeof(int32_t) * 32));
-  UT_HIP(c, ut::dmalloc((void**)&c->gp_XsT, sizeof(double) * npad * kstar_dpad(d)));
-  c->gp_cap_n = npad;
+  UT_HIP(c, c->gp_LinvT_f.alloc((((npad + 255) / 256) * 256) * npad));
+  UT_HIP(c, c->gp_ctr.alloc(32));
+  UT_HIP(c, c->gp_XsT.alloc(npad * kstar_dpad(d)));
+  c->gp_cap_n = (int64_t)npad;
   c->gp_d = d;
   return 0;
 }
@@ -887,31 +878,31 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
   double* hX = c->fit_host;
   double* hy = hX + (size_t)n * d;
   double* hinv = hy + n;
-  double* dX = c->gp_tmp;           // [n][d] staging (gp_tmp holds npad*(d+1))
-  double* dy = c->gp_tmp + (int64_t)npad * d;
+  double* dX = c->gp_tmp.p;           // [n][d] staging (gp_tmp holds npad*(d+1))
+  double* dy = c->gp_tmp.p + (int64_t)npad * d;
   if (part == 0) {
-    UT_HIP(c, hipMemcpyAsync(c->gp_inv_ell, hinv, sizeof(double) * d, hipMemcpyHostToDevice, c->stream));
+    UT_HIP(c, hipMemcpyAsync(c->gp_inv_ell.p, hinv, sizeof(double) * d, hipMemcpyHostToDevice, c->stream));
     UT_HIP(c, hipMemcpyAsync(dX + (size_t)xr0 * d, hX + (size_t)xr0 * d, sizeof(double) * (size_t)(n - xr0) * d,
                              hipMemcpyHostToDevice, c->stream));
     UT_HIP(c, hipMemcpyAsync(dy, hy, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    if (!app) UT_HIP(c, hipMemsetAsync(c->gp_flag, 0, sizeof(int32_t), c->stream));
+    if (!app) UT_HIP(c, hipMemsetAsync(c->gp_flag.p, 0, sizeof(int32_t), c->stream));
     hipLaunchKernelGGL(k_gp_prep_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, dX, n, npad, d,
-                       c->gp_inv_ell, c->gp_Xs, c->gp_xnorm);
+                       c->gp_inv_ell.p, c->gp_Xs.p, c->gp_xnorm.p);
     // the candidate side of K* needs only the scaled inputs: fp64 scoring starts
     // its K* here while the factorisation below is still running
-    if ((rc = launch_xs_t(c, c->gp_Xs, npad, d, kstar_dpad(d), c->gp_XsT))) return rc;
+    if ((rc = launch_xs_t(c, c->gp_Xs.p, npad, d, kstar_dpad(d), c->gp_XsT.p))) return rc;
     if (c->cat_on) {
-      hipLaunchKernelGGL(k_gp_num_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, c->gp_Xs, npad, d,
-                         sp.d_num_feat, sp.n_num, dpn, c->gp_XsT_num.p, c->gp_xnorm_num.p);
+      hipLaunchKernelGGL(k_gp_num_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, c->gp_Xs.p, npad, d,
+                         sp.d_num_feat.p, sp.n_num, dpn, c->gp_XsT_num.p, c->gp_xnorm_num.p);
       UT_HIP(c, hipMemsetAsync(c->gp_acat.p, 0, (size_t)sp.cat_k * npad, c->stream));
-      hipLaunchKernelGGL(k_gp_cat_train, dim3(grid1(n, 256)), dim3(256), 0, c->stream, sp.d_params, sp.P, sp.d_cat_ccol,
+      hipLaunchKernelGGL(k_gp_cat_train, dim3(grid1(n, 256)), dim3(256), 0, c->stream, sp.d_params.p, sp.P, sp.d_cat_ccol.p,
                          dX, n, d, npad, c->gp_acat.p);
       UT_LAUNCH_CHECK(c);
     }
     // precision 8: K*'s training operand as int8 digit planes (gp_kq.hip;
     // numeric fits only, gp_score_impl)
     if (c->gp_prec == 8 && c->kstar_q && !c->cat_on &&
-        (rc = launch_split_x8(c, c->gp_XsT, kstar_dpad(d), npad)))
+        (rc = launch_split_x8(c, c->gp_XsT.p, kstar_dpad(d), npad)))
       return rc;
     return 0;
   }
@@ -921,41 +912,41 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
     // block rows b0 .. b1 hold the new rows (b0 may also hold old ones: it is
     // recomputed whole)
     const int32_t b0 = n0 / NB, b1 = (n - 1) / NB;
-    hipLaunchKernelGGL(k_gp_kmat, dim3(b1 + 1, b1 - b0 + 1), dim3(256), 0, c->stream, c->gp_Xs, c->gp_xnorm, n,
-                       npad, d, sf2, diag, c->gp_K, b0);
-    hipLaunchKernelGGL(k_gp_ystats, dim3(1), dim3(256), 0, c->stream, dy, n, npad, c->gp_y, c->gp_stats);
-    double* Et = c->gp_T + (int64_t)NB * npad;
+    hipLaunchKernelGGL(k_gp_kmat, dim3(b1 + 1, b1 - b0 + 1), dim3(256), 0, c->stream, c->gp_Xs.p, c->gp_xnorm.p, n,
+                       npad, d, sf2, diag, c->gp_K.p, b0);
+    hipLaunchKernelGGL(k_gp_ystats, dim3(1), dim3(256), 0, c->stream, dy, n, npad, c->gp_y.p, c->gp_stats.p);
+    double* Et = c->gp_T.p + (int64_t)NB * npad;
     for (int32_t b = b0; b <= b1; ++b) {
       const int32_t maxq = (b * NB + APP_KC - 1) / APP_KC;
       if (b > 0) {
         double* W = c->app_ws.p;
-        hipLaunchKernelGGL(k_app_part<0>, dim3(maxq, b), dim3(256), 0, c->stream, c->gp_Linv, c->gp_LinvT,
-                           c->gp_K, c->gp_T, npad, b, maxq, W);
-        hipLaunchKernelGGL(k_app_red<0>, dim3(b), dim3(256), 0, c->stream, c->gp_Linv, c->gp_LinvT, c->gp_K,
-                           c->gp_T, npad, b, maxq, W, Et);
-        hipLaunchKernelGGL(k_app_part<1>, dim3(maxq, 1), dim3(256), 0, c->stream, c->gp_Linv, c->gp_LinvT,
-                           c->gp_K, c->gp_T, npad, b, maxq, W);
-        hipLaunchKernelGGL(k_app_red<1>, dim3(1), dim3(256), 0, c->stream, c->gp_Linv, c->gp_LinvT, c->gp_K,
-                           c->gp_T, npad, b, maxq, W, Et);
+        hipLaunchKernelGGL(k_app_part<0>, dim3(maxq, b), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p,
+                           c->gp_K.p, c->gp_T.p, npad, b, maxq, W);
+        hipLaunchKernelGGL(k_app_red<0>, dim3(b), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p, c->gp_K.p,
+                           c->gp_T.p, npad, b, maxq, W, Et);
+        hipLaunchKernelGGL(k_app_part<1>, dim3(maxq, 1), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p,
+                           c->gp_K.p, c->gp_T.p, npad, b, maxq, W);
+        hipLaunchKernelGGL(k_app_red<1>, dim3(1), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p, c->gp_K.p,
+                           c->gp_T.p, npad, b, maxq, W, Et);
       }
       launch_chol_diag(c, npad, b);
       if (b > 0) {
         double* W = c->app_ws.p;
-        hipLaunchKernelGGL(k_app_part<2>, dim3(maxq, b), dim3(256), 0, c->stream, c->gp_Linv, c->gp_LinvT,
-                           c->gp_K, c->gp_T, npad, b, maxq, W);
-        hipLaunchKernelGGL(k_app_red<2>, dim3(b), dim3(256), 0, c->stream, c->gp_Linv, c->gp_LinvT, c->gp_K,
-                           c->gp_T, npad, b, maxq, W, Et);
+        hipLaunchKernelGGL(k_app_part<2>, dim3(maxq, b), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p,
+                           c->gp_K.p, c->gp_T.p, npad, b, maxq, W);
+        hipLaunchKernelGGL(k_app_red<2>, dim3(b), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p, c->gp_K.p,
+                           c->gp_T.p, npad, b, maxq, W, Et);
       }
-      hipLaunchKernelGGL(k_app_c, dim3(b + 1), dim3(256), 0, c->stream, c->gp_Linv, c->gp_LinvT, Et, npad, b);
+      hipLaunchKernelGGL(k_app_c, dim3(b + 1), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p, Et, npad, b);
     }
     UT_LAUNCH_CHECK(c);
   } else {
-    hipLaunchKernelGGL(k_gp_kmat, dim3(npad / 64, npad / 64), dim3(256), 0, c->stream, c->gp_Xs,
-                       c->gp_xnorm, n, npad, d, sf2, diag, c->gp_K, 0);
-    hipLaunchKernelGGL(k_gp_ystats, dim3(1), dim3(256), 0, c->stream, dy, n, npad, c->gp_y, c->gp_stats);
+    hipLaunchKernelGGL(k_gp_kmat, dim3(npad / 64, npad / 64), dim3(256), 0, c->stream, c->gp_Xs.p,
+                       c->gp_xnorm.p, n, npad, d, sf2, diag, c->gp_K.p, 0);
+    hipLaunchKernelGGL(k_gp_ystats, dim3(1), dim3(256), 0, c->stream, dy, n, npad, c->gp_y.p, c->gp_stats.p);
     UT_LAUNCH_CHECK(c);
     const int32_t nb = npad / NB;
-    UT_HIP(c, hipMemsetAsync(c->gp_Linv, 0, sizeof(double) * npad * npad, c->stream));
+    UT_HIP(c, hipMemsetAsync(c->gp_Linv.p, 0, sizeof(double) * npad * npad, c->stream));
     const bool fuse = c->chol_fuse > 0 || (c->chol_fuse < 0 && npad >= 2048);
     for (int32_t kb = 0; kb < nb; ++kb) {
       // (fused: diagonal blocks after the first come from the previous update)
@@ -963,12 +954,12 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
         launch_chol_diag(c, npad, kb);
       const int32_t T = nb - kb - 1;
       if (T > 0) {
-        hipLaunchKernelGGL(k_chol_rows, dim3(T), dim3(256), 0, c->stream, c->gp_K, c->gp_Linv, npad, kb);
+        hipLaunchKernelGGL(k_chol_rows, dim3(T), dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, npad, kb);
         if (fuse)
           hipLaunchKernelGGL(c->chol_merged ? k_chol_update_diag<true> : k_chol_update_diag<false>,
-                             dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->gp_K, c->gp_Linv, npad, kb, c->gp_flag);
+                             dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, npad, kb, c->gp_flag.p);
         else
-          hipLaunchKernelGGL(k_chol_update, dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->gp_K, npad, kb);
+          hipLaunchKernelGGL(k_chol_update, dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->gp_K.p, npad, kb);
       }
     }
     UT_LAUNCH_CHECK(c);
@@ -979,20 +970,20 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
         // k_trinv_big's tiles: every pair's sizes are multiples of 128
         UT_CHECK(c, npad % TRB_BM == 0 && lv % TRB_BM == 0, UT_EINVAL, "gp_fit: npad not a multiple of 128");
         const dim3 gb(lv / TRB_BM, lv / TRB_BM, pairs);
-        hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, c->gp_K, c->gp_Linv, c->gp_T, npad, lv, 0);
-        hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, c->gp_K, c->gp_Linv, c->gp_T, npad, lv, 1);
+        hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 0);
+        hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 1);
         continue;
       }
       const dim3 grid(lv / 64, lv / 64, pairs);
-      hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, c->gp_K, c->gp_Linv, c->gp_T, npad, lv, 0);
-      hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, c->gp_K, c->gp_Linv, c->gp_T, npad, lv, 1);
+      hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 0);
+      hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 1);
     }
     UT_LAUNCH_CHECK(c);
   }
-  hipLaunchKernelGGL(k_lower_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_Linv, npad, c->gp_y,
-                     c->gp_beta);
+  hipLaunchKernelGGL(k_lower_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_Linv.p, npad, c->gp_y.p,
+                     c->gp_beta.p);
   UT_LAUNCH_CHECK(c);
-  if (c->gp_prec == 32 && (rc = launch_to_f32(c, c->gp_Xs, c->gp_Xs_f, (int64_t)npad * d))) return rc;
+  if (c->gp_prec == 32 && (rc = launch_to_f32(c, c->gp_Xs.p, c->gp_Xs_f.p, (int64_t)npad * d))) return rc;
   // precision 8 scores from the digit planes of L^-1 and beta alone: a refit
   // leaves (L^-1)^T and alpha = L^-T beta to the paths that read them (the fp64
   // recompute, the next append: gp_ensure_linvt), off the chain the variance
@@ -1004,13 +995,13 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
   }
   // (an append wrote its rows of LinvT itself)
   if ((!app || c->gp_prec == 32) &&
-      (rc = launch_transpose(c, c->gp_Linv, npad, c->gp_LinvT, c->gp_prec == 32 ? c->gp_LinvT_f : nullptr)))
+      (rc = launch_transpose(c, c->gp_Linv.p, npad, c->gp_LinvT.p, c->gp_prec == 32 ? c->gp_LinvT_f.p : nullptr)))
     return rc;
-  hipLaunchKernelGGL(k_upper_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_LinvT, npad, c->gp_beta,
-                     c->gp_alpha);
+  hipLaunchKernelGGL(k_upper_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_LinvT.p, npad, c->gp_beta.p,
+                     c->gp_alpha.p);
   UT_LAUNCH_CHECK(c);
   c->gp_linvt_stale = false;
-  if (c->gp_prec == 16 && (rc = launch_split_h3(c, c->gp_Linv, npad, reinterpret_cast<_Float16*>(c->gp_LinvT_f))))
+  if (c->gp_prec == 16 && (rc = launch_split_h3(c, c->gp_Linv.p, npad, reinterpret_cast<_Float16*>(c->gp_LinvT_f.p))))
     return rc;
   if (c->gp_prec == 8 && (rc = launch_split_i8(c, n, npad))) return rc;
   return 0;
@@ -1021,9 +1012,9 @@ int gp_ensure_linvt(ut_ctx* c) {
   if (!c->gp_linvt_stale) return 0;
   const int32_t npad = c->gp_npad_fit;
   int rc;
-  if ((rc = launch_transpose(c, c->gp_Linv, npad, c->gp_LinvT, nullptr))) return rc;
-  hipLaunchKernelGGL(k_upper_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_LinvT, npad, c->gp_beta,
-                     c->gp_alpha);
+  if ((rc = launch_transpose(c, c->gp_Linv.p, npad, c->gp_LinvT.p, nullptr))) return rc;
+  hipLaunchKernelGGL(k_upper_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_LinvT.p, npad, c->gp_beta.p,
+                     c->gp_alpha.p);
   UT_LAUNCH_CHECK(c);
   c->gp_linvt_stale = false;
   return 0;
@@ -1075,7 +1066,7 @@ int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32
   // refactoring (k_app_*).  y is restandardised in full either way.
   const int32_t n0 = c->gp_n;
   bool app = false;
-  if (c->fit_append && c->gp_ready && c->gp_Xs && n > n0 && npad == c->gp_npad_fit && d == c->gp_d &&
+  if (c->fit_append && c->gp_ready && c->gp_Xs.p && n > n0 && npad == c->gp_npad_fit && d == c->gp_d &&
       c->gp_prec == c->gp_fit_prec && c->gp_sf2 == h->sigma_f2 && c->gp_diag_fit == h->sigma_n2 + h->jitter) {
     const double* oinv = c->fit_host + (size_t)n0 * d + n0;
     app = std::memcmp(c->fit_host, X, sizeof(double) * n0 * d) == 0;
@@ -1085,7 +1076,7 @@ int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32
     }
     if (app) {
       if (!c->flag_host) UT_HIP(c, hipHostMalloc((void**)&c->flag_host, sizeof(int32_t), hipHostMallocDefault));
-      UT_HIP(c, hipMemcpyAsync(c->flag_host, c->gp_flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->fit_stream));
+      UT_HIP(c, hipMemcpyAsync(c->flag_host, c->gp_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->fit_stream));
       UT_HIP(c, hipStreamSynchronize(c->fit_stream));
       app = *c->flag_host == 0;
     }
@@ -1224,7 +1215,7 @@ int gp_wait_fit(ut_ctx* c) {
   // asynchronous copy and that stream's sync: ~10 us once the fit is done,
   // where a blocking hipMemcpy took ~1 ms per call in the C5 loop)
   if (!c->flag_host) UT_HIP(c, hipHostMalloc((void**)&c->flag_host, sizeof(int32_t), hipHostMallocDefault));
-  UT_HIP(c, hipMemcpyAsync(c->flag_host, c->gp_flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->fit_stream));
+  UT_HIP(c, hipMemcpyAsync(c->flag_host, c->gp_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->fit_stream));
   UT_HIP(c, hipStreamSynchronize(c->fit_stream));
   const int32_t flag = *c->flag_host;
   if (flag != 0) {
@@ -1321,10 +1312,10 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
     // hash its MFMAs issue under the hash's integer VALU work (C2 ~1 % per
     // round).  Categorical fits keep the fp64-MFMA K* (C3 HPL-64: K* 43 against
     // 28.5 ms, the round 288 against 270; C4 no better; scripts/r06_lines.sh)
-    if ((rc = launch_gemm_kstar_q(c, true, c->gp_XsT, npad, c->ucand.p, dpad, m, c->kst.p, ldk, nullptr, -1, nullptr,
+    if ((rc = launch_gemm_kstar_q(c, true, c->gp_XsT.p, npad, c->ucand.p, dpad, m, c->kst.p, ldk, nullptr, -1, nullptr,
                                   nullptr, KstarCat(), nullptr, c->u8, c->scol)))
       return rc;
-  } else if ((rc = launch_gemm_kstar(c, prec, cat ? c->gp_XsT_num.p : c->gp_XsT, npad, c->ucand.p, dpad, m, c->kst.p,
+  } else if ((rc = launch_gemm_kstar(c, prec, cat ? c->gp_XsT_num.p : c->gp_XsT.p, npad, c->ucand.p, dpad, m, c->kst.p,
                                      ldk, kmu ? c->mu_part.p : nullptr, -1, nullptr, nullptr,
                                      cat ? kstar_cat(c, c->bcat.p) : KstarCat(), cat ? c->gp_xnorm_num.p : nullptr))) {
     return rc;
@@ -1344,8 +1335,8 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
     if ((rc = launch_gemm_var_i8(c, npad, reinterpret_cast<const int8_t*>(c->kst.p), ldk, m, c->var_part.p,
                                  c->mu_part.p)))
       return rc;
-  } else if ((rc = launch_gemm_var(c, prec, fp32 ? (const void*)c->gp_LinvT_f : (const void*)c->gp_LinvT, npad,
-                                   c->kst.p, ldk, npad, m, c->var_part.p, fp32 ? nullptr : c->gp_beta,
+  } else if ((rc = launch_gemm_var(c, prec, fp32 ? (const void*)c->gp_LinvT_f.p : (const void*)c->gp_LinvT.p, npad,
+                                   c->kst.p, ldk, npad, m, c->var_part.p, fp32 ? nullptr : c->gp_beta.p,
                                    fp32 ? nullptr : c->mu_part.p))) {
     return rc;
   }
@@ -1355,7 +1346,7 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
     // the bound test, then the fp64 recompute of the candidates it did not clear
     UT_HIP(c, hipMemsetAsync(c->pr_count.p, 0, sizeof(int64_t), c->stream));
     hipLaunchKernelGGL(k_gp_finalize_i8, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, 2 * RT, 2 * RT, c->mu_part.p,
-                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats, c->gp_flag, acq->kind, acq->xi, acq->kappa, dup,
+                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
                        mu, var, score, c->gp_i8rs.p + 2 * npad, c->i8_tol, n, c->pr_idx.p,
                        reinterpret_cast<unsigned long long*>(c->pr_count.p));
     UT_LAUNCH_CHECK(c);
@@ -1370,26 +1361,26 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
       // fp64 contraction, with the mean from its epilogue
       c->i8_recomputed = -1;
       if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldk))) return rc;
-      if ((rc = launch_gemm_kstar(c, 64, cat ? c->gp_XsT_num.p : c->gp_XsT, npad, c->ucand.p, dpad, m, c->kst.p, ldk,
+      if ((rc = launch_gemm_kstar(c, 64, cat ? c->gp_XsT_num.p : c->gp_XsT.p, npad, c->ucand.p, dpad, m, c->kst.p, ldk,
                                   nullptr, -1, nullptr, nullptr, cat ? kstar_cat(c, c->bcat.p) : KstarCat(),
                                   cat ? c->gp_xnorm_num.p : nullptr)))
         return rc;
-      if ((rc = launch_gemm_var(c, 64, c->gp_LinvT, npad, c->kst.p, ldk, npad, m, c->var_part.p, c->gp_beta,
+      if ((rc = launch_gemm_var(c, 64, c->gp_LinvT.p, npad, c->kst.p, ldk, npad, m, c->var_part.p, c->gp_beta.p,
                                 c->pr_mpart.p)))
         return rc;
       hipLaunchKernelGGL(k_gp_finalize, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, RT, c->pr_mpart.p,
-                         c->var_part.p, ldk, c->gp_sf2, c->gp_stats, c->gp_flag, acq->kind, acq->xi, acq->kappa, dup,
+                         c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
                          mu, var, score);
       UT_LAUNCH_CHECK(c);
     } else if (nf > 0) {
       const int64_t ldf = (nf + VAR_BN - 1) / VAR_BN * VAR_BN;
       if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldf))) return rc;
       if ((rc = gather_kstar_cols(c, cat, dpad, ldk, c->pr_idx.p, 0, nf, ldf))) return rc;
-      if ((rc = launch_gemm_var(c, 64, c->gp_LinvT, npad, c->pr_kst.p, ldf, npad, nf, c->pr_vpart.p, c->gp_beta,
+      if ((rc = launch_gemm_var(c, 64, c->gp_LinvT.p, npad, c->pr_kst.p, ldf, npad, nf, c->pr_vpart.p, c->gp_beta.p,
                                 c->pr_mpart.p)))
         return rc;
       hipLaunchKernelGGL(k_gp_fix_i8, dim3(grid1(nf, 256)), dim3(256), 0, c->stream, nf, c->pr_idx.p, RT,
-                         c->pr_mpart.p, c->pr_vpart.p, ldf, c->gp_sf2, c->gp_stats, acq->kind, acq->xi, acq->kappa,
+                         c->pr_mpart.p, c->pr_vpart.p, ldf, c->gp_sf2, c->gp_stats.p, acq->kind, acq->xi, acq->kappa,
                          dup, mu, var, score);
       UT_LAUNCH_CHECK(c);
     }
@@ -1399,7 +1390,7 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
   // h3's variance partials come per 256-row tile
   const int32_t RTv = prec == 16 ? (npad + 255) / 256 : RT;
   hipLaunchKernelGGL(k_gp_finalize, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, RTv, c->mu_part.p,
-                     c->var_part.p, ldk, c->gp_sf2, c->gp_stats, c->gp_flag, acq->kind, acq->xi, acq->kappa, dup,
+                     c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
                      mu, var, score);
   UT_LAUNCH_CHECK(c);
   mark(c, "finalize");
@@ -1689,7 +1680,7 @@ static int gather_kstar_cols(ut_ctx* c, bool cat, int32_t dpad, int64_t ldk, con
                              int64_t nc, int64_t ldc, double* mu_part) {
   const int32_t npad = ((c->gp_n + NPAD - 1) / NPAD) * NPAD;
   const int32_t RT = npad / NPAD;
-  const double* XsT = cat ? c->gp_XsT_num.p : c->gp_XsT;
+  const double* XsT = cat ? c->gp_XsT_num.p : c->gp_XsT.p;
   const double* xn = cat ? c->gp_xnorm_num.p : nullptr;
   int r2;
   if ((r2 = ensure(c, c->pr_kst, (size_t)npad * ldc))) return r2;
@@ -1755,7 +1746,7 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   if (f32 && (rc = ensure(c, c->pr_sa, (size_t)RT * ldk))) return rc;
   if (f32 && (rc = ensure(c, c->pr_gmu, (size_t)RT * (ldk + 1024)))) return rc;   // survivors / threshold set
   if ((rc = ensure(c, c->pr_exact, (size_t)ldk))) return rc;
-  const double* LinvT = c->gp_LinvT;
+  const double* LinvT = c->gp_LinvT.p;
   // 1. K* with the mean in its epilogue, 2. the first R row tiles of L^-1 K*^T
   if (feat) {
     if (cat) {
@@ -1768,7 +1759,7 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   }
   if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));   // K* takes mu = k* . alpha
   mark(c, "fit_wait");   // (the wait is not K* time)
-  const double* XsT = cat ? c->gp_XsT_num.p : c->gp_XsT;
+  const double* XsT = cat ? c->gp_XsT_num.p : c->gp_XsT.p;
   const double* xn = cat ? c->gp_xnorm_num.p : nullptr;
   // K* stores only the bound rows; the mean sums every row.  The few
   // candidates that need every row (threshold set, survivors) get their K*
@@ -1777,7 +1768,7 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   if (f32) {
     // the bound rows through the fp64 kernel (tiles < R), every other tile
     // through k_gp_kstar_f32c on f32 copies of the operands (Xs^T once per fit)
-    const double* xnn = xn ? xn : c->gp_xnorm;
+    const double* xnn = xn ? xn : c->gp_xnorm.p;
     // the f32 copy depends on the operand as well as the fit: the numeric
     // block (categorical mode, cat_dpad rows, gp_xnorm_num) or every feature
     // (kstar_dpad rows, gp_xnorm) -- within one categorical fit the feature
@@ -1819,28 +1810,28 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
     return 0;
   };
   if (!c->pr_f2_valid) {
-    if ((rc = sumsq(false, c->gp_Linv, (int64_t)npad * npad, c->pr_f2.p))) return rc;
+    if ((rc = sumsq(false, c->gp_Linv.p, (int64_t)npad * npad, c->pr_f2.p))) return rc;
     c->pr_f2_valid = true;
   }
   if (f32 && !c->pr_ab_valid) {   // the f32 bound's per-fit constants
     double* cst = c->pr_f2.p + 1 + SQ_BLOCKS;
-    if ((rc = sumsq(true, c->gp_alpha, n, cst))) return rc;
+    if ((rc = sumsq(true, c->gp_alpha.p, n, cst))) return rc;
     c->pr_ab_valid = true;
   }
   mark(c, "kstar");
-  if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->kst.p, ldk, R * NPAD, m, c->var_part.p, c->gp_beta,
+  if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->kst.p, ldk, R * NPAD, m, c->var_part.p, c->gp_beta.p,
                             c->pr_mpart.p)))
     return rc;
   mark(c, "bound");
   if (dup_ready) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));   // the dup mask (side stream)
   if (f32)
     hipLaunchKernelGGL(k_prune_bound32, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, c->mu_part.p,
-                       c->pr_sa.p, c->pr_k2.p, R, c->var_part.p, ldk, c->gp_sf2, n, c->gp_stats, c->gp_flag,
+                       c->pr_sa.p, c->pr_k2.p, R, c->var_part.p, ldk, c->gp_sf2, n, c->gp_stats.p, c->gp_flag.p,
                        acq->kind, acq->xi, acq->kappa, dup, c->pr_f2.p, c->pr_ub.p, c->pr_exact.p,
                        dpad + (cat ? 1 : 0), cat ? fabs(c->cat_c0) : 0.0, c->cnorm.p);
   else
     hipLaunchKernelGGL(k_prune_bound, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, c->mu_part.p, R,
-                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats, c->gp_flag, acq->kind, acq->xi, acq->kappa, dup,
+                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
                        c->pr_mu.p, c->pr_ub.p, c->pr_k2.p, c->pr_f2.p, c->pr_exact.p);
   UT_LAUNCH_CHECK(c);
   // 3. threshold: exact scores of the best 1024 bounds, tau = their k-th best
@@ -1856,12 +1847,12 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   };
   const int64_t ldt = ((int64_t)kp + VAR_BN - 1) / VAR_BN * VAR_BN;
   if ((rc = recompute_cols(tset, cand_base, kp, ldt))) return rc;
-  if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->pr_kst.p, ldt, npad, kp, c->pr_vpart.p, c->gp_beta,
+  if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->pr_kst.p, ldt, npad, kp, c->pr_vpart.p, c->gp_beta.p,
                             c->pr_mpart.p)))
     return rc;
   const double* mu_full = f32 ? nullptr : c->pr_mu.p;
   hipLaunchKernelGGL(k_prune_exact, dim3(grid1(kp, 256)), dim3(256), 0, c->stream, (int64_t)kp, tset, cand_base, RT,
-                     c->pr_vpart.p, ldt, mu_full, c->gp_sf2, c->gp_stats, c->gp_flag, acq->kind, acq->xi,
+                     c->pr_vpart.p, ldt, mu_full, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi,
                      acq->kappa, tex, nullptr, gmu);
   UT_LAUNCH_CHECK(c);
   int64_t* tk_i = out_idx;   // the caller's [k] outputs hold tau's top-k for now
@@ -1886,11 +1877,11 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
     if ((rc = launch_gemm_kstar(c, 64, XsT, npad, c->ucand.p, dpad, m, c->kst.p, ldk, c->mu_part.p, -1, nullptr,
                                 nullptr, cat ? kstar_cat(c, c->bcat.p) : KstarCat(), xn)))
       return rc;
-    if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->kst.p, ldk, npad, m, c->var_part.p, c->gp_beta,
+    if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->kst.p, ldk, npad, m, c->var_part.p, c->gp_beta.p,
                               c->pr_mpart.p)))
       return rc;
     hipLaunchKernelGGL(k_gp_finalize, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, RT, c->mu_part.p,
-                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats, c->gp_flag, acq->kind, acq->xi, acq->kappa, dup,
+                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
                        nullptr, nullptr, c->pr_score.p);
     UT_LAUNCH_CHECK(c);
   } else {
@@ -1900,11 +1891,11 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
     if (ns > 0) {
       const int64_t lds = (ns + VAR_BN - 1) / VAR_BN * VAR_BN;
       if ((rc = recompute_cols(c->pr_idx.p, 0, ns, lds))) return rc;
-      if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->pr_kst.p, lds, npad, ns, c->pr_vpart.p, c->gp_beta,
+      if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->pr_kst.p, lds, npad, ns, c->pr_vpart.p, c->gp_beta.p,
                                 c->pr_mpart.p)))
         return rc;
       hipLaunchKernelGGL(k_prune_exact, dim3(grid1(ns, 256)), dim3(256), 0, c->stream, ns, c->pr_idx.p, (int64_t)0,
-                         RT, c->pr_vpart.p, lds, mu_full, c->gp_sf2, c->gp_stats, c->gp_flag, acq->kind, acq->xi,
+                         RT, c->pr_vpart.p, lds, mu_full, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi,
                          acq->kappa, nullptr, c->pr_score.p, gmu);
       UT_LAUNCH_CHECK(c);
     }

@@ -690,15 +690,15 @@ int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, int32_t npad, const fl
   const int64_t items = (int64_t)(RT - rt0) * CT;
   int32_t nb = 2 * (c->n_cu / 8) * 8;
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-  UT_HIP(c, hipMemsetAsync(c->gp_ctr + 8, 0, sizeof(int32_t) * 8, c->stream));
+  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
   const float c0 = (float)(cat.c0 * KSTAR_T_SCALE), c1 = (float)(cat.c1 * KSTAR_T_SCALE);
   if (has_cat)
     hipLaunchKernelGGL(k_gp_kstar_f32c<true>, dim3(nb), dim3(K_NT), 0, c->stream, XsT_f, (int64_t)npad, ucand_f, ldk,
-                       dpad, rt0, RT, CT, xn, cn, c->gp_alpha, c->gp_sf2, c->gp_n, m, c->gp_ctr + 8, ldk, part, part2,
+                       dpad, rt0, RT, CT, xn, cn, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, ldk, part, part2,
                        part3, cat.acat, cat.bcat, cat.nkc, c0, c1);
   else
     hipLaunchKernelGGL(k_gp_kstar_f32c<false>, dim3(nb), dim3(K_NT), 0, c->stream, XsT_f, (int64_t)npad, ucand_f, ldk,
-                       dpad, rt0, RT, CT, xn, cn, c->gp_alpha, c->gp_sf2, c->gp_n, m, c->gp_ctr + 8, ldk, part, part2,
+                       dpad, rt0, RT, CT, xn, cn, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, ldk, part, part2,
                        part3, cat.acat, cat.bcat, cat.nkc, c0, c1);
   UT_LAUNCH_CHECK(c);
   return 0;
@@ -733,12 +733,12 @@ int launch_gemm_kstar(ut_ctx* c, int prec, const double* XsT, int32_t npad, cons
   const int32_t spare = fit_in_flight ? KSTAR_SPARE_PER_XCD : 0;
   int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-  UT_HIP(c, hipMemsetAsync(c->gp_ctr + 8, 0, sizeof(int32_t) * 8, c->stream));
-  const double* xnorm = xn ? xn : c->gp_xnorm;
+  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
+  const double* xnorm = xn ? xn : c->gp_xnorm.p;
   const double* cnorm = cn ? cn : c->cnorm.p;
 #define UT_KSTAR_LAUNCH(TS, MU, CAT, KST, PART, KSCALE, LOOFF, SRT, PART2)                                         \
   hipLaunchKernelGGL((k_gp_kstar<TS, MU, CAT>), dim3(nb), dim3(K_NT), 0, c->stream, XsT, (int64_t)npad, ucand, ldk, \
-                     dpad, RT, CT, xnorm, cnorm, c->gp_alpha, c->gp_sf2, c->gp_n, m, c->gp_ctr + 8, KST, ldk, PART, \
+                     dpad, RT, CT, xnorm, cnorm, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, KST, ldk, PART, \
                      KSCALE, LOOFF, SRT, PART2, cat.acat, cat.bcat, cat.nkc, cat.c0 * KSTAR_T_SCALE,        \
                      cat.c1 * KSTAR_T_SCALE, RTe)
 #define UT_KSTAR_BOTH(TS, MU, ...)                   \
@@ -783,7 +783,7 @@ __global__ void k_gp_prep_cand(const double* __restrict__ feat, int64_t ld, int6
 int launch_prep_cand(ut_ctx* c, const double* feat, int64_t ld, int64_t m, int32_t d, int32_t dpad, double* u,
                      int64_t ldu, double* cn) {
   hipLaunchKernelGGL(k_gp_prep_cand, dim3(grid1(ldu, 256)), dim3(256), 0, c->stream, feat, ld, m, d, dpad,
-                     c->gp_inv_ell, u, ldu, cn);
+                     c->gp_inv_ell.p, u, ldu, cn);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -841,7 +841,7 @@ int launch_prep_cand_cat(ut_ctx* c, const double* feat, int64_t ld, int64_t m, d
   const Space& s = c->space;
   UT_CHECK(c, ldu % 256 == 0 && s.cat_k % 128 == 0, UT_EINVAL, "prep_cand_cat: bad padding");
   hipLaunchKernelGGL(k_gp_prep_cand_cat, dim3((unsigned)(ldu / 256)), dim3(256), code_rows_lds(s.cat_k), c->stream,
-                     s.d_params, s.P, feat, ld, m, s.d_num_feat, s.n_num, dpad, c->gp_inv_ell, s.d_cat_ccol, s.cat_k,
+                     s.d_params.p, s.P, feat, ld, m, s.d_num_feat.p, s.n_num, dpad, c->gp_inv_ell.p, s.d_cat_ccol.p, s.cat_k,
                      u, ldu, cn, bcat);
   UT_LAUNCH_CHECK(c);
   return 0;
@@ -1530,7 +1530,7 @@ __global__ void k_split_h3(const double* __restrict__ x, int32_t n, int32_t n256
 int launch_split_h3(ut_ctx* c, const double* Linv, int32_t n, _Float16* dst) {
   const int64_t cnt = (int64_t)n * n;
   const int32_t n256 = ((n + H3_BM - 1) / H3_BM) * H3_BM;
-  unsigned long long* amax = reinterpret_cast<unsigned long long*>(c->gp_ctr + 16);
+  unsigned long long* amax = reinterpret_cast<unsigned long long*>(c->gp_ctr.p + 16);
   UT_HIP(c, hipMemsetAsync(amax, 0, sizeof(unsigned long long), c->stream));
   hipLaunchKernelGGL(k_absmax, dim3(1024), dim3(256), 0, c->stream, Linv, cnt, amax);
   hipLaunchKernelGGL(k_split_h3, dim3(grid1((int64_t)n256 * n, 256)), dim3(256), 0, c->stream, Linv, n, n256, amax,
@@ -1553,7 +1553,7 @@ int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const v
   // every XCD group has workers; never more blocks than work items
   int32_t nb = (c->n_cu / 8) * 8;
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-  UT_HIP(c, hipMemsetAsync(c->gp_ctr, 0, sizeof(int32_t) * 8, c->stream));
+  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p, 0, sizeof(int32_t) * 8, c->stream));
   if (prec == 16) {  // LinvT / kst: the blocked hi / lo planes of L^-1 and K* (see k_gp_var_h3)
     UT_CHECK(c, ldk % H3_BN == 0, UT_EINVAL, "gemm_var: h3 needs 256-candidate padding");
     const int32_t n256 = ((npad + H3_BM - 1) / H3_BM) * H3_BM;
@@ -1561,17 +1561,17 @@ int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const v
     const int64_t items2 = (int64_t)RT2 * CT2;
     int32_t nb2 = (c->n_cu / 8) * 8;
     if (items2 < nb2) nb2 = (int32_t)(((items2 + 7) / 8) * 8);
-    const unsigned long long* amax = reinterpret_cast<const unsigned long long*>(c->gp_ctr + 16);
+    const unsigned long long* amax = reinterpret_cast<const unsigned long long*>(c->gp_ctr.p + 16);
     // paired groups: S strips per group so that P x S items fill an XCD's workgroups
     const int32_t P2 = (RT2 + 1) / 2, W = nb2 / 8;
     const int32_t S2 = W / P2 > 1 ? W / P2 : 1;
     hipLaunchKernelGGL(k_gp_var_h3, dim3(nb2), dim3(512), 0, c->stream, (const _Float16*)LinvT, (int64_t)n256 * npad,
                        (const _Float16*)kst, ldk * (int64_t)npad, npad, RT2, (int32_t)((m + H3_BN - 1) / H3_BN), m,
-                       c->gp_ctr, part, ldk, amax, h3_kstar_exp(c->gp_sf2), S2);
+                       c->gp_ctr.p, part, ldk, amax, h3_kstar_exp(c->gp_sf2), S2);
   }
   else if (fp32)
     hipLaunchKernelGGL(k_gp_var_f32, dim3(nb), dim3(V_NT), 0, c->stream, (const float*)LinvT, lda,
-                       (const float*)kst, ldk, npad, RT, CT, m, c->gp_ctr, part, ldk);
+                       (const float*)kst, ldk, npad, RT, CT, m, c->gp_ctr.p, part, ldk);
   else {
     // two workgroups per CU on 128-candidate column tiles
     const int32_t CTp = (int32_t)((m + VP_BN - 1) / VP_BN);
@@ -1591,7 +1591,7 @@ int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const v
       if ((rc = ensure(c, c->var_vbuf, (size_t)items_s * VAR_BM * VP_BN))) return rc;
       if (items_s < nbp) nbp = (int32_t)(((items_s + 7) / 8) * 8);
       hipLaunchKernelGGL(k_gp_var_pp<true>, dim3(nbp), dim3(VP_NT), 0, c->stream, (const double*)LinvT, lda,
-                         (const double*)kst, ldk, npad, RT, CTp, m, c->gp_ctr, part, ldk, beta, mpart, kcs, per_strip,
+                         (const double*)kst, ldk, npad, RT, CTp, m, c->gp_ctr.p, part, ldk, beta, mpart, kcs, per_strip,
                          c->var_vbuf.p, 1);
       hipLaunchKernelGGL(k_var_split_red, dim3(RT, CTp), dim3(1024), 0, c->stream, c->var_vbuf.p, npad, kcs, per_strip,
                          m, beta, part, mpart, ldk);
@@ -1600,7 +1600,7 @@ int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const v
       const int32_t Pp = (RT + 1) / 2, Wp = nbp / 8;
       const int32_t Sp = Wp / Pp > 1 ? Wp / Pp : 1;
       hipLaunchKernelGGL(k_gp_var_pp<false>, dim3(nbp), dim3(VP_NT), 0, c->stream, (const double*)LinvT, lda,
-                         (const double*)kst, ldk, npad, RT, CTp, m, c->gp_ctr, part, ldk, beta, mpart, 0, 0, nullptr,
+                         (const double*)kst, ldk, npad, RT, CTp, m, c->gp_ctr.p, part, ldk, beta, mpart, 0, 0, nullptr,
                          Sp);
     }
   }

@@ -130,9 +130,9 @@ int launch_split_i8(ut_ctx* c, int32_t n, int32_t npad) {
   UT_CHECK(c, c->gp_i8a.n >= (size_t)I8_S * npad * npad && c->gp_i8rs.n >= (size_t)2 * npad + 2, UT_EINVAL,
            "split_i8: planes not allocated (alloc_split_i8)");
   double* rs = c->gp_i8rs.p;
-  hipLaunchKernelGGL(k_split_i8, dim3(npad), dim3(256), 0, c->stream, c->gp_Linv, n, npad, c->gp_i8_eb,
+  hipLaunchKernelGGL(k_split_i8, dim3(npad), dim3(256), 0, c->stream, c->gp_Linv.p, n, npad, c->gp_i8_eb,
                      c->gp_i8a.p, rs, rs + npad);
-  hipLaunchKernelGGL(k_i8_errsum, dim3(1), dim3(256), 0, c->stream, rs + npad, c->gp_beta, npad, rs + 2 * npad);
+  hipLaunchKernelGGL(k_i8_errsum, dim3(1), dim3(256), 0, c->stream, rs + npad, c->gp_beta.p, npad, rs + 2 * npad);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -306,9 +306,9 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
   int32_t nb = 2 * (c->n_cu / 8) * 8;   // two workgroups per CU, a multiple of 8 (every XCD group works)
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
   const int32_t W = nb / 8, Sg = W / P > 1 ? W / P : 1;
-  UT_HIP(c, hipMemsetAsync(c->gp_ctr, 0, sizeof(int32_t) * 8, c->stream));
+  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p, 0, sizeof(int32_t) * 8, c->stream));
   hipLaunchKernelGGL(k_gp_var_i8, dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT, m,
-                     c->gp_ctr, c->gp_i8rs.p, c->gp_beta, part, mpart, Sg);
+                     c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

@@ -499,7 +499,7 @@ int launch_gemm_kstar_q(ut_ctx* c, bool planes, const double* XsT, int32_t npad,
   UT_CHECK(c, K32 + cat.nkc >= 1, UT_EINVAL, "gemm_kstar_q: no features");
   // the library runs it for the variance's digit planes of numeric fits (the
   // mean from the variance epilogue, no one-hot codes: gp.hip gp_score_impl)
-  UT_CHECK(c, planes && !part && !part2 && !has_cat && XsT == c->gp_XsT, UT_EINVAL,
+  UT_CHECK(c, planes && !part && !part2 && !has_cat && XsT == c->gp_XsT.p, UT_EINVAL,
            "gemm_kstar_q: digit planes of a numeric fit only");
   int rc;
   if ((rc = ensure(c, u8, (size_t)I8_S * (K32 > 0 ? K32 : 1) * 32 * ldk))) return rc;
@@ -515,12 +515,12 @@ int launch_gemm_kstar_q(ut_ctx* c, bool planes, const double* XsT, int32_t npad,
   const int32_t spare = fit_in_flight ? 2 : 0;   // as launch_gemm_kstar
   int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-  const double* xnorm = xn ? xn : c->gp_xnorm;
+  const double* xnorm = xn ? xn : c->gp_xnorm.p;
   const double* cnorm = cn ? cn : c->cnorm.p;
   const double kscale = planes ? ldexp(1.0, -i8_kstar_exp(c->gp_sf2)) : 1.0;
 #define UT_KQ_LAUNCH(PAIR)                                                                                     \
   hipLaunchKernelGGL((k_gp_kstar_q<int8_t, false, false, PAIR>), dim3(nb), dim3(Q_NT), 0, c->stream, xd.p, npad,    \
-                     u8.p, ldk, K32, scol.p, RT, CT, xnorm, cnorm, c->gp_alpha, c->gp_sf2, c->gp_n, m, (int8_t*)kst, \
+                     u8.p, ldk, K32, scol.p, RT, CT, xnorm, cnorm, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, (int8_t*)kst, \
                      nullptr, kscale, (int64_t)npad * ldk, store_rt, nullptr, cat.acat, cat.bcat, cat.nkc,         \
                      cat.c0 * KSTAR_T_SCALE, cat.c1 * KSTAR_T_SCALE)
   if (pair) UT_KQ_LAUNCH(true);

@@ -234,10 +234,10 @@ int gp_lml_impl(ut_ctx* c, double* lml_host) {
   UT_CHECK(c, c->gp_ready || c->fit_pending, UT_EINVAL, "gp_lml: call ut_gp_fit first");
   int rc;
   if ((rc = gp_wait_fit(c))) return rc;   // a staged fit is flushed, a failed one reported
-  UT_CHECK(c, c->gp_ready && c->gp_K && c->gp_beta, UT_EINVAL, "gp_lml: no fitted GP");
+  UT_CHECK(c, c->gp_ready && c->gp_K.p && c->gp_beta.p, UT_EINVAL, "gp_lml: no fitted GP");
   if (!c->lml_host) UT_HIP(c, hipHostMalloc((void**)&c->lml_host, sizeof(double), hipHostMallocDefault));
   // the fit stream is idle (gp_wait_fit); scoring on the caller's stream only reads the factor
-  hipLaunchKernelGGL(k_lml_fit, dim3(1), dim3(256), 0, c->stream, c->gp_K, c->gp_beta, c->gp_flag, c->gp_n,
+  hipLaunchKernelGGL(k_lml_fit, dim3(1), dim3(256), 0, c->stream, c->gp_K.p, c->gp_beta.p, c->gp_flag.p, c->gp_n,
                      c->gp_npad_fit, c->lml_host);
   UT_LAUNCH_CHECK(c);
   UT_HIP(c, hipStreamSynchronize(c->stream));

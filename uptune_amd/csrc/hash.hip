@@ -453,8 +453,8 @@ static int launch_hash_impl(ut_ctx* c, const double* values, int64_t ld, int64_t
   if (s.n_perm > 0) {
     int rc = ensure(c, c->perm_dig, (size_t)s.n_perm * (size_t)m * 8);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_perm_digest, dim3(grid1(m, PD_NT)), dim3(PD_NT), 0, c->stream, s.d_params, s.d_perm_params,
-                       s.n_perm, s.d_perm_bytes, s.d_perm_off, s.d_perm_offbase, s.d_perm_len, values, ld, m,
+    hipLaunchKernelGGL(k_perm_digest, dim3(grid1(m, PD_NT)), dim3(PD_NT), 0, c->stream, s.d_params.p, s.d_perm_params.p,
+                       s.n_perm, s.d_perm_bytes.p, s.d_perm_off.p, s.d_perm_offbase.p, s.d_perm_len.p, values, ld, m,
                        c->perm_dig.p);
     UT_LAUNCH_CHECK(c);
     pd = c->perm_dig.p;
@@ -466,9 +466,9 @@ static int launch_hash_impl(ut_ctx* c, const double* values, int64_t ld, int64_t
 #define UT_HASH_REF_WAVES 4
 #endif
   auto kern = ref.cache ? k_hash<true, UT_HASH_REF_WAVES> : k_hash<false, 1>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(HASH_NT), 0, c->stream, s.d_params, s.d_order,
-                     s.d_order_col, reinterpret_cast<const uint2*>(s.d_words), s.d_block_last,
-                     (int32_t)s.outer_blocks, s.P, reinterpret_cast<const uint4*>(s.d_lut), values, ld, m,
+  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_order.p,
+                     s.d_order_col.p, reinterpret_cast<const uint2*>(s.d_words.p), s.d_block_last.p,
+                     (int32_t)s.outer_blocks, s.P, reinterpret_cast<const uint4*>(s.d_lut.p), values, ld, m,
                      reinterpret_cast<const uint4*>(pd), out, ref);
   UT_LAUNCH_CHECK(c);
   return 0;
@@ -490,7 +490,7 @@ int launch_hash(ut_ctx* c, const double* values, int64_t ld, int64_t m, uint32_t
     UT_HIP(c, hipMemsetAsync(c->hs_mask.p, 0xFF, sizeof(uint32_t) * nw * m, c->stream));
     const int64_t want = ((int64_t)s.n_comp * m + HASH_NT - 1) / HASH_NT;
     const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)c->n_cu * 8);
-    hipLaunchKernelGGL(k_inner_all, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params, s.d_comp, s.n_comp, values,
+    hipLaunchKernelGGL(k_inner_all, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_comp.p, s.n_comp, values,
                        ld, m, reinterpret_cast<uint4*>(c->hs_fresh.p));
     UT_LAUNCH_CHECK(c);
     // every mask bit set: k_hash reads each computed digest from hs_fresh (the
@@ -503,37 +503,31 @@ int launch_hash(ut_ctx* c, const double* values, int64_t ld, int64_t m, uint32_t
 
 int launch_pop_digests_window(ut_ctx* c, int64_t lo, int64_t wn) {
   const Space& s = c->space;
-  if (s.n_comp == 0 || c->npop == 0) return 0;
-  lo = std::max<int64_t>(0, std::min(lo, c->npop - 1));
-  wn = std::max<int64_t>(1, std::min(wn, c->npop - lo));
+  if (s.n_comp == 0 || c->cur.npop == 0) return 0;
+  lo = std::max<int64_t>(0, std::min(lo, c->cur.npop - 1));
+  wn = std::max<int64_t>(1, std::min(wn, c->cur.npop - lo));
   const int64_t need = (int64_t)s.n_comp * wn * 16;   // 64 hex characters per digest
-  if (c->pop_dig_cap < need) {
-    if (c->pop_dig) {
-      UT_HIP(c, sync_all(c));
-      ut::dfree(c->pop_dig);
-      c->pop_dig = nullptr;
-      c->pop_dig_cap = 0;
-    }
-    const hipError_t e = ut::dmalloc((void**)&c->pop_dig, sizeof(uint32_t) * need);
+  if ((int64_t)c->cur.pop_dig.n < need) {
+    if (c->cur.pop_dig.p) UT_HIP(c, sync_all(c));
+    const hipError_t e = c->cur.pop_dig.alloc((size_t)need);
     if (e != hipSuccess) return set_err(c, UT_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    c->pop_dig_cap = need;
   }
   hipLaunchKernelGGL(k_pop_digests, dim3(grid1(wn, HASH_NT), (unsigned)s.n_comp), dim3(HASH_NT), 0, c->stream,
-                     s.d_params, s.d_comp, s.n_comp, c->pop, c->npop, (const int64_t*)nullptr, (int64_t)0, lo, wn,
-                     reinterpret_cast<uint4*>(c->pop_dig));
+                     s.d_params.p, s.d_comp.p, s.n_comp, c->cur.pop.p, c->cur.npop, (const int64_t*)nullptr, (int64_t)0, lo, wn,
+                     reinterpret_cast<uint4*>(c->cur.pop_dig.p));
   UT_LAUNCH_CHECK(c);
-  c->pop_dig_lo = lo;
-  c->pop_dig_n = wn;
-  c->pop_dig_valid = true;
+  c->cur.pop_dig_lo = lo;
+  c->cur.pop_dig_n = wn;
+  c->cur.pop_dig_valid = true;
   return 0;
 }
 
 int launch_pop_digests(ut_ctx* c, const int64_t* idx, int64_t n) {
   const Space& s = c->space;
-  if (s.n_comp == 0 || c->npop == 0 || !c->pop_dig_valid || n <= 0) return 0;
+  if (s.n_comp == 0 || c->cur.npop == 0 || !c->cur.pop_dig_valid || n <= 0) return 0;
   hipLaunchKernelGGL(k_pop_digests, dim3(grid1(n, HASH_NT), (unsigned)s.n_comp), dim3(HASH_NT), 0, c->stream,
-                     s.d_params, s.d_comp, s.n_comp, c->pop, c->npop, idx, n, c->pop_dig_lo, c->pop_dig_n,
-                     reinterpret_cast<uint4*>(c->pop_dig));
+                     s.d_params.p, s.d_comp.p, s.n_comp, c->cur.pop.p, c->cur.npop, idx, n, c->cur.pop_dig_lo, c->cur.pop_dig_n,
+                     reinterpret_cast<uint4*>(c->cur.pop_dig.p));
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -555,16 +549,16 @@ int launch_hash_de(ut_ctx* c, const double* values, int64_t ld, int64_t m, int64
   int rc;
   // the targets of this call: members (cand_base + i) % npop, i < m -- one
   // contiguous range unless it wraps around the population (then all of it)
-  int64_t tlo = (int64_t)((uint64_t)cand_base % (uint64_t)c->npop), tn = m;
-  if (tlo + tn > c->npop) tlo = 0, tn = c->npop;
-  const bool covered = c->pop_dig_valid && tlo >= c->pop_dig_lo && tlo + tn <= c->pop_dig_lo + c->pop_dig_n;
+  int64_t tlo = (int64_t)((uint64_t)cand_base % (uint64_t)c->cur.npop), tn = m;
+  if (tlo + tn > c->cur.npop) tlo = 0, tn = c->cur.npop;
+  const bool covered = c->cur.pop_dig_valid && tlo >= c->cur.pop_dig_lo && tlo + tn <= c->cur.pop_dig_lo + c->cur.pop_dig_n;
   if (!covered && (rc = launch_pop_digests_window(c, tlo, tn))) return rc;
   if ((rc = ensure_de_diff(c, ld))) return rc;
   unsigned long long* np = reinterpret_cast<unsigned long long*>(c->r_npairs.p);
   if (!have_diff) {
     UT_HIP(c, hipMemsetAsync(c->r_npairs.p, 0, sizeof(int64_t), c->stream));
-    hipLaunchKernelGGL(k_de_diff, dim3(grid1(m, DIFF_NT)), dim3(DIFF_NT), 0, c->stream, s.d_params, s.d_comp,
-                       s.n_comp, values, ld, m, c->pop, c->npop, cand_base, c->r_mask.p, c->r_pairs.p, np);
+    hipLaunchKernelGGL(k_de_diff, dim3(grid1(m, DIFF_NT)), dim3(DIFF_NT), 0, c->stream, s.d_params.p, s.d_comp.p,
+                       s.n_comp, values, ld, m, c->cur.pop.p, c->cur.npop, cand_base, c->r_mask.p, c->r_pairs.p, np);
     UT_LAUNCH_CHECK(c);
   }
   const int64_t want = ((int64_t)s.n_comp * m + HASH_NT - 1) / HASH_NT;
@@ -573,13 +567,13 @@ int launch_hash_de(ut_ctx* c, const double* values, int64_t ld, int64_t m, int64
   const int32_t cap = hash_cap(c, m, false, hold);
   const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), (int64_t)c->n_cu * (cap > 0 ? cap : 8));
   if (hold) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));
-  hipLaunchKernelGGL(k_inner_pairs, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params, s.d_comp, values, ld,
+  hipLaunchKernelGGL(k_inner_pairs, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_comp.p, values, ld,
                      c->r_pairs.p, np, reinterpret_cast<uint4*>(c->r_fresh.p));
   UT_LAUNCH_CHECK(c);
   return launch_hash_impl(c, values, ld, m, out,
                           InnerRef{c->r_mask.p, reinterpret_cast<const uint4*>(c->r_fresh.p),
-                                   reinterpret_cast<const uint4*>(c->pop_dig), c->npop, cand_base, c->pop_dig_lo,
-                                   c->pop_dig_n, ld},
+                                   reinterpret_cast<const uint4*>(c->cur.pop_dig.p), c->cur.npop, cand_base, c->cur.pop_dig_lo,
+                                   c->cur.pop_dig_n, ld},
                           hold);
 }
 
@@ -590,19 +584,19 @@ int launch_hash_parent(ut_ctx* c, const double* values, int64_t ld, int64_t m, c
   if ((rc = ensure(c, c->par_dig, (size_t)s.n_comp * 16))) return rc;
   if ((rc = ensure_de_diff(c, ld))) return rc;
   // the parent's hex inner digests: a population of one member (column p at parent[col])
-  hipLaunchKernelGGL(k_pop_digests, dim3(1, (unsigned)s.n_comp), dim3(HASH_NT), 0, c->stream, s.d_params, s.d_comp,
+  hipLaunchKernelGGL(k_pop_digests, dim3(1, (unsigned)s.n_comp), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_comp.p,
                      s.n_comp, parent, (int64_t)1, (const int64_t*)nullptr, (int64_t)0, (int64_t)0, (int64_t)1,
                      reinterpret_cast<uint4*>(c->par_dig.p));
   UT_LAUNCH_CHECK(c);
   // which computed-digest values differ from the parent's: every child "targets" member 0
   unsigned long long* np = reinterpret_cast<unsigned long long*>(c->r_npairs.p);
   UT_HIP(c, hipMemsetAsync(c->r_npairs.p, 0, sizeof(int64_t), c->stream));
-  hipLaunchKernelGGL(k_de_diff, dim3(grid1(m, DIFF_NT)), dim3(DIFF_NT), 0, c->stream, s.d_params, s.d_comp, s.n_comp,
+  hipLaunchKernelGGL(k_de_diff, dim3(grid1(m, DIFF_NT)), dim3(DIFF_NT), 0, c->stream, s.d_params.p, s.d_comp.p, s.n_comp,
                      values, ld, m, parent, (int64_t)1, (int64_t)0, c->r_mask.p, c->r_pairs.p, np);
   UT_LAUNCH_CHECK(c);
   const int64_t want = ((int64_t)s.n_comp * m + HASH_NT - 1) / HASH_NT;
   const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), (int64_t)c->n_cu * 8);
-  hipLaunchKernelGGL(k_inner_pairs, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params, s.d_comp, values, ld,
+  hipLaunchKernelGGL(k_inner_pairs, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_comp.p, values, ld,
                      c->r_pairs.p, np, reinterpret_cast<uint4*>(c->r_fresh.p));
   UT_LAUNCH_CHECK(c);
   return launch_hash_impl(c, values, ld, m, out,

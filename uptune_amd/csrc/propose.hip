@@ -773,8 +773,8 @@ static int perm_workspace(ut_ctx* c, int64_t m, double** ws, int64_t* ldw) {
 }
 
 int launch_population_init(ut_ctx* c, uint32_t round_) {
-  hipLaunchKernelGGL(k_population_init, dim3(grid1(c->npop, 256)), dim3(256), 0, c->stream, c->space.d_params,
-                     c->space.P, c->pop, c->npop, c->npop, c->seed, round_);
+  hipLaunchKernelGGL(k_population_init, dim3(grid1(c->cur.npop, 256)), dim3(256), 0, c->stream, c->space.d_params.p,
+                     c->space.P, c->cur.pop.p, c->cur.npop, c->cur.npop, c->seed, round_);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -831,32 +831,26 @@ __global__ void k_pop_aos_rows(const DevParam* __restrict__ params, const int32_
 }
 
 int ensure_pop_aos(ut_ctx* c) {
-  if (c->pop_aos_valid) return 0;
+  if (c->cur.pop_aos_valid) return 0;
   const int64_t lda = pop_aos_ld(c);
-  const int64_t need = (c->npop + 1) * lda;   // + the best-config row
-  if (c->pop_aos_cap < need) {
-    if (c->pop_aos) {
-      UT_HIP(c, sync_all(c));
-      (void)ut::dfree(c->pop_aos);
-      c->pop_aos = nullptr;
-      c->pop_aos_cap = 0;
-    }
-    const hipError_t e = ut::dmalloc((void**)&c->pop_aos, sizeof(double) * need);
-    if (e != hipSuccess) return set_err(c, UT_ENOMEM, std::string("ut::dmalloc(pop_aos): ") + hipGetErrorString(e));
-    c->pop_aos_cap = need;
+  const int64_t need = (c->cur.npop + 1) * lda;   // + the best-config row
+  if ((int64_t)c->cur.pop_aos.n < need) {
+    if (c->cur.pop_aos.p) UT_HIP(c, sync_all(c));
+    const hipError_t e = c->cur.pop_aos.alloc((size_t)need);
+    if (e != hipSuccess) return set_err(c, UT_ENOMEM, std::string("hipMalloc (pop_aos): ") + hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(k_pop_to_aos, dim3(grid1(c->npop, 64), (unsigned)(lda / 16)), dim3(256), 0, c->stream,
-                     c->space.d_params, c->space.d_col_param, c->space.d_vtab, c->space.ncols, c->pop, c->npop,
-                     c->npop, c->pop_aos, lda);
+  hipLaunchKernelGGL(k_pop_to_aos, dim3(grid1(c->cur.npop, 64), (unsigned)(lda / 16)), dim3(256), 0, c->stream,
+                     c->space.d_params.p, c->space.d_col_param.p, c->space.d_vtab.p, c->space.ncols, c->cur.pop.p, c->cur.npop,
+                     c->cur.npop, c->cur.pop_aos.p, lda);
   UT_LAUNCH_CHECK(c);
-  c->pop_aos_valid = true;
+  c->cur.pop_aos_valid = true;
   return 0;
 }
 
 int launch_pop_aos_rows(ut_ctx* c, const double* trial, int64_t ld, const int64_t* idx, int64_t n) {
   const int64_t e = n * c->space.ncols;
-  hipLaunchKernelGGL(k_pop_aos_rows, dim3(grid1(e, 256)), dim3(256), 0, c->stream, c->space.d_params,
-                     c->space.d_col_param, c->space.d_vtab, c->space.ncols, c->pop_aos, pop_aos_ld(c), trial, ld, idx,
+  hipLaunchKernelGGL(k_pop_aos_rows, dim3(grid1(e, 256)), dim3(256), 0, c->stream, c->space.d_params.p,
+                     c->space.d_col_param.p, c->space.d_vtab.p, c->space.ncols, c->cur.pop_aos.p, pop_aos_ld(c), trial, ld, idx,
                      n);
   UT_LAUNCH_CHECK(c);
   return 0;
@@ -870,8 +864,8 @@ __global__ void k_aos_row(const DevParam* __restrict__ params, const int32_t* __
 }
 
 int launch_aos_row(ut_ctx* c, const double* src, int64_t row) {
-  hipLaunchKernelGGL(k_aos_row, dim3(grid1(c->space.ncols, 64)), dim3(64), 0, c->stream, c->space.d_params,
-                     c->space.d_col_param, c->space.d_vtab, c->space.ncols, src, c->pop_aos + row * pop_aos_ld(c));
+  hipLaunchKernelGGL(k_aos_row, dim3(grid1(c->space.ncols, 64)), dim3(64), 0, c->stream, c->space.d_params.p,
+                     c->space.d_col_param.p, c->space.d_vtab.p, c->space.ncols, src, c->cur.pop_aos.p + row * pop_aos_ld(c));
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -898,7 +892,7 @@ int launch_de(ut_ctx* c, const ut_de_params* p, uint32_t round_, int64_t cand_ba
     if (rc) return rc;
     lda = pop_aos_ld(c);
     if (share) {   // row npop: the best config, the donor of pool positions >= npop - 1
-      const int rc = launch_aos_row(c, p->best, c->npop);
+      const int rc = launch_aos_row(c, p->best, c->cur.npop);
       if (rc) return rc;
     }
   }
@@ -912,23 +906,23 @@ int launch_de(ut_ctx* c, const ut_de_params* p, uint32_t round_, int64_t cand_ba
                    c->space.n_comp};
   }
   auto kern = aos ? (diff ? k_de<true, true> : k_de<false, true>) : (diff ? k_de<true, false> : k_de<false, false>);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, c->space.d_params, c->space.P, c->space.d_vtab,
-                     c->pop, c->npop, c->npop, p->best, share, p->cr, p->n_cross, c->seed, round_, cand_base, m, out,
-                     ld, dd, xg, c->pop_aos, lda);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, c->space.d_params.p, c->space.P, c->space.d_vtab.p,
+                     c->cur.pop.p, c->cur.npop, c->cur.npop, p->best, share, p->cr, p->n_cross, c->seed, round_, cand_base, m, out,
+                     ld, dd, xg, c->cur.pop_aos.p, lda);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
 
 int launch_pso(ut_ctx* c, const ut_pso_params* a, const double* gbest, uint32_t round_, int64_t cand_base,
                int64_t m, double* out_x, double* out_v, int64_t ld) {
-  const double* pb = a->alias_pbest ? c->pop : c->pso_best;
+  const double* pb = a->alias_pbest ? c->cur.pop.p : c->cur.pso_best.p;
   double* ws;
   int64_t ldw;
   int rc = perm_workspace(c, m, &ws, &ldw);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_pso, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->space.d_params, c->space.P,
-                     c->space.d_vtab, c->pop,
-                     c->pso_vel, pb, c->npop, c->npop, gbest, a->omega, a->phi_g, a->phi_l, a->sigma, a->enum_mode,
+  hipLaunchKernelGGL(k_pso, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->space.d_params.p, c->space.P,
+                     c->space.d_vtab.p, c->cur.pop.p,
+                     c->cur.pso_vel.p, pb, c->cur.npop, c->cur.npop, gbest, a->omega, a->phi_g, a->phi_l, a->sigma, a->enum_mode,
                      a->crossover, c->seed, round_, cand_base, m, out_x, out_v, ld, ws, ldw, 2 * c->space.perm_cols);
   UT_LAUNCH_CHECK(c);
   return 0;
@@ -941,8 +935,8 @@ int launch_ga(ut_ctx* c, const ut_ga_params* a, const double* parent1, const dou
   int64_t ldw;
   int rc = perm_workspace(c, m, &ws, &ldw);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_ga, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->space.d_params, c->space.P,
-                     c->space.d_vtab, parent1,
+  hipLaunchKernelGGL(k_ga, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->space.d_params.p, c->space.P,
+                     c->space.d_vtab.p, parent1,
                      parent2, a->mutation_rate, a->sigma, a->crossover_rate, d, a->must_mutate_count, a->normal,
                      a->max_retries, (uint32_t)a->op, a->crossover, c->seed, round_, cand_base, m, out, ld, invalid,
                      ws, ldw, c->space.perm_cols);
@@ -951,16 +945,16 @@ int launch_ga(ut_ctx* c, const ut_ga_params* a, const double* parent1, const dou
 }
 
 int launch_encode(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* feat, int64_t ldf) {
-  hipLaunchKernelGGL(k_encode, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->space.d_params, c->space.P,
-                     c->space.d_vtab, values, ld, m, feat, ldf);
+  hipLaunchKernelGGL(k_encode, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->space.d_params.p, c->space.P,
+                     c->space.d_vtab.p, values, ld, m, feat, ldf);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
 
 int launch_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* u, int32_t dpad, int64_t ldu,
                          double* cn) {
-  hipLaunchKernelGGL(k_encode_scaled, dim3(grid1(ldu, 256)), dim3(256), 0, c->stream, c->space.d_params, c->space.P,
-                     c->space.d_vtab, values, ld, m, c->space.n_feat, c->gp_inv_ell, dpad, u, ldu, cn);
+  hipLaunchKernelGGL(k_encode_scaled, dim3(grid1(ldu, 256)), dim3(256), 0, c->stream, c->space.d_params.p, c->space.P,
+                     c->space.d_vtab.p, values, ld, m, c->space.n_feat, c->gp_inv_ell.p, dpad, u, ldu, cn);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -970,8 +964,8 @@ int launch_encode_scaled_cat(ut_ctx* c, const double* values, int64_t ld, int64_
   const Space& s = c->space;
   UT_CHECK(c, ldu % 256 == 0 && s.cat_k % 128 == 0, UT_EINVAL, "encode_scaled_cat: bad padding");
   hipLaunchKernelGGL(k_encode_scaled_cat, dim3((unsigned)(ldu / 256)), dim3(256), code_rows_lds(s.cat_k), c->stream,
-                     s.d_params, s.P, s.d_vtab, values, ld, m, s.d_feat_num, s.n_num, dpad, c->gp_inv_ell,
-                     s.d_cat_ccol, s.cat_k, u, ldu, cn, bcat);
+                     s.d_params.p, s.P, s.d_vtab.p, values, ld, m, s.d_feat_num.p, s.n_num, dpad, c->gp_inv_ell.p,
+                     s.d_cat_ccol.p, s.cat_k, u, ldu, cn, bcat);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -989,44 +983,39 @@ int launch_gather_rows(ut_ctx* c, const double* values, int64_t ld, const int64_
 extern "C" int ut_population_replace(ut_ctx* c, const double* trial, int64_t ld, const int64_t* idx, int64_t n) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, c->has_space, UT_ENOSPACE, "space not defined");
-  UT_CHECK(c, c->pop != nullptr, UT_EINVAL, "population not initialised");
+  UT_CHECK(c, c->cur.pop.p != nullptr, UT_EINVAL, "population not initialised");
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(ut::k_pop_replace, dim3(ut::grid1(n, 64)), dim3(64), 0, c->stream, c->space.ncols, c->pop,
-                     c->npop, trial, ld, idx, n);
+  hipLaunchKernelGGL(ut::k_pop_replace, dim3(ut::grid1(n, 64)), dim3(64), 0, c->stream, c->space.ncols, c->cur.pop.p,
+                     c->cur.npop, trial, ld, idx, n);
   UT_LAUNCH_CHECK(c);
-  if (c->pop_aos_valid) {
+  if (c->cur.pop_aos_valid) {
     const int rc = ut::launch_pop_aos_rows(c, trial, ld, idx, n);
     if (rc) return rc;
   }
   // keep the population's inner-digest cache current: only the replaced rows
-  if (c->pop_dig_valid) return ut::launch_pop_digests(c, idx, n);
+  if (c->cur.pop_dig_valid) return ut::launch_pop_digests(c, idx, n);
   return 0;
 }
 
 extern "C" int ut_pso_reset(ut_ctx* c) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->has_space && c->pop != nullptr, UT_EINVAL, "pso_reset: population not initialised");
-  const int64_t need = c->npop * c->space.ncols;
-  if (c->pso_cap < need) {
-    if (c->pso_vel) {
-      UT_HIP(c, ut::sync_all(c));
-      ut::dfree(c->pso_vel);
-      ut::dfree(c->pso_best);
-    }
-    UT_HIP(c, ut::dmalloc((void**)&c->pso_vel, sizeof(double) * need));
-    UT_HIP(c, ut::dmalloc((void**)&c->pso_best, sizeof(double) * need));
-    c->pso_cap = need;
+  UT_CHECK(c, c->has_space && c->cur.pop.p != nullptr, UT_EINVAL, "pso_reset: population not initialised");
+  const int64_t need = c->cur.npop * c->space.ncols;
+  if ((int64_t)c->cur.pso_best.n < need) {   // (allocated last: both hold `need` once it does)
+    if (c->cur.pso_vel.p) UT_HIP(c, ut::sync_all(c));
+    UT_HIP(c, c->cur.pso_vel.alloc((size_t)need));
+    UT_HIP(c, c->cur.pso_best.alloc((size_t)need));
   }
-  UT_HIP(c, hipMemsetAsync(c->pso_vel, 0, sizeof(double) * need, c->stream));
-  UT_HIP(c, hipMemcpyAsync(c->pso_best, c->pop, sizeof(double) * need, hipMemcpyDeviceToDevice, c->stream));
+  UT_HIP(c, hipMemsetAsync(c->cur.pso_vel.p, 0, sizeof(double) * need, c->stream));
+  UT_HIP(c, hipMemcpyAsync(c->cur.pso_best.p, c->cur.pop.p, sizeof(double) * need, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
 extern "C" int ut_propose_pso(ut_ctx* c, const ut_pso_params* a, const double* gbest, uint32_t round_,
                               int64_t cand_base, int64_t m, double* out_values, double* out_vel, int64_t ld) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->has_space && c->pop != nullptr, UT_EINVAL, "propose_pso: population not initialised");
-  UT_CHECK(c, c->pso_vel != nullptr && c->pso_cap >= c->npop * c->space.ncols, UT_EINVAL,
+  UT_CHECK(c, c->has_space && c->cur.pop.p != nullptr, UT_EINVAL, "propose_pso: population not initialised");
+  UT_CHECK(c, c->cur.pso_vel.p != nullptr && (int64_t)c->cur.pso_best.n >= c->cur.npop * c->space.ncols, UT_EINVAL,
            "propose_pso: call ut_pso_reset after (re)initialising the population");
   UT_CHECK(c, a && gbest && (out_values || m == 0) && m >= 0 && cand_base >= 0 && ld >= m, UT_EINVAL,
            "propose_pso: bad arguments");
@@ -1042,25 +1031,25 @@ extern "C" int ut_propose_pso(ut_ctx* c, const ut_pso_params* a, const double* g
 extern "C" int ut_pso_commit(ut_ctx* c, const double* values, const double* vel, int64_t ld, int64_t cand_base,
                              int64_t m) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->pso_vel != nullptr && values && cand_base >= 0 && m >= 0 && cand_base + m <= c->npop && ld >= m,
+  UT_CHECK(c, c->cur.pso_vel.p != nullptr && values && cand_base >= 0 && m >= 0 && cand_base + m <= c->cur.npop && ld >= m,
            UT_EINVAL, "pso_commit: bad arguments");
   if (m == 0) return 0;
-  c->pop_dig_valid = false;   // positions moved: the inner-digest cache is rebuilt when a DE round needs it
-  c->pop_aos_valid = false;   // and so is the member-major copy
-  UT_HIP(c, hipMemcpy2DAsync(c->pop + cand_base, sizeof(double) * c->npop, values, sizeof(double) * ld,
+  c->cur.pop_dig_valid = false;   // positions moved: the inner-digest cache is rebuilt when a DE round needs it
+  c->cur.pop_aos_valid = false;   // and so is the member-major copy
+  UT_HIP(c, hipMemcpy2DAsync(c->cur.pop.p + cand_base, sizeof(double) * c->cur.npop, values, sizeof(double) * ld,
                              sizeof(double) * m, c->space.ncols, hipMemcpyDeviceToDevice, c->stream));
   if (vel)
-    UT_HIP(c, hipMemcpy2DAsync(c->pso_vel + cand_base, sizeof(double) * c->npop, vel, sizeof(double) * ld,
+    UT_HIP(c, hipMemcpy2DAsync(c->cur.pso_vel.p + cand_base, sizeof(double) * c->cur.npop, vel, sizeof(double) * ld,
                                sizeof(double) * m, c->space.ncols, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
 extern "C" int ut_pso_update_best(ut_ctx* c, const double* values, int64_t ld, const int64_t* idx, int64_t n) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->pso_best != nullptr && values && idx && n >= 0, UT_EINVAL, "pso_update_best: bad arguments");
+  UT_CHECK(c, c->cur.pso_best.p != nullptr && values && idx && n >= 0, UT_EINVAL, "pso_update_best: bad arguments");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(ut::k_pop_replace, dim3(ut::grid1(n, 64)), dim3(64), 0, c->stream, c->space.ncols, c->pso_best,
-                     c->npop, values, ld, idx, n);
+  hipLaunchKernelGGL(ut::k_pop_replace, dim3(ut::grid1(n, 64)), dim3(64), 0, c->stream, c->space.ncols, c->cur.pso_best.p,
+                     c->cur.npop, values, ld, idx, n);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

@@ -7,6 +7,8 @@
 #include <functional>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/uthot.h"
@@ -59,6 +61,55 @@ enum : uint32_t {
   HW_HOLE = 1u << 31,
 };
 
+// every device allocation of the library goes through these two (api.hip):
+// the bytes held per device are what ut_device_bytes reports (a rank's HBM
+// footprint in the bench line)
+hipError_t dmalloc(void** p, size_t bytes);
+void dfree(void* p);
+
+// An owning device array: the destructor frees it, so a buffer that is a
+// member of the context (or of a Space, a PopSlot) or a local needs no line
+// anywhere else.  Move-only; never give one static storage duration (it would
+// be freed after the HIP runtime has shut down).  Kernels take b.p.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;   // elements
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept { swap(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    swap(o);
+    return *this;
+  }
+  ~DevBuf() { ut::dfree(p); }
+  void swap(DevBuf& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(n, o.n);
+  }
+  void reset() {
+    ut::dfree(p);
+    p = nullptr;
+    n = 0;
+  }
+  // exactly `count` elements in place of what it held, outside the fault
+  // injection's count (ensure() and dalloc() below are the counted ways).  The
+  // caller waits for the context's streams first if the old array may be in use.
+  hipError_t alloc(size_t count) {
+    reset();
+    const hipError_t e = ut::dmalloc((void**)&p, count * sizeof(T));
+    if (e == hipSuccess) n = count;
+    else p = nullptr;
+    return e;
+  }
+};
+static_assert(!std::is_copy_constructible<DevBuf<double>>::value && !std::is_copy_assignable<DevBuf<double>>::value,
+              "DevBuf owns its array: two owners would free it twice");
+static_assert(std::is_nothrow_move_constructible<DevBuf<double>>::value &&
+                  std::is_nothrow_move_assignable<DevBuf<double>>::value,
+              "DevBuf moves by exchanging p and n");
+
 struct Space {
   int32_t P = 0;                          // parameters
   int32_t ncols = 0;                      // SoA value columns (P + sum over PERM of size - 1)
@@ -71,21 +122,21 @@ struct Space {
   std::vector<int32_t> host_order;        // sorted position -> param index
   int64_t outer_len = 0;
   int64_t outer_blocks = 0;
-  DevParam* d_params = nullptr;
-  int32_t* d_order = nullptr;             // sorted position -> param index
-  HashWord* d_words = nullptr;            // outer_blocks * 16
-  int32_t* d_block_last = nullptr;        // last sorted position needed by each block
-  uint32_t* d_lut = nullptr;              // digests as hex [*][16 words]
-  double* d_vtab = nullptr;               // LOGINT get_value tables (host-computed by CPython)
-  int32_t* d_order_col = nullptr;         // sorted position -> first value column
-  int32_t* d_perm_params = nullptr;       // PERM param indices, by digest slot
-  uint8_t* d_perm_bytes = nullptr;        // concatenated repr(item) bytes of every PERM param
-  int32_t* d_perm_off = nullptr;          // per PERM param: S + 1 offsets into d_perm_bytes
-  int32_t* d_perm_offbase = nullptr;      // per PERM slot: first entry in d_perm_off
-  int32_t* d_perm_len = nullptr;          // per PERM slot: len(repr(list)) (constant per param)
+  DevBuf<DevParam> d_params;
+  DevBuf<int32_t> d_order;                // sorted position -> param index
+  DevBuf<HashWord> d_words;               // outer_blocks * 16
+  DevBuf<int32_t> d_block_last;           // last sorted position needed by each block
+  DevBuf<uint32_t> d_lut;                 // digests as hex [*][16 words]
+  DevBuf<double> d_vtab;                  // LOGINT get_value tables (host-computed by CPython)
+  DevBuf<int32_t> d_order_col;            // sorted position -> first value column
+  DevBuf<int32_t> d_perm_params;          // PERM param indices, by digest slot
+  DevBuf<uint8_t> d_perm_bytes;           // concatenated repr(item) bytes of every PERM param
+  DevBuf<int32_t> d_perm_off;             // per PERM param: S + 1 offsets into d_perm_bytes
+  DevBuf<int32_t> d_perm_offbase;         // per PERM slot: first entry in d_perm_off
+  DevBuf<int32_t> d_perm_len;             // per PERM slot: len(repr(list)) (constant per param)
   int32_t n_comp = 0;                     // params whose inner digest is computed (cslot >= 0)
-  int32_t* d_comp = nullptr;              // cslot -> param index
-  int32_t* d_col_param = nullptr;         // value column -> its param (first column of a non-PERM param), or -1
+  DevBuf<int32_t> d_comp;                 // cslot -> param index
+  DevBuf<int32_t> d_col_param;            // value column -> its param (first column of a non-PERM param), or -1
   // categorical K* (gp_gemm.hip): ENUM / BOOL params are one-hot blocks of the
   // GP features, so their part of |x - u|^2 is (2 or 1) / ell^2 per mismatching
   // param -- an integer dot product of one-hot codes, taken on the int8 MFMA;
@@ -95,15 +146,9 @@ struct Space {
   int32_t n_num = 0;                      // numeric features
   std::vector<int32_t> host_cat;          // the ENUM / BOOL param indices
   std::vector<int32_t> host_num_feat;     // numeric k -> feature column
-  int32_t* d_cat_ccol = nullptr;          // per param: first code column (-1: numeric param)
-  int32_t* d_num_feat = nullptr;          // numeric k -> feature column
-  int32_t* d_feat_num = nullptr;          // feature column -> numeric k, or -1 (categorical)
-};
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
+  DevBuf<int32_t> d_cat_ccol;             // per param: first code column (-1: numeric param)
+  DevBuf<int32_t> d_num_feat;             // numeric k -> feature column
+  DevBuf<int32_t> d_feat_num;             // feature column -> numeric k, or -1 (categorical)
 };
 
 // Per-stage device time of the scoring rounds: events are recorded while the
@@ -125,6 +170,10 @@ struct Timing {
 
 }  // namespace ut
 
+// Every device array of a context is a DevBuf: a member here, of its Space or
+// of a PopSlot.  `delete c` frees them all, so a new buffer is one declaration
+// and nothing else; ut_ctx_destroy itself releases only the streams, events
+// and pinned host buffers.
 struct ut_ctx {
   int device = 0;
   uint64_t seed = 0;
@@ -160,39 +209,38 @@ struct ut_ctx {
   ut::Space space;
   bool has_space = false;
 
-  // population of the selected slot (ut_population_select)
-  double* pop = nullptr;
-  int64_t npop = 0;
-  int64_t pop_cap = 0;
-
-  // PSO state of the selected slot
-  double* pso_vel = nullptr;    // [P][npop]
-  double* pso_best = nullptr;   // [P][npop]
-  int64_t pso_cap = 0;
-
-  // population slots: the techniques of one bandit share a context (its GP
-  // fit, history set, scratch) and keep one population each; the fields
-  // above are the selected slot's, the others are parked here
-  // inner digests sha256(repr(get_value)) of the selected population's
-  // computed-digest params ([n_comp][npop][8]): a DE trial keeps most of its
-  // target's values, so its hash reuses the target's inner digests and
-  // computes only the changed ones (hash.hip launch_hash_de)
-  uint32_t* pop_dig = nullptr;
-  int64_t pop_dig_cap = 0;
-  bool pop_dig_valid = false;
-  // the cache covers members [pop_dig_lo, pop_dig_lo + pop_dig_n) only: the
-  // targets of this context's candidates (a rank's shard of the global pool,
-  // cand_base .. cand_base + m), not the whole replicated population
-  int64_t pop_dig_lo = 0, pop_dig_n = 0;
-  // member-major donor copy of the selected population ([npop + 1][ld], ld =
-  // ncols rounded up to 16 columns = whole 128-B lines), primitive params
-  // stored as their unit values (unit_of), the others raw: k_de gathers its
-  // donors' rows from it in line pieces staged in LDS, with no unit_of left to
-  // compute; row npop holds the best config of the current DE launch.  Rebuilt
-  // from pop when stale, patched by replace.
-  double* pop_aos = nullptr;
-  int64_t pop_aos_cap = 0;
-  bool pop_aos_valid = false;
+  // One population and what is derived from it.  The techniques of one bandit
+  // share a context (its GP fit, history set, scratch) and keep one population
+  // each: `cur` is the selected slot's, the others are parked in pop_slots
+  // (ut_population_select swaps them).
+  struct PopSlot {
+    ut::DevBuf<double> pop;
+    int64_t npop = 0;
+    // PSO state
+    ut::DevBuf<double> pso_vel;    // [P][npop]
+    ut::DevBuf<double> pso_best;   // [P][npop]
+    // inner digests sha256(repr(get_value)) of the population's computed-digest
+    // params ([n_comp][npop][8]): a DE trial keeps most of its target's values,
+    // so its hash reuses the target's inner digests and computes only the
+    // changed ones (hash.hip launch_hash_de)
+    ut::DevBuf<uint32_t> pop_dig;
+    bool pop_dig_valid = false;
+    // the cache covers members [pop_dig_lo, pop_dig_lo + pop_dig_n) only: the
+    // targets of this context's candidates (a rank's shard of the global pool,
+    // cand_base .. cand_base + m), not the whole replicated population
+    int64_t pop_dig_lo = 0, pop_dig_n = 0;
+    // member-major donor copy of the population ([npop + 1][ld], ld = ncols
+    // rounded up to 16 columns = whole 128-B lines), primitive params stored
+    // as their unit values (unit_of), the others raw: k_de gathers its donors'
+    // rows from it in line pieces staged in LDS, with no unit_of left to
+    // compute; row npop holds the best config of the current DE launch.
+    // Rebuilt from pop when stale, patched by replace.
+    ut::DevBuf<double> pop_aos;
+    bool pop_aos_valid = false;
+  };
+  PopSlot cur;
+  std::vector<PopSlot> pop_slots;   // [pop_slot] is empty while that slot is in `cur`
+  int32_t pop_slot = 0;
   int32_t de_aos = 1;   // 0: k_de gathers donor values from the column-major population (UT_DE_AOS=0)
   // the round being enqueued holds its hash for an in-flight fit (dense fp64
   // rounds: api.hip score_round_de_impl)
@@ -213,48 +261,30 @@ struct ut_ctx {
   // (gp.hip chol_diag_core<true>); UT_CHOL_MERGED
   int32_t chol_merged = 1;
 
-  struct PopSlot {
-    double* pop = nullptr;
-    int64_t npop = 0, pop_cap = 0;
-    double* pso_vel = nullptr;
-    double* pso_best = nullptr;
-    int64_t pso_cap = 0;
-    uint32_t* pop_dig = nullptr;
-    int64_t pop_dig_cap = 0;
-    bool pop_dig_valid = false;
-    int64_t pop_dig_lo = 0, pop_dig_n = 0;
-    double* pop_aos = nullptr;
-    int64_t pop_aos_cap = 0;
-    bool pop_aos_valid = false;
-  };
-  std::vector<PopSlot> pop_slots;
-  int32_t pop_slot = 0;
-
   // history set
-  uint32_t* hist_keys = nullptr;   // [cap][8]
-  uint32_t* hist_state = nullptr;  // [cap] 0 empty / 1 full
+  ut::DevBuf<uint32_t> hist_keys;   // [cap][8]
+  ut::DevBuf<uint32_t> hist_state;  // [cap] 0 empty / 1 full
   int64_t hist_cap = 0;
   int64_t hist_count = 0;
 
   // batch dedup table
-  int32_t* batch_slots = nullptr;
-  int64_t batch_cap = 0;
+  ut::DevBuf<int32_t> batch_slots;
 
   // GP state
   int32_t gp_n = 0, gp_d = 0;
   bool gp_ready = false;
-  double* gp_Xs = nullptr;     // [n][d] scaled features
-  double* gp_xnorm = nullptr;  // [n]
-  double* gp_K = nullptr;      // [n][n] work / L
-  double* gp_Linv = nullptr;   // [n][n]
-  double* gp_T = nullptr;      // [n][n] scratch of the recursive inverse
-  double* gp_y = nullptr;      // [n] standardised
-  double* gp_tmp = nullptr;    // [n]
-  double* gp_alpha = nullptr;  // [n]  K^-1 y
-  double* gp_beta = nullptr;   // [n]  L^-1 y (mean from the variance epilogue: mu = (L^-1 k*) . beta)
-  double* gp_inv_ell = nullptr;// [d]
-  double* gp_stats = nullptr;  // [4]: f_best, mean, std, flag
-  int32_t* gp_flag = nullptr;
+  ut::DevBuf<double> gp_Xs;     // [n][d] scaled features
+  ut::DevBuf<double> gp_xnorm;  // [n]
+  ut::DevBuf<double> gp_K;      // [n][n] work / L
+  ut::DevBuf<double> gp_Linv;   // [n][n]
+  ut::DevBuf<double> gp_T;      // [n][n] scratch of the recursive inverse
+  ut::DevBuf<double> gp_y;      // [n] standardised
+  ut::DevBuf<double> gp_tmp;    // [n]
+  ut::DevBuf<double> gp_alpha;  // [n]  K^-1 y
+  ut::DevBuf<double> gp_beta;   // [n]  L^-1 y (mean from the variance epilogue: mu = (L^-1 k*) . beta)
+  ut::DevBuf<double> gp_inv_ell;// [d]
+  ut::DevBuf<double> gp_stats;  // [4]: f_best, mean, std, flag
+  ut::DevBuf<int32_t> gp_flag;
   double gp_sf2 = 1.0;
   int32_t gp_prec = 64;        // precision requested for the next fit
   int32_t gp_fit_prec = 64;    // precision of the fitted factors used by scoring
@@ -266,9 +296,9 @@ struct ut_ctx {
   int32_t gp_fit_kind = 0;     // 0 = the last fit refactored, 1 = it appended rows
   bool gp_linvt_stale = false; // gp_LinvT / gp_alpha not yet written for the current factor (gp_ensure_linvt)
   int32_t* flag_host = nullptr;  // pinned readback of the previous fit's flag
-  float* gp_Xs_f = nullptr;    // fp32 copies for the fp32 MFMA path
-  double* gp_LinvT = nullptr;  // (L^-1)^T [k][row]: the A operand of the variance contraction
-  double* gp_XsT = nullptr;    // (X/ell)^T [dpad][npad]: the A operand of the K* contraction
+  ut::DevBuf<float> gp_Xs_f;    // fp32 copies for the fp32 MFMA path
+  ut::DevBuf<double> gp_LinvT;  // (L^-1)^T [k][row]: the A operand of the variance contraction
+  ut::DevBuf<double> gp_XsT;    // (X/ell)^T [dpad][npad]: the A operand of the K* contraction
   // categorical K* of the current fit (cat_on): numeric-feature operands and
   // the training rows' weighted one-hot codes; c0 + c1 * matches starts the
   // fp64 accumulator (= -|x_cat - u_cat|^2 / 2)
@@ -282,7 +312,7 @@ struct ut_ctx {
   ut::DevBuf<int8_t> bcat;         // [cat_k / 128][ldk][128] candidate codes (one-hot 0/1)
   bool ucand_cat = false;          // ucand / cnorm / bcat hold the categorical K*'s operands (encode path)
   ut::DevBuf<int8_t> pr_bcat;      // pruned scoring: the gathered candidates' codes
-  float* gp_LinvT_f = nullptr;  // fp32 (L^-1)^T; in h3 mode the fp16 hi/lo planes of L^-1 [row][k]
+  ut::DevBuf<float> gp_LinvT_f;  // fp32 (L^-1)^T; in h3 mode the fp16 hi/lo planes of L^-1 [row][k]
   // int8-sliced fp64 tier (precision 8, gp_i8.hip): L^-1 as I8_S digit planes,
   // per-row scales 2^(ea_i + eb) [npad] | e_i^2 [npad] | the bound E [1]
   ut::DevBuf<int8_t> gp_i8a;
@@ -297,7 +327,7 @@ struct ut_ctx {
   int32_t gp_i8_eb = 0;          // K* digit scale: y = k* 2^-eb <= 0.49
   double i8_tol = 0x1p-20;       // accepted relative variance error (ut_gp_set_i8_tol)
   int64_t i8_recomputed = 0;     // candidates of the last score recomputed in fp64 (-1: all, dense)
-  int32_t* gp_ctr = nullptr;   // [32] per-XCD work tickets: [0,8) variance, [8,16) K*; [16,18) max|L^-1| bits (h3)
+  ut::DevBuf<int32_t> gp_ctr;   // [32] per-XCD work tickets: [0,8) variance, [8,16) K*; [16,18) max|L^-1| bits (h3)
   int32_t n_cu = 256;
   // LDS one workgroup may hold (hipDeviceAttributeMaxSharedMemoryPerBlock): the
   // categorical K*'s code-row kernels need code_rows_lds(cat_k) of it
@@ -356,8 +386,8 @@ struct ut_ctx {
   bool r_feat_valid = false;        // r_feat holds the last round's features (pruned rounds only)
 
   // tree-ensemble surrogate (forest.hip)
-  ut_tree_node* forest_nodes = nullptr;
-  int32_t* forest_roots = nullptr;
+  ut::DevBuf<ut_tree_node> forest_nodes;
+  ut::DevBuf<int32_t> forest_roots;
   int32_t forest_trees = 0, forest_rule = 0;
   int32_t forest_max_feat = -1;   // largest feature index of the loaded ensemble's splits
   double forest_base = 0.0, forest_scale = 1.0, forest_div = 1.0;
@@ -393,12 +423,6 @@ struct ut_ctx {
 namespace ut {
 
 int set_err(ut_ctx* c, int code, const std::string& msg);
-
-// every device allocation of the library goes through these two (api.hip):
-// the bytes held per device are what ut_device_bytes reports (a rank's HBM
-// footprint in the bench line)
-hipError_t dmalloc(void** p, size_t bytes);
-void dfree(void* p);
 
 // wait for every stream of the context (before freeing or reusing buffers)
 inline hipError_t sync_all(ut_ctx* c) {
@@ -463,35 +487,34 @@ int ensure(ut_ctx* c, DevBuf<T>& b, size_t n) {
   size_t want = n;
   if (b.p) {
     want = n + std::min(n / 4, ((size_t)2 << 30) / sizeof(T));
-    hipError_t e = ut::sync_all(c);
-    (void)e;
-    (void)ut::dfree(b.p);
-    b.p = nullptr;
-    b.n = 0;
+    (void)ut::sync_all(c);
+    b.reset();
   }
-  hipError_t e = ut::dmalloc((void**)&b.p, (want ? want : 1) * sizeof(T));
+  hipError_t e = b.alloc(want ? want : 1);
   if (e != hipSuccess && want > n) {   // no room for the headroom: exactly n
     (void)hipGetLastError();
     want = n;
-    e = ut::dmalloc((void**)&b.p, (want ? want : 1) * sizeof(T));
+    e = b.alloc(want ? want : 1);
   }
   if (e != hipSuccess) return set_err(c, UT_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  b.n = want;
+  b.n = want;   // (an empty request holds one element and still counts as 0)
   return 0;
 }
 
-// a plain device array outside a DevBuf (the history and batch dedup tables):
-// dmalloc under the same fault injection as ensure().  *p is written only on
-// success, so a caller allocates into locals and commits them once it has all.
-inline int dalloc(ut_ctx* c, void** p, size_t bytes) {
+// a new array of exactly n elements under the same fault injection as
+// ensure(), with neither its headroom nor its sync (the history and batch
+// dedup tables): b is written only on success, so a caller allocates into
+// locals and swaps them in once it has all.
+template <class T>
+int dalloc(ut_ctx* c, DevBuf<T>& b, size_t n) {
   if (inject_alloc_failure(c)) return set_err(c, UT_ENOMEM, "hipMalloc: injected failure (ut_debug_fail_alloc)");
-  void* q = nullptr;
-  const hipError_t e = ut::dmalloc(&q, bytes ? bytes : 1);
+  DevBuf<T> q;
+  const hipError_t e = q.alloc(n ? n : 1);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return set_err(c, UT_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
   }
-  *p = q;
+  b.swap(q);
   return 0;
 }
 
