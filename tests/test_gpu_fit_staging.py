@@ -1,4 +1,4 @@
-"""The staged asynchronous fit (gp.hip gp_fit_enqueue / gp_fit_flush):
+"""The staged asynchronous fit (gp_fit.hip gp_fit_enqueue / gp_fit_flush):
 ut_gp_fit_async stages X, y and the host-side decisions and the fit's launches
 are issued by the next call that needs them -- after a round's proposal, or on
 entry to anything that reads GP state.  Every path must give what a synchronous

@@ -72,7 +72,7 @@ def test_kstar_q_equals_fp64_kstar(monkeypatch, which, n, sf2, ell):
     b = _round(monkeypatch, space, False, n, sf2, ell)
     assert a[5] == b[5] == ("dense" if which == "r64" else "categorical")
     if which == "cat":
-        # categorical fits keep the fp64-MFMA K* (gp.hip gp_score_impl): the same kernels
+        # categorical fits keep the fp64-MFMA K* (gp_score.hip gp_score_impl): the same kernels
         for x, y in zip(a[:5], b[:5]):
             np.testing.assert_array_equal(x, y)
         return

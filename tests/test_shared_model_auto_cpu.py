@@ -1,6 +1,6 @@
 """SharedModel(lengthscale="auto") (technique.py): the lengthscale is the grid
 candidate with the largest log marginal likelihood, chosen at the first fit and
-wherever the fit's padded size (128 rows, gp.hip NPAD) changes -- never between,
+wherever the fit's padded size (128 rows, ut_internal.h NPAD) changes -- never between,
 so the device's incremental fits keep identical hyperparameters.  CPU only: the
 oracle engine grows a gp_lml_grid built on oracle/gp.py and records every call."""
 import os

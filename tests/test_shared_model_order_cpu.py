@@ -1,5 +1,5 @@
 """SharedModel's training-row order (technique.py SharedModel.fit): best y first
-at every refit point (a new padded size of 128 rows, as gp.hip NPAD), new results
+at every refit point (a new padded size of 128 rows, as ut_internal.h NPAD), new results
 appended in arriving order in between, so the device's incremental fit still
 sees a bitwise prefix.  CPU only: a stand-in engine records what gp_fit gets."""
 import types

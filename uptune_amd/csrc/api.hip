@@ -259,7 +259,7 @@ int ut_ctx_create(int device, uint64_t seed, ut_ctx** out) {
   if (const char* e = getenv("UT_CHOL_FUSE")) c->chol_fuse = atoi(e);
   if (const char* e = getenv("UT_TRINV_BIG")) c->trinv_big = atoi(e);
   if (const char* e = getenv("UT_CHOL_MERGED")) c->chol_merged = atoi(e);
-  // the fit kernels' waves at s_setprio 3 (gp.hip g_fit_prio): beside the
+  // the fit kernels' waves at s_setprio 3 (gp_fit.hip g_fit_prio): beside the
   // round's hash grid their instructions go first
   if (ut::set_fit_prio(1)) {
     ut_ctx_destroy(c);

@@ -1,4 +1,5 @@
-// gp.hip -- Gaussian-process surrogate (fit + batched posterior + acquisition).
+// gp_fit.hip -- Gaussian-process surrogate: the spec, and the fit.  (The
+// batched posterior + acquisition: gp_score.hip; the pruned top-k: gp_prune.hip.)
 //
 // No reference arithmetic exists for this stage; the spec is
 // SURVEY.md §8(a) row a7 / "GP spec for a7":
@@ -13,27 +14,13 @@
 // Fit (per round, O(n^3), small): blocked right-looking Cholesky (NB = 64,
 // panel factor + solve in LDS, trailing update tiles), blocked triangular
 // inverse by block rows, two mat-vecs for alpha.
-//
-// Score (per candidate, the MFMA-bound stage): both dense contractions are
-//   C[n x m] = A[n x K] * B[K x m]
-// with A small and row-major (L2/MALL resident) and B the candidate-major
-// stream (columns = candidates, coalesced along m):
-//   GEMM1: A = Xs [n x d],    B = U^T (features, [d][m]) -> K*^T  [n][m] + mu partials
-//   GEMM2: A = L^-1 [n x n],  B = K*^T [n][m]  (lower-triangular A: K loop stops
-//          at the tile's diagonal)  -> |L^-1 k*|^2 partials
-// Both run in gp_gemm.hip (fp64 MFMA by default, fp32 MFMA when
-// ut_gp_set_precision(ctx, 32); with 16 the variance GEMM runs as three fp16
-// MFMA products of hi/lo split operands, fp32-class accuracy).
 #include <cstring>
-
 #include <thread>
 
 #include "gp_tiles.h"
 #include "ut_internal.h"
 
 namespace ut {
-
-constexpr int NPAD = 128;  // training set padded to the GEMM row tile
 
 // ---------------------------------------------------------------------------
 // fit
@@ -676,132 +663,6 @@ __global__ __launch_bounds__(256) void k_app_c(double* __restrict__ Li, double* 
 }
 
 // ---------------------------------------------------------------------------
-// score
-// ---------------------------------------------------------------------------
-// scaled candidate norms |u / ell|^2
-__global__ void k_gp_cnorm(const double* __restrict__ feat, int64_t ld, int64_t m, int32_t d,
-                           const double* __restrict__ inv_ell, double* __restrict__ cn) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  double s = 0.0;
-  for (int32_t k = 0; k < d; ++k) {
-    const double v = feat[(int64_t)k * ld + i] * inv_ell[k];
-    s += v * v;
-  }
-  cn[i] = s;
-}
-
-__device__ __forceinline__ double acq_score(int kind, double mu, double var, double f_best, double xi,
-                                            double kappa) {
-  const double sigma = sqrt(var);
-  if (kind == UT_ACQ_UCB) return kappa * sigma - mu;
-  const double I = f_best - mu - xi;
-  if (!(sigma > 0.0)) return I > 0.0 ? I : 0.0;
-  const double z = I / sigma;
-  const double Phi = 0.5 * erfc(-z * 0.70710678118654752440);
-  const double phi = exp(-0.5 * z * z) * 0.39894228040143267794;
-  return I * Phi + sigma * phi;
-}
-
-__global__ void k_gp_finalize(int64_t m, int32_t RT1, int32_t RT2, const double* __restrict__ mu_part,
-                              const double* __restrict__ var_part, int64_t ldp, double sf2,
-                              const double* __restrict__ stats, const int32_t* __restrict__ fit_flag, int32_t kind,
-                              double xi, double kappa, const uint8_t* __restrict__ dup, double* __restrict__ mu_out,
-                              double* __restrict__ var_out, double* __restrict__ score_out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  double mu = 0.0, vs = 0.0;
-  for (int32_t r = 0; r < RT1; ++r) mu += mu_part[(int64_t)r * ldp + i];
-  for (int32_t r = 0; r < RT2; ++r) vs += var_part[(int64_t)r * ldp + i];
-  double var = sf2 - vs;
-  var = var > 0.0 ? var : 0.0;
-  double sc = acq_score(kind, mu, var, stats[0], xi, kappa);
-  if (*fit_flag != 0) {  // failed (asynchronous) fit: nothing is selectable
-    mu = var = sc = __builtin_nan("");
-  }
-  if (dup && dup[i]) sc = -1.0 / 0.0;
-  if (mu_out) mu_out[i] = mu;
-  if (var_out) var_out[i] = var;
-  if (score_out) score_out[i] = sc;
-}
-
-// precision 8 (gp_i8.hip): |v|^2 and the mean mu = v . beta (beta = L^-1 y)
-// from the int8 contraction's partials; a candidate is finished here only if
-//   | |v|^2 - s | <= E (2 sqrt(s) + E) + s (2n + 64) 2^-53     (s = the computed sum)
-// is at most tol * (sf2 - s) -- its variance is then within tol relative of the
-// exact one -- and the mean's bound Emu = sum_r e_r |beta_r| (+ the fp64
-// rounding of the sums, (2n + 64) 2^-53 |mu| |beta|-weighted, below Emu's own
-// 2^-40 slack at these sizes) is at most tol * sigma: the mean within tol of
-// the posterior's own scale.  Every other candidate (near a training point sf2 - |v|^2 cancels;
-// or a failed fit) is appended to idx_out for the fp64 recompute (k_gp_fix_i8),
-// one atomic per wave; its outputs are written anyway and overwritten there.
-// Duplicates (dup[i], score -inf) are never flagged.
-__global__ void k_gp_finalize_i8(int64_t m, int32_t RT1, int32_t RT2, const double* __restrict__ mu_part,
-                                 const double* __restrict__ var_part, int64_t ldp, double sf2,
-                                 const double* __restrict__ stats, const int32_t* __restrict__ fit_flag, int32_t kind,
-                                 double xi, double kappa, const uint8_t* __restrict__ dup, double* __restrict__ mu_out,
-                                 double* __restrict__ var_out, double* __restrict__ score_out,
-                                 const double* __restrict__ Ebound, double tol, int32_t n, int64_t* __restrict__ idx_out,
-                                 unsigned long long* __restrict__ count) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  bool flag = false;
-  if (i < m) {
-    double mu = 0.0, vs = 0.0;
-    for (int32_t r = 0; r < RT1; ++r) mu += mu_part[(int64_t)r * ldp + i];
-    for (int32_t r = 0; r < RT2; ++r) vs += var_part[(int64_t)r * ldp + i];
-    double var = sf2 - vs;
-    var = var > 0.0 ? var : 0.0;
-    const double E = Ebound[0], Emu = Ebound[1];
-    const double bound = E * (2.0 * sqrt(vs) + E) + vs * (double)(2 * n + 64) * 0x1p-53;
-    flag = !(bound <= tol * var) || !(Emu <= tol * sqrt(var));   // (NaN: flagged)
-    double sc = acq_score(kind, mu, var, stats[0], xi, kappa);
-    if (*fit_flag != 0) {
-      mu = var = sc = __builtin_nan("");
-      flag = false;   // nothing to recompute: the fit failed
-    }
-    if (dup && dup[i]) {
-      // a duplicate of the history is a training point, where sf2 - |v|^2
-      // cancels and the bound always fails: its score is -inf whatever the
-      // variance, so it is not recomputed (its var output stays this tier's)
-      sc = -1.0 / 0.0;
-      flag = false;
-    }
-    if (mu_out) mu_out[i] = mu;
-    if (var_out) var_out[i] = var;
-    if (score_out) score_out[i] = sc;
-  }
-  const unsigned long long ball = __ballot(flag);
-  const uint32_t nf = __builtin_popcountll(ball);
-  unsigned long long base = 0;
-  if (lane == 0 && nf) base = atomicAdd(count, (unsigned long long)nf);
-  base = __shfl(base, 0, 64);
-  if (flag) idx_out[base + __builtin_popcountll(ball & ((1ull << lane) - 1ull))] = i;
-}
-
-// the flagged candidates' fp64 mean and variance (recomputed K* columns through
-// the fp64 contraction, RT partials each of v^2 and of v . beta) -> mu, var, score
-__global__ void k_gp_fix_i8(int64_t nf, const int64_t* __restrict__ idx, int32_t RT, const double* __restrict__ mpart,
-                            const double* __restrict__ vpart, int64_t ldv, double sf2,
-                            const double* __restrict__ stats, int32_t kind, double xi, double kappa,
-                            const uint8_t* __restrict__ dup, double* __restrict__ mu_out, double* __restrict__ var_out,
-                            double* __restrict__ score_out) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= nf) return;
-  const int64_t i = idx[j];
-  double mu = 0.0, vs = 0.0;
-  for (int32_t r = 0; r < RT; ++r) mu += mpart[(int64_t)r * ldv + j];
-  for (int32_t r = 0; r < RT; ++r) vs += vpart[(int64_t)r * ldv + j];
-  double var = sf2 - vs;
-  var = var > 0.0 ? var : 0.0;
-  double sc = acq_score(kind, mu, var, stats[0], xi, kappa);
-  if (dup && dup[i]) sc = -1.0 / 0.0;
-  if (mu_out) mu_out[i] = mu;
-  if (var_out) var_out[i] = var;
-  if (score_out) score_out[i] = sc;
-}
-
-// ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
 static void launch_chol_diag(ut_ctx* c, int32_t npad, int32_t kb) {
@@ -815,7 +676,7 @@ static int gp_alloc(ut_ctx* c, int32_t npad_need, int32_t d) {
   // a new padded size then reuses the buffers instead of freeing and
   // allocating ~5 n^2 doubles behind a device-wide sync (2.5-10 ms per 128
   // rows in the C5 loop).  Every kernel indexes with the fit's own npad.
-  const size_t npad = (size_t)((npad_need + npad_need / 4 + NPAD - 1) / NPAD) * NPAD;
+  const size_t npad = (size_t)gp_npad(npad_need + npad_need / 4);
   UT_HIP(c, ut::sync_all(c));   // earlier rounds may still read the buffers replaced here
   // no capacity until every buffer exists: after a failure part-way the next
   // call allocates them all again
@@ -1051,7 +912,7 @@ static bool par_rows(int32_t r0, int32_t r1, int32_t d, F&& f) {
 // and, on the device, by NaN scores from k_gp_finalize.
 int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h) {
   UT_CHECK(c, n >= 1 && d >= 1 && X && y && h && h->lengthscale_host, UT_EINVAL, "gp_fit: bad arguments");
-  const int32_t npad = ((n + NPAD - 1) / NPAD) * NPAD;
+  const int32_t npad = gp_npad(n);
   UT_CHECK(c, c->gp_prec != 8 || npad <= I8_MAX_K, UT_EINVAL,
            "gp_fit: precision 8 takes at most 16384 training points (exact int32 digit sums)");
   // a fit staged and never used is enqueued first (its staging is about to be
@@ -1082,9 +943,7 @@ int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32
     }
   }
   if ((rc = gp_alloc(c, npad, d))) return rc;
-  c->pr_f2_valid = false;   // |L^-1|_F^2 (pruned scoring) belongs to the previous factor
-  c->pr_ab_valid = false;
-  c->pr_xf_valid = false;
+  ++c->fit_gen;   // what pruned scoring cached of the previous fit (|L^-1|_F^2, ...) is stale
   const size_t need = (size_t)n * d + n + d;
   bool fresh = false;   // a new staging buffer holds no previous rows
   if (c->fit_host_n < need) {
@@ -1221,693 +1080,6 @@ int gp_wait_fit(ut_ctx* c) {
   if (flag != 0) {
     c->gp_ready = false;
     return set_err(c, UT_ENOTPD, "gp_fit: kernel matrix is not positive definite (raise jitter)");
-  }
-  return 0;
-}
-
-int gp_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m) {
-  UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_score: call ut_gp_fit first");
-  if (m <= 0) return 0;
-  int rc;
-  if ((rc = gp_fit_flush(c))) return rc;
-  // 1/ell comes with the fit's scaled training inputs
-  if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit_x, 0));
-  const int64_t ldk = ((m + VAR_BN - 1) / VAR_BN) * VAR_BN;   // as gp_score_impl
-  if ((rc = ensure(c, c->cnorm, (size_t)ldk))) return rc;
-  if (c->cat_on) {   // numeric U', norms and the one-hot codes (categorical K*)
-    const int32_t dpn = cat_dpad(c);
-    if ((rc = ensure(c, c->ucand, (size_t)(dpn > 0 ? dpn : 1) * ldk))) return rc;
-    if ((rc = ensure(c, c->bcat, (size_t)c->space.cat_k * ldk))) return rc;
-    c->ucand_cat = true;
-    return launch_encode_scaled_cat(c, values, ld, m, c->ucand.p, dpn, ldk, c->cnorm.p, c->bcat.p);
-  }
-  const int32_t dpad = kstar_dpad(c->gp_d);
-  if ((rc = ensure(c, c->ucand, (size_t)dpad * ldk))) return rc;
-  c->ucand_cat = false;
-  return launch_encode_scaled(c, values, ld, m, c->ucand.p, dpad, ldk, c->cnorm.p);
-}
-
-// the categorical operands of the current fit for launch_gemm_kstar
-static KstarCat kstar_cat(ut_ctx* c, const int8_t* bcat) {
-  KstarCat k;
-  k.acat = c->gp_acat.p;
-  k.bcat = bcat;
-  k.nkc = c->space.cat_k / 128;
-  k.c0 = c->cat_c0;
-  k.c1 = c->cat_c1;
-  return k;
-}
-
-static int gather_kstar_cols(ut_ctx* c, bool cat, int32_t dpad, int64_t ldk, const int64_t* idx, int64_t base,
-                             int64_t nc, int64_t ldc, double* mu_part = nullptr);
-
-int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
-                  double* mu, double* var, double* score, hipEvent_t dup_ready) {
-  UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_score: call ut_gp_fit first");
-  UT_CHECK(c, acq != nullptr, UT_EINVAL, "gp_score: acq is NULL");
-  if (m <= 0) return 0;
-  if (int rc0 = gp_fit_flush(c)) return rc0;
-  const int prec = c->gp_fit_prec;
-  const bool fp32 = prec != 64;  // fp32, h3 (f16x3) and i8: K* stores a reduced-precision K*
-  const bool i8 = prec == 8;
-  // the mean in K*'s fp64 epilogue (k* . alpha, before k* is rounded): fp32 and h3
-  const bool kmu = fp32 && !i8;
-  // fp64 and i8: K* needs only the scaled training inputs (ev_fit_x) and the
-  // mean comes from the variance epilogue, mu = (L^-1 k*) . (L^-1 y), so K*
-  // overlaps the rest of an asynchronous fit and only the variance GEMM waits
-  // for L^-1 (i8: |mu - mu^| <= Emu, gp_i8.hip).  fp32 / h3 keep the mean in
-  // K*'s fp64 epilogue and wait for the whole fit.
-  if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, kmu ? c->ev_fit : c->ev_fit_x, 0));
-  mark(c, "fit_wait");   // (the wait is not K* time)
-  const int32_t n = c->gp_n, d = c->gp_d;
-  const int32_t npad = ((n + NPAD - 1) / NPAD) * NPAD;
-  // the categorical K* when the candidates came through ut's encoder
-  // (gp_encode_scaled in categorical mode); a caller's feature matrix takes the
-  // dense contraction over every feature
-  const bool cat = !feat && c->cat_on && c->ucand_cat;
-  const int32_t dpad = cat ? cat_dpad(c) : kstar_dpad(d);
-  // K* rows padded to whole variance column tiles: the variance kernel reads
-  // full 256-candidate strips (the K* kernel writes zeros past m)
-  const int64_t ldk = ((m + VAR_BN - 1) / VAR_BN) * VAR_BN;
-  const int32_t RT = npad / NPAD;
-  int rc;
-  if ((rc = ensure(c, c->kst, (size_t)npad * ldk))) return rc;
-  // (i8: the variance and mean partials come per 64-row tile)
-  if ((rc = ensure(c, c->mu_part, (size_t)(i8 ? 2 * RT : RT) * ldk))) return rc;
-  if ((rc = ensure(c, c->var_part, (size_t)(i8 ? 2 * RT : RT) * ldk))) return rc;
-  if ((rc = ensure(c, c->cnorm, (size_t)ldk))) return rc;
-  if ((rc = ensure(c, c->ucand, (size_t)(dpad > 0 ? dpad : 1) * ldk))) return rc;
-  if (i8) {
-    UT_CHECK(c, npad <= I8_MAX_K, UT_EINVAL, "gp_score: precision 8 takes at most 16384 training points");
-    if ((rc = ensure(c, c->pr_idx, (size_t)ldk))) return rc;
-    if ((rc = ensure(c, c->pr_count, 1))) return rc;
-  }
-  if (feat) {
-    if ((rc = launch_prep_cand(c, feat, ld, m, d, dpad, c->ucand.p, ldk, c->cnorm.p))) return rc;
-    c->ucand_cat = false;
-    mark(c, "cnorm");
-  }
-  if (i8 && c->kstar_q && !c->cat_on && c->gp_x8.p) {
-    // the distance contraction on the int8 MFMA (gp_kq.hip): beside the round's
-    // hash its MFMAs issue under the hash's integer VALU work (C2 ~1 % per
-    // round).  Categorical fits keep the fp64-MFMA K* (C3 HPL-64: K* 43 against
-    // 28.5 ms, the round 288 against 270; C4 no better; scripts/r06_lines.sh)
-    if ((rc = launch_gemm_kstar_q(c, true, c->gp_XsT.p, npad, c->ucand.p, dpad, m, c->kst.p, ldk, nullptr, -1, nullptr,
-                                  nullptr, KstarCat(), nullptr, c->u8, c->scol)))
-      return rc;
-  } else if ((rc = launch_gemm_kstar(c, prec, cat ? c->gp_XsT_num.p : c->gp_XsT.p, npad, c->ucand.p, dpad, m, c->kst.p,
-                                     ldk, kmu ? c->mu_part.p : nullptr, -1, nullptr, nullptr,
-                                     cat ? kstar_cat(c, c->bcat.p) : KstarCat(), cat ? c->gp_xnorm_num.p : nullptr))) {
-    return rc;
-  }
-  mark(c, "kstar");
-  if (c->fit_pending && !kmu) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));
-  // fp64 / fp32 / h3: the variance GEMM runs alone, the side stream's hash +
-  // dedup share the CUs with K* only (C2: 27.95 -> 28.2 ms per round when they
-  // spilled into it, the GEMM at 0.74 instead of 0.80 of peak; round 1).  i8:
-  // it starts when K* ends and the hash's tail runs beside it (only the
-  // finalize needs the dup mask): C2 16.60 -> 16.40 ms at ell 0.2, 19.62 ->
-  // 19.36 at ell 2, C3 / C4 unchanged (their hash ends before K*;
-  // scripts/ab/r06_varjoin*.sh, r06_sched.sh)
-  if (dup_ready && !i8) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));
-  mark(c, "var_wait");  // the wait for the fit (and the dup mask) is not variance time
-  if (i8) {
-    if ((rc = launch_gemm_var_i8(c, npad, reinterpret_cast<const int8_t*>(c->kst.p), ldk, m, c->var_part.p,
-                                 c->mu_part.p)))
-      return rc;
-  } else if ((rc = launch_gemm_var(c, prec, fp32 ? (const void*)c->gp_LinvT_f.p : (const void*)c->gp_LinvT.p, npad,
-                                   c->kst.p, ldk, npad, m, c->var_part.p, fp32 ? nullptr : c->gp_beta.p,
-                                   fp32 ? nullptr : c->mu_part.p))) {
-    return rc;
-  }
-  mark(c, "var");
-  if (dup_ready) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));
-  if (i8) {
-    // the bound test, then the fp64 recompute of the candidates it did not clear
-    UT_HIP(c, hipMemsetAsync(c->pr_count.p, 0, sizeof(int64_t), c->stream));
-    hipLaunchKernelGGL(k_gp_finalize_i8, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, 2 * RT, 2 * RT, c->mu_part.p,
-                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
-                       mu, var, score, c->gp_i8rs.p + 2 * npad, c->i8_tol, n, c->pr_idx.p,
-                       reinterpret_cast<unsigned long long*>(c->pr_count.p));
-    UT_LAUNCH_CHECK(c);
-    mark(c, "finalize");
-    int64_t nf = 0;
-    UT_HIP(c, hipMemcpyAsync(&nf, c->pr_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    UT_HIP(c, hipStreamSynchronize(c->stream));
-    c->i8_recomputed = nf;
-    if (nf > 0 && (rc = gp_ensure_linvt(c))) return rc;   // (the fp64 contraction reads (L^-1)^T)
-    if (nf * 2 > m) {
-      // most candidates need fp64: the whole K* (fp64, over the planes) and the
-      // fp64 contraction, with the mean from its epilogue
-      c->i8_recomputed = -1;
-      if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldk))) return rc;
-      if ((rc = launch_gemm_kstar(c, 64, cat ? c->gp_XsT_num.p : c->gp_XsT.p, npad, c->ucand.p, dpad, m, c->kst.p, ldk,
-                                  nullptr, -1, nullptr, nullptr, cat ? kstar_cat(c, c->bcat.p) : KstarCat(),
-                                  cat ? c->gp_xnorm_num.p : nullptr)))
-        return rc;
-      if ((rc = launch_gemm_var(c, 64, c->gp_LinvT.p, npad, c->kst.p, ldk, npad, m, c->var_part.p, c->gp_beta.p,
-                                c->pr_mpart.p)))
-        return rc;
-      hipLaunchKernelGGL(k_gp_finalize, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, RT, c->pr_mpart.p,
-                         c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
-                         mu, var, score);
-      UT_LAUNCH_CHECK(c);
-    } else if (nf > 0) {
-      const int64_t ldf = (nf + VAR_BN - 1) / VAR_BN * VAR_BN;
-      if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldf))) return rc;
-      if ((rc = gather_kstar_cols(c, cat, dpad, ldk, c->pr_idx.p, 0, nf, ldf))) return rc;
-      if ((rc = launch_gemm_var(c, 64, c->gp_LinvT.p, npad, c->pr_kst.p, ldf, npad, nf, c->pr_vpart.p, c->gp_beta.p,
-                                c->pr_mpart.p)))
-        return rc;
-      hipLaunchKernelGGL(k_gp_fix_i8, dim3(grid1(nf, 256)), dim3(256), 0, c->stream, nf, c->pr_idx.p, RT,
-                         c->pr_mpart.p, c->pr_vpart.p, ldf, c->gp_sf2, c->gp_stats.p, acq->kind, acq->xi, acq->kappa,
-                         dup, mu, var, score);
-      UT_LAUNCH_CHECK(c);
-    }
-    mark(c, "recompute");
-    return 0;
-  }
-  // h3's variance partials come per 256-row tile
-  const int32_t RTv = prec == 16 ? (npad + 255) / 256 : RT;
-  hipLaunchKernelGGL(k_gp_finalize, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, RTv, c->mu_part.p,
-                     c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
-                     mu, var, score);
-  UT_LAUNCH_CHECK(c);
-  mark(c, "finalize");
-  return 0;
-}
-
-
-// ---------------------------------------------------------------------------
-// Selection-exact EI-bound pruning (ut_gp_topk_pruned).
-//   var = sf2 - sum_r (L^-1 k*)_r^2 and every term is >= 0, so the partial
-//   sum over the first R row tiles bounds var from above; EI (and UCB with
-//   kappa >= 0) increases with sigma, so the same holds for the score.  The
-//   R-tile partials are bitwise the first R partials of the full GEMM (same
-//   tiles, same k order) and fp addition of non-negative terms and sf2 - x are
-//   monotone, so var_exact <= var_bound holds in floating point too; the score
-//   bound gets a 1e-12 relative margin for the acquisition's own rounding.
-// ---------------------------------------------------------------------------
-// The score bound of a candidate from the first RTv row tiles of the
-// variance contraction.  The mean is exact (every row's k* went into it).
-//   var_ub = sf2 - S_R, S_R = the sum of the first RTv partials; the score of
-//   var_ub, raised by a 1e-12 relative margin for the rounding of the
-//   acquisition function, bounds the exact score from above.
-//   Exactness test: the rows past the bound contribute at most
-//   T = sum_{r >= R} v_r^2 <= |L^-1|_F^2 |k*|^2 (|v_r| <= |L^-1_r| |k*|), the
-//   computed partials at most 1.001 T, and the exact path's running sum starts
-//   from the same S_R (its first RTv partials are bitwise these) and only adds
-//   non-negative terms, so its var lies in [max(sf2 - S_hi, 0), var_ub] with
-//   S_hi = (S_R + 1.001 T)(1 + 2^-40).  When both ends round to the same double
-//   the exact var IS var_ub, and so is the exact score: it is stored without
-//   the margin and flagged exact, and ties with it can be broken by index
-//   (a flat GP -- every k* ~ 0 -- gives every candidate the same score).
-__global__ void k_prune_bound(int64_t m, int32_t RTm, const double* __restrict__ mu_part, int32_t RTv,
-                              const double* __restrict__ var_part, int64_t ldp, double sf2,
-                              const double* __restrict__ stats, const int32_t* __restrict__ fit_flag, int32_t kind,
-                              double xi, double kappa, const uint8_t* __restrict__ dup, double* __restrict__ mu_out,
-                              double* __restrict__ ub_out, const double* __restrict__ k2_part,
-                              const double* __restrict__ linv_f2, uint8_t* __restrict__ exact_out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  double mu = 0.0, vs = 0.0, k2 = 0.0;
-  for (int32_t r = 0; r < RTm; ++r) mu += mu_part[(int64_t)r * ldp + i];
-  for (int32_t r = 0; r < RTv; ++r) vs += var_part[(int64_t)r * ldp + i];
-  double var = sf2 - vs;
-  var = var > 0.0 ? var : 0.0;
-  double ub = acq_score(kind, mu, var, stats[0], xi, kappa);
-  bool exact = false;
-  if (k2_part && RTv < RTm) {
-    for (int32_t r = 0; r < RTm; ++r) k2 += k2_part[(int64_t)r * ldp + i];
-    const double tail = 1.001 * (*linv_f2) * k2;
-    const double s_hi = (vs + tail) * (1.0 + 0x1p-40);
-    double var_lo = sf2 - s_hi;
-    var_lo = var_lo > 0.0 ? var_lo : 0.0;
-    exact = tail == tail && var_lo == var;   // (NaN tail: not exact)
-  } else if (RTv >= RTm) {
-    exact = true;   // the bound GEMM covered every row
-  }
-  if (!exact) ub = ub + fabs(ub) * 1e-12 + 1e-300;
-  if (*fit_flag != 0) {
-    mu = ub = __builtin_nan("");
-    exact = false;
-  }
-  if (dup && dup[i]) ub = -1.0 / 0.0;
-  mu_out[i] = mu;
-  ub_out[i] = ub;
-  if (exact_out) exact_out[i] = exact ? 1 : 0;
-}
-
-// The bound of the f32 pass (ut_gp_set_prune_pass 32, k_gp_kstar_f32c): the
-// stored bound rows in fp64 as before, every other k*^ = sf2 2^t^ with |k*^ -
-// k*| <= rho k*^ / (1 - rho) + 2^-125 sf2 (v_exp_f32 flushes below 2^-126), its
-// f32 tile sums within 2^-19 of sum |alpha| k*^.  rho = 2^dt (1 + 2^-21) - 1 per
-// candidate, dt = (Kc + 9) 2^-24 (2 |c0| + max_r |x_r|^2 + |u|^2) / ln 2 (log2
-// units; Kc the contraction length, c0 the categorical offset; the f32
-// contraction's bound, see k_gp_kstar_f32c).  Per candidate:
-//   mean  |mu - mu^| <= dmu = (rho / (1 - rho) + 2^-19) S + 2^-125 sf2 sum|alpha|
-//         + RT 2^-51 sum_rt |mu^_rt|: S = sum_r |alpha_r| k*^_r over the f32 rows (part3),
-//         mu the fp64 k* . alpha the survivors are scored with (k_gp_kstar's
-//         fp64 epilogue on their columns: its bound-row tile partials are these
-//         bitwise, its other tiles within the first term; the last term the
-//         different rounding of the two sums over tiles);
-//   bound rows  exact k*: var <= var_ub = sf2 - |v^_R|^2 (as k_prune_bound);
-//   lower end (rows past R: |L^-1|_F^2 |k*|^2 as k_prune_bound's tail)
-//         var >= var_lo = sf2 - (|v^_R|^2 + 1.001 |L^-1|_F^2 ((1 + rho') |k*^| +
-//         sqrt(n) 2^-125 sf2)^2);
-// the score bound is the acquisition at (mu^ - dmu, var_ub), raised by
-// k_prune_bound's 1e-12 margin -- unless both ends pin the exact score: var_lo
-// == var_ub and the mean's two ends give the same I = f_best - mu - xi (EI) or
-// the same score (UCB); then the exact score is that double, stored as is and
-// flagged exact (a flat GP keeps its index tie-break).  fp64 rounding of the
-// sums: a 2^-36 margin.  cst: [0] |L^-1|_F^2, [1 + SQ_BLOCKS] sum |alpha|,
-// [2 + SQ_BLOCKS] max_r |x_r|^2.
-constexpr int SQ_BLOCKS = 1024;
-__global__ void k_prune_bound32(int64_t m, int32_t RTm, const double* __restrict__ mu_part,
-                                const double* __restrict__ sa_part, const double* __restrict__ k2_part, int32_t RTv,
-                                const double* __restrict__ var_part, int64_t ldp, double sf2, int32_t n,
-                                const double* __restrict__ stats, const int32_t* __restrict__ fit_flag, int32_t kind,
-                                double xi, double kappa, const uint8_t* __restrict__ dup,
-                                const double* __restrict__ cst, double* __restrict__ ub_out,
-                                uint8_t* __restrict__ exact_out, int32_t Kc, double c0abs,
-                                const double* __restrict__ cnorm) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  double mu = 0.0, mabs = 0.0, sa = 0.0, k2 = 0.0, vs = 0.0;
-  for (int32_t r = 0; r < RTm; ++r) {
-    const int64_t o = (int64_t)r * ldp + i;
-    mu += mu_part[o];
-    mabs += fabs(mu_part[o]);
-    sa += sa_part[o];
-    k2 += k2_part[o];
-  }
-  for (int32_t r = 0; r < RTv; ++r) vs += var_part[(int64_t)r * ldp + i];
-  const double F2 = cst[0], A1 = cst[1 + SQ_BLOCKS];
-  const double tiny = 0x1p-125 * sf2;
-  const double dt = (Kc + 9.0) * 0x1p-24 * (2.0 * c0abs + cst[2 + SQ_BLOCKS] + cnorm[i]) * 1.4426950408889634 *
-                        (1.0 + 0x1p-20) + Kc * 0x1p-120;
-  const double rho = (exp2(dt) * (1.0 + 0x1p-21) - 1.0) * (1.0 + 0x1p-20) + 0x1p-50;
-  const double rp = rho / (1.0 - rho);   // |k*^ - k*| / k*^ (rho < 1/2, or the bound is useless: NaN below)
-  const double dmu = ((rp + 0x1p-19) * sa * (1.0 + 0x1p-18) + tiny * A1 + (double)RTm * 0x1p-51 * mabs) *
-                     (1.0 + 0x1p-20);
-  double var_ub = sf2 - vs;   // the bound rows' partials: bitwise the exact GEMM's first RTv (k_prune_bound)
-  var_ub = var_ub > 0.0 ? var_ub : 0.0;
-  const double kn = (1.0 + rp) * sqrt(k2 * (1.0 + 0x1p-18)) + sqrt((double)n) * tiny;
-  const double tail = 1.001 * F2 * kn * kn;
-  double var_lo = sf2 - (vs + tail) * (1.0 + 0x1p-36);
-  var_lo = var_lo > 0.0 ? var_lo : 0.0;
-  double ub = acq_score(kind, mu - dmu, var_ub, stats[0], xi, kappa);
-  bool exact = var_lo == var_ub && dmu == dmu;
-  if (exact) {
-    if (kind == UT_ACQ_UCB)
-      exact = ub == acq_score(kind, mu + dmu, var_lo, stats[0], xi, kappa);
-    else
-      exact = (stats[0] - (mu - dmu) - xi) == (stats[0] - (mu + dmu) - xi);
-  }
-  if (!exact) ub = ub + fabs(ub) * 1e-12 + 1e-300;
-  if (!(rho < 0.5)) {   // no usable bound: the candidate survives
-    ub = 1.0 / 0.0;
-    exact = false;
-  }
-  if (*fit_flag != 0) {
-    ub = __builtin_nan("");
-    exact = false;
-  }
-  if (dup && dup[i]) ub = -1.0 / 0.0;
-  ub_out[i] = ub;
-  exact_out[i] = exact ? 1 : 0;
-}
-
-// max of x[0 .. n) (one workgroup): the f32-contraction bound's max_r |x_r|^2
-__global__ __launch_bounds__(256) void k_max_n(const double* __restrict__ x, int32_t n, double* __restrict__ out) {
-  __shared__ double red[4];
-  double v = 0.0;
-  for (int32_t e = threadIdx.x; e < n; e += 256) v = fmax(v, x[e]);
-  for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
-// sum of squares of cnt doubles (|L^-1|_F^2), deterministic: pass 1 writes one
-// partial per block (grid-stride), pass 2 (one block) adds them in order
-template <bool ABS>   // ABS: sum |x| instead
-__global__ __launch_bounds__(256) void k_sumsq_part(const double* __restrict__ x, int64_t cnt,
-                                                    double* __restrict__ part) {
-  __shared__ double red[4];
-  double s = 0.0;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (int64_t)gridDim.x * 256)
-    s += ABS ? fabs(x[e]) : x[e] * x[e];
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-__global__ __launch_bounds__(256) void k_sumsq_final(const double* __restrict__ part, int32_t n,
-                                                     double* __restrict__ out) {
-  __shared__ double red[4];
-  double s = 0.0;
-  for (int32_t e = threadIdx.x; e < n; e += 256) s += part[e];
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the categorical K* codes of gathered candidates: 16-byte pieces of their
-// 128-byte rows, code block blockIdx.y (zeros past n and for empty slots)
-__global__ void k_gather_code_rows(const int8_t* __restrict__ bcat, int64_t ldk, const int64_t* __restrict__ idx,
-                                   int64_t base, int64_t n, int64_t ldo, int8_t* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t kb = blockIdx.y;
-  const int64_t j = e >> 3;
-  const int piece = (int)(e & 7);
-  if (j >= ldo) return;
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (j < n) {
-    const int64_t q = idx[j];
-    if (q >= 0) v = reinterpret_cast<const uint4*>(bcat + (kb * ldk + (q - base)) * 128)[piece];
-  }
-  reinterpret_cast<uint4*>(out + (kb * ldo + j) * 128)[piece] = v;
-}
-
-__global__ void k_gather_cols(const double* __restrict__ kst, int64_t ldk, const int64_t* __restrict__ idx,
-                                  int64_t base, int64_t n, int64_t ldo, double* __restrict__ out) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t r = blockIdx.y;
-  if (j >= ldo) return;
-  double v = 0.0;
-  if (j < n) {
-    const int64_t q = idx[j];
-    if (q >= 0) v = kst[r * ldk + (q - base)];
-  }
-  out[r * ldo + j] = v;
-}
-
-// exact scores of the gathered candidates: compact[j], and scattered to full[idx[j]]
-// mu_full: the bound pass's exact mean by global index; or (nullptr) the fp64
-// mean partials k* . alpha of these columns' K* (gather_kstar_cols: the f32
-// bound pass has no exact mean)
-__global__ void k_prune_exact(int64_t n, const int64_t* __restrict__ idx, int64_t base, int32_t RT,
-                              const double* __restrict__ var_part, int64_t ldp, const double* __restrict__ mu_full,
-                              double sf2, const double* __restrict__ stats, const int32_t* __restrict__ fit_flag,
-                              int32_t kind, double xi, double kappa, double* __restrict__ compact,
-                              double* __restrict__ full, const double* __restrict__ mu_part) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const int64_t q = idx[j];
-  if (q < 0) {
-    if (compact) compact[j] = -1.0 / 0.0;
-    return;
-  }
-  double vs = 0.0, mu = 0.0;
-  for (int32_t r = 0; r < RT; ++r) vs += var_part[(int64_t)r * ldp + j];
-  if (mu_full) {
-    mu = mu_full[q - base];
-  } else {
-    for (int32_t r = 0; r < RT; ++r) mu += mu_part[(int64_t)r * ldp + j];
-  }
-  double var = sf2 - vs;
-  var = var > 0.0 ? var : 0.0;
-  double sc = acq_score(kind, mu, var, stats[0], xi, kappa);
-  if (*fit_flag != 0) sc = __builtin_nan("");
-  if (compact) compact[j] = sc;
-  if (full) full[q - base] = sc;
-}
-
-// survivors: bound >= tau (tau = the k-th best exact score of the threshold
-// set, a device scalar); appended with one atomic per wave
-// survivors: candidates that may be in the top-k.  An exact candidate (its
-// stored score is its exact score) survives iff (score, -index) >= (tau,
-// -tau_index), the k-th best pair of the threshold set -- a lower bound on the
-// k-th best pair overall; any other survives iff its bound >= tau.
-__global__ void k_prune_survivors(int64_t m, const double* __restrict__ ub, const double* __restrict__ tau_p,
-                                  const int64_t* __restrict__ tau_idx_p, const uint8_t* __restrict__ exact,
-                                  int64_t cand_base, int64_t* __restrict__ out, unsigned long long* __restrict__ count) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const double tau = *tau_p;
-  const int64_t tau_g = *tau_idx_p;
-  bool keep = false;
-  if (i < m) {
-    const double b = ub[i];
-    if (exact && exact[i])
-      keep = b > tau || (b == tau && (tau_g < 0 || cand_base + i <= tau_g));
-    else
-      keep = b >= tau;
-  }
-  const unsigned long long ball = __ballot(keep);
-  const uint32_t n = __builtin_popcountll(ball);
-  unsigned long long base = 0;
-  if (lane == 0 && n) base = atomicAdd(count, (unsigned long long)n);
-  base = __shfl(base, 0, 64);
-  if (keep) out[base + __builtin_popcountll(ball & ((1ull << lane) - 1ull))] = i;
-}
-
-__global__ void k_fill(double* __restrict__ p, int64_t n, double v) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
-// full fp64 K* columns of the candidates idx[0..nc) (global indices - base;
-// idx < 0: an empty slot) into c->pr_kst [npad][ldc]: their scaled features
-// and norms (and categorical codes) gathered from the K* operands of the
-// round (c->ucand / c->cnorm / c->bcat, leading dimension ldk), then the K*
-// GEMM on those columns only (pruned scoring's threshold set and survivors,
-// precision 8's flagged candidates); mu_part: also their fp64 mean partials
-// k* . alpha per row tile [RT][ldc] (pruned scoring's f32 bound pass)
-static int gather_kstar_cols(ut_ctx* c, bool cat, int32_t dpad, int64_t ldk, const int64_t* idx, int64_t base,
-                             int64_t nc, int64_t ldc, double* mu_part) {
-  const int32_t npad = ((c->gp_n + NPAD - 1) / NPAD) * NPAD;
-  const int32_t RT = npad / NPAD;
-  const double* XsT = cat ? c->gp_XsT_num.p : c->gp_XsT.p;
-  const double* xn = cat ? c->gp_xnorm_num.p : nullptr;
-  int r2;
-  if ((r2 = ensure(c, c->pr_kst, (size_t)npad * ldc))) return r2;
-  if ((r2 = ensure(c, c->pr_vpart, (size_t)RT * ldc))) return r2;
-  if ((r2 = ensure(c, c->pr_ucand, (size_t)(dpad > 0 ? dpad : 1) * ldc))) return r2;
-  if ((r2 = ensure(c, c->pr_cnorm, (size_t)ldc))) return r2;
-  if (dpad > 0)
-    hipLaunchKernelGGL(k_gather_cols, dim3(grid1(ldc, 256), (unsigned)dpad), dim3(256), 0, c->stream, c->ucand.p,
-                       ldk, idx, base, nc, ldc, c->pr_ucand.p);
-  hipLaunchKernelGGL(k_gather_cols, dim3(grid1(ldc, 256), 1u), dim3(256), 0, c->stream, c->cnorm.p, ldk, idx, base,
-                     nc, ldc, c->pr_cnorm.p);
-  if (cat) {   // the gathered candidates' 128-byte code rows, per code block
-    if ((r2 = ensure(c, c->pr_bcat, (size_t)c->space.cat_k * ldc))) return r2;
-    hipLaunchKernelGGL(k_gather_code_rows, dim3(grid1(ldc * 8, 256), (unsigned)(c->space.cat_k / 128)), dim3(256), 0,
-                       c->stream, c->bcat.p, ldk, idx, base, nc, ldc, c->pr_bcat.p);
-  }
-  UT_LAUNCH_CHECK(c);
-  return launch_gemm_kstar(c, 64, XsT, npad, c->pr_ucand.p, dpad, nc, c->pr_kst.p, ldc, mu_part, -1,
-                           c->pr_cnorm.p, nullptr, cat ? kstar_cat(c, c->pr_bcat.p) : KstarCat(), xn);
-}
-
-int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
-                        int64_t cand_base, int32_t k, int32_t bound_rows, int64_t* out_idx, double* out_score,
-                        ut_prune_stats* stats, hipEvent_t dup_ready, bool feat_ours) {
-  UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_topk_pruned: call ut_gp_fit first");
-  UT_CHECK(c, c->gp_fit_prec == 64, UT_EINVAL, "gp_topk_pruned: needs an fp64 fit (ut_gp_set_precision 64)");
-  UT_CHECK(c, acq->kind == UT_ACQ_EI || (acq->kind == UT_ACQ_UCB && acq->kappa >= 0.0), UT_EINVAL,
-           "gp_topk_pruned: the score must increase with sigma (EI, or UCB with kappa >= 0)");
-  UT_CHECK(c, k >= 1 && k <= 1024, UT_EINVAL, "gp_topk_pruned: k must be in [1, 1024]");
-  if (int rc0 = gp_fit_flush(c)) return rc0;
-  // the candidates' K* operands need only the fit's scaled inputs (1/ell):
-  // they are prepared while the factorisation still runs, and K* then waits
-  // for the whole fit (C3 pruned: the 2.8-ms categorical prep came off the
-  // critical path, scripts/ab/r04ad_prep_early.sh)
-  if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit_x, 0));
-  const int32_t n = c->gp_n, d = c->gp_d;
-  const int32_t npad = ((n + NPAD - 1) / NPAD) * NPAD;
-  // feat == nullptr: the K* operands are already in c->ucand / c->cnorm (/ c->bcat),
-  // from gp_encode_scaled (a scoring round's fused encode)
-  const bool cat = feat ? feat_ours && c->cat_on : c->ucand_cat;   // the categorical K* (ut's encoder)
-  const int32_t dpad = cat ? cat_dpad(c) : kstar_dpad(d);
-  const int32_t RT = npad / NPAD;
-  int32_t R = (bound_rows + NPAD - 1) / NPAD;
-  R = R < 1 ? 1 : (R > RT ? RT : R);
-  const int64_t ldk = ((m + VAR_BN - 1) / VAR_BN) * VAR_BN;
-  int rc;
-  if ((rc = ensure(c, c->kst, (size_t)npad * ldk))) return rc;
-  if ((rc = ensure(c, c->mu_part, (size_t)RT * ldk))) return rc;
-  if ((rc = ensure(c, c->var_part, (size_t)RT * ldk))) return rc;
-  if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldk))) return rc;
-  if ((rc = ensure(c, c->cnorm, (size_t)ldk))) return rc;
-  if ((rc = ensure(c, c->ucand, (size_t)(dpad > 0 ? dpad : 1) * ldk))) return rc;
-  if (cat && (rc = ensure(c, c->bcat, (size_t)c->space.cat_k * ldk))) return rc;
-  if ((rc = ensure(c, c->pr_mu, (size_t)ldk))) return rc;
-  if ((rc = ensure(c, c->pr_ub, (size_t)ldk))) return rc;
-  if ((rc = ensure(c, c->pr_score, (size_t)ldk + 2048))) return rc;   // + the threshold set's two [1024] arrays
-  if ((rc = ensure(c, c->pr_idx, (size_t)ldk + 2048))) return rc;
-  if ((rc = ensure(c, c->pr_count, 1))) return rc;
-  if ((rc = ensure(c, c->pr_k2, (size_t)RT * ldk))) return rc;
-  // [0] |L^-1|_F^2, [1..] block partials, then the f32 passes' sum |alpha|, max |x|^2
-  if ((rc = ensure(c, c->pr_f2, 3 + SQ_BLOCKS))) return rc;
-  const bool f32 = c->prune_pass == 32;   // the bound pass in f32 (k_gp_kstar_f32c)
-  if (f32 && (rc = ensure(c, c->pr_sa, (size_t)RT * ldk))) return rc;
-  if (f32 && (rc = ensure(c, c->pr_gmu, (size_t)RT * (ldk + 1024)))) return rc;   // survivors / threshold set
-  if ((rc = ensure(c, c->pr_exact, (size_t)ldk))) return rc;
-  const double* LinvT = c->gp_LinvT.p;
-  // 1. K* with the mean in its epilogue, 2. the first R row tiles of L^-1 K*^T
-  if (feat) {
-    if (cat) {
-      if ((rc = launch_prep_cand_cat(c, feat, ld, m, c->ucand.p, dpad, ldk, c->cnorm.p, c->bcat.p))) return rc;
-    } else if ((rc = launch_prep_cand(c, feat, ld, m, d, dpad, c->ucand.p, ldk, c->cnorm.p))) {
-      return rc;
-    }
-    c->ucand_cat = cat;
-    mark(c, "prep");
-  }
-  if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));   // K* takes mu = k* . alpha
-  mark(c, "fit_wait");   // (the wait is not K* time)
-  const double* XsT = cat ? c->gp_XsT_num.p : c->gp_XsT.p;
-  const double* xn = cat ? c->gp_xnorm_num.p : nullptr;
-  // K* stores only the bound rows; the mean sums every row.  The few
-  // candidates that need every row (threshold set, survivors) get their K*
-  // columns recomputed from their features (recompute_cols below): cheaper than
-  // writing and re-reading the whole n x m matrix
-  if (f32) {
-    // the bound rows through the fp64 kernel (tiles < R), every other tile
-    // through k_gp_kstar_f32c on f32 copies of the operands (Xs^T once per fit)
-    const double* xnn = xn ? xn : c->gp_xnorm.p;
-    // the f32 copy depends on the operand as well as the fit: the numeric
-    // block (categorical mode, cat_dpad rows, gp_xnorm_num) or every feature
-    // (kstar_dpad rows, gp_xnorm) -- within one categorical fit the feature
-    // entry (ut_gp_topk_pruned: cat = false) and the fused DE round (cat =
-    // true) take different ones, so the cache is keyed on (fit, cat, dpad)
-    if (!c->pr_xf_valid || c->pr_xf_cat != cat || c->pr_xf_dpad != dpad) {
-      if ((rc = ensure(c, c->pr_xsT_f, (size_t)dpad * npad))) return rc;
-      if ((rc = launch_to_f32(c, XsT, c->pr_xsT_f.p, (int64_t)dpad * npad))) return rc;
-      hipLaunchKernelGGL(k_max_n, dim3(1), dim3(256), 0, c->stream, xnn, n, c->pr_f2.p + 2 + SQ_BLOCKS);
-      UT_LAUNCH_CHECK(c);
-      c->pr_xf_valid = true;
-      c->pr_xf_cat = cat;
-      c->pr_xf_dpad = dpad;
-    }
-    if ((rc = ensure(c, c->pr_ucand_f, (size_t)(dpad > 0 ? dpad : 1) * ldk))) return rc;
-    if ((rc = launch_to_f32(c, c->ucand.p, c->pr_ucand_f.p, (int64_t)dpad * ldk))) return rc;
-    if ((rc = launch_gemm_kstar(c, 64, XsT, npad, c->ucand.p, dpad, m, c->kst.p, ldk, c->mu_part.p, R * NPAD,
-                                nullptr, c->pr_k2.p, cat ? kstar_cat(c, c->bcat.p) : KstarCat(), xn, R)))
-      return rc;
-    UT_HIP(c, hipMemsetAsync(c->pr_sa.p, 0, sizeof(double) * R * ldk, c->stream));
-    if (R < RT &&
-        (rc = launch_gemm_kstar_f32c(c, c->pr_xsT_f.p, npad, c->pr_ucand_f.p, dpad, m, ldk, R, c->mu_part.p,
-                                     c->pr_k2.p, c->pr_sa.p, cat ? kstar_cat(c, c->bcat.p) : KstarCat(), xnn,
-                                     c->cnorm.p)))
-      return rc;
-  } else if ((rc = launch_gemm_kstar(c, 64, XsT, npad, c->ucand.p, dpad, m, c->kst.p, ldk, c->mu_part.p, R * NPAD,
-                                     nullptr, c->pr_k2.p, cat ? kstar_cat(c, c->bcat.p) : KstarCat(), xn))) {
-    return rc;
-  }
-  // |L^-1|_F^2 for the variance tail bound, once per fit (the block partials
-  // in pr_f2[1..] are scratch, reused pass after pass in stream order)
-  auto sumsq = [&](bool abs_, const double* x, int64_t cnt, double* out) -> int {
-    if (abs_)
-      hipLaunchKernelGGL(k_sumsq_part<true>, dim3(SQ_BLOCKS), dim3(256), 0, c->stream, x, cnt, c->pr_f2.p + 1);
-    else
-      hipLaunchKernelGGL(k_sumsq_part<false>, dim3(SQ_BLOCKS), dim3(256), 0, c->stream, x, cnt, c->pr_f2.p + 1);
-    hipLaunchKernelGGL(k_sumsq_final, dim3(1), dim3(256), 0, c->stream, c->pr_f2.p + 1, SQ_BLOCKS, out);
-    UT_LAUNCH_CHECK(c);
-    return 0;
-  };
-  if (!c->pr_f2_valid) {
-    if ((rc = sumsq(false, c->gp_Linv.p, (int64_t)npad * npad, c->pr_f2.p))) return rc;
-    c->pr_f2_valid = true;
-  }
-  if (f32 && !c->pr_ab_valid) {   // the f32 bound's per-fit constants
-    double* cst = c->pr_f2.p + 1 + SQ_BLOCKS;
-    if ((rc = sumsq(true, c->gp_alpha.p, n, cst))) return rc;
-    c->pr_ab_valid = true;
-  }
-  mark(c, "kstar");
-  if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->kst.p, ldk, R * NPAD, m, c->var_part.p, c->gp_beta.p,
-                            c->pr_mpart.p)))
-    return rc;
-  mark(c, "bound");
-  if (dup_ready) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));   // the dup mask (side stream)
-  if (f32)
-    hipLaunchKernelGGL(k_prune_bound32, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, c->mu_part.p,
-                       c->pr_sa.p, c->pr_k2.p, R, c->var_part.p, ldk, c->gp_sf2, n, c->gp_stats.p, c->gp_flag.p,
-                       acq->kind, acq->xi, acq->kappa, dup, c->pr_f2.p, c->pr_ub.p, c->pr_exact.p,
-                       dpad + (cat ? 1 : 0), cat ? fabs(c->cat_c0) : 0.0, c->cnorm.p);
-  else
-    hipLaunchKernelGGL(k_prune_bound, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, c->mu_part.p, R,
-                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
-                       c->pr_mu.p, c->pr_ub.p, c->pr_k2.p, c->pr_f2.p, c->pr_exact.p);
-  UT_LAUNCH_CHECK(c);
-  // 3. threshold: exact scores of the best 1024 bounds, tau = their k-th best
-  const int32_t kp = (int32_t)(m < 1024 ? m : 1024);
-  int64_t* tset = c->pr_idx.p + ldk;                   // [1024] threshold set (global indices)
-  double* tsc = c->pr_score.p + ldk;                   // [1024] their bounds
-  double* tex = c->pr_score.p + ldk + 1024;            // [1024] their exact scores
-  if ((rc = topk_impl(c, c->pr_ub.p, dup, m, cand_base, kp < k ? k : kp, tset, tsc))) return rc;
-  // (the f32 pass has no exact mean: the recomputed columns' fp64 k* . alpha)
-  double* gmu = f32 ? c->pr_gmu.p : nullptr;
-  auto recompute_cols = [&](const int64_t* idx, int64_t base, int64_t nc, int64_t ldc) -> int {
-    return gather_kstar_cols(c, cat, dpad, ldk, idx, base, nc, ldc, gmu);
-  };
-  const int64_t ldt = ((int64_t)kp + VAR_BN - 1) / VAR_BN * VAR_BN;
-  if ((rc = recompute_cols(tset, cand_base, kp, ldt))) return rc;
-  if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->pr_kst.p, ldt, npad, kp, c->pr_vpart.p, c->gp_beta.p,
-                            c->pr_mpart.p)))
-    return rc;
-  const double* mu_full = f32 ? nullptr : c->pr_mu.p;
-  hipLaunchKernelGGL(k_prune_exact, dim3(grid1(kp, 256)), dim3(256), 0, c->stream, (int64_t)kp, tset, cand_base, RT,
-                     c->pr_vpart.p, ldt, mu_full, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi,
-                     acq->kappa, tex, nullptr, gmu);
-  UT_LAUNCH_CHECK(c);
-  int64_t* tk_i = out_idx;   // the caller's [k] outputs hold tau's top-k for now
-  double* tk_s = out_score;
-  // tau: the k-th best (exact score, global index) pair of the threshold set
-  if ((rc = topk_pairs_impl(c, tex, tset, kp, k, tk_i, tk_s))) return rc;
-  // 4. survivors: bound >= tau
-  UT_HIP(c, hipMemsetAsync(c->pr_count.p, 0, sizeof(int64_t), c->stream));
-  hipLaunchKernelGGL(k_prune_survivors, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, c->pr_ub.p, tk_s + (k - 1),
-                     tk_i + (k - 1), c->pr_exact.p, cand_base, c->pr_idx.p,
-                     reinterpret_cast<unsigned long long*>(c->pr_count.p));
-  UT_LAUNCH_CHECK(c);
-  int64_t ns = 0;
-  double tau = 0.0;
-  UT_HIP(c, hipMemcpyAsync(&ns, c->pr_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  UT_HIP(c, hipMemcpyAsync(&tau, tk_s + (k - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  UT_HIP(c, hipStreamSynchronize(c->stream));
-  mark(c, "prune");
-  const bool dense = ns * 2 > m;
-  if (dense) {
-    // most candidates survive: the whole K* (this time every row) and the dense variance
-    if ((rc = launch_gemm_kstar(c, 64, XsT, npad, c->ucand.p, dpad, m, c->kst.p, ldk, c->mu_part.p, -1, nullptr,
-                                nullptr, cat ? kstar_cat(c, c->bcat.p) : KstarCat(), xn)))
-      return rc;
-    if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->kst.p, ldk, npad, m, c->var_part.p, c->gp_beta.p,
-                              c->pr_mpart.p)))
-      return rc;
-    hipLaunchKernelGGL(k_gp_finalize, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, RT, c->mu_part.p,
-                       c->var_part.p, ldk, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi, acq->kappa, dup,
-                       nullptr, nullptr, c->pr_score.p);
-    UT_LAUNCH_CHECK(c);
-  } else {
-    // 5. the full variance for the survivors only, their exact scores into a -inf array
-    hipLaunchKernelGGL(k_fill, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->pr_score.p, m, -1.0 / 0.0);
-    UT_LAUNCH_CHECK(c);
-    if (ns > 0) {
-      const int64_t lds = (ns + VAR_BN - 1) / VAR_BN * VAR_BN;
-      if ((rc = recompute_cols(c->pr_idx.p, 0, ns, lds))) return rc;
-      if ((rc = launch_gemm_var(c, 64, LinvT, npad, c->pr_kst.p, lds, npad, ns, c->pr_vpart.p, c->gp_beta.p,
-                                c->pr_mpart.p)))
-        return rc;
-      hipLaunchKernelGGL(k_prune_exact, dim3(grid1(ns, 256)), dim3(256), 0, c->stream, ns, c->pr_idx.p, (int64_t)0,
-                         RT, c->pr_vpart.p, lds, mu_full, c->gp_sf2, c->gp_stats.p, c->gp_flag.p, acq->kind, acq->xi,
-                         acq->kappa, nullptr, c->pr_score.p, gmu);
-      UT_LAUNCH_CHECK(c);
-    }
-  }
-  mark(c, "var");
-  if ((rc = topk_impl(c, c->pr_score.p, dup, m, cand_base, k, out_idx, out_score))) return rc;
-  mark(c, "topk");
-  if (stats) {
-    stats->survivors = dense ? m : ns;
-    stats->bound_rows = R * NPAD;
-    stats->dense = dense ? 1 : 0;
-    stats->threshold = tau;
   }
   return 0;
 }

@@ -15,7 +15,7 @@
 
 namespace ut {
 
-// the fit kernels here (see gp.hip g_fit_prio): s_setprio 3 when set
+// the fit kernels here (see gp_fit.hip g_fit_prio): s_setprio 3 when set
 __device__ int32_t g_fit_prio_g = 0;
 __device__ __forceinline__ void fit_prio_g() {
   if (g_fit_prio_g) __builtin_amdgcn_s_setprio(3);
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar(const double* __restrict__
                                                       const int8_t* __restrict__ acat, const int8_t* __restrict__ bcat,
                                                       int32_t nkc, double cat_c0, double cat_c1, int32_t RTe) {
   // part2 (MU, fp64/fp32 only; pruned scoring): the column partial sum_r k*_r^2
-  // as well, for the tail bound of the variance (gp.hip k_prune_bound)
+  // as well, for the tail bound of the variance (gp_prune.hip k_prune_bound)
   // TS = _Float16 (h3): k* * kscale split into fp16 hi + lo, stored candidate-major
   // in the blocked layout of k_gp_var_h3 (K = npad = RT * K_BM; ldk % 256 == 0);
   // the lo plane starts lo_off elements after the hi plane.  h3 permutes the
@@ -676,39 +676,39 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar_f32c(const float* __restri
   }
 }
 
-int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, int32_t npad, const float* ucand_f, int32_t dpad,
-                           int64_t m, int64_t ldk, int32_t rt0, double* part, double* part2, double* part3,
-                           const KstarCat& cat, const double* xn, const double* cn) {
+int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, int32_t npad, const KstarArgs& a) {
+  const KstarCat& cat = a.train.cat;
+  const int64_t m = a.m, ldk = a.ldk;
   const bool has_cat = cat.nkc > 0;
-  UT_CHECK(c, npad % K_BM == 0 && dpad % 4 == 0 && (dpad >= 4 || has_cat) && ldk % K_BN == 0 && ldk >= m, UT_EINVAL,
-           "gemm_kstar_f32c: bad padding");
+  UT_CHECK(c, npad % K_BM == 0 && a.dpad % 4 == 0 && (a.dpad >= 4 || has_cat) && ldk % K_BN == 0 && ldk >= m,
+           UT_EINVAL, "gemm_kstar_f32c: bad padding");
   UT_CHECK(c, !has_cat || (cat.acat && cat.bcat), UT_EINVAL, "gemm_kstar_f32c: categorical operands missing");
-  UT_CHECK(c, part && part2 && part3, UT_EINVAL, "gemm_kstar_f32c: partial outputs missing");
+  UT_CHECK(c, a.part && a.part2 && a.part3, UT_EINVAL, "gemm_kstar_f32c: partial outputs missing");
   const int32_t RT = npad / K_BM;
-  UT_CHECK(c, rt0 >= 0 && rt0 < RT, UT_EINVAL, "gemm_kstar_f32c: bad first row tile");
+  UT_CHECK(c, a.rt0 >= 0 && a.rt0 < RT, UT_EINVAL, "gemm_kstar_f32c: bad first row tile");
   const int32_t CT = (int32_t)(ldk / K_BN);
-  const int64_t items = (int64_t)(RT - rt0) * CT;
+  const int64_t items = (int64_t)(RT - a.rt0) * CT;
   int32_t nb = 2 * (c->n_cu / 8) * 8;
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
   UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
   const float c0 = (float)(cat.c0 * KSTAR_T_SCALE), c1 = (float)(cat.c1 * KSTAR_T_SCALE);
-  if (has_cat)
-    hipLaunchKernelGGL(k_gp_kstar_f32c<true>, dim3(nb), dim3(K_NT), 0, c->stream, XsT_f, (int64_t)npad, ucand_f, ldk,
-                       dpad, rt0, RT, CT, xn, cn, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, ldk, part, part2,
-                       part3, cat.acat, cat.bcat, cat.nkc, c0, c1);
-  else
-    hipLaunchKernelGGL(k_gp_kstar_f32c<false>, dim3(nb), dim3(K_NT), 0, c->stream, XsT_f, (int64_t)npad, ucand_f, ldk,
-                       dpad, rt0, RT, CT, xn, cn, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, ldk, part, part2,
-                       part3, cat.acat, cat.bcat, cat.nkc, c0, c1);
+  hipLaunchKernelGGL(has_cat ? k_gp_kstar_f32c<true> : k_gp_kstar_f32c<false>, dim3(nb), dim3(K_NT), 0, c->stream,
+                     XsT_f, (int64_t)npad, ucand_f, ldk, a.dpad, a.rt0, RT, CT,
+                     a.train.xnorm ? a.train.xnorm : c->gp_xnorm.p, a.cn ? a.cn : c->cnorm.p, c->gp_alpha.p, c->gp_sf2,
+                     c->gp_n, m, c->gp_ctr.p + 8, ldk, a.part, a.part2, a.part3, cat.acat, cat.bcat, cat.nkc, c0, c1);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
 
 int h3_kstar_exp(double sf2) { return H3_KSCALE_EXP - ilogb(sf2); }  // sf2 * 2^e < 2^15
 
-int launch_gemm_kstar(ut_ctx* c, int prec, const double* XsT, int32_t npad, const double* ucand, int32_t dpad,
-                      int64_t m, void* kst, int64_t ldk, double* part, int32_t store_rows, const double* cn,
-                      double* part2, const KstarCat& cat, const double* xn, int32_t row_tiles) {
+int launch_gemm_kstar(ut_ctx* c, int prec, int32_t npad, const KstarArgs& a) {
+  const KstarCat& cat = a.train.cat;
+  const double *XsT = a.train.XsT, *ucand = a.ucand;
+  const int32_t dpad = a.dpad, store_rows = a.store_rows, row_tiles = a.row_tiles;
+  const int64_t m = a.m, ldk = a.ldk;
+  void* kst = a.kst;
+  double *part = a.part, *part2 = a.part2;
   const bool has_cat = cat.nkc > 0;
   UT_CHECK(c, npad % K_BM == 0 && dpad % 4 == 0 && (dpad >= 4 || has_cat) && ldk % K_BN == 0 && ldk >= m, UT_EINVAL,
            "gemm_kstar: bad padding");
@@ -734,8 +734,8 @@ int launch_gemm_kstar(ut_ctx* c, int prec, const double* XsT, int32_t npad, cons
   int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
   UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
-  const double* xnorm = xn ? xn : c->gp_xnorm.p;
-  const double* cnorm = cn ? cn : c->cnorm.p;
+  const double* xnorm = a.train.xnorm ? a.train.xnorm : c->gp_xnorm.p;
+  const double* cnorm = a.cn ? a.cn : c->cnorm.p;
 #define UT_KSTAR_LAUNCH(TS, MU, CAT, KST, PART, KSCALE, LOOFF, SRT, PART2)                                         \
   hipLaunchKernelGGL((k_gp_kstar<TS, MU, CAT>), dim3(nb), dim3(K_NT), 0, c->stream, XsT, (int64_t)npad, ucand, ldk, \
                      dpad, RT, CT, xnorm, cnorm, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, KST, ldk, PART, \
@@ -1547,7 +1547,7 @@ int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const v
            "gemm_var: the mean partial is taken here in fp64 mode (only)");
   UT_CHECK(c, npad % VAR_BM == 0 && ldk % VAR_BN == 0 && ldk >= m, UT_EINVAL, "gemm_var: bad padding");
   const int32_t RT = npad / VAR_BM;
-  const int32_t CT = (int32_t)((m + VAR_BN - 1) / VAR_BN);
+  const int32_t CT = (int32_t)(gp_ldk(m) / VAR_BN);
   const int64_t items = (int64_t)RT * CT;
   // one block per CU (the 144 KiB LDS ring allows no more), a multiple of 8 so
   // every XCD group has workers; never more blocks than work items

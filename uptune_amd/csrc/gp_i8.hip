@@ -23,12 +23,14 @@
 // C = 3.5 2^-49, so |v_ic - v^_ic| <= e_i = (i + 1) C 2^(ea_i + eb) for every
 // candidate, and |v - v^| <= E = |e|_2 (k_i8_errsum).  With s = |v^|^2 the
 // exact |v|^2 lies within E (2 |v^| + E) of s, plus the fp64 rounding of the
-// recombination and the sums (< s (2n + 64) 2^-53).  k_gp_finalize_i8 (gp.hip)
+// recombination and the sums (< s (2n + 64) 2^-53).  k_gp_finalize_i8 (gp_score.hip)
 // accepts a candidate when that bound is <= tau * (sf2 - s) (tau: ut_gp_set_i8_tol,
 // default 2^-20), i.e. its variance is within tau relative of the exact one;
 // every other candidate -- next to a training point, where sf2 - |v|^2 is a
-// cancellation -- is recomputed in fp64 (gp.hip gp_score_impl).  The mean is
-// k* . alpha from K*'s fp64 epilogue, as in the fp32 tier.
+// cancellation -- is recomputed in fp64 (gp_score.hip gp_score_impl).  The mean
+// is mu^ = v^ . L^-1 y from k_gp_var_i8's epilogue (K* computes none), with
+// |mu - mu^| <= Emu = sum_r e_r |(L^-1 y)_r| (k_i8_errsum): a candidate is
+// accepted only if Emu <= tau * sigma as well.
 //
 // Layouts (bytes): A = [6][npad/32][npad][32] (L^-1 rows), B = [6][npad/32][ldk][32]
 // (written by k_gp_kstar<int8_t>); row / candidate r's 16-byte chunk c of a

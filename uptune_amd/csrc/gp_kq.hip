@@ -482,25 +482,18 @@ int launch_split_x8(ut_ctx* c, const double* XsT, int32_t K, int32_t npad) {
   return 0;
 }
 
-int launch_gemm_kstar_q(ut_ctx* c, bool planes, const double* XsT, int32_t npad, const double* ucand, int32_t dpad,
-                        int64_t m, void* kst, int64_t ldk, double* part, int32_t store_rows, const double* cn,
-                        double* part2, const KstarCat& cat, const double* xn, DevBuf<int8_t>& u8,
-                        DevBuf<double>& scol) {
+int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m, void* kst, int64_t ldk,
+                        DevBuf<int8_t>& u8, DevBuf<double>& scol) {
   const DevBuf<int8_t>& xd = c->gp_x8;
+  const int32_t npad = gp_npad(c->gp_n);
   const int32_t K32 = (dpad + 31) / 32;
   const bool pair = K32 * 32 <= Q_PAIR_MAX_K;
-  const bool has_cat = cat.nkc > 0;
   // exact int32 group sums: K 6 2^14 < 2^31
   UT_CHECK(c, npad % Q_BM == 0 && ldk % Q_BN == 0 && ldk >= m && (int64_t)K32 * 32 * 6 * 16384 < (1LL << 31),
            UT_EINVAL, "gemm_kstar_q: bad padding or too many features");
   UT_CHECK(c, xd.p && xd.n >= (size_t)I8_S * K32 * 32 * npad, UT_EINVAL,
            "gemm_kstar_q: the fit has no training digit planes");
-  UT_CHECK(c, !has_cat || (cat.acat && cat.bcat), UT_EINVAL, "gemm_kstar_q: categorical operands missing");
-  UT_CHECK(c, K32 + cat.nkc >= 1, UT_EINVAL, "gemm_kstar_q: no features");
-  // the library runs it for the variance's digit planes of numeric fits (the
-  // mean from the variance epilogue, no one-hot codes: gp.hip gp_score_impl)
-  UT_CHECK(c, planes && !part && !part2 && !has_cat && XsT == c->gp_XsT.p, UT_EINVAL,
-           "gemm_kstar_q: digit planes of a numeric fit only");
+  UT_CHECK(c, K32 >= 1, UT_EINVAL, "gemm_kstar_q: no features");
   int rc;
   if ((rc = ensure(c, u8, (size_t)I8_S * (K32 > 0 ? K32 : 1) * 32 * ldk))) return rc;
   if ((rc = ensure(c, scol, (size_t)ldk))) return rc;
@@ -509,20 +502,16 @@ int launch_gemm_kstar_q(ut_ctx* c, bool planes, const double* XsT, int32_t npad,
   UT_LAUNCH_CHECK(c);
   const int32_t RT = npad / Q_BM;
   const int32_t CT = (int32_t)(ldk / Q_BN);
-  const int32_t store_rt = store_rows < 0 ? RT : (store_rows + Q_BM - 1) / Q_BM;
   const int64_t items = (int64_t)RT * CT;
   const bool fit_in_flight = c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
   const int32_t spare = fit_in_flight ? 2 : 0;   // as launch_gemm_kstar
   int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-  const double* xnorm = xn ? xn : c->gp_xnorm.p;
-  const double* cnorm = cn ? cn : c->cnorm.p;
-  const double kscale = planes ? ldexp(1.0, -i8_kstar_exp(c->gp_sf2)) : 1.0;
+  const double kscale = ldexp(1.0, -i8_kstar_exp(c->gp_sf2));
 #define UT_KQ_LAUNCH(PAIR)                                                                                     \
   hipLaunchKernelGGL((k_gp_kstar_q<int8_t, false, false, PAIR>), dim3(nb), dim3(Q_NT), 0, c->stream, xd.p, npad,    \
-                     u8.p, ldk, K32, scol.p, RT, CT, xnorm, cnorm, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, (int8_t*)kst, \
-                     nullptr, kscale, (int64_t)npad * ldk, store_rt, nullptr, cat.acat, cat.bcat, cat.nkc,         \
-                     cat.c0 * KSTAR_T_SCALE, cat.c1 * KSTAR_T_SCALE)
+                     u8.p, ldk, K32, scol.p, RT, CT, c->gp_xnorm.p, c->cnorm.p, c->gp_alpha.p, c->gp_sf2, c->gp_n, m,     \
+                     (int8_t*)kst, nullptr, kscale, (int64_t)npad * ldk, RT, nullptr, nullptr, nullptr, 0, 0.0, 0.0)
   if (pair) UT_KQ_LAUNCH(true);
   else UT_KQ_LAUNCH(false);
 #undef UT_KQ_LAUNCH

@@ -30,7 +30,6 @@
 
 namespace ut {
 
-constexpr int LML_NPAD = 128;                       // the fit's padding (gp.hip NPAD)
 constexpr size_t LML_BUDGET = (size_t)1 << 30;      // bytes of K_z matrices one chunk may hold
 
 // lower-triangle tile number -> (i, j), j <= i
@@ -252,7 +251,7 @@ int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int
            "gp_lml_grid: NULL argument");
   for (int32_t z = 0; z < g; ++z)
     UT_CHECK(c, std::isfinite(scale[z]) && scale[z] > 0.0, UT_EINVAL, "gp_lml_grid: scales must be finite and > 0");
-  const int64_t npad = ((int64_t)(n + LML_NPAD - 1) / LML_NPAD) * LML_NPAD;
+  const int64_t npad = gp_npad(n);   // the fit's padding
   const int32_t nb = (int32_t)(npad / NB);
   const size_t mat = (size_t)npad * npad;
   int64_t B = c->lml_batch > 0 ? c->lml_batch : (int64_t)(LML_BUDGET / (mat * sizeof(double)));

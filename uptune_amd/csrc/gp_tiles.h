@@ -1,5 +1,5 @@
 // gp_tiles.h -- device building blocks of the blocked Cholesky shared by the
-// GP fit (gp.hip) and the batched log-marginal-likelihood grid (gp_lml.hip):
+// GP fit (gp_fit.hip) and the batched log-marginal-likelihood grid (gp_lml.hip):
 // the 64 x 64 fp64-MFMA tile product, its accumulator -> tile coordinates and
 // the diagonal-block factor + inverse.
 #pragma once

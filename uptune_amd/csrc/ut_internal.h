@@ -258,7 +258,7 @@ struct ut_ctx {
   // ring) instead of k_trinv_level (64 x 64 tiles, plain loads); UT_TRINV_BIG
   int32_t trinv_big = 1;
   // the diagonal blocks' inverse solved inside the Cholesky column loop
-  // (gp.hip chol_diag_core<true>); UT_CHOL_MERGED
+  // (gp_tiles.h chol_diag_core<true>); UT_CHOL_MERGED
   int32_t chol_merged = 1;
 
   // history set
@@ -273,6 +273,7 @@ struct ut_ctx {
   // GP state
   int32_t gp_n = 0, gp_d = 0;
   bool gp_ready = false;
+  uint64_t fit_gen = 0;        // counts the fits staged (gp_fit_enqueue): the key of every per-fit cache
   ut::DevBuf<double> gp_Xs;     // [n][d] scaled features
   ut::DevBuf<double> gp_xnorm;  // [n]
   ut::DevBuf<double> gp_K;      // [n][n] work / L
@@ -288,7 +289,7 @@ struct ut_ctx {
   double gp_sf2 = 1.0;
   int32_t gp_prec = 64;        // precision requested for the next fit
   int32_t gp_fit_prec = 64;    // precision of the fitted factors used by scoring
-  // incremental fit (gp.hip gp_fit_enqueue): 1 = a fit whose training set
+  // incremental fit (gp_fit.hip gp_fit_enqueue): 1 = a fit whose training set
   // extends the previous one's extends its factor (ut_gp_set_fit_append)
   int32_t fit_append = 1;
   int32_t gp_npad_fit = 0;     // padded size of the current factor
@@ -359,7 +360,7 @@ struct ut_ctx {
   ut::DevBuf<uint32_t> par_dig;     // [n_comp][16]: hex inner digests of ut_hash_parent's parent row
   ut::DevBuf<uint32_t> hs_mask;     // small-m ut_hash: all-ones reuse mask [ceil(n_comp / 32)][ld]
   ut::DevBuf<uint32_t> hs_fresh;    // small-m ut_hash: every inner digest, hex [n_comp][ld][16]
-  // EI-bound pruned scoring (gp.hip ut_gp_topk_pruned)
+  // EI-bound pruned scoring (gp_prune.hip ut_gp_topk_pruned)
   ut::DevBuf<double> pr_mu, pr_ub, pr_score;   // [ld] exact mean, score bound, exact scores (-inf if pruned)
   ut::DevBuf<double> pr_mpart;                 // [RT][ldk] unused mean partials of the bound / survivor GEMMs
   ut::DevBuf<double> pr_kst, pr_vpart;         // survivors' K* columns [npad][lds] and variance partials
@@ -371,10 +372,10 @@ struct ut_ctx {
   ut::DevBuf<double> pr_k2;                    // [RT][ldk] partials of |k*|^2 (the variance tail bound)
   ut::DevBuf<double> pr_f2;                    // [1] |L^-1|_F^2 (+ its block partials), then the f32
                                                // pass's sum |alpha|
-  bool pr_f2_valid = false;                    // pr_f2 belongs to the current fit
-  bool pr_ab_valid = false;                    // ... and its sum |alpha|
-  bool pr_xf_valid = false;                    // pr_xsT_f and max |x|^2 belong to the current fit,
-  bool pr_xf_cat = false;                      // ... built from this operand (numeric block or all features)
+  // the fit (fit_gen) each per-fit cache was built from; 0 = never built
+  uint64_t pr_f2_gen = 0, pr_ab_gen = 0;       // pr_f2[0] and the sum |alpha|
+  uint64_t pr_xf_gen = 0;                      // pr_xsT_f and max |x|^2,
+  bool pr_xf_cat = false;                     // ... built from this operand (numeric block or all features)
   int32_t pr_xf_dpad = -1;                     // ... with this many rows
   ut::DevBuf<float> pr_xsT_f, pr_ucand_f;      // f32 K* operands of the f32-contraction bound pass
   ut::DevBuf<double> pr_sa;                    // [RT][ldk] partials of sum |alpha_r| k*_r (f32 bound pass)
@@ -464,6 +465,31 @@ struct StreamScope {
 
 // feature rows of the K* operands (Xs^T, U'): d rounded up to the f64 MFMA's k = 4
 inline int32_t kstar_dpad(int32_t d) { return ((d + 3) / 4) * 4; }
+// ... and of the categorical K*'s operands: the numeric features only
+inline int32_t cat_dpad(const ut_ctx* c) { return kstar_dpad(c->space.n_num); }
+
+constexpr int NPAD = 128;                  // training set padded to the GEMM row tile
+constexpr int VAR_BM = 128, VAR_BN = 256;  // variance-contraction tile (rows of L^-1 x candidates)
+inline int32_t gp_npad(int32_t n) { return ((n + NPAD - 1) / NPAD) * NPAD; }
+// K* rows padded to whole variance column tiles: the variance kernel reads
+// full 256-candidate strips (the K* kernel writes zeros past m)
+inline int64_t gp_ldk(int64_t m) { return ((m + VAR_BN - 1) / VAR_BN) * VAR_BN; }
+
+// The padded sizes of one scoring call over m candidates of the current fit:
+// which K* it takes (cat) is the caller's own rule, every size that follows
+// from it is taken from here.  n, d: training rows, features; RT: 128-row
+// tiles; ldk: padded candidates; dpad: feature rows of the K* operands
+struct ScoreShape {
+  int32_t n, d, npad, RT;
+  int64_t ldk;
+  bool cat;
+  int32_t dpad;
+  size_t urows() const { return (size_t)(dpad > 0 ? dpad : 1); }   // ... to allocate (never 0)
+};
+inline ScoreShape score_shape(const ut_ctx* c, int64_t m, bool cat) {
+  const int32_t npad = gp_npad(c->gp_n);
+  return ScoreShape{c->gp_n, c->gp_d, npad, npad / NPAD, gp_ldk(m), cat, cat ? cat_dpad(c) : kstar_dpad(c->gp_d)};
+}
 
 // fault injection (tests): true when this counted allocation is to fail as
 // hipMalloc would -- after dbg_fail_skip counted allocations went through, the
@@ -524,7 +550,7 @@ int gp_wait_fit(ut_ctx* c);
 int gp_fit_flush(ut_ctx* c);
 int gp_ensure_linvt(ut_ctx* c);
 int gp_fit_prefit(ut_ctx* c);
-// gp.hip's staging kernels on any buffers: scaled rows + norms, standardised y + stats
+// gp_fit.hip's staging kernels on any buffers: scaled rows + norms, standardised y + stats
 int launch_gp_prep_train(ut_ctx* c, const double* X, int32_t n, int32_t npad, int32_t d, const double* inv_ell,
                          double* Xs, double* xnorm);
 int launch_gp_ystats(ut_ctx* c, const double* y, int32_t n, int32_t npad, double* ys, double* stats);
@@ -583,6 +609,9 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
 int gp_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m);
 int launch_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* u, int32_t dpad, int64_t ldu,
                          double* cn);
+// gp_score.hip: fp64 K* columns of the candidates idx[0..nc) of a call of shape s
+int gather_kstar_cols(ut_ctx* c, const ScoreShape& s, const int64_t* idx, int64_t base, int64_t nc, int64_t ldc,
+                      double* mu_part = nullptr);
 int topk_impl(ut_ctx* c, const double* score, const uint8_t* dup, int64_t m, int64_t cand_base, int32_t k,
               int64_t* out_idx, double* out_score);
 int topk_pairs_impl(ut_ctx* c, const double* score, const int64_t* idx, int64_t n, int32_t k, int64_t* out_idx,
@@ -638,33 +667,50 @@ struct KstarCat {
   int32_t nkc = 0;
   double c0 = 0.0, c1 = 0.0;
 };
-int launch_gemm_kstar(ut_ctx* c, int prec, const double* XsT, int32_t npad, const double* ucand, int32_t dpad,
-                      int64_t m, void* kst, int64_t ldk, double* part, int32_t store_rows = -1,
-                      const double* cn = nullptr,    // candidate norms (nullptr: c->cnorm)
-                      double* part2 = nullptr,       // fp64 with part: also sum_r k*_r^2 partials
-                      const KstarCat& cat = KstarCat(),
-                      const double* xn = nullptr,    // training norms (nullptr: c->gp_xnorm)
-                      int32_t row_tiles = -1);       // > 0: only the first row_tiles 128-row tiles
+// the training side of the K* contraction for the current fit: every feature
+// (cat = false) or the numeric block, the one-hot codes (the candidates': bcat) beside it
+struct KstarTrain {
+  const double* XsT = nullptr;     // [dpad][npad]
+  const double* xnorm = nullptr;   // training norms (nullptr: c->gp_xnorm)
+  KstarCat cat;
+};
+inline KstarTrain kstar_train(const ut_ctx* c, bool cat, const int8_t* bcat) {
+  if (!cat) return KstarTrain{c->gp_XsT.p};
+  return {c->gp_XsT_num.p, c->gp_xnorm_num.p, {c->gp_acat.p, bcat, c->space.cat_k / 128, c->cat_c0, c->cat_c1}};
+}
+// one K* launch over the npad training rows of the current fit
+struct KstarArgs {
+  KstarTrain train;
+  const double* ucand = nullptr;   // candidate operand [dpad][ldk] (launch_gemm_kstar_f32c: unused)
+  int32_t dpad = 0;
+  int64_t m = 0;
+  void* kst = nullptr;             // K* [npad][ldk] in the precision's format (f32c stores none)
+  int64_t ldk = 0;
+  double* part = nullptr;          // mean partials k* . alpha [RT][ldk] (fp32 / h3 / f32c: required)
+  double* part2 = nullptr;         // fp64 with part, f32c: also sum_r k*_r^2 partials
+  double* part3 = nullptr;         // f32c: sum_r |alpha_r| k*_r partials
+  int32_t store_rows = -1;         // fp64: only the first store_rows rows of K* are written
+  int32_t row_tiles = -1;          // > 0: only the first row_tiles 128-row tiles
+  int32_t rt0 = 0;                 // f32c: the first row tile
+  const double* cn = nullptr;      // candidate norms (nullptr: c->cnorm)
+};
+int launch_gemm_kstar(ut_ctx* c, int prec, int32_t npad, const KstarArgs& a);
+int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, int32_t npad, const KstarArgs& a);
 // gp_kq.hip: K* of a numeric precision-8 fit as the distance contraction on
 // the int8 MFMA (digit planes of the training operand from the fit, of the
 // candidates' operand per call into u8 / scol), stored as the six digit planes
-// the int8 variance reads (planes = true; no mean partial, no one-hot codes).
+// the int8 variance reads (no mean partial, no one-hot codes; norms in
+// c->gp_xnorm / c->cnorm).
 int alloc_split_x8(ut_ctx* c, int32_t npad, int32_t K);
 int launch_split_x8(ut_ctx* c, const double* XsT, int32_t K, int32_t npad);
-int launch_gemm_kstar_q(ut_ctx* c, bool planes, const double* XsT, int32_t npad, const double* ucand, int32_t dpad,
-                        int64_t m, void* kst, int64_t ldk, double* part, int32_t store_rows, const double* cn,
-                        double* part2, const KstarCat& cat, const double* xn, DevBuf<int8_t>& u8,
-                        DevBuf<double>& scol);
-int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, int32_t npad, const float* ucand_f, int32_t dpad,
-                           int64_t m, int64_t ldk, int32_t rt0, double* part, double* part2, double* part3,
-                           const KstarCat& cat, const double* xn, const double* cn);
+int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m, void* kst, int64_t ldk,
+                        DevBuf<int8_t>& u8, DevBuf<double>& scol);
 int launch_prep_cand(ut_ctx* c, const double* feat, int64_t ld, int64_t m, int32_t d, int32_t dpad, double* u,
                      int64_t ldu, double* cn);
 // categorical K*: the K* operands of the candidate side when the fit is in
 // categorical mode -- numeric features / ell (dpad_num rows), their norms, and
 // one-hot codes into c->bcat (from values, or from features made by ut's own
-// encoder)
-inline int32_t cat_dpad(const ut_ctx* c) { return kstar_dpad(c->space.n_num); }
+// encoder); cat_dpad(c) rows
 // the candidates' 128-byte code rows of one 256-candidate workgroup, written
 // coalesced: each thread sets its codes as bits in LDS (bits [256][stride],
 // stride = cat_k / 32 + 1 dwords), then every 128-column block is expanded to
@@ -700,6 +746,11 @@ int launch_prep_cand_cat(ut_ctx* c, const double* feat, int64_t ld, int64_t m, d
 int launch_xs_t(ut_ctx* c, const double* Xs, int32_t npad, int32_t d, int32_t dpad, double* XsT);
 int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const void* kst, int64_t ldk, int32_t npad,
                     int64_t m, double* part, const double* beta, double* mpart);
+// the fp64 contraction of cnt columns against the first `rows` rows of L^-1, the mean partials into c->pr_mpart
+inline int launch_gemm_var64(ut_ctx* c, int32_t npad, const double* kst, int64_t ldk, int32_t rows, int64_t cnt,
+                             double* vpart) {
+  return launch_gemm_var(c, 64, c->gp_LinvT.p, npad, kst, ldk, rows, cnt, vpart, c->gp_beta.p, c->pr_mpart.p);
+}
 int launch_transpose(ut_ctx* c, const double* src, int32_t n, double* dst, float* dst_f);
 // ---- int8-sliced fp64 tier (gp_i8.hip) ----
 // six balanced 8-bit digits per operand value; tiles of the variance contraction
@@ -753,9 +804,8 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
 // L^-1 [row][k] (n x n, fp64) -> scaled fp16 hi/lo planes, blocked (h3 A operand, rows padded to 256);
 // the scale exponent is derived on the device from max|L^-1| (kept in gp_ctr[16..17])
 int launch_split_h3(ut_ctx* c, const double* Linv, int32_t n, _Float16* dst);
-constexpr int VAR_BM = 128, VAR_BN = 256;  // variance-contraction tile (rows of L^-1 x candidates)
 int launch_to_f32(ut_ctx* c, const double* src, float* dst, int64_t n);
-// gp.hip: the fit kernels' issue priority (UT_FIT_SETPRIO; process-wide)
+// gp_fit.hip: the fit kernels' issue priority (UT_FIT_SETPRIO; process-wide)
 int set_fit_prio(int32_t on);
 int set_fit_prio_gemm(int32_t on);   // gp_gemm.hip's fit kernels
 int launch_gather_rows(ut_ctx* c, const double* values, int64_t ld, const int64_t* idx, int64_t cand_base,

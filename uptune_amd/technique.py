@@ -434,7 +434,7 @@ class SharedModel:
         # children (mutations of the best configuration) live in (the C5 GGA
         # round: 262,144 survivors -> 8, 75 -> 5 ms; a GA round: 2,459 -> 8,
         # scripts/exp/gga_prune_probe.py).  The rows are re-sorted only where
-        # the device refits anyway (a new padded size, gp.hip NPAD = 128, or a
+        # the device refits anyway (a new padded size, ut_internal.h NPAD = 128, or a
         # re-encode); in between the new results are appended, so the
         # incremental fit still applies.
         n = self._n
