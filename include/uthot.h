@@ -390,6 +390,20 @@ int ut_gp_lml(ut_ctx* ctx, double* lml_host);
 int ut_gp_lml_grid(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
                    const ut_gp_hyper* hyper, int32_t g, const double* scale_host,
                    const double* noise_host, double* lml_host, int32_t* best_host);
+/* Gradient of the LML of the current fit in the log hyperparameters.  With
+ *   W = alpha alpha^T - K^-1,  Kf_ij = sigma_f2 exp(-1/2 |xs_i - xs_j|^2)  (K, xs as in ut_gp_lml):
+ *   dlog_ell_host[k] = dLML / dlog ell_k     = 1/2 sum_ij W_ij Kf_ij (xs_ik - xs_jk)^2   (d values)
+ *   *dlog_sf2_host   = dLML / dlog sigma_f2  = 1/2 sum_ij W_ij Kf_ij
+ *   *dlog_sn2_host   = dLML / dlog sigma_n2  = 1/2 sigma_n2 tr W   (the jitter is a constant)
+ * over the n training rows.  Waits for an in-flight fit like ut_gp_lml;
+ * UT_ENOTPD if that fit was not positive definite; UT_EINVAL if d is not the
+ * fit's feature count or dlog_ell_host is NULL (the two scalar outputs may be
+ * NULL).  Always fp64, whatever ut_gp_set_precision says, and over every
+ * feature, whichever K* the fit scores with.  Reads the fit, writes scratch of
+ * its own: the fit and every scoring result stay as they are.  Sums in a fixed
+ * order: two calls on one fit return the same bits. */
+int ut_gp_lml_grad(ut_ctx* ctx, int32_t d, double* dlog_ell_host, double* dlog_sf2_host,
+                   double* dlog_sn2_host);
 
 /* ---- selection ---------------------------------------------------------- */
 /* k largest scores, ties -> smallest global index; entries with dup[i]!=0 or

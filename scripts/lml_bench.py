@@ -9,6 +9,13 @@ parent commit's, through UTHOT_LIB) in the same session:
     python scripts/lml_bench.py grid --out grid.json     # the grid per shape
     python scripts/lml_bench.py merge --fit fit.json --grid grid.json --out profiles/lml_grid.json
 
+and the gradient's leg (profiles/lml_grad.json): ut_gp_lml_grad alone on a fit
+in place per shape, and one whole SharedModel(lengthscale="ard") selection at
+n = 1024, against the same fit times:
+
+    python scripts/lml_bench.py grad --out grad.json
+    python scripts/lml_bench.py merge-grad --fit fit.json --grad grad.json --out profiles/lml_grad.json
+
 Every timed call ends in a device synchronisation (both entry points are
 synchronous), so the host clock around it is the call's wall time; the median
 of the repeats after two warm-up calls is recorded, with the spread.
@@ -57,7 +64,14 @@ def run(mode, repeats, label):
         X, y = data(n, d)
         e = engine(d)
         rec = dict(s)
-        if mode == "fit":
+        if mode == "grad":
+            e.gp_fit(X, y, lengthscale=2.0, **HYP)
+            res = {}
+            rec.update(timed(lambda: res.update(v=e.gp_lml_grad()), repeats))
+            rec.update(max_abs_dlog_ell=float(np.max(np.abs(res["v"][0]))), dlog_sf2=res["v"][1], dlog_sn2=res["v"][2])
+            if n == 1024:
+                rec.update(ard=ard_selection(e, X, y, max(2, repeats // 3)))
+        elif mode == "fit":
             # the same rows again are no append (n does not grow): every call refactors
             rec.update(timed(lambda: e.gp_fit(X, y, lengthscale=2.0, **HYP), repeats))
             assert e.gp_last_fit_kind() == "refit"
@@ -71,6 +85,50 @@ def run(mode, repeats, label):
         out["shapes"].append(rec)
         print(json.dumps(rec), flush=True)
     return out
+
+
+def ard_selection(e, X, y, repeats):
+    """one whole "ard" selection (the grid, then L-BFGS-B: a fit, its LML and its
+    gradient per evaluation) on the engine, as SharedModel.fit runs it"""
+    from uptune_amd.technique import SharedModel
+    m = SharedModel(lengthscale="ard", **HYP)
+    m.engine = e
+    evals = []
+    inner = e.gp_lml_grad
+
+    def counted():
+        evals[-1] += 1
+        return inner()
+    e.gp_lml_grad = counted
+
+    def once():
+        evals.append(0)
+        m._select_ard(X, y)
+    rec = timed(once, repeats, warmup=1)
+    e.gp_lml_grad = inner
+    n, ell, lml = m.ell_history[-1]
+    grid = np.sqrt(X.shape[1]) * np.geomspace(0.05, 4.0, 16)   # the selection's own default grid
+    rec.update(evaluations=evals[-1], maxiter=m.ard_maxiter, lml=float(lml),
+               lml_start=float(np.nanmax(e.gp_lml_grid(X, y, 1.0, grid, **HYP)[0])),
+               ell_min=float(np.min(ell)), ell_max=float(np.max(ell)))
+    return rec
+
+
+def merge_grad(fit, grad):
+    rows = []
+    for f, q in zip(fit["shapes"], grad["shapes"]):
+        assert (f["n"], f["d"]) == (q["n"], q["d"])
+        row = dict(n=q["n"], d=q["d"], grad_ms=q["median_ms"], grad_min_ms=q["min_ms"], grad_max_ms=q["max_ms"],
+                   fit_ms=f["median_ms"], fit_min_ms=f["min_ms"], fit_max_ms=f["max_ms"],
+                   ratio=q["median_ms"] / f["median_ms"], repeats=q["repeats"])
+        if "ard" in q:
+            a = q["ard"]
+            row["ard_selection"] = dict(a, selection_ms=a["median_ms"], fits_equivalent=a["median_ms"] / f["median_ms"])
+        rows.append(row)
+    return dict(what="ut_gp_lml_grad wall time on a fit in place against one synchronous ut_gp_fit of the same "
+                     "shape, and one whole SharedModel(lengthscale='ard') selection (median of the repeats, host "
+                     "clock around synchronous calls)",
+                fit_library=fit["library"], grad_library=grad["library"], shapes=rows)
 
 
 def merge(fit, grid):
@@ -89,15 +147,18 @@ def merge(fit, grid):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["fit", "grid", "merge"])
+    ap.add_argument("mode", choices=["fit", "grid", "merge", "grad", "merge-grad"])
     ap.add_argument("--out", default=os.path.join("profiles", "lml_grid.json"))
     ap.add_argument("--fit")
     ap.add_argument("--grid")
+    ap.add_argument("--grad")
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--label", default="this commit", help="which build of the library is timed (UTHOT_LIB)")
     a = ap.parse_args()
     if a.mode == "merge":
         res = merge(json.load(open(a.fit)), json.load(open(a.grid)))
+    elif a.mode == "merge-grad":
+        res = merge_grad(json.load(open(a.fit)), json.load(open(a.grad)))
     else:
         res = run(a.mode, a.repeats, a.label)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

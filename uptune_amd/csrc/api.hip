@@ -827,6 +827,12 @@ int ut_gp_lml_grid(ut_ctx* c, const double* X, const double* y, int32_t n, int32
   return gp_lml_grid_impl(c, X, y, n, d, h, g, scale, noise, lml_host, best_host);
 }
 
+int ut_gp_lml_grad(ut_ctx* c, int32_t d, double* dlog_ell_host, double* dlog_sf2_host, double* dlog_sn2_host) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_lml_grad_impl(c, d, dlog_ell_host, dlog_sf2_host, dlog_sn2_host);
+}
+
 int ut_gp_kstar_mode(ut_ctx* c, int32_t* categorical) {
   if (!c || !categorical) return UT_EINVAL;
   *categorical = c->cat_on ? 1 : 0;

@@ -1021,6 +1021,7 @@ int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32
   c->gp_fit_prec = c->gp_prec;
   c->gp_npad_fit = npad;
   c->gp_diag_fit = diag;
+  c->gp_sn2_fit = h->sigma_n2;
   c->gp_fit_kind = app ? 1 : 0;
   c->gp_ready = true;
   ut_ctx::FitJob& j = c->fit_job;

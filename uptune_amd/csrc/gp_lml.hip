@@ -32,13 +32,6 @@ namespace ut {
 
 constexpr size_t LML_BUDGET = (size_t)1 << 30;      // bytes of K_z matrices one chunk may hold
 
-// lower-triangle tile number -> (i, j), j <= i
-__device__ __forceinline__ void lower_tile(int32_t tid, int32_t& i, int32_t& j) {
-  i = 0;
-  while ((i + 1) * (i + 2) / 2 <= tid) ++i;
-  j = tid - i * (i + 1) / 2;
-}
-
 // sum over rows < n of log L_ii and of beta_i^2 -> the LML; one workgroup
 __device__ __forceinline__ double lml_reduce(const double* __restrict__ L, const double* __restrict__ beta, int32_t n,
                                              int32_t npad, double* red) {

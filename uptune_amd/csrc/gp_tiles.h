@@ -1,7 +1,8 @@
 // gp_tiles.h -- device building blocks of the blocked Cholesky shared by the
-// GP fit (gp_fit.hip) and the batched log-marginal-likelihood grid (gp_lml.hip):
-// the 64 x 64 fp64-MFMA tile product, its accumulator -> tile coordinates and
-// the diagonal-block factor + inverse.
+// GP fit (gp_fit.hip), the batched log-marginal-likelihood grid (gp_lml.hip)
+// and its gradient (gp_lml_grad.hip): the 64 x 64 fp64-MFMA tile product, its
+// accumulator -> tile coordinates, the lower-triangle tile numbering and the
+// diagonal-block factor + inverse.
 #pragma once
 #include "ut_internal.h"
 
@@ -12,10 +13,28 @@ constexpr int NB = 64;     // Cholesky / inverse block
 // 64 x 64 tile  acc = A[64 x K] * B[64 x K]^T  (both row-major in global,
 // leading dims lda / ldb) on v_mfma_f64_16x16x4; each wave 32 x 32.
 typedef double fd4 __attribute__((ext_vector_type(4)));
+// one staged 16-k step: As / Bs [16][80] hold the operands k-major (element (k, row) at k * 80 + row)
+__device__ __forceinline__ void tile64_step(const double* As, const double* Bs, fd4 (&acc)[2][2]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int wr = w >> 1, wc = w & 1;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int kr = ks * 4 + (lane >> 4);
+    double af[2], bf[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) af[i] = As[kr * 80 + wr * 32 + i * 16 + (lane & 15)];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bf[j] = Bs[kr * 80 + wc * 32 + j * 16 + (lane & 15)];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
+  }
+}
+
 __device__ void tile64_nt(const double* __restrict__ A, int64_t lda, const double* __restrict__ B, int64_t ldb,
                           int32_t K, double* As, double* Bs, fd4 (&acc)[2][2]) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int wr = w >> 1, wc = w & 1;
+  const int t = threadIdx.x;
   for (int32_t k0 = 0; k0 < K; k0 += 16) {
     for (int e = t; e < 64 * 16; e += 256) {
       const int r = e >> 4, kk = e & 15;
@@ -24,19 +43,26 @@ __device__ void tile64_nt(const double* __restrict__ A, int64_t lda, const doubl
       Bs[kk * 80 + r] = in ? B[(int64_t)r * ldb + k0 + kk] : 0.0;
     }
     __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int kr = ks * 4 + (lane >> 4);
-      double af[2], bf[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) af[i] = As[kr * 80 + wr * 32 + i * 16 + (lane & 15)];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bf[j] = Bs[kr * 80 + wc * 32 + j * 16 + (lane & 15)];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
+    tile64_step(As, Bs, acc);
+    __syncthreads();
+  }
+}
+
+// 64 x 64 tile  acc += A[k0 .. k1)[ia .. ia + 64)^T A[k0 .. k1)[ja .. ja + 64)
+// of one row-major matrix A (leading dim ld; k0, k1 multiples of 16): the
+// operands' k index is the row, so a staged line is 64 contiguous doubles
+__device__ __forceinline__ void tile64_tn(const double* __restrict__ A, int64_t ld, int64_t ia, int64_t ja, int32_t k0,
+                                          int32_t k1, double* As, double* Bs, fd4 (&acc)[2][2]) {
+  const int t = threadIdx.x;
+  for (int32_t kb = k0; kb < k1; kb += 16) {
+    for (int e = t; e < 64 * 16; e += 256) {
+      const int kk = e >> 6, r = e & 63;
+      const double* row = A + (int64_t)(kb + kk) * ld;
+      As[kk * 80 + r] = row[ia + r];
+      Bs[kk * 80 + r] = row[ja + r];
     }
+    __syncthreads();
+    tile64_step(As, Bs, acc);
     __syncthreads();
   }
 }
@@ -44,6 +70,13 @@ __device__ void tile64_nt(const double* __restrict__ A, int64_t lda, const doubl
 // acc element (i, j, r) -> tile row / column
 __device__ __forceinline__ int tile_row(int i, int r) { return ((threadIdx.x >> 6) >> 1) * 32 + i * 16 + ((threadIdx.x & 63) >> 4) + 4 * r; }
 __device__ __forceinline__ int tile_col(int j) { return ((threadIdx.x >> 6) & 1) * 32 + j * 16 + (threadIdx.x & 15); }
+
+// lower-triangle tile number -> (i, j), j <= i
+__device__ __forceinline__ void lower_tile(int32_t tid, int32_t& i, int32_t& j) {
+  i = 0;
+  while ((i + 1) * (i + 2) / 2 <= tid) ++i;
+  j = tid - i * (i + 1) / 2;
+}
 
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
   const uint64_t u = __builtin_bit_cast(uint64_t, v);

@@ -294,6 +294,7 @@ struct ut_ctx {
   int32_t fit_append = 1;
   int32_t gp_npad_fit = 0;     // padded size of the current factor
   double gp_diag_fit = 0.0;    // its sigma_n2 + jitter
+  double gp_sn2_fit = 0.0;     // ... and its sigma_n2 alone (the LML gradient's noise component)
   int32_t gp_fit_kind = 0;     // 0 = the last fit refactored, 1 = it appended rows
   bool gp_linvt_stale = false; // gp_LinvT / gp_alpha not yet written for the current factor (gp_ensure_linvt)
   int32_t* flag_host = nullptr;  // pinned readback of the previous fit's flag
@@ -415,6 +416,9 @@ struct ut_ctx {
   ut::DevBuf<int32_t> lml_flag;   // [g] point z is not positive definite
   int32_t lml_batch = 0;          // grid points per chunk; 0 = what fits LML_BUDGET (UT_LML_BATCH)
   double* lml_host = nullptr;     // pinned: ut_gp_lml's result, written by its kernel
+  // the LML gradient's scratch (gp_lml_grad.hip): alpha [npad] | the components [d + 2] |
+  // the lower tiles' shares of them [tiles][d + 2]
+  ut::DevBuf<double> lml_grad;
   int32_t dbg_fail_alloc = 0;              // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
@@ -558,6 +562,8 @@ int launch_gp_ystats(ut_ctx* c, const double* y, int32_t n, int32_t npad, double
 int gp_lml_impl(ut_ctx* c, double* lml_host);
 int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
                      int32_t g, const double* scale, const double* noise, double* lml_host, int32_t* best_host);
+// gp_lml_grad.hip: its gradient at the fit in place
+int gp_lml_grad_impl(ut_ctx* c, int32_t d, double* dlog_ell_host, double* dlog_sf2_host, double* dlog_sn2_host);
 
 // kernel launchers implemented in the .hip translation units
 int launch_population_init(ut_ctx* c, uint32_t round_);

@@ -319,6 +319,7 @@ class BatchEngine:
         h = L.GpHyper(sigma_f2=float(sigma_f2), sigma_n2=float(sigma_n2), jitter=float(jitter),
                       lengthscale_host=ell.ctypes.data)
         fn = self.lib.ut_gp_fit if wait else self.lib.ut_gp_fit_async
+        self._gp_d = d
         L.check(self.ctx, fn(self.ctx, X.ctypes.data, y.ctypes.data, n, d, C.byref(h)), "ut_gp_fit")
 
     def gp_join_fit(self):
@@ -355,6 +356,17 @@ class BatchEngine:
         v = C.c_double()
         L.check(self.ctx, self.lib.ut_gp_lml(self.ctx, C.byref(v)), "ut_gp_lml")
         return float(v.value)
+
+    def gp_lml_grad(self) -> Tuple[np.ndarray, float, float]:
+        """ut_gp_lml_grad: the gradient of the current fit's log marginal
+        likelihood in (log lengthscale [d], log sigma_f2, log sigma_n2); fp64,
+        deterministic, waits for an in-flight fit and raises as gp_lml does"""
+        d = int(getattr(self, "_gp_d", self.spec.n_features))   # the last gp_fit's feature count
+        g = np.empty(d, dtype=np.float64)
+        sf, sn = C.c_double(), C.c_double()
+        L.check(self.ctx, self.lib.ut_gp_lml_grad(self.ctx, d, g.ctypes.data, C.byref(sf), C.byref(sn)),
+                "ut_gp_lml_grad")
+        return g, float(sf.value), float(sn.value)
 
     def gp_lml_grid(self, X: np.ndarray, y: np.ndarray, lengthscale, scales, noises=None, sigma_f2: float = 1.0,
                     sigma_n2: float = 1e-6, jitter: float = 0.0) -> Tuple[np.ndarray, int]:

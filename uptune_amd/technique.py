@@ -273,11 +273,21 @@ class SharedModel:
 
     def __init__(self, device: int = 0, seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4,
                  precision: int = 64, sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 1e-8,
-                 engine_factory=None, y_transform: Optional[str] = None, ell_grid=None):
-        if isinstance(lengthscale, str) and lengthscale != "auto":
-            raise ValueError("lengthscale: a number (or one per feature) or 'auto'")
+                 engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40):
+        if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
+            raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
         self.precision = precision
+        # lengthscale="ard": one lengthscale per feature group, by L-BFGS-B on the
+        # log marginal likelihood over log ell (engine.gp_lml_grad: the gradient
+        # of the fit in place), started at "auto"'s isotropic choice, at most
+        # ard_maxiter iterations, every ell within [grid min, 4 grid max]; at the
+        # same moments as "auto".  A group is one numeric feature, one PERM
+        # parameter's columns, or all ENUM / BOOL one-hot columns together (the
+        # categorical K* needs one lengthscale over those).  Never worse than
+        # "auto": a result whose LML does not exceed the start's is dropped for
+        # the start.  lengthscale_ is then the per-feature array.
+        self.ard_maxiter = int(ard_maxiter)
         # lengthscale="auto": the lengthscale is the candidate of ell_grid
         # (isotropic; default sqrt(n_features) * geomspace(0.05, 4, 16)) with the
         # largest log marginal likelihood on the fit's own rows and targets
@@ -458,9 +468,12 @@ class SharedModel:
             r = rankdata(y, method="average") - 1.0
             y = ndtri((r + 0.5) / n)
         ell = self.lengthscale
-        if isinstance(ell, str):   # "auto"
+        if isinstance(ell, str):   # "auto" / "ard"
             if npad != self._ell_npad:
-                self._select_lengthscale(self._Xf[:n], y)
+                if ell == "ard":
+                    self._select_ard(self._Xf[:n], y)
+                else:
+                    self._select_lengthscale(self._Xf[:n], y)
                 self._ell_npad = npad
             ell = self.lengthscale_
         self.engine.gp_fit(self._Xf[:n], y, lengthscale=ell, wait=False, **self.hyper)
@@ -469,20 +482,88 @@ class SharedModel:
         self.fits += 1
         return True
 
+    def _grid(self, d: int) -> np.ndarray:
+        return math.sqrt(d) * np.geomspace(0.05, 4.0, 16) if self.ell_grid is None else self.ell_grid
+
     def _select_lengthscale(self, X, y) -> None:
         """lengthscale_ := the grid candidate with the largest log marginal
         likelihood of (X, y); when no candidate is positive definite the previous
         choice stays (the grid's median on the first fit) and the fit's jitter
         retry takes it from there"""
-        grid = self.ell_grid
-        if grid is None:
-            grid = math.sqrt(X.shape[1]) * np.geomspace(0.05, 4.0, 16)
+        grid = self._grid(X.shape[1])
         lml, best = self.engine.gp_lml_grid(X, y, 1.0, grid, **self.hyper)
         if best >= 0:
             self.lengthscale_ = float(grid[best])
         elif self.lengthscale_ is None:
             self.lengthscale_ = float(np.median(grid))
         self.ell_history.append((len(y), self.lengthscale_, float(lml[best]) if best >= 0 else float("nan")))
+
+    def _ell_groups(self, d: int) -> np.ndarray:
+        """feature column -> its lengthscale group ("ard"): numeric features one
+        each, a PERM parameter's columns one, every ENUM / BOOL column the same one"""
+        from . import _lib as L
+        gid = np.zeros(d, dtype=np.int64)
+        ng, cat = 0, -1
+        for p in self.engine.spec.params:
+            if p.kind in (L.UT_ENUM, L.UT_BOOL):
+                if cat < 0:
+                    cat, ng = ng, ng + 1
+                g = cat
+            else:
+                g, ng = ng, ng + 1
+            gid[p.feat_col:p.feat_col + p.n_feat] = g
+        return gid
+
+    def _select_ard(self, X, y) -> None:
+        """lengthscale_ := one lengthscale per feature (per group, _ell_groups)
+        by L-BFGS-B on the log marginal likelihood of (X, y) from the grid's
+        isotropic best; each evaluation is a fit at the point, its LML and its
+        gradient on the device.  A point that is not positive definite is
+        rejected, and a result no better than the start keeps the start."""
+        from scipy.optimize import minimize
+
+        from ._lib import UthotError
+        d = X.shape[1]
+        grid = self._grid(d)
+        lml, best = self.engine.gp_lml_grid(X, y, 1.0, grid, **self.hyper)
+        if best < 0:   # as "auto": the previous choice stays (the grid's median on the first fit)
+            if self.lengthscale_ is None:
+                self.lengthscale_ = np.full(d, float(np.median(grid)))
+            self.ell_history.append((len(y), self.lengthscale_, float("nan")))
+            return
+        ell0, lml0 = float(grid[best]), float(lml[best])
+        gid = self._ell_groups(d)
+        ng = int(gid.max()) + 1
+        top = {"lml": lml0, "theta": None}
+        reject = -lml0 + 1e3 * (1.0 + abs(lml0))   # a rejected point: far worse than the start, flat
+
+        def neg_lml(theta):
+            ell = np.exp(theta)[gid]
+            try:
+                self.engine.gp_fit(X, y, lengthscale=ell, wait=True, **self.hyper)
+                ok = self.engine.gp_fit_ok()
+            except UthotError as e:
+                if "UT_ENOTPD" not in str(e):
+                    raise
+                ok = False
+            if not ok:
+                return reject, np.zeros(ng)
+            v = float(self.engine.gp_lml())
+            g = self.engine.gp_lml_grad()[0]
+            if v > top["lml"] and not np.array_equal(theta, theta0):   # (the start is the grid's own point)
+                top["lml"], top["theta"] = v, np.array(theta, dtype=np.float64)
+            return -v, -np.bincount(gid, weights=g, minlength=ng)
+
+        lo, hi = math.log(float(np.min(grid))), math.log(4.0 * float(np.max(grid)))
+        theta0 = np.full(ng, math.log(ell0))
+        minimize(neg_lml, theta0, jac=True, method="L-BFGS-B", bounds=[(lo, hi)] * ng,
+                 options={"maxiter": self.ard_maxiter})
+        if top["theta"] is None:   # nothing beat the isotropic start
+            ell = np.full(d, ell0)
+        else:
+            ell = np.ascontiguousarray(np.exp(top["theta"])[gid])
+        self.lengthscale_ = ell
+        self.ell_history.append((len(y), ell, top["lml"]))
 
     def note_selections(self, hexes) -> None:
         """a round's selections are requests the driver has not made yet: they
