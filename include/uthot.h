@@ -440,9 +440,21 @@ int ut_score_round_de_pruned(ut_ctx* ctx, const ut_de_params* de, const ut_acq* 
                              ut_prune_stats* stats_host);
 /* device pointers to the last round's internal buffers (for tests/bench);
  * features is NULL: the rounds (dense and pruned) encode straight into the K*
- * operands (features / ell, norms, one-hot codes) and keep no feature matrix */
+ * operands (features / ell, norms, one-hot codes) and keep no feature matrix.
+ * After a lazy round that did not fall back (ut_round_lazy_stats) digests and
+ * dup are NULL -- only the round's score-sorted prefix was hashed -- and score
+ * holds the unmasked scores (no -inf on duplicates); asking for either of the
+ * two waits for the round. */
 int ut_round_buffers(ut_ctx* ctx, double** values, double** features, uint32_t** digests, uint8_t** dup,
                      double** mu, double** var, double** score, int64_t* ld);
+/* Dense DE rounds (ut_score_round_de) are lazy when K', the smallest power of
+ * two >= 2k, is at most 1024 and less than m: only the K' best-scoring
+ * candidates are hashed and deduplicated, which selects what hashing all m
+ * would.  A round whose prefix holds fewer than k distinct new configurations
+ * falls back, on the device, to hashing all m.  UT_LAZY_HASH=0 (read per
+ * round) keeps every round eager.  The counts since ut_ctx_create; reading
+ * fallback_rounds waits for the stream. */
+int ut_round_lazy_stats(ut_ctx* ctx, int64_t* lazy_rounds, int64_t* fallback_rounds);
 
 /* ---- tree-ensemble surrogate (the reference's own model family:
  *      plugins/xgbregressor.py:50-63, src/multi_stage.py:8-22) ------------- */

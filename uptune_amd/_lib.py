@@ -145,6 +145,7 @@ SIGNATURES = {
                                     I32, C.POINTER(RoundOut)]),
     "ut_score_round_de": (C.c_int, [P, C.POINTER(DeParams), C.POINTER(Acq), U32, I64, I64, I32,
                                     C.POINTER(RoundOut)]),
+    "ut_round_lazy_stats": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ut_round_buffers": (C.c_int, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
                                    C.POINTER(P), C.POINTER(P), C.POINTER(I64)]),
     "ut_comm_unique_id": (C.c_int, [P]),

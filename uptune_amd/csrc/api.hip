@@ -900,6 +900,31 @@ static int score_round_de_impl(ut_ctx* c, const ut_de_params* de, const ut_acq* 
   if ((rc = ensure(c, c->r_topk_score, (size_t)k))) return rc;
   c->r_ld = ld;
   c->r_m = m;
+  // A dense round is lazy when the prefix of kp >= 2k score-sorted candidates
+  // (a power of two, within the top-k kernel's limit) is shorter than the
+  // batch: only the prefix is hashed and deduplicated (lazy_tail below).
+  // UT_LAZY_HASH=0 keeps every round eager.
+  int32_t kp = 2;
+  while (kp < 2 * (int64_t)k && kp <= 1024) kp <<= 1;
+  const char* lz_env = getenv("UT_LAZY_HASH");
+  const bool lazy = prune_rows == 0 && k >= 1 && kp <= 1024 && kp < m && !(lz_env && atoi(lz_env) == 0);
+  c->r_lazy = false;
+  if (lazy) {
+    if ((rc = ensure(c, c->lz_idx, (size_t)kp))) return rc;
+    if ((rc = ensure(c, c->lz_score, (size_t)kp))) return rc;
+    if ((rc = ensure(c, c->lz_vals, (size_t)NC * kp))) return rc;
+    if ((rc = ensure(c, c->lz_dig, (size_t)8 * kp))) return rc;
+    if ((rc = ensure(c, c->lz_out_dig, (size_t)8 * k))) return rc;
+    if ((rc = ensure(c, c->r_topk_vals, (size_t)NC * k))) return rc;
+    if (!c->lz_gate.p) {
+      if ((rc = ensure(c, c->lz_gate, 1))) return rc;
+      UT_HIP(c, hipMemsetAsync(c->lz_gate.p, 0, sizeof(int32_t), c->stream));
+    }
+    if (!c->lz_nfall.p) {
+      if ((rc = ensure(c, c->lz_nfall, 1))) return rc;
+      UT_HIP(c, hipMemsetAsync(c->lz_nfall.p, 0, sizeof(int64_t), c->stream));
+    }
+  }
   timing_begin(c);
   // the proposal also writes the DE-diff mask / pairs the hash reuses
   if ((rc = check_de_params(c, de, m, cand_base))) return rc;
@@ -931,6 +956,57 @@ static int score_round_de_impl(ut_ctx* c, const ut_de_params* de, const ut_acq* 
     UT_HIP(c, hipEventRecord(c->ev_join, c->side));
     return 0;
   };
+  // A lazy round: everything on the caller's stream, scores unmasked.  A
+  // duplicate matters only if it would be selected, and in the score-sorted
+  // list its first occurrence (equal configuration, bitwise-equal score,
+  // smaller index) comes directly ahead of it: so the top kp by score are
+  // hashed (the small-m path: no DE-diff pairs, no target cache), deduplicated
+  // against the history and each other, and their first k survivors are the
+  // eager round's selections.  Fewer than k survivors in a full prefix set
+  // the device flag lz_gate, and the eager remainder -- enqueued every round,
+  // each kernel returning at once while the flag is 0 -- redoes the selection
+  // over all m candidates: no host wait, no kernel waiting on another.
+  auto lazy_tail = [&]() -> int {
+    int r;
+    if ((r = topk_impl(c, c->r_score.p, nullptr, m, cand_base, kp, c->lz_idx.p, c->lz_score.p))) return r;
+    mark(c, "topk");
+    if ((r = launch_gather_prefix_rows(c, c->r_values.p, ld, c->lz_idx.p, cand_base, kp, c->lz_vals.p))) return r;
+    if ((r = launch_hash(c, c->lz_vals.p, kp, kp, c->lz_dig.p))) return r;
+    mark(c, "hash");
+    double* vals = out && out->topk_values ? out->topk_values : c->r_topk_vals.p;
+    uint32_t* digs = out && out->topk_digest ? out->topk_digest : c->lz_out_dig.p;
+    if ((r = launch_prefix_dedup(c, c->lz_idx.p, c->lz_score.p, c->lz_dig.p, c->lz_vals.p, kp, cand_base, k,
+                                 c->r_topk_idx.p, c->r_topk_score.p, vals, digs, c->lz_gate.p, c->lz_nfall.p)))
+      return r;
+    mark(c, "dedup");
+    {
+      GateScope gated(c, c->lz_gate.p);
+      if ((r = launch_hash_de(c, c->r_values.p, ld, m, cand_base, c->r_digest.p, true))) return r;
+      if ((r = launch_dedup(c, c->r_digest.p, m, c->r_dup.p))) return r;
+      if ((r = launch_mask_score(c, c->r_score.p, c->r_dup.p, m))) return r;
+      if ((r = topk_impl(c, c->r_score.p, c->r_dup.p, m, cand_base, k, c->r_topk_idx.p, c->r_topk_score.p))) return r;
+      if ((r = launch_gather_rows(c, c->r_values.p, ld, c->r_topk_idx.p, cand_base, k, vals, k, c->r_digest.p, digs)))
+        return r;
+    }
+    if (out && out->topk_idx)
+      UT_HIP(c, hipMemcpyAsync(out->topk_idx, c->r_topk_idx.p, sizeof(int64_t) * k, hipMemcpyDeviceToDevice,
+                               c->stream));
+    if (out && out->topk_score)
+      UT_HIP(c, hipMemcpyAsync(out->topk_score, c->r_topk_score.p, sizeof(double) * k, hipMemcpyDeviceToDevice,
+                               c->stream));
+    mark(c, "outputs");
+    ++c->lazy_rounds;
+    c->r_lazy = true;
+    return 0;
+  };
+  if (lazy) {
+    if ((rc = gp_encode_scaled(c, c->r_values.p, ld, m))) return rc;
+    c->r_feat_valid = false;
+    mark(c, "encode");
+    if ((rc = gp_score_impl(c, nullptr, ld, m, acq, nullptr, c->r_mu.p, c->r_var.p, c->r_score.p))) return rc;
+    if ((rc = lazy_tail())) return rc;
+    return timing_end(c);
+  }
   if ((rc = fork_hash())) return rc;
   // encode straight into the K* operands (features * 1/ell, their norms and
   // the one-hot codes); the pruned round gathers its threshold set's and
@@ -1014,6 +1090,7 @@ int ut_score_round_ga(ut_ctx* c, const ut_ga_params* ga, const double* parent1, 
   c->r_ld = ld;
   c->r_m = m;
   c->r_feat_valid = false;
+  c->r_lazy = false;
   timing_begin(c);
   if ((rc = gp_fit_prefit(c))) return rc;   // (as score_round_de_impl)
   if ((rc = launch_ga(c, ga, parent1, parent2, round_, cand_base, m, c->r_values.p, ld, c->r_inval.p))) return rc;
@@ -1052,12 +1129,34 @@ int ut_round_buffers(ut_ctx* c, double** values, double** features, uint32_t** d
   if (!c) return UT_EINVAL;
   if (values) *values = c->r_values.p;
   if (features) *features = c->r_feat_valid ? c->r_feat.p : nullptr;   // dense rounds keep no feature matrix
-  if (digests) *digests = c->r_digest.p;
-  if (dup) *dup = c->r_dup.p;
+  // a lazy round that did not fall back hashed only its prefix: no digest
+  // array, no dup mask, and its scores are unmasked
+  bool full = true;
+  if (c->r_lazy && (digests || dup)) {
+    int32_t need = 0;
+    UT_HIP(c, hipMemcpyAsync(&need, c->lz_gate.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    UT_HIP(c, hipStreamSynchronize(c->stream));
+    full = need != 0;
+  }
+  if (digests) *digests = full ? c->r_digest.p : nullptr;
+  if (dup) *dup = full ? c->r_dup.p : nullptr;
   if (mu) *mu = c->r_mu.p;
   if (var) *var = c->r_var.p;
   if (score) *score = c->r_score.p;
   if (ld) *ld = c->r_ld;
+  return 0;
+}
+
+int ut_round_lazy_stats(ut_ctx* c, int64_t* lazy_rounds, int64_t* fallback_rounds) {
+  if (!c) return UT_EINVAL;
+  if (lazy_rounds) *lazy_rounds = c->lazy_rounds;
+  if (fallback_rounds) {
+    *fallback_rounds = 0;
+    if (c->lz_nfall.p) {
+      UT_HIP(c, hipStreamSynchronize(c->stream));
+      UT_HIP(c, hipMemcpy(fallback_rounds, c->lz_nfall.p, sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+  }
   return 0;
 }
 

@@ -40,10 +40,11 @@ __global__ void k_hist_insert(uint32_t* __restrict__ keys, uint32_t* __restrict_
   }
 }
 
+// gate (both batch kernels): a lazy round's remainder, skipped when *gate == 0
 __global__ void k_batch_insert(const uint32_t* __restrict__ dig, int64_t m, int32_t* __restrict__ slots,
-                               int64_t cap) {
+                               int64_t cap, const int32_t* __restrict__ gate) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
+  if (i >= m || (gate && *gate == 0)) return;
   const uint32_t* d = dig + i * 8;
   uint64_t h = d[0] & (uint64_t)(cap - 1);
   for (int64_t probe = 0; probe < cap; ++probe) {
@@ -59,9 +60,9 @@ __global__ void k_batch_insert(const uint32_t* __restrict__ dig, int64_t m, int3
 
 __global__ void k_dedup_mark(const uint32_t* __restrict__ dig, int64_t m, const int32_t* __restrict__ slots,
                              int64_t cap, const uint32_t* __restrict__ hkeys, const uint32_t* __restrict__ hstate,
-                             int64_t hcap, uint8_t* __restrict__ dup) {
+                             int64_t hcap, uint8_t* __restrict__ dup, const int32_t* __restrict__ gate) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
+  if (i >= m || (gate && *gate == 0)) return;
   const uint32_t* d = dig + i * 8;
   bool is_dup = false;
   if (hcap > 0) {
@@ -136,6 +137,125 @@ int launch_mask_or(ut_ctx* c, uint8_t* dst, const uint8_t* src, int64_t m) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Lazy rounds: dedup + compaction of the score-sorted prefix (kp <= 1024
+// entries, one workgroup, thread p = prefix entry p).  The batch table lives
+// in LDS: a digest's slot is claimed by whichever of its entries comes first
+// (cls), and the slot's `best` ends as the smallest candidate index among
+// them (atomicMin), so the surviving entry does not depend on scheduling.
+// The entries that are neither in the history nor behind a smaller index keep
+// their prefix order; the first k of them are the round's selections.
+// ---------------------------------------------------------------------------
+constexpr int PFX_NT = 1024;
+constexpr int PFX_CAP = 2048;   // table slots: twice the entries
+
+__global__ __launch_bounds__(PFX_NT) void k_prefix_dedup(
+    const int64_t* __restrict__ idx, const double* __restrict__ score, const uint32_t* __restrict__ dig,
+    const double* __restrict__ vals, int32_t NC, int32_t kp, int64_t cand_base, const uint32_t* __restrict__ hkeys,
+    const uint32_t* __restrict__ hstate, int64_t hcap, int32_t k, int64_t* __restrict__ out_idx,
+    double* __restrict__ out_score, double* __restrict__ out_vals, uint32_t* __restrict__ out_dig,
+    int32_t* __restrict__ gate, int64_t* __restrict__ nfall) {
+  __shared__ int32_t cls[PFX_CAP];    // slot -> the prefix entry that claimed it, -1 = empty
+  __shared__ int32_t best[PFX_CAP];   // slot -> smallest candidate index (local) with its digest
+  __shared__ int32_t wkeep[PFX_NT / 64], wvalid[PFX_NT / 64];
+  const int p = threadIdx.x;
+  for (int e = p; e < PFX_CAP; e += PFX_NT) {
+    cls[e] = -1;
+    best[e] = 0x7FFFFFFF;
+  }
+  __syncthreads();
+  const int64_t g = p < kp ? idx[p] : -1;
+  const bool valid = g >= 0;
+  const int32_t li = valid ? (int32_t)(g - cand_base) : 0;
+  const uint32_t* d = dig + (int64_t)(p < kp ? p : 0) * 8;
+  int32_t slot = -1;
+  if (valid) {
+    uint32_t h = d[0] & (PFX_CAP - 1);
+    for (int probe = 0; probe < PFX_CAP; ++probe) {
+      const int32_t cur = atomicCAS(&cls[h], -1, p);
+      if (cur == -1 || cur == p || key_eq(dig + (int64_t)cur * 8, d)) {
+        slot = (int32_t)h;
+        break;
+      }
+      h = (h + 1) & (PFX_CAP - 1);
+    }
+    if (slot >= 0) atomicMin(&best[slot], li);
+  }
+  __syncthreads();
+  bool keep = valid && slot >= 0 && best[slot] == li;
+  if (keep && hcap > 0) {   // the history probe of k_dedup_mark
+    uint64_t h = d[0] & (uint64_t)(hcap - 1);
+    for (int64_t probe = 0; probe < hcap; ++probe) {
+      if (hstate[h] == 0u) break;
+      if (key_eq(hkeys + h * 8, d)) {
+        keep = false;
+        break;
+      }
+      h = (h + 1) & (uint64_t)(hcap - 1);
+    }
+  }
+  // rank among the kept entries, in prefix order
+  const int lane = p & 63, w = p >> 6;
+  const unsigned long long bk = __ballot(keep), bv = __ballot(valid);
+  if (lane == 0) {
+    wkeep[w] = __builtin_popcountll(bk);
+    wvalid[w] = __builtin_popcountll(bv);
+  }
+  __syncthreads();
+  int32_t rank = __builtin_popcountll(bk & ((1ull << lane) - 1ull)), total = 0, nvalid = 0;
+  for (int q = 0; q < PFX_NT / 64; ++q) {
+    if (q < w) rank += wkeep[q];
+    total += wkeep[q];
+    nvalid += wvalid[q];
+  }
+  if (keep && rank < k) {
+    out_idx[rank] = g;
+    out_score[rank] = score[p];
+    for (int32_t col = 0; col < NC; ++col) out_vals[(int64_t)col * k + rank] = vals[(int64_t)col * kp + p];
+    for (int q = 0; q < 8; ++q) out_dig[(int64_t)rank * 8 + q] = d[q];
+  }
+  // fewer than k: empty slots as the row gather writes them; their score is
+  // that of the prefix's own empty entry at the slot, -inf (a duplicate's
+  // masked score) where the prefix holds a candidate
+  for (int32_t j = total + p; j < k; j += PFX_NT) {
+    out_idx[j] = -1;
+    out_score[j] = (j < kp && idx[j] < 0) ? score[j] : -1.0 / 0.0;
+    for (int32_t col = 0; col < NC; ++col) out_vals[(int64_t)col * k + j] = 0.0;
+    for (int q = 0; q < 8; ++q) out_dig[(int64_t)j * 8 + q] = 0u;
+  }
+  if (p == 0) {
+    // candidates beyond the prefix exist only if every prefix entry is one
+    const int32_t need = (total < k && nvalid == kp) ? 1 : 0;
+    *gate = need;
+    if (need) *nfall += 1;
+  }
+}
+
+int launch_prefix_dedup(ut_ctx* c, const int64_t* idx, const double* score, const uint32_t* dig, const double* vals,
+                        int32_t kp, int64_t cand_base, int32_t k, int64_t* out_idx, double* out_score,
+                        double* out_vals, uint32_t* out_dig, int32_t* gate, int64_t* nfall) {
+  UT_CHECK(c, kp >= 1 && kp <= PFX_NT && k >= 1 && k <= kp, UT_EINVAL, "prefix dedup: 1 <= k <= prefix <= 1024");
+  hipLaunchKernelGGL(k_prefix_dedup, dim3(1), dim3(PFX_NT), 0, c->stream, idx, score, dig, vals, c->space.ncols, kp,
+                     cand_base, c->hist_keys.p, c->hist_state.p, c->hist_cap, k, out_idx, out_score, out_vals, out_dig,
+                     gate, nfall);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
+__global__ void k_mask_score(double* __restrict__ score, const uint8_t* __restrict__ dup, int64_t m,
+                             const int32_t* __restrict__ gate) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m || (gate && *gate == 0)) return;
+  if (dup[i]) score[i] = -1.0 / 0.0;
+}
+
+int launch_mask_score(ut_ctx* c, double* score, const uint8_t* dup, int64_t m) {
+  if (m <= 0) return 0;
+  hipLaunchKernelGGL(k_mask_score, dim3(grid1(m, 256)), dim3(256), 0, c->stream, score, dup, m, c->round_gate);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 int launch_dedup(ut_ctx* c, const uint32_t* dig, int64_t m, uint8_t* dup) {
   if (m <= 0) return 0;
   int64_t cap = 1024;
@@ -149,10 +269,11 @@ int launch_dedup(ut_ctx* c, const uint32_t* dig, int64_t m, uint8_t* dup) {
     if (int rc = ut::dalloc(c, c->batch_slots, (size_t)cap)) return rc;
   }
   UT_HIP(c, hipMemsetAsync(c->batch_slots.p, 0xFF, cap * sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(k_batch_insert, dim3(grid1(m, 256)), dim3(256), 0, c->stream, dig, m, c->batch_slots.p, cap);
+  hipLaunchKernelGGL(k_batch_insert, dim3(grid1(m, 256)), dim3(256), 0, c->stream, dig, m, c->batch_slots.p, cap,
+                     c->round_gate);
   UT_LAUNCH_CHECK(c);
   hipLaunchKernelGGL(k_dedup_mark, dim3(grid1(m, 256)), dim3(256), 0, c->stream, dig, m, c->batch_slots.p, cap,
-                     c->hist_keys.p, c->hist_state.p, c->hist_cap, dup);
+                     c->hist_keys.p, c->hist_state.p, c->hist_cap, dup, c->round_gate);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

@@ -101,11 +101,13 @@ __global__ __launch_bounds__(PD_NT) void k_perm_digest(const DevParam* __restric
                                                        const int32_t* __restrict__ offbase,
                                                        const int32_t* __restrict__ msg_len,
                                                        const double* __restrict__ values, int64_t ld, int64_t m,
-                                                       uint32_t* __restrict__ out) {
+                                                       uint32_t* __restrict__ out,
+                                                       const int32_t* __restrict__ gate) {
   __shared__ uint32_t lds[16 * PD_NT];
   const int lane = threadIdx.x;
   const int64_t i = (int64_t)blockIdx.x * PD_NT + lane;
-  if (i >= m) return;  // no barriers below: every lane owns its LDS column
+  // (gate: a lazy round's remainder, skipped when *gate == 0)
+  if (i >= m || (gate && *gate == 0)) return;  // no barriers below: every lane owns its LDS column
   LdsEmitN<PD_NT> e{reinterpret_cast<uint8_t*>(lds), lane};
   for (int32_t q = 0; q < n_perm; ++q) {
     const DevParam pr = params[perm_params[q]];
@@ -247,9 +249,11 @@ __global__ __launch_bounds__(HASH_NT) void k_inner_pairs(const DevParam* __restr
                                                          const double* __restrict__ values, int64_t ld,
                                                          const uint64_t* __restrict__ pairs,
                                                          const unsigned long long* __restrict__ npairs,
-                                                         uint4* __restrict__ fresh) {
+                                                         uint4* __restrict__ fresh,
+                                                         const int32_t* __restrict__ gate) {
   __shared__ uint32_t lds[SCR_WORDS * HASH_NT];
   const int lane = threadIdx.x;
+  if (gate && *gate == 0) return;
   const int64_t n = (int64_t)*npairs;
   for (int64_t q = (int64_t)blockIdx.x * HASH_NT + lane; q < n; q += (int64_t)gridDim.x * HASH_NT) {
     const uint64_t e = pairs[q];
@@ -292,6 +296,7 @@ struct InnerRef {
   int64_t npop, cand_base;
   int64_t wlo, wn;        // the cache's member window (every target (cand_base + i) % npop lies in it)
   int64_t ldf;            // leading dimension of mask / fresh
+  const int32_t* gate = nullptr;   // a lazy round's remainder: k_hash returns at once when *gate == 0
 };
 
 // REF: every computed inner digest comes from ref (cache / fresh) and the
@@ -325,6 +330,7 @@ __global__ __launch_bounds__(HASH_NT, MINW) void k_hash(const DevParam* __restri
                                                   uint32_t* __restrict__ out, InnerRef ref) {
   __shared__ uint32_t lds[REF ? 1 : SCR_WORDS * HASH_NT];
   const int lane = threadIdx.x;
+  if (ref.gate && *ref.gate == 0) return;
   // grid-stride over candidate blocks (launch_hash gives one block per 128
   // candidates; a smaller grid stays correct)
   for (int64_t blk = blockIdx.x; blk * HASH_NT < m; blk += gridDim.x) {
@@ -455,13 +461,15 @@ static int launch_hash_impl(ut_ctx* c, const double* values, int64_t ld, int64_t
     if (rc) return rc;
     hipLaunchKernelGGL(k_perm_digest, dim3(grid1(m, PD_NT)), dim3(PD_NT), 0, c->stream, s.d_params.p, s.d_perm_params.p,
                        s.n_perm, s.d_perm_bytes.p, s.d_perm_off.p, s.d_perm_offbase.p, s.d_perm_len.p, values, ld, m,
-                       c->perm_dig.p);
+                       c->perm_dig.p, c->round_gate);
     UT_LAUNCH_CHECK(c);
     pd = c->perm_dig.p;
   }
   // (grid-stride: a cap on the grid leaves CU slots to the fit stream's kernels)
   int64_t nb = (int64_t)grid1(m, HASH_NT);
-  if (const int32_t cap = hash_cap(c, m, true, after_fit)) nb = std::min<int64_t>(nb, (int64_t)c->n_cu * cap);
+  // (a gated launch comes after the round's scoring, which has waited for the fit)
+  ref.gate = c->round_gate;
+  if (const int32_t cap = hash_cap(c, m, true, after_fit || ref.gate)) nb = std::min<int64_t>(nb, (int64_t)c->n_cu * cap);
 #ifndef UT_HASH_REF_WAVES
 #define UT_HASH_REF_WAVES 4
 #endif
@@ -564,11 +572,11 @@ int launch_hash_de(ut_ctx* c, const double* values, int64_t ld, int64_t m, int64
   const int64_t want = ((int64_t)s.n_comp * m + HASH_NT - 1) / HASH_NT;
   // (ctx.round_hash_hold: the round's inner digests and outer hash wait for an in-flight fit)
   const bool hold = c->round_hash_hold && c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
-  const int32_t cap = hash_cap(c, m, false, hold);
+  const int32_t cap = hash_cap(c, m, false, hold || c->round_gate);
   const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), (int64_t)c->n_cu * (cap > 0 ? cap : 8));
   if (hold) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));
   hipLaunchKernelGGL(k_inner_pairs, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_comp.p, values, ld,
-                     c->r_pairs.p, np, reinterpret_cast<uint4*>(c->r_fresh.p));
+                     c->r_pairs.p, np, reinterpret_cast<uint4*>(c->r_fresh.p), c->round_gate);
   UT_LAUNCH_CHECK(c);
   return launch_hash_impl(c, values, ld, m, out,
                           InnerRef{c->r_mask.p, reinterpret_cast<const uint4*>(c->r_fresh.p),
@@ -597,7 +605,7 @@ int launch_hash_parent(ut_ctx* c, const double* values, int64_t ld, int64_t m, c
   const int64_t want = ((int64_t)s.n_comp * m + HASH_NT - 1) / HASH_NT;
   const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), (int64_t)c->n_cu * 8);
   hipLaunchKernelGGL(k_inner_pairs, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_comp.p, values, ld,
-                     c->r_pairs.p, np, reinterpret_cast<uint4*>(c->r_fresh.p));
+                     c->r_pairs.p, np, reinterpret_cast<uint4*>(c->r_fresh.p), c->round_gate);
   UT_LAUNCH_CHECK(c);
   return launch_hash_impl(c, values, ld, m, out,
                           InnerRef{c->r_mask.p, reinterpret_cast<const uint4*>(c->r_fresh.p),

@@ -511,9 +511,9 @@ __global__ __launch_bounds__(256) void k_encode_scaled_cat(const DevParam* __res
 __global__ void k_gather_rows(int32_t NC, const double* __restrict__ values, int64_t ld,
                               const int64_t* __restrict__ idx, int64_t cand_base, int32_t k,
                               double* __restrict__ out, int64_t ldo, const uint32_t* __restrict__ dig,
-                              uint32_t* __restrict__ out_dig) {
+                              uint32_t* __restrict__ out_dig, const int32_t* __restrict__ gate) {
   const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= k) return;
+  if (j >= k || (gate && *gate == 0)) return;   // (gate: a lazy round's remainder)
   const int64_t g = idx[j];
   const int64_t i = g - cand_base;
   for (int32_t p = 0; p < NC; ++p) out[(int64_t)p * ldo + j] = (g >= 0) ? values[(int64_t)p * ld + i] : 0.0;
@@ -973,7 +973,27 @@ int launch_encode_scaled_cat(ut_ctx* c, const double* values, int64_t ld, int64_
 int launch_gather_rows(ut_ctx* c, const double* values, int64_t ld, const int64_t* idx, int64_t cand_base,
                        int32_t k, double* out, int64_t ldo, const uint32_t* dig, uint32_t* out_dig) {
   hipLaunchKernelGGL(k_gather_rows, dim3(grid1(k, 64)), dim3(64), 0, c->stream, c->space.ncols, values, ld, idx,
-                     cand_base, k, out, ldo, dig, out_dig);
+                     cand_base, k, out, ldo, dig, out_dig, c->round_gate);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
+// a lazy round's prefix rows, to be hashed: an empty entry (idx < 0) gets the
+// first candidate's row, legal values whose digest nobody reads
+__global__ void k_gather_prefix_rows(int32_t NC, const double* __restrict__ values, int64_t ld,
+                                     const int64_t* __restrict__ idx, int64_t cand_base, int32_t kp,
+                                     double* __restrict__ out) {
+  const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= kp) return;
+  const int64_t g = idx[j];
+  const int64_t i = g >= 0 ? g - cand_base : 0;
+  for (int32_t p = 0; p < NC; ++p) out[(int64_t)p * kp + j] = values[(int64_t)p * ld + i];
+}
+
+int launch_gather_prefix_rows(ut_ctx* c, const double* values, int64_t ld, const int64_t* idx, int64_t cand_base,
+                              int32_t kp, double* out) {
+  hipLaunchKernelGGL(k_gather_prefix_rows, dim3(grid1(kp, 64)), dim3(64), 0, c->stream, c->space.ncols, values, ld,
+                     idx, cand_base, kp, out);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

@@ -32,9 +32,11 @@ __global__ __launch_bounds__(TK_NT) void k_topk_chunk(const double* __restrict__
                                                       const int64_t* __restrict__ in_i,
                                                       const uint8_t* __restrict__ dup, int64_t count,
                                                       int64_t cand_base, int32_t k, double* __restrict__ out_s,
-                                                      int64_t* __restrict__ out_i) {
+                                                      int64_t* __restrict__ out_i,
+                                                      const int32_t* __restrict__ gate) {
   __shared__ double ss[TK_CH];
   __shared__ int64_t si[TK_CH];
+  if (gate && *gate == 0) return;   // a lazy round's remainder that is not needed (the whole grid returns)
   const int t = threadIdx.x;
   const int64_t base = (int64_t)blockIdx.x * TK_CH;
   // mode 1, k a power of two: the chunk holds 2048 / k sorted lists (best
@@ -98,14 +100,15 @@ int topk_pairs_impl(ut_ctx* c, const double* score, const int64_t* idx, int64_t 
   if ((rc = ensure(c, c->tk_idx[1], (size_t)chunks * k))) return rc;
   // first pass: whole network (the input is not made of sorted lists)
   hipLaunchKernelGGL(k_topk_chunk<2>, dim3((unsigned)chunks), dim3(TK_NT), 0, c->stream, score, idx, nullptr, n, 0, k,
-                     c->tk_score[0].p, c->tk_idx[0].p);
+                     c->tk_score[0].p, c->tk_idx[0].p, nullptr);
   UT_LAUNCH_CHECK(c);
   int cur = 0;
   count = chunks * k;
   while (chunks > 1) {
     chunks = (count + TK_CH - 1) / TK_CH;
     hipLaunchKernelGGL(k_topk_chunk<1>, dim3((unsigned)chunks), dim3(TK_NT), 0, c->stream, c->tk_score[cur].p,
-                       c->tk_idx[cur].p, nullptr, count, 0, k, c->tk_score[cur ^ 1].p, c->tk_idx[cur ^ 1].p);
+                       c->tk_idx[cur].p, nullptr, count, 0, k, c->tk_score[cur ^ 1].p, c->tk_idx[cur ^ 1].p,
+                       nullptr);
     UT_LAUNCH_CHECK(c);
     cur ^= 1;
     count = chunks * k;
@@ -129,19 +132,27 @@ int topk_impl(ut_ctx* c, const double* score, const uint8_t* dup, int64_t m, int
   if ((rc = ensure(c, c->tk_idx[0], (size_t)chunks * k))) return rc;
   if ((rc = ensure(c, c->tk_score[1], (size_t)chunks * k))) return rc;
   if ((rc = ensure(c, c->tk_idx[1], (size_t)chunks * k))) return rc;
+  // gated (a lazy round's remainder, c->round_gate): every pass returns at
+  // once when the gate is 0, and the last pass writes the caller's arrays
+  // itself -- a copy after it would overwrite them whatever the gate says
+  const int32_t* gate = c->round_gate;
+  UT_CHECK(c, !gate || (out_idx && out_score), UT_EINVAL, "topk: a gated call writes both outputs");
   hipLaunchKernelGGL(k_topk_chunk<0>, dim3((unsigned)chunks), dim3(TK_NT), 0, c->stream, score, nullptr, dup, m,
-                     cand_base, k, c->tk_score[0].p, c->tk_idx[0].p);
+                     cand_base, k, gate && chunks == 1 ? out_score : c->tk_score[0].p,
+                     gate && chunks == 1 ? out_idx : c->tk_idx[0].p, gate);
   UT_LAUNCH_CHECK(c);
   int cur = 0;
   int64_t count = chunks * k;
   while (chunks > 1) {
     chunks = (count + TK_CH - 1) / TK_CH;
     hipLaunchKernelGGL(k_topk_chunk<1>, dim3((unsigned)chunks), dim3(TK_NT), 0, c->stream, c->tk_score[cur].p,
-                       c->tk_idx[cur].p, nullptr, count, 0, k, c->tk_score[cur ^ 1].p, c->tk_idx[cur ^ 1].p);
+                       c->tk_idx[cur].p, nullptr, count, 0, k, gate && chunks == 1 ? out_score : c->tk_score[cur ^ 1].p,
+                       gate && chunks == 1 ? out_idx : c->tk_idx[cur ^ 1].p, gate);
     UT_LAUNCH_CHECK(c);
     cur ^= 1;
     count = chunks * k;
   }
+  if (gate) return 0;
   if (out_idx)
     UT_HIP(c, hipMemcpyAsync(out_idx, c->tk_idx[cur].p, sizeof(int64_t) * k, hipMemcpyDeviceToDevice, c->stream));
   if (out_score)

@@ -386,6 +386,21 @@ struct ut_ctx {
   int64_t r_ld = 0;
   int64_t r_m = 0;
   bool r_feat_valid = false;        // r_feat holds the last round's features (pruned rounds only)
+  // lazy dense DE rounds (api.hip score_round_de_impl): only the score-sorted
+  // prefix of K' >= 2k candidates is hashed and deduplicated
+  ut::DevBuf<int64_t> lz_idx;       // [K'] the prefix: top-K' by unmasked score (-1 = none)
+  ut::DevBuf<double> lz_score;      // [K'] their scores
+  ut::DevBuf<double> lz_vals;       // [ncols][K'] their value rows
+  ut::DevBuf<uint32_t> lz_dig;      // [K'][8] their digests
+  ut::DevBuf<uint32_t> lz_out_dig;  // [k][8] the selections' digests when the caller wants none
+  ut::DevBuf<int32_t> lz_gate;      // [1] need_full: the prefix held fewer than k distinct new configs
+  ut::DevBuf<int64_t> lz_nfall;     // [1] rounds that set need_full, since context creation
+  int64_t lazy_rounds = 0;          // lazy rounds enqueued, since context creation
+  bool r_lazy = false;              // the last round was lazy
+  // while the gated remainder of a lazy round is enqueued: the launchers of
+  // hash.hip, dedup.hip, topk.hip and the row gather pass it to their kernels,
+  // which return at once when it points at 0
+  const int32_t* round_gate = nullptr;
 
   // tree-ensemble surrogate (forest.hip)
   ut::DevBuf<ut_tree_node> forest_nodes;
@@ -606,6 +621,23 @@ int launch_hist_rehash(ut_ctx* c, const uint32_t* okeys, const uint32_t* ostate,
                        uint32_t* state, int64_t cap);
 int launch_dedup(ut_ctx* c, const uint32_t* dig, int64_t m, uint8_t* dup);
 int launch_mask_or(ut_ctx* c, uint8_t* dst, const uint8_t* src, int64_t m);
+// lazy rounds (dedup.hip).  The prefix of kp <= 1024 score-sorted candidates
+// (idx, -1 = none; score; digests; value rows [ncols][kp]): entry p is a
+// duplicate when its digest is in the history or an entry with a smaller
+// index has it; the first k others, in prefix order, go to out_* (padded with
+// index -1).  *gate = 1 when fewer than k were found and every prefix entry
+// was a candidate (nfall counts those rounds), else 0.
+int launch_prefix_dedup(ut_ctx* c, const int64_t* idx, const double* score, const uint32_t* dig, const double* vals,
+                        int32_t kp, int64_t cand_base, int32_t k, int64_t* out_idx, double* out_score,
+                        double* out_vals, uint32_t* out_dig, int32_t* gate, int64_t* nfall);
+// score[i] = -inf where dup[i] (what the finalize kernels write for a duplicate)
+int launch_mask_score(ut_ctx* c, double* score, const uint8_t* dup, int64_t m);
+// c->round_gate for the calls inside the scope
+struct GateScope {
+  ut_ctx* c;
+  GateScope(ut_ctx* ctx, const int32_t* gate) : c(ctx) { ctx->round_gate = gate; }
+  ~GateScope() { c->round_gate = nullptr; }
+};
 // feat == nullptr: the candidates' scaled features and norms are already in
 // c->ucand / c->cnorm (gp_encode_scaled); dup_ready: the event of the dup
 // mask (the round's side stream), joined before the variance GEMM
@@ -816,6 +848,8 @@ int set_fit_prio(int32_t on);
 int set_fit_prio_gemm(int32_t on);   // gp_gemm.hip's fit kernels
 int launch_gather_rows(ut_ctx* c, const double* values, int64_t ld, const int64_t* idx, int64_t cand_base,
                        int32_t k, double* out, int64_t ldo, const uint32_t* dig, uint32_t* out_dig);
+int launch_gather_prefix_rows(ut_ctx* c, const double* values, int64_t ld, const int64_t* idx, int64_t cand_base,
+                              int32_t kp, double* out);
 // comm.hip: release the context's communicator (ut_ctx_destroy)
 void comm_release(ut_ctx* c);
 

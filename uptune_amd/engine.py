@@ -531,7 +531,19 @@ class BatchEngine:
         return idx, top, dig, vals, {"survivors": st.survivors, "bound_rows": st.bound_rows, "dense": bool(st.dense),
                                      "threshold": st.threshold, "m": m}
 
+    def round_lazy_stats(self) -> Tuple[int, int]:
+        """(lazy dense DE rounds, those of them that fell back to hashing every
+        candidate) since the context was created; waits for the stream"""
+        lz, fb = C.c_int64(), C.c_int64()
+        L.check(self.ctx, self.lib.ut_round_lazy_stats(self.ctx, C.byref(lz), C.byref(fb)), "ut_round_lazy_stats")
+        return int(lz.value), int(fb.value)
+
     def round_buffers(self):
+        """device pointers (values, features, digests, dup, mu, var, score) of the
+        last round and their leading dimension.  features is None; after a lazy
+        round that did not fall back (round_lazy_stats) digests and dup are None
+        too -- only its score-sorted prefix was hashed -- and score holds the
+        unmasked scores."""
         ptrs = [C.c_void_p() for _ in range(7)]
         ld = C.c_int64()
         L.check(self.ctx, self.lib.ut_round_buffers(self.ctx, *[C.byref(p) for p in ptrs], C.byref(ld)),
