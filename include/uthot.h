@@ -404,6 +404,42 @@ int ut_gp_lml_grid(ut_ctx* ctx, const double* X_host, const double* y_host, int3
  * order: two calls on one fit return the same bits. */
 int ut_gp_lml_grad(ut_ctx* ctx, int32_t d, double* dlog_ell_host, double* dlog_sf2_host,
                    double* dlog_sn2_host);
+/* Batch-aware selection: k picks from a shortlist of p candidates (values
+ * [ncols][ld], raw values as for ut_gp_score_values), each conditioned on the
+ * picks before it, so that one round's batch is not k neighbours.  With U the
+ * shortlist's features and the current fit:
+ *   mu_i = k*_i . alpha,  V = L^-1 K*^T  (n x p),
+ *   Sigma = Kss - V^T V,  Kss_ij = sigma_f2 exp(-1/2 |us_i - us_j|^2)  (every scaled feature),
+ *   var_i = max(Sigma_ii, 0)           (the sigma_f2 - |v|^2 of ut_gp_score)
+ * and for t = 0 .. k-1:
+ *   1. s_i = acq(mu_i, var_i) with the fit's f_best (the acquisition of
+ *      ut_gp_score, the same ut_acq); -inf where dup[i] != 0 (dup may be NULL)
+ *      and for a candidate already picked;
+ *   2. j = argmax s, ties to the smallest position; if the maximum is -inf or
+ *      NaN this slot and every later one is empty;
+ *   3. c_i = Sigma_ij - sum_{s<t} G_is G_js,  q = c_j + sigma_n2 + jitter (the
+ *      believed observation is as noisy as a training point),
+ *      G_it = c_i / sqrt(q),  var_i <- max(var_i - G_it^2, 0).
+ * mu and f_best never change: conditioning on an observation equal to its own
+ * posterior mean moves no other mean, and a lowered f_best would penalise a
+ * pick's neighbours twice (GP-BUCB's variance-only update, for EI as for UCB).
+ * So the first pick is the plain top-1, and for EI, and UCB with kappa >= 0,
+ * the scores at pick time never increase.
+ * Device outputs, in pick order: out_pos [k] positions in [0, p), out_score [k]
+ * the score at pick time, out_var [k] the conditioned variance at pick time;
+ * an empty slot holds -1, -inf, NaN.  out_score and out_var may be NULL.
+ * Stream-ordered, no host wait: an in-flight fit is waited for on the device,
+ * and a failed fit makes every score NaN, so every slot is empty.  Always
+ * fp64, whatever ut_gp_set_precision says, and over every feature, whichever
+ * K* the fit scores with.  Reads the fit, writes scratch of its own: the fit,
+ * every scoring result and the round buffers stay as they are.  Sums in a
+ * fixed order: two calls on one fit return the same bits.  The loop is one
+ * small launch per pick (k + 1 in all).
+ * UT_EINVAL: p < 1, k < 1, k > p, p > 4096, ld < p, a NULL values, acq or
+ * out_pos, a fit whose feature count is not the space's, no fit (as
+ * ut_gp_score_values).  UT_ENOMEM: the scratch could not be allocated. */
+int ut_gp_select_batch(ut_ctx* ctx, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
+                       const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);
 
 /* ---- selection ---------------------------------------------------------- */
 /* k largest scores, ties -> smallest global index; entries with dup[i]!=0 or

@@ -140,6 +140,7 @@ SIGNATURES = {
     "ut_gp_lml": (C.c_int, [P, C.POINTER(D)]),
     "ut_gp_lml_grad": (C.c_int, [P, I32, P, C.POINTER(D), C.POINTER(D)]),
     "ut_gp_lml_grid": (C.c_int, [P, P, P, I32, I32, C.POINTER(GpHyper), I32, P, P, P, C.POINTER(I32)]),
+    "ut_gp_select_batch": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, I32, P, P, P]),
     "ut_topk": (C.c_int, [P, P, P, I64, I64, I32, P, P]),
     "ut_score_round_ga": (C.c_int, [P, C.POINTER(GaParams), C.c_void_p, C.c_void_p, C.POINTER(Acq), U32, I64, I64,
                                     I32, C.POINTER(RoundOut)]),

@@ -833,6 +833,18 @@ int ut_gp_lml_grad(ut_ctx* c, int32_t d, double* dlog_ell_host, double* dlog_sf2
   return gp_lml_grad_impl(c, d, dlog_ell_host, dlog_sf2_host, dlog_sn2_host);
 }
 
+int ut_gp_select_batch(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, const uint8_t* dup,
+                       int32_t k, int64_t* out_pos, double* out_score, double* out_var) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  // a stand-alone call is a timing round of its own (stages bs_kstar, bs_v, bs_sigma, bs_loop)
+  const bool own = c->timing.on && !c->timing.in_round;
+  if (own) timing_begin(c);
+  const int rc = gp_select_batch_impl(c, values, ld, p, acq, dup, k, out_pos, out_score, out_var);
+  if (own) timing_end(c);
+  return rc;
+}
+
 int ut_gp_kstar_mode(ut_ctx* c, int32_t* categorical) {
   if (!c || !categorical) return UT_EINVAL;
   *categorical = c->cat_on ? 1 : 0;

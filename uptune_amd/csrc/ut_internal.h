@@ -434,7 +434,15 @@ struct ut_ctx {
   // the LML gradient's scratch (gp_lml_grad.hip): alpha [npad] | the components [d + 2] |
   // the lower tiles' shares of them [tiles][d + 2]
   ut::DevBuf<double> lml_grad;
-  int32_t dbg_fail_alloc = 0;              // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
+  // batch-aware selection's scratch (gp_batch.hip), p the shortlist, ldp its padding
+  ut::DevBuf<double> bs_u, bs_cn;          // scaled features [dpad to 16][ldp] and norms [ldp]
+  ut::DevBuf<double> bs_kst, bs_v;         // K*^T and V = L^-1 K*^T, [npad][ldp]
+  ut::DevBuf<double> bs_sig;               // Sigma [p to 64][ldp], the full symmetric matrix
+  ut::DevBuf<double> bs_g;                 // G [k][ldp]
+  ut::DevBuf<double> bs_vec;               // mu [ldp] | var [ldp] | the launches' partial scores [2][16]
+  ut::DevBuf<int32_t> bs_pos;              // ... and partial positions [2][16]
+  ut::DevBuf<uint8_t> bs_picked;           // [ldp]
+  int32_t dbg_fail_alloc = 0;             // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
   ut::Timing timing;
@@ -579,6 +587,9 @@ int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int
                      int32_t g, const double* scale, const double* noise, double* lml_host, int32_t* best_host);
 // gp_lml_grad.hip: its gradient at the fit in place
 int gp_lml_grad_impl(ut_ctx* c, int32_t d, double* dlog_ell_host, double* dlog_sf2_host, double* dlog_sn2_host);
+// gp_batch.hip: k picks from a shortlist of p, each conditioned on the picks before it
+int gp_select_batch_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
+                         const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);
 
 // kernel launchers implemented in the .hip translation units
 int launch_population_init(ut_ctx* c, uint32_t round_);

@@ -425,6 +425,27 @@ class BatchEngine:
                 "ut_gp_score_values")
         return mu, var, score
 
+    def gp_select_batch(self, values: torch.Tensor, k: int, acq: Optional[L.Acq] = None,
+                        dup: Optional[torch.Tensor] = None, p: Optional[int] = None):
+        """ut_gp_select_batch: k picks from the shortlist values[:, :p], each
+        conditioned on the picks before it (the posterior variance shrinks
+        around a pick; the mean and f_best stay).  -> (pos [k] positions in
+        [0, p) in pick order, score [k] and var [k] at pick time); an empty
+        slot holds -1, -inf, NaN.  Always fp64; stream-ordered, no host wait."""
+        if values.dim() != 2 or values.shape[0] != self.spec.ncols:
+            raise ValueError(f"gp_select_batch: values must be [{self.spec.ncols}][p]")
+        if values.stride(1) != 1:
+            values = values.contiguous()
+        p = values.shape[1] if p is None else int(p)
+        k = int(k)
+        acq = acq or self.acq()
+        n = max(k, 1)
+        pos, score, var = self._empty(n, dtype=torch.int64), self._empty(n), self._empty(n)
+        L.check(self.ctx, self.lib.ut_gp_select_batch(self.ctx, _ptr(values), values.stride(0), p, C.byref(acq),
+                                                      _ptr(dup), k, _ptr(pos), _ptr(score), _ptr(var)),
+                "ut_gp_select_batch")
+        return pos, score, var
+
     def gp_topk_pruned(self, feat: torch.Tensor, k: int, m: Optional[int] = None, acq: Optional[L.Acq] = None,
                        dup: Optional[torch.Tensor] = None, cand_base: int = 0, bound_rows: int = 256):
         """ut_gp_topk_pruned: the top-k of the GP score, selection-exact, with the

@@ -626,8 +626,21 @@ class GpuBatchTechnique(SearchTechnique):
     def __init__(self, pool: int = 1 << 14, batch: int = 8, population: int = 1024, device: int = 0,
                  seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4, acq: str = "ei",
                  group=None, surrogate=None, shared: Optional[SharedModel] = None, engine_factory=None,
-                 prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, *pargs, **kwargs):
+                 prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
+                 *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
+        # diversify = D > 0: a round with a GP takes the D best-scoring candidates
+        # as a shortlist and picks its `batch` from them with ut_gp_select_batch,
+        # each pick conditioned on the picks before it, so that a batch drawn
+        # around one population is not `batch` neighbours; 0 = the plain top-k
+        self.diversify = int(diversify)
+        if self.diversify:
+            if not int(batch) <= self.diversify <= 4096:
+                raise ValueError("diversify must be 0 or in [batch, 4096]")
+            if int(prune_rows) > 0:
+                raise ValueError("diversify needs every candidate's score: not with prune_rows")
+            if surrogate is not None:
+                raise ValueError("diversify conditions a GP posterior: not with a tree surrogate")
         # prune_rows > 0: score rounds with ut_gp_topk_pruned (selection-exact EI
         # bound from the first prune_rows rows of L^-1 k*; fp64 fits, EI / UCB):
         # the same selections as the dense variance at a fraction of its cost
@@ -742,15 +755,36 @@ class GpuBatchTechnique(SearchTechnique):
                 return vals, idx, top, dig[loc], vals[:, loc]
             # encoding fused into the K* operand pass (no feature matrix)
             _, _, score = eng.gp_score_values(vals, acq=eng.acq(self.acq_kind), dup=dup)
+            if self.diversify > 0:
+                return self._diverse_picks(vals, score, dup, dig, base)
         else:  # no model yet: every non-duplicate candidate is equally good (lowest index first)
             score = torch.zeros(vals.shape[1], dtype=torch.float64, device=vals.device)
         idx, top = eng.topk(score, self.batch, dup=dup, cand_base=base)   # GLOBAL candidate indices
         loc = torch.where(idx >= 0, idx - base, torch.zeros_like(idx))
         return vals, idx, top, dig[loc], vals[:, loc]
 
+    def _diverse_picks(self, vals, score, dup, dig, base):
+        """the round's selections from the `diversify` best-scoring candidates,
+        each conditioned on the picks before it (BatchEngine.gp_select_batch);
+        what _local_round returns, in pick order"""
+        import torch
+        eng = self.engine
+        D = min(self.diversify, vals.shape[1])
+        sidx, _ = eng.topk(score, D, dup=dup, cand_base=0)       # local positions, -1 = none
+        none = sidx < 0
+        sloc = torch.where(none, torch.zeros_like(sidx), sidx)
+        pos, top, _ = eng.gp_select_batch(vals[:, sloc].contiguous(), min(self.batch, D), acq=eng.acq(self.acq_kind),
+                                          dup=none.to(torch.uint8))
+        loc = sloc[torch.where(pos >= 0, pos, torch.zeros_like(pos))]
+        idx = torch.where(pos >= 0, loc + base, torch.full_like(pos, -1))
+        return vals, idx, top, dig[loc], vals[:, loc]
+
     def _round(self):
         from .engine import digests_to_hex
         rank, world = self._dist()
+        if self.diversify > 0 and world > 1 and self.sharded:
+            # (every rank holds the same setting: all raise together, before any collective)
+            raise ValueError("diversify is not built for sharded rounds over several ranks")
         if world > 1 and self.sharded:
             # a failure on any rank must not leave the others inside the
             # all-gather: agree first, then all proceed or all give up
