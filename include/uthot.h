@@ -441,6 +441,65 @@ int ut_gp_lml_grad(ut_ctx* ctx, int32_t d, double* dlog_ell_host, double* dlog_s
 int ut_gp_select_batch(ut_ctx* ctx, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
                        const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);
 
+/* ---- failure-aware scoring ---------------------------------------------- */
+/* The surrogate is fitted on results that succeeded; a configuration that
+ * failed (compile error, crash, timeout) only joins the dedup set.  These calls
+ * load the FAILED configurations' features, and every dense EI score is then
+ * weighted by an estimate p(u) of the probability that candidate u succeeds
+ * (constrained EI: score = EI * p).  The reference has no counterpart: a
+ * failed result is only ever "worst" there.
+ *
+ * p is a kernel vote (Nadaraya-Watson) over the current fit's training rows
+ * x_r (r < n, the results that succeeded) and the loaded failed rows f_q
+ * (q < nf), with the GP's own kernel and lengthscales ell, sigma_f2 left out:
+ *   k(a, u)   = exp(-1/2 |(a - u) / ell|^2 / s^2)          (k(a, a) = 1)
+ *   S_ok(u)   = sum_{r < n}  k(x_r, u)
+ *   S_fail(u) = sum_{q < nf} k(f_q, u)
+ *   p(u)      = (S_ok + lambda p0) / (S_ok + S_fail + lambda)
+ * p lies in [0, 1]; far from all data p -> p0, on a lone failed row
+ * p ~ lambda p0 / (1 + lambda).  A finite score becomes score * p^gamma (no pow
+ * when gamma == 1); -inf (a duplicate) and NaN (a failed fit) pass through, and
+ * mu and var are never changed.  The sums run in a fixed order: two calls return
+ * the same bits. */
+typedef struct ut_feas_params {
+  double prior;      /* p0 in (0, 1]; <= 0: n / (n + nf) of the fit in use, taken at scoring time */
+  double strength;   /* lambda > 0: the prior's weight in pseudo-observations */
+  double ell_scale;  /* s > 0: the vote's kernel is the GP's with every lengthscale times s */
+  double power;      /* gamma >= 0 */
+} ut_feas_params;
+/* Load (replace) the failed rows: Xfail_host [nf][d], features as ut_gp_fit takes
+ * them; nf = 0 clears (Xfail_host and p may then be NULL).  p == NULL: prior
+ * from the fit, lambda = s = gamma = 1.  May be called before any fit;
+ * synchronous on the host side (the caller's buffer is free on return).  The
+ * rows' scaled K* operands are rebuilt for every new fit, so a refit with
+ * other lengthscales needs no second call.
+ * While rows are loaded the weight applies to ut_gp_score, ut_gp_score_values,
+ * ut_score_round_de and ut_score_round_ga at every precision, and, as it is
+ * defined for EI only (a UCB score can be negative), a scoring call with
+ * UT_ACQ_UCB returns UT_EUNSUPPORTED; so do ut_gp_topk_pruned and
+ * ut_score_round_de_pruned (their bound does not know the weight) and
+ * ut_gp_select_batch (its per-pick acquisition does not either).  A fit that
+ * scores with the categorical K* needs failed rows that are one-hot in the
+ * ENUM blocks and 0 / 1 in the BOOL columns: otherwise the scoring call returns
+ * UT_EINVAL naming the first row that is not.
+ * UT_EINVAL (what was loaded before stays loaded): Xfail_host NULL with nf > 0,
+ * nf < 0, d not the space's feature count, a non-finite row entry, strength or
+ * ell_scale not finite and > 0 (or 1 / ell_scale^2 not a normal number), power
+ * not finite or < 0, prior > 1 or NaN. */
+int ut_gp_feas_set(ut_ctx* ctx, const double* Xfail_host, int32_t nf, int32_t d, const ut_feas_params* p);
+/* p (and optionally S_ok, S_fail) of m candidates, by the formulae above, for
+ * the fit in use and the rows loaded (none: S_fail = 0, p0 = 1).  Exactly one
+ * of values ([ncols][ld], raw values as for ut_gp_score_values: the K* the fit
+ * scores with) and features ([d][ld], as for ut_gp_score: the dense contraction
+ * over every feature) is non-NULL.  Device outputs [m]; p_out is required,
+ * s_ok_out and s_fail_out may be NULL.  Needs a fit (UT_EINVAL without one);
+ * stream-ordered, no host wait: it waits on the device for an in-flight fit's
+ * scaled training inputs only, as K* does. */
+int ut_gp_feas_prob(ut_ctx* ctx, const double* values, const double* features, int64_t ld, int64_t m,
+                    double* p_out, double* s_ok_out, double* s_fail_out);
+/* what is loaded: the row count (0: nothing) and the parameters as given (either may be NULL) */
+int ut_gp_feas_info(ut_ctx* ctx, int32_t* nf, ut_feas_params* p);
+
 /* ---- selection ---------------------------------------------------------- */
 /* k largest scores, ties -> smallest global index; entries with dup[i]!=0 or
  * NaN score are never selected; missing slots get index -1. */

@@ -748,6 +748,9 @@ int ut_gp_topk_pruned(ut_ctx* c, const double* feat, int64_t ld, int64_t m, cons
   if (!c) return UT_EINVAL;
   UT_CHECK(c, m >= 1 && feat && ld >= m && acq && out_idx && out_score && cand_base >= 0, UT_EINVAL,
            "gp_topk_pruned: bad arguments");
+  UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
+           "gp_topk_pruned: failed rows are loaded (ut_gp_feas_set) and the pruning bound does not know the "
+           "feasibility weight");
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
   int rc = gp_topk_pruned_impl(c, feat, ld, m, acq, dup, cand_base, k, bound_rows, out_idx, out_score, stats);
@@ -837,12 +840,40 @@ int ut_gp_select_batch(ut_ctx* c, const double* values, int64_t ld, int32_t p, c
                        int32_t k, int64_t* out_pos, double* out_score, double* out_var) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
+  UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
+           "gp_select_batch: failed rows are loaded (ut_gp_feas_set) and the per-pick acquisition does not know the "
+           "feasibility weight");
   // a stand-alone call is a timing round of its own (stages bs_kstar, bs_v, bs_sigma, bs_loop)
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
   const int rc = gp_select_batch_impl(c, values, ld, p, acq, dup, k, out_pos, out_score, out_var);
   if (own) timing_end(c);
   return rc;
+}
+
+int ut_gp_feas_set(ut_ctx* c, const double* Xfail_host, int32_t nf, int32_t d, const ut_feas_params* p) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_feas_set_impl(c, Xfail_host, nf, d, p);
+}
+
+int ut_gp_feas_prob(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
+                    double* s_ok_out, double* s_fail_out) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  // a stand-alone call is a timing round of its own (stages encode / cnorm, feas)
+  const bool own = c->timing.on && !c->timing.in_round;
+  if (own) timing_begin(c);
+  const int rc = gp_feas_prob_impl(c, values, features, ld, m, p_out, s_ok_out, s_fail_out);
+  if (own) timing_end(c);
+  return rc;
+}
+
+int ut_gp_feas_info(ut_ctx* c, int32_t* nf, ut_feas_params* p) {
+  if (!c) return UT_EINVAL;
+  if (nf) *nf = c->fs_n;
+  if (p) *p = c->fs_par;
+  return 0;
 }
 
 int ut_gp_kstar_mode(ut_ctx* c, int32_t* categorical) {
@@ -887,6 +918,9 @@ int ut_score_round_de_pruned(ut_ctx* c, const ut_de_params* de, const ut_acq* ac
                              ut_prune_stats* stats) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, bound_rows >= 1, UT_EINVAL, "score_round_pruned: bound_rows must be >= 1");
+  UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
+           "score_round_de_pruned: failed rows are loaded (ut_gp_feas_set) and the pruning bound does not know the "
+           "feasibility weight");
   return score_round_de_impl(c, de, acq, round_, cand_base, m, k, out, bound_rows, stats);
 }
 

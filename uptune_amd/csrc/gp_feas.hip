@@ -1,0 +1,394 @@
+// gp_feas.hip -- failure-aware scoring: EI weighted by a kernel vote over the
+// results that succeeded and the configurations that failed (uthot.h
+// "failure-aware scoring"):
+//   k(a, u) = exp(-1/2 |(a - u) / ell|^2 / s^2)
+//   S_ok(u) = sum_{r < n} k(x_r, u),  S_fail(u) = sum_{q < nf} k(f_q, u)
+//   p(u)    = (S_ok + lambda p0) / (S_ok + S_fail + lambda),   score <- score p^gamma
+// Both sums are the K* contraction of gp_gemm.hip with another epilogue, over
+// operands the scoring call already has: the fit's scaled training operand
+// (Xs^T, or its numeric block and the one-hot codes), the candidates' U', norms
+// and codes in c->ucand / c->cnorm / c->bcat.  The failed rows get the same
+// operands, built by the fit's own kernels once per fit (feas_operands).
+#include "gp_kstar_tile.h"
+#include "gp_post.h"
+
+#include <cmath>
+
+namespace ut {
+
+// one row set of the vote: the A operand of the contraction and what goes with it
+struct FeasRows {
+  const double* AT;      // [dpad][npad] scaled rows, transposed, times KSTAR_T_SCALE
+  const double* norm;    // [npad] |row / ell|^2 over the operand's features
+  const int8_t* acat;    // [nkc][npad][128] weighted one-hot codes (categorical)
+  int32_t n, npad;       // rows, padded to 128
+};
+
+// k_gp_kstar<double, MU>'s tiling (128 x 128 items, v_mfma_f64_16x16x4f64, the
+// 2-stage glds ring, per-XCD tickets, two 256-thread workgroups per CU, the int8
+// code stages first when CAT) with another epilogue:
+//   1. one launch covers both row sets: item j of an XCD group is row tile
+//      j % (RT_ok + RT_fail) -- the training operand's tiles, then the failed one's;
+//   2. the exponent is scaled by 1 / s^2 (the categorical c0 + c1 M start with
+//      it: s scales every lengthscale).  Each of its three terms is scaled, not
+//      their sum, so that a padding row's or column's -1e300 stays what it is
+//      whatever s (inv_s2 == 1: the same bits as K*'s (acc + hx) + hc);
+//   3. no K* is stored;
+//   4. part [RT_ok + RT_fail][ldk] gets the tile's column sums of k (no alpha,
+//      no second moment, sigma_f2 = 1 in the exp table).
+// Padding rows (row >= n of their set) and columns (>= m) contribute exactly
+// 0: their half-norm is -1e300, and the clamp at KSTAR_T_MIN is where the
+// table's 2^k' underflows to 0.
+template <bool CAT>
+__global__ __launch_bounds__(K_NT, 2) void k_feas_sums(FeasRows ok, FeasRows fail, int32_t RT_ok, int32_t RT_fail,
+                                                       const double* __restrict__ B, int64_t ldb, int32_t dpad,
+                                                       int32_t CT, const double* __restrict__ cnorm, int64_t m,
+                                                       int32_t* __restrict__ ticket, double* __restrict__ part,
+                                                       const int8_t* __restrict__ bcat, int32_t nkc, double cat_c0,
+                                                       double cat_c1, double inv_s2) {
+  constexpr int MAIN = 2 * K_STAGE;
+  static_assert(K_NT == 2 * K_BM && K_BM == K_BN, "one thread per epilogue operand (rowop)");
+  // the ring, the exp table, the ticket slot, the item's |row|^2 and |u_c|^2
+  __shared__ __attribute__((aligned(16))) double lds[MAIN + EXP_TAB + 2 + 2 * K_BM];
+  double* etab = lds + MAIN;
+  int32_t& s_item = *reinterpret_cast<int32_t*>(lds + MAIN + EXP_TAB);
+  double* const rowop = lds + MAIN + EXP_TAB + 2;   // [norm 128][cnorm 128]
+  const int t = threadIdx.x, lane = t & 63;
+  if (t < EXP_TAB) etab[t] = exp2((double)t / EXP_TAB);   // published by the first ticket barrier
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wm = w >> 1, wn = w & 1;
+  const int32_t xcd = blockIdx.x & 7;
+  const int32_t nk_full = dpad / K_BK, k_rem = (dpad % K_BK) / 4;
+  const int32_t nk = nk_full + (k_rem ? 1 : 0);
+  const int32_t ncs = CAT ? nkc : 0;          // int8 stages first, then the fp64 ones
+  const int32_t ntot = ncs + nk;
+  const int32_t RTt = RT_ok + RT_fail;
+  // the i8 MFMA's row rho of A is tile row sigma(rho) (gp_gemm.hip "Categorical K*")
+  const int sig = ((lane & 15) >> 2) + 4 * (lane & 3);
+  const int arow = lane & 15;
+
+  int32_t nxt = 0;
+  if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+  for (;;) {
+    if (t == 0) s_item = nxt;
+    __syncthreads();
+    const int32_t j = __builtin_amdgcn_readfirstlane(s_item);   // uniform: the row set's pointers stay scalar
+    const int32_t ct = (j / RTt) * 8 + xcd;
+    if (ct >= CT) break;
+    if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+    const int32_t rtt = j % RTt;              // the partial's row in `part`
+    const bool second = rtt >= RT_ok;
+    const FeasRows& R = second ? fail : ok;
+    const int32_t rt = second ? rtt - RT_ok : rtt;
+    const double* AT = R.AT;
+    const int8_t* acat = R.acat;
+    const int32_t npad_a = R.npad, nrows = R.n;
+    const int64_t col0 = (int64_t)ct * K_BN;
+    const int32_t row0 = rt * K_BM;
+
+    auto issue_stage = [&](int32_t s2, double* st) {
+      if (CAT && s2 < ncs)
+        kcat_issue(acat + ((int64_t)s2 * npad_a + row0) * 128, bcat + ((int64_t)s2 * ldb + col0) * 128, st, w, lane);
+      else
+        kstar_issue(AT, npad_a, B, ldb, row0, col0, (s2 - ncs) * K_BK, st, w, lane, dpad);
+    };
+    if (ntot > 0) issue_stage(0, lds);
+    if (w < 2) {  // one 1-KiB glds per operand (rows < npad, columns < ldk are in range)
+      const double* src = w == 0 ? R.norm + row0 : cnorm + col0;
+      __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + w * K_BM), 16,
+                                       0, 0);
+    }
+    kd4 acc[4][4];
+    if constexpr (CAT) {
+      ki4 iacc[4][4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) iacc[i][jj] = (ki4){0, 0, 0, 0};
+      for (int32_t s2 = 0; s2 < ncs; ++s2) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
+        asm volatile("" ::: "memory");
+        if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
+        const int8_t* as8 = reinterpret_cast<const int8_t*>(lds + (s2 & 1) * K_STAGE);
+        const int8_t* bs8 = as8 + K_SA * 8;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          const int c16 = (lane >> 4) + 4 * kk;
+          ki4 af[4], bf[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int row = wm * 64 + i * 16 + sig;
+            af[i] = *reinterpret_cast<const ki4*>(as8 + row * 128 + ((c16 ^ (row & 7)) << 4));
+          }
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int col = wn * 64 + jj * 16 + (lane & 15);
+            bf[jj] = *reinterpret_cast<const ki4*>(bs8 + col * 128 + ((c16 ^ (col & 7)) << 4));
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+              iacc[i][jj] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[jj], iacc[i][jj], 0, 0, 0);
+        }
+      }
+      // c0 + c1 M, in t units (see the launch); scaled by 1 / s^2 in the epilogue with the rest
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[i][jj][r] = __builtin_fma((double)iacc[i][jj][r], cat_c1, cat_c0);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (kd4){0.0, 0.0, 0.0, 0.0};
+    }
+    for (int32_t s2 = ncs; s2 < ntot; ++s2) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
+      asm volatile("" ::: "memory");
+      if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
+      const double* as = lds + (s2 & 1) * K_STAGE;
+      const int32_t kt = s2 - ncs;
+      const double* bs = as + K_SA;
+      // the last stage of a dpad that is not a multiple of 16 has k_rem k4 steps
+      const int nks = kt < nk_full ? K_BK / 4 : k_rem;
+#pragma unroll
+      for (int ks = 0; ks < K_BK / 4; ++ks) {
+        if (ks >= nks) break;
+        const int kr = ks * 4 + (lane >> 4);
+        double af[4], bf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = as[kr * K_BM + wm * 64 + i * 16 + arow];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) bf[jj] = bs[kr * K_BN + wn * 64 + jj * 16 + (lane & 15)];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj)
+            acc[i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[jj], acc[i][jj], 0, 0, 0);
+      }
+    }
+    if (ntot == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the epilogue operands
+
+    __syncthreads();  // ring free: reuse as the column reduction buffer
+    // the item's half-norms once per item, not once per element (as k_gp_kstar<int8_t> keeps
+    // its rows'): scaled by 1 / s^2, and -1e300 for a padding row (>= n of its set) or column
+    // (>= m), whose k is then exactly 0 without a select in the element code
+    {
+      const double hv = ((-0.5 * KSTAR_T_SCALE) * rowop[t]) * inv_s2;
+      const bool in = t < K_BM ? row0 + t < nrows : col0 + (t - K_BM) < m;
+      rowop[t] = in ? hv : -1e300;
+    }
+    __syncthreads();
+    double* red = lds;  // [2][128]
+    double hc[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int cl = wn * 64 + jj * 16 + (lane & 15);
+      hc[jj] = rowop[K_BM + cl];
+    }
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rl = wm * 64 + i * 16 + (lane >> 4) + 4 * r;
+        const double hx = rowop[rl];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          // t = (C - |x|^2/2 - |u|^2/2) / s^2 * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]
+          const double x = __builtin_fmax(__builtin_fmin((acc[i][jj][r] * inv_s2 + hx) + hc[jj], 0.0), KSTAR_T_MIN);
+          s[jj] += sf2_exp2t_nonpos(x, etab);
+        }
+      }
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int cl = wn * 64 + jj * 16 + (lane & 15);
+      double a = s[jj];
+      a += __shfl_xor(a, 16);
+      a += __shfl_xor(a, 32);
+      if ((lane >> 4) == 0) red[wm * K_BN + cl] = a;
+    }
+    __syncthreads();
+    if (t < K_BN) {
+      const int64_t col = col0 + t;
+      if (col < m) part[(int64_t)rtt * ldb + col] = red[t] + red[K_BN + t];
+    }
+  }
+}
+
+// One lane per candidate: the OK partials tile 0 upward, then the failed
+// ones; p; the outputs asked for; a finite score times p^gamma.
+__global__ void k_feas_apply(int64_t m, int32_t RT_ok, int32_t RT_fail, const double* __restrict__ part, int64_t ldp,
+                             double lam_p0, double lam, double gamma, double* __restrict__ p_out,
+                             double* __restrict__ s_ok_out, double* __restrict__ s_fail_out,
+                             double* __restrict__ score) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const double s_ok = part_sum(part, RT_ok, ldp, i);
+  const double s_fail = part_sum(part + (int64_t)RT_ok * ldp, RT_fail, ldp, i);
+  const double p = (s_ok + lam_p0) / ((s_ok + s_fail) + lam);
+  if (p_out) p_out[i] = p;
+  if (s_ok_out) s_ok_out[i] = s_ok;
+  if (s_fail_out) s_fail_out[i] = s_fail;
+  if (score) {
+    const double sc = score[i];
+    // -inf (a duplicate) and NaN (a failed fit) pass through
+    if (__builtin_isfinite(sc)) score[i] = sc * (gamma == 1.0 ? p : pow(p, gamma));
+  }
+}
+
+// The failed rows' K* operands under the current fit's lengthscales, by the
+// kernels the fit builds its own with (so KSTAR_T_SCALE and the categorical
+// conventions are theirs): rebuilt when the fit changed (fit_gen) or the rows
+// did (ut_gp_feas_set zeroes fs_gen).  On c->stream, after the fit's 1/ell.
+static int feas_operands(ut_ctx* c) {
+  if (c->fs_n == 0 || c->fs_gen == c->fit_gen) return 0;
+  const int32_t nf = c->fs_n, d = c->gp_d, nfpad = gp_npad(nf), dpad = kstar_dpad(d);
+  int rc;
+  if ((rc = ensure(c, c->fs_Xs, (size_t)nfpad * d))) return rc;
+  if ((rc = ensure(c, c->fs_norm, (size_t)nfpad))) return rc;
+  if ((rc = ensure(c, c->fs_XsT, (size_t)dpad * nfpad))) return rc;
+  const bool cat = c->cat_on && c->fs_bad_row < 0;
+  const int32_t dpn = cat_dpad(c);
+  if (cat) {
+    if ((rc = ensure(c, c->fs_XsT_num, (size_t)(dpn > 0 ? dpn : 1) * nfpad))) return rc;
+    if ((rc = ensure(c, c->fs_norm_num, (size_t)nfpad))) return rc;
+    if ((rc = ensure(c, c->fs_acat, (size_t)c->space.cat_k * nfpad))) return rc;
+  }
+  if ((rc = launch_gp_prep_train(c, c->fs_X.p, nf, nfpad, d, c->gp_inv_ell.p, c->fs_Xs.p, c->fs_norm.p))) return rc;
+  if ((rc = launch_xs_t(c, c->fs_Xs.p, nfpad, d, dpad, c->fs_XsT.p))) return rc;
+  if (cat && (rc = launch_gp_cat_train(c, c->fs_Xs.p, c->fs_X.p, nf, nfpad, d, dpn, c->fs_XsT_num.p,
+                                       c->fs_norm_num.p, c->fs_acat.p)))
+    return rc;
+  c->fs_gen = c->fit_gen;
+  return 0;
+}
+
+// The vote over the m candidates whose K* operands (shape s) are in c->ucand /
+// c->cnorm / c->bcat, then k_feas_apply with the given outputs.
+static int feas_vote(ut_ctx* c, const ScoreShape& s, int64_t m, double* p_out, double* s_ok_out, double* s_fail_out,
+                     double* score) {
+  const int32_t nf = c->fs_n;
+  UT_CHECK(c, nf == 0 || c->fs_d == s.d, UT_EINVAL,
+           "gp_feas: the failed rows have " + std::to_string(c->fs_d) + " features, the fit " + std::to_string(s.d));
+  UT_CHECK(c, !(s.cat && nf > 0 && c->fs_bad_row >= 0), UT_EINVAL,
+           "gp_feas: the fit scores with the categorical K* and failed row " + std::to_string(c->fs_bad_row) +
+               " is not one-hot in an ENUM block / 0-1 in a BOOL column");
+  const int64_t ldk = s.ldk;
+  UT_CHECK(c, s.npad % K_BM == 0 && s.dpad % 4 == 0 && ldk % K_BN == 0 && ldk >= m, UT_EINVAL, "gp_feas: bad padding");
+  int rc;
+  if ((rc = feas_operands(c))) return rc;
+  const int32_t nfpad = nf > 0 ? gp_npad(nf) : 0;
+  const int32_t RT_ok = s.RT, RT_fail = nfpad / K_BM;
+  if ((rc = ensure(c, c->fs_part, (size_t)(RT_ok + RT_fail) * ldk))) return rc;
+  const KstarTrain tr = kstar_train(c, s.cat, c->bcat.p);
+  const bool has_cat = tr.cat.nkc > 0;
+  UT_CHECK(c, s.dpad >= 4 || has_cat, UT_EINVAL, "gp_feas: bad padding");
+  UT_CHECK(c, !has_cat || (tr.cat.acat && tr.cat.bcat), UT_EINVAL, "gp_feas: categorical operands missing");
+  const FeasRows ok{tr.XsT, tr.xnorm ? tr.xnorm : c->gp_xnorm.p, tr.cat.acat, s.n, s.npad};
+  const FeasRows fail = s.cat ? FeasRows{c->fs_XsT_num.p, c->fs_norm_num.p, c->fs_acat.p, nf, nfpad}
+                              : FeasRows{c->fs_XsT.p, c->fs_norm.p, nullptr, nf, nfpad};
+  const int32_t CT = (int32_t)(ldk / K_BN);
+  const int64_t items = (int64_t)(RT_ok + RT_fail) * CT;
+  // CUs left to an in-flight fit, as launch_gemm_kstar leaves them
+  const bool fit_in_flight = c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
+  const int32_t spare = fit_in_flight ? KSTAR_SPARE_PER_XCD : 0;
+  int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
+  if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
+  const ut_feas_params& fp = c->fs_par;
+  const double inv_s2 = 1.0 / (fp.ell_scale * fp.ell_scale);
+  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
+  hipLaunchKernelGGL(has_cat ? k_feas_sums<true> : k_feas_sums<false>, dim3(nb), dim3(K_NT), 0, c->stream, ok, fail,
+                     RT_ok, RT_fail, c->ucand.p, ldk, s.dpad, CT, c->cnorm.p, m, c->gp_ctr.p + 8, c->fs_part.p,
+                     tr.cat.bcat, tr.cat.nkc, tr.cat.c0 * KSTAR_T_SCALE, tr.cat.c1 * KSTAR_T_SCALE, inv_s2);
+  UT_LAUNCH_CHECK(c);
+  // the prior success rate: as given, or the share of successes among the rows in use
+  const double p0 = fp.prior > 0.0 ? fp.prior : (double)s.n / (double)(s.n + nf);
+  hipLaunchKernelGGL(k_feas_apply, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT_ok, RT_fail, c->fs_part.p, ldk,
+                     fp.strength * p0, fp.strength, fp.power, p_out, s_ok_out, s_fail_out, score);
+  UT_LAUNCH_CHECK(c);
+  mark(c, "feas");
+  return 0;
+}
+
+int feas_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double* score) {
+  return feas_vote(c, s, m, nullptr, nullptr, nullptr, score);
+}
+
+int gp_feas_prob_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
+                      double* s_ok_out, double* s_fail_out) {
+  UT_CHECK(c, m >= 0 && ld >= m && (values != nullptr) != (features != nullptr) && (p_out || m == 0), UT_EINVAL,
+           "gp_feas_prob: bad arguments (exactly one of values and features, p_out required)");
+  UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_feas_prob: call ut_gp_fit first");
+  if (m == 0) return 0;
+  int rc;
+  if (values) {
+    UT_CHECK(c, c->has_space, UT_ENOSPACE, "space not defined");
+    UT_CHECK(c, c->gp_d == c->space.n_feat, UT_EINVAL, "gp_feas_prob: GP feature width != space feature width");
+    // (flushes a staged fit and waits on the device for its scaled inputs)
+    if ((rc = gp_encode_scaled(c, values, ld, m))) return rc;
+    mark(c, "encode");
+    return feas_vote(c, score_shape(c, m, c->cat_on && c->ucand_cat), m, p_out, s_ok_out, s_fail_out, nullptr);
+  }
+  if ((rc = gp_fit_flush(c))) return rc;
+  if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit_x, 0));
+  const ScoreShape s = score_shape(c, m, false);
+  if ((rc = ensure(c, c->cnorm, (size_t)s.ldk))) return rc;
+  if ((rc = ensure(c, c->ucand, s.urows() * s.ldk))) return rc;
+  if ((rc = launch_prep_cand(c, features, ld, m, s.d, s.dpad, c->ucand.p, s.ldk, c->cnorm.p))) return rc;
+  c->ucand_cat = false;
+  mark(c, "cnorm");
+  return feas_vote(c, s, m, p_out, s_ok_out, s_fail_out, nullptr);
+}
+
+int gp_feas_set_impl(ut_ctx* c, const double* X, int32_t nf, int32_t d, const ut_feas_params* p) {
+  UT_CHECK(c, nf >= 0, UT_EINVAL, "gp_feas_set: nf < 0");
+  const ut_feas_params par = p ? *p : ut_feas_params{0.0, 1.0, 1.0, 1.0};
+  if (nf > 0) {
+    UT_CHECK(c, X != nullptr, UT_EINVAL, "gp_feas_set: Xfail_host is NULL");
+    UT_CHECK(c, c->has_space, UT_ENOSPACE, "space not defined");
+    UT_CHECK(c, d == c->space.n_feat, UT_EINVAL,
+             "gp_feas_set: d = " + std::to_string(d) + ", the space has " + std::to_string(c->space.n_feat) +
+                 " features");
+    UT_CHECK(c, std::isfinite(par.strength) && par.strength > 0.0, UT_EINVAL,
+             "gp_feas_set: strength must be finite and > 0");
+    const double inv_s2 = 1.0 / (par.ell_scale * par.ell_scale);
+    UT_CHECK(c, std::isfinite(par.ell_scale) && par.ell_scale > 0.0 && std::isnormal(inv_s2), UT_EINVAL,
+             "gp_feas_set: ell_scale must be finite and > 0 (and 1 / ell_scale^2 a normal number)");
+    UT_CHECK(c, std::isfinite(par.power) && par.power >= 0.0, UT_EINVAL, "gp_feas_set: power must be finite and >= 0");
+    UT_CHECK(c, par.prior <= 1.0, UT_EINVAL, "gp_feas_set: prior must be <= 1 (<= 0: from the fit)");   // (NaN fails)
+    for (size_t e = 0; e < (size_t)nf * d; ++e)
+      UT_CHECK(c, std::isfinite(X[e]), UT_EINVAL,
+               "gp_feas_set: row " + std::to_string(e / d) + " has a non-finite entry");
+  }
+  if (nf == 0) {
+    // nothing is weighted from here on; the rows go once no kernel can be reading them
+    UT_HIP(c, ut::sync_all(c));
+    c->fs_X.reset();
+    c->fs_n = 0, c->fs_d = 0, c->fs_bad_row = -1, c->fs_gen = 0;
+    c->fs_par = ut_feas_params{0.0, 1.0, 1.0, 1.0};
+    return 0;
+  }
+  // the first row the categorical K* could not read as option codes
+  int32_t bad = -1;
+  for (int32_t r = 0; r < nf && bad < 0; ++r)
+    if (!cat_rows_ok(c->space, X, d, r, r + 1)) bad = r;
+  // staged into a new array; what was loaded stays until it is complete
+  DevBuf<double> q;
+  int rc;
+  if ((rc = dalloc(c, q, (size_t)nf * d))) return rc;
+  UT_HIP(c, hipMemcpy(q.p, X, sizeof(double) * (size_t)nf * d, hipMemcpyHostToDevice));
+  UT_HIP(c, ut::sync_all(c));   // an operand build enqueued earlier may still read the old rows
+  c->fs_X.swap(q);
+  c->fs_n = nf, c->fs_d = d, c->fs_bad_row = bad, c->fs_gen = 0;
+  c->fs_par = par;
+  return 0;
+}
+
+}  // namespace ut

@@ -163,6 +163,21 @@ int launch_gp_ystats(ut_ctx* c, const double* y, int32_t n, int32_t npad, double
   return 0;
 }
 
+// the categorical K*'s training-side operands (numeric block, its norms, the
+// weighted one-hot codes) of npad scaled rows Xs whose first n raw rows are X:
+// the fit's own rows, and the failed rows of the feasibility vote (gp_feas.hip)
+int launch_gp_cat_train(ut_ctx* c, const double* Xs, const double* X, int32_t n, int32_t npad, int32_t d, int32_t dpn,
+                        double* XsT_num, double* xnorm_num, int8_t* acat) {
+  const Space& sp = c->space;
+  hipLaunchKernelGGL(k_gp_num_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, Xs, npad, d, sp.d_num_feat.p,
+                     sp.n_num, dpn, XsT_num, xnorm_num);
+  UT_HIP(c, hipMemsetAsync(acat, 0, (size_t)sp.cat_k * npad, c->stream));
+  hipLaunchKernelGGL(k_gp_cat_train, dim3(grid1(n, 256)), dim3(256), 0, c->stream, sp.d_params.p, sp.P, sp.d_cat_ccol.p,
+                     X, n, d, npad, acat);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 // (tile64_nt, tile_row / tile_col, readlane_f64 and chol_diag_core: gp_tiles.h)
 //
 // Panel kb, step 1 (one workgroup): L_kk = chol(A_kk) written to K, and
@@ -706,7 +721,7 @@ static int gp_alloc(ut_ctx* c, int32_t npad_need, int32_t d) {
 
 // rows [r0, r1) of X [n][d] have exact one-hot ENUM blocks and 0 / 1 BOOL
 // features: the categorical K* reads the training rows as option codes
-static bool cat_rows_ok(const Space& s, const double* X, int32_t d, int32_t r0, int32_t r1) {
+bool cat_rows_ok(const Space& s, const double* X, int32_t d, int32_t r0, int32_t r1) {
   for (int32_t r = r0; r < r1; ++r) {
     const double* row = X + (size_t)r * d;
     for (int32_t p : s.host_cat) {
@@ -735,7 +750,6 @@ static bool cat_rows_ok(const Space& s, const double* X, int32_t d, int32_t r0, 
 static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int32_t npad, int32_t dpn, bool app,
                       int32_t xr0, double diag, double sf2) {
   int rc;
-  const Space& sp = c->space;
   double* hX = c->fit_host;
   double* hy = hX + (size_t)n * d;
   double* hinv = hy + n;
@@ -752,14 +766,9 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
     // the candidate side of K* needs only the scaled inputs: fp64 scoring starts
     // its K* here while the factorisation below is still running
     if ((rc = launch_xs_t(c, c->gp_Xs.p, npad, d, kstar_dpad(d), c->gp_XsT.p))) return rc;
-    if (c->cat_on) {
-      hipLaunchKernelGGL(k_gp_num_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, c->gp_Xs.p, npad, d,
-                         sp.d_num_feat.p, sp.n_num, dpn, c->gp_XsT_num.p, c->gp_xnorm_num.p);
-      UT_HIP(c, hipMemsetAsync(c->gp_acat.p, 0, (size_t)sp.cat_k * npad, c->stream));
-      hipLaunchKernelGGL(k_gp_cat_train, dim3(grid1(n, 256)), dim3(256), 0, c->stream, sp.d_params.p, sp.P, sp.d_cat_ccol.p,
-                         dX, n, d, npad, c->gp_acat.p);
-      UT_LAUNCH_CHECK(c);
-    }
+    if (c->cat_on && (rc = launch_gp_cat_train(c, c->gp_Xs.p, dX, n, npad, d, dpn, c->gp_XsT_num.p, c->gp_xnorm_num.p,
+                                               c->gp_acat.p)))
+      return rc;
     // precision 8: K*'s training operand as int8 digit planes (gp_kq.hip;
     // numeric fits only, gp_score_impl)
     if (c->gp_prec == 8 && c->kstar_q && !c->cat_on &&

@@ -11,6 +11,7 @@
 //   fp32: v_mfma_f32_32x32x2_f32   (C/D: col = lane&31, row = (r&3) + 8(r>>2) + 4(lane>>5))
 #include <type_traits>
 
+#include "gp_kstar_tile.h"
 #include "ut_internal.h"
 
 namespace ut {
@@ -42,8 +43,7 @@ __global__ void k_to_f32(const double* __restrict__ src, float* __restrict__ dst
 //   A = Xs^T [dpad][npad] (rows >= d zero), B = U' [dpad][ldk] (rows >= d and
 //   columns >= m zero; written by k_gp_prep_cand)
 // ---------------------------------------------------------------------------
-constexpr int K_NT = 256, K_BM = 128, K_BN = 128, K_BK = 16;
-constexpr int KSTAR_SPARE_PER_XCD = 2;
+// (K_NT, K_BM, K_BN, K_BK, KSTAR_SPARE_PER_XCD, kstar_issue, kcat_issue: gp_kstar_tile.h)
 
 // f16x3 operand layout (k_gp_var_h3): 256-row x 32-k blocks of 16 KiB per
 // plane, pre-swizzled into the variance kernel's LDS image
@@ -61,32 +61,6 @@ __device__ __forceinline__ int64_t h3_blk_off(int64_t r, int32_t k, int32_t K) {
   // CUs left to an in-flight GP fit (launch_gemm_kstar)
 
 // (sf2_exp2t_nonpos, EXP_TAB, KSTAR_T_MIN: ut_internal.h)
-
-constexpr int K_SA = K_BK * K_BM, K_SB = K_BK * K_BN, K_STAGE = K_SA + K_SB;
-
-__device__ __forceinline__ void kstar_issue(const double* __restrict__ AT, int64_t lda, const double* __restrict__ B,
-                                            int64_t ldb, int32_t row0, int64_t col0, int32_t k0, double* st, int w,
-                                            int lane, int32_t dpad) {
-  // 16 KiB of A and 16 KiB of B per stage = 32 wave-instructions, 8 per wave;
-  // wave w loads k rows 4w .. 4w+3, none past dpad (a multiple of 4: the last
-  // stage of a dpad that is not a multiple of 16 is partial)
-  if (k0 + 4 * w >= dpad) return;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int q = 4 * w + u;  // 0..15: A tile row k = q (128 doubles = 1 KiB)
-    const double* src = AT + (int64_t)(k0 + q) * lda + row0 + lane * 2;
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(st + q * 128), 16, 0, 0);
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int q = 4 * w + u;
-    const double* src = B + (int64_t)(k0 + q) * ldb + col0 + lane * 2;
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(st + K_SA + q * 128), 16, 0, 0);
-  }
-}
-
-typedef double kd4 __attribute__((ext_vector_type(4)));
-typedef int32_t ki4 __attribute__((ext_vector_type(4)));
 
 // Categorical K* (CAT): ENUM and BOOL params are one-hot blocks of the GP
 // features (SURVEY.md §8 GP spec: Enum one-hot, Bool {0, 1}), and with one
@@ -111,21 +85,6 @@ typedef int32_t ki4 __attribute__((ext_vector_type(4)));
 //   (l >> 4) + 4 q, so the A fragment of MFMA row rho loads tile row
 //   sigma(rho) = (rho >> 2) + 4 (rho & 3): iacc[i][jj][q] then sits where
 //   acc[i][jj][q] does (scripts/exp/i8_mfma_probe.hip checks both maps).
-__device__ __forceinline__ void kcat_issue(const int8_t* __restrict__ Ab, const int8_t* __restrict__ Bb,
-                                           double* st, int w, int lane) {
-  uint8_t* sb = reinterpret_cast<uint8_t*>(st);
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int q = 4 * w + u;                      // rows 8q .. 8q + 7 of the tile (1 KiB)
-    const int r = 8 * q + (lane >> 3);
-    const int cch = (lane & 7) ^ (r & 7);         // the global chunk that lands at position lane & 7
-    __builtin_amdgcn_global_load_lds(Ab + r * 128 + cch * 16, (__attribute__((address_space(3))) void*)(sb + q * 1024),
-                                     16, 0, 0);
-    __builtin_amdgcn_global_load_lds(Bb + r * 128 + cch * 16,
-                                     (__attribute__((address_space(3))) void*)(sb + K_SA * 8 + q * 1024), 16, 0, 0);
-  }
-}
-
 // MU: also the column partial of the mean, sum_r alpha_r k*_r (fp32 scoring;
 // fp64 takes the mean from the variance epilogue instead)
 template <typename TS, bool MU, bool CAT>

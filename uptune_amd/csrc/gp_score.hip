@@ -177,8 +177,9 @@ int gp_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m) {
   return launch_encode_scaled(c, values, ld, m, c->ucand.p, s.dpad, s.ldk, c->cnorm.p);
 }
 
-int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
-                  double* mu, double* var, double* score, hipEvent_t dup_ready) {
+// the dense posterior and acquisition of every tier (gp_score_impl below adds the feasibility weight)
+static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
+                          double* mu, double* var, double* score, hipEvent_t dup_ready) {
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_score: call ut_gp_fit first");
   UT_CHECK(c, acq != nullptr, UT_EINVAL, "gp_score: acq is NULL");
   if (m <= 0) return 0;
@@ -294,6 +295,23 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
   if ((rc = launch_gp_finalize(c, m, RT, RTv, c->mu_part.p, c->var_part.p, ldk, pa, dup, mu, var, score))) return rc;
   mark(c, "finalize");
   return 0;
+}
+
+// The single choke point of dense scoring (ut_gp_score, ut_gp_score_values,
+// the DE and GA rounds, every precision tier and both of precision 8's
+// recompute paths).  While failed rows are loaded (ut_gp_feas_set) the scores
+// the dense body wrote are weighted by the feasibility vote (gp_feas.hip) over
+// the K* operands it left in c->ucand / c->cnorm / c->bcat, categorical
+// exactly when its K* was.  With nothing loaded: no launch, no wait.
+int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
+                  double* mu, double* var, double* score, hipEvent_t dup_ready) {
+  const bool weigh = c->fs_n > 0 && score != nullptr;
+  UT_CHECK(c, !(weigh && acq && acq->kind == UT_ACQ_UCB), UT_EUNSUPPORTED,
+           "gp_score: failed rows are loaded (ut_gp_feas_set) and the feasibility weight is defined for EI only: "
+           "a UCB score can be negative");
+  const int rc = gp_score_dense(c, feat, ld, m, acq, dup, mu, var, score, dup_ready);
+  if (rc || !weigh || m <= 0) return rc;
+  return feas_weight(c, score_shape(c, m, !feat && c->cat_on && c->ucand_cat), m, score);
 }
 
 }  // namespace ut

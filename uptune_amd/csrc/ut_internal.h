@@ -442,6 +442,18 @@ struct ut_ctx {
   ut::DevBuf<double> bs_vec;               // mu [ldp] | var [ldp] | the launches' partial scores [2][16]
   ut::DevBuf<int32_t> bs_pos;              // ... and partial positions [2][16]
   ut::DevBuf<uint8_t> bs_picked;           // [ldp]
+  // failure-aware scoring (gp_feas.hip): the loaded failed rows, and their K*
+  // operands under the current fit's lengthscales -- a per-fit cache like pr_f2
+  ut::DevBuf<double> fs_X;                 // [fs_n][fs_d] features as given to ut_gp_feas_set
+  int32_t fs_n = 0, fs_d = 0;              // fs_n = 0: nothing loaded, no score is weighted
+  ut_feas_params fs_par{0.0, 1.0, 1.0, 1.0};
+  int32_t fs_bad_row = -1;                 // the first row that is not one-hot / 0-1 in the ENUM / BOOL blocks
+  uint64_t fs_gen = 0;                     // the fit (fit_gen) the operands below were built from; 0 = stale
+  ut::DevBuf<double> fs_Xs, fs_norm;       // scaled rows [nfpad][d] and their norms [nfpad]
+  ut::DevBuf<double> fs_XsT;               // [dpad][nfpad], every feature
+  ut::DevBuf<double> fs_XsT_num, fs_norm_num;   // the numeric block [dpad_num][nfpad] and its norms (categorical fits)
+  ut::DevBuf<int8_t> fs_acat;              // [cat_k / 128][nfpad][128] weighted one-hot codes
+  ut::DevBuf<double> fs_part;              // [RT + RT_fail][ldk] column partials of sum k
   int32_t dbg_fail_alloc = 0;             // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
@@ -587,6 +599,17 @@ int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int
                      int32_t g, const double* scale, const double* noise, double* lml_host, int32_t* best_host);
 // gp_lml_grad.hip: its gradient at the fit in place
 int gp_lml_grad_impl(ut_ctx* c, int32_t d, double* dlog_ell_host, double* dlog_sf2_host, double* dlog_sn2_host);
+// gp_fit.hip: the categorical K*'s training-side operands of rows Xs (scaled) / X (raw), as the fit builds its own
+int launch_gp_cat_train(ut_ctx* c, const double* Xs, const double* X, int32_t n, int32_t npad, int32_t d, int32_t dpn,
+                        double* XsT_num, double* xnorm_num, int8_t* acat);
+// ... and the host check that goes with the codes: rows [r0, r1) of X [n][d] are one-hot / 0-1 there
+bool cat_rows_ok(const Space& s, const double* X, int32_t d, int32_t r0, int32_t r1);
+// gp_feas.hip: the feasibility vote.  feas_weight: score[i] *= p_i^gamma for the m candidates whose K*
+// operands (of shape s) are in c->ucand / c->cnorm / c->bcat
+int gp_feas_set_impl(ut_ctx* c, const double* X, int32_t nf, int32_t d, const ut_feas_params* p);
+int gp_feas_prob_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
+                      double* s_ok_out, double* s_fail_out);
+int feas_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double* score);
 // gp_batch.hip: k picks from a shortlist of p, each conditioned on the picks before it
 int gp_select_batch_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
                          const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);

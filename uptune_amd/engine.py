@@ -446,6 +446,53 @@ class BatchEngine:
                 "ut_gp_select_batch")
         return pos, score, var
 
+    # -- failure-aware scoring ----------------------------------------------
+    def gp_feas_set(self, X_fail, prior: Optional[float] = None, strength: float = 1.0, ell_scale: float = 1.0,
+                    power: float = 1.0):
+        """ut_gp_feas_set: load (replace) the features [nf][F] of the configurations
+        that FAILED.  While rows are loaded every dense EI score is multiplied by
+        p^power, p = (S_ok + strength p0) / (S_ok + S_fail + strength) the kernel
+        vote of the fit's rows against these (the GP's kernel, lengthscales times
+        ell_scale); prior=None: p0 = n / (n + nf) of the fit in use.  UCB scoring,
+        pruned scoring and gp_select_batch raise UT_EUNSUPPORTED meanwhile."""
+        X = np.ascontiguousarray(X_fail, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("gp_feas_set: X_fail must be [nf][n_features]")
+        nf, d = X.shape
+        par = L.FeasParams(prior=0.0 if prior is None else float(prior), strength=float(strength),
+                           ell_scale=float(ell_scale), power=float(power))
+        L.check(self.ctx, self.lib.ut_gp_feas_set(self.ctx, X.ctypes.data if nf else None, nf, d, C.byref(par)),
+                "ut_gp_feas_set")
+
+    def gp_feas_clear(self):
+        """no failed rows: every call scores as it did before any were loaded"""
+        L.check(self.ctx, self.lib.ut_gp_feas_set(self.ctx, None, 0, 0, None), "ut_gp_feas_set")
+
+    def gp_feas_prob(self, values: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None,
+                     m: Optional[int] = None):
+        """ut_gp_feas_prob: (p, S_ok, S_fail), each [m], of candidates given as raw
+        values [ncols][m] (the K* the fit scores with) or as features [F][m] (the
+        dense contraction); stream-ordered, no host wait"""
+        if (values is None) == (features is None):
+            raise ValueError("gp_feas_prob: exactly one of values and features")
+        x = values if values is not None else features
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        m = x.shape[1] if m is None else int(m)
+        p, s_ok, s_fail = self._empty(m), self._empty(m), self._empty(m)
+        L.check(self.ctx, self.lib.ut_gp_feas_prob(self.ctx, _ptr(x) if values is not None else None,
+                                                   _ptr(x) if values is None else None, x.stride(0), m, _ptr(p),
+                                                   _ptr(s_ok), _ptr(s_fail)), "ut_gp_feas_prob")
+        return p, s_ok, s_fail
+
+    def gp_feas_info(self) -> Dict[str, Any]:
+        """what is loaded: {"nf": rows (0: nothing), "prior" (None: from the fit),
+        "strength", "ell_scale", "power"}"""
+        nf, par = C.c_int32(), L.FeasParams()
+        L.check(self.ctx, self.lib.ut_gp_feas_info(self.ctx, C.byref(nf), C.byref(par)), "ut_gp_feas_info")
+        return {"nf": int(nf.value), "prior": float(par.prior) if par.prior > 0.0 else None,
+                "strength": float(par.strength), "ell_scale": float(par.ell_scale), "power": float(par.power)}
+
     def gp_topk_pruned(self, feat: torch.Tensor, k: int, m: Optional[int] = None, acq: Optional[L.Acq] = None,
                        dup: Optional[torch.Tensor] = None, cand_base: int = 0, bound_rows: int = 256):
         """ut_gp_topk_pruned: the top-k of the GP score, selection-exact, with the

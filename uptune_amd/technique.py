@@ -273,7 +273,8 @@ class SharedModel:
 
     def __init__(self, device: int = 0, seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4,
                  precision: int = 64, sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 1e-8,
-                 engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40):
+                 engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40,
+                 feasibility: Union[bool, Dict[str, Any]] = False):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -312,6 +313,12 @@ class SharedModel:
         # substitute a CPU stand-in to exercise the plugin plumbing without a GPU.
         self.engine_factory = engine_factory
         self.hyper = dict(sigma_f2=sigma_f2, sigma_n2=sigma_n2, jitter=jitter)
+        # feasibility: False, True or a dict of prior / strength / ell_scale /
+        # power (engine.gp_feas_set).  When on, fit() also loads the features of
+        # the driver's results that FAILED (not usable, but with a configuration),
+        # in arrival order, and every EI score is weighted by the kernel vote of
+        # the training rows against them.  n_failed is how many are loaded.
+        self.feasibility = _feas_setting(feasibility)
         self._reset()
         self.slots: Dict[str, int] = {}
 
@@ -346,6 +353,14 @@ class SharedModel:
         self._scan_last = None
         self._scan_rows: List[Any] = []
         self._scan_ids: List[Any] = []
+        # feasibility: the failed results found so far (list drivers: by the
+        # same scan), their features in arrival order and how many of them the
+        # engine holds (-1: what it holds is stale)
+        self._scan_failed: List[Any] = []
+        self._fail_X = np.zeros((0, 0))
+        self._fail_k = 0
+        self._fail_sent = 0
+        self.n_failed = 0
 
     def __deepcopy__(self, memo):
         # techniques (and so their shared model) are deep-copied per driver
@@ -396,22 +411,31 @@ class SharedModel:
         def usable(r):
             return getattr(r, "state", "OK") == "OK" and r.time is not None and math.isfinite(r.time)
 
+        def failed(r):   # (feasibility) a result that is not usable but says where it failed
+            return self.feasibility is not None and getattr(r, "configuration", None) is not None
+
         res = driver.results_query()
         if isinstance(res, list):
             # an in-memory table only grows: scan the rows added since the last
             # call (a table that shrank or changed under us is rescanned)
             if len(res) < self._scan_n or (self._scan_n and res[self._scan_n - 1] is not self._scan_last):
-                self._scan_n, self._scan_rows, self._scan_ids = 0, [], []
+                self._scan_n, self._scan_rows, self._scan_ids, self._scan_failed = 0, [], [], []
+                self._fail_k = 0
             for r in res[self._scan_n:]:
                 if usable(r):
                     self._scan_ids.append(getattr(r, "id", len(self._scan_rows)))
                     self._scan_rows.append(r)
+                elif failed(r):
+                    self._scan_failed.append(r)
             self._scan_n = len(res)
             self._scan_last = res[-1] if res else None
-            rows, ids = self._scan_rows, self._scan_ids
+            rows, ids, bad = self._scan_rows, self._scan_ids, self._scan_failed
         else:   # a SQL query (reference driver): every row, filtered
+            res = list(res)
             rows = [r for r in res if usable(r)]
             ids = [getattr(r, "id", i) for i, r in enumerate(rows)]
+            bad = [r for r in res if not usable(r) and failed(r)]
+            self._fail_k = 0
         if len(rows) < self.min_train:
             return False
         if self._fit_unverified and self._fit_key is not None:
@@ -426,10 +450,14 @@ class SharedModel:
                 self._fit_key = None
         key = (len(rows), ids[-1])
         if key == self._fit_key:
+            self._load_failed(bad)      # failures alone do not refit, but they count
             return True
         k = self._n
         if k == 0 or ids[:k] != self._res_ids:      # not an append: re-encode everything
             k = self._n = self._nf = 0
+            self._fail_k = 0
+            if self._fail_sent > 0:
+                self._fail_sent = -1
         new = rows[k:]
         if new:
             n = k + len(new)
@@ -480,7 +508,24 @@ class SharedModel:
         self._fit_key = key
         self._fit_unverified = True
         self.fits += 1
+        self._load_failed(bad)
         return True
+
+    def _load_failed(self, bad) -> None:
+        """(feasibility) the failed results' features to the engine, whenever
+        their number changed or the model was re-encoded: the new ones encoded
+        through _features (the round's cached encodings), rows in arrival order"""
+        if self.feasibility is None:
+            return
+        k, n = min(self._fail_k, len(bad)), len(bad)
+        if n > k:
+            X, _ = _rows_room(self._fail_X, np.zeros(self._fail_X.shape[0]), k, n, self.engine.spec.n_features)
+            X[k:n] = self._features(bad[k:])
+            self._fail_X, self._fail_k = X, n
+        if n == self._fail_sent:
+            return
+        self.engine.gp_feas_set(self._fail_X[:n], **self.feasibility)
+        self._fail_sent = self.n_failed = n
 
     def _grid(self, d: int) -> np.ndarray:
         return math.sqrt(d) * np.geomspace(0.05, 4.0, 16) if self.ell_grid is None else self.ell_grid
@@ -598,6 +643,17 @@ class SharedModel:
         return out
 
 
+def _feas_setting(feasibility) -> Optional[Dict[str, Any]]:
+    """feasibility= as gp_feas_set's keyword arguments; None = off"""
+    if feasibility is False or feasibility is None:
+        return None
+    if feasibility is True:
+        return {}
+    if not isinstance(feasibility, dict) or set(feasibility) - {"prior", "strength", "ell_scale", "power"}:
+        raise ValueError("feasibility: False, True or a dict of prior, strength, ell_scale, power")
+    return dict(feasibility)
+
+
 def _rows_room(X, y, used, n, d):
     """(X, y) with room for n rows of d features, the first `used` rows kept"""
     if X.shape[0] >= n and X.shape[1] == d:
@@ -627,8 +683,20 @@ class GpuBatchTechnique(SearchTechnique):
                  seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4, acq: str = "ei",
                  group=None, surrogate=None, shared: Optional[SharedModel] = None, engine_factory=None,
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
-                 *pargs, **kwargs):
+                 feasibility: Union[bool, Dict[str, Any]] = False, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
+        # feasibility (SharedModel): EI times the estimated probability that the
+        # candidate does not fail.  A shared model carries its own setting; the
+        # weight is defined for the dense EI score only
+        if (shared.feasibility if shared is not None else _feas_setting(feasibility)) is not None:
+            if int(prune_rows) > 0:
+                raise ValueError("feasibility weights every candidate's score: not with prune_rows")
+            if int(diversify) > 0:
+                raise ValueError("feasibility is not known to the per-pick acquisition: not with diversify")
+            if acq == "ucb":
+                raise ValueError("feasibility multiplies a score that is >= 0: EI, not acq='ucb'")
+            if surrogate is not None:
+                raise ValueError("feasibility weights the GP's EI: not with a tree surrogate")
         # diversify = D > 0: a round with a GP takes the D best-scoring candidates
         # as a shortlist and picks its `batch` from them with ut_gp_select_batch,
         # each pick conditioned on the picks before it, so that a batch drawn
@@ -657,7 +725,8 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    lengthscale=lengthscale, min_train=min_train,
                                                                    precision=precision,
                                                                    engine_factory=engine_factory,
-                                                                   y_transform=y_transform)
+                                                                   y_transform=y_transform,
+                                                                   feasibility=feasibility)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -960,7 +1029,8 @@ class GpuGGA(GpuGA):
 def _shared_model(kw) -> SharedModel:
     return SharedModel(device=kw.get("device", 0), seed=kw.get("seed", 0), lengthscale=kw.get("lengthscale", 0.3),
                        min_train=kw.get("min_train", 4), precision=kw.get("precision", 64),
-                       engine_factory=kw.pop("engine_factory", None), y_transform=kw.get("y_transform"))
+                       engine_factory=kw.pop("engine_factory", None), y_transform=kw.get("y_transform"),
+                       feasibility=kw.get("feasibility", False))
 
 
 def pso_ga_de_bandit(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
