@@ -309,7 +309,8 @@ typedef struct ut_prune_stats {
   int64_t survivors;     /* candidates that got the full variance (m if the round fell back to dense) */
   int32_t bound_rows;    /* rows of L^-1 k* in the bound (a multiple of 128) */
   int32_t dense;         /* 1: too many survivors, the round ran the dense variance instead */
-  double threshold;      /* tau */
+  double threshold;      /* tau; -inf when the threshold set holds fewer than k valid candidates
+                            (m < k, or nearly all duplicates): then nothing is pruned */
 } ut_prune_stats;
 int ut_gp_topk_pruned(ut_ctx* ctx, const double* features, int64_t ld, int64_t m, const ut_acq* acq,
                       const uint8_t* dup, int64_t cand_base, int32_t k, int32_t bound_rows, int64_t* out_idx,
@@ -542,6 +543,15 @@ int ut_score_round_de_pruned(ut_ctx* ctx, const ut_de_params* de, const ut_acq* 
  * two waits for the round. */
 int ut_round_buffers(ut_ctx* ctx, double** values, double** features, uint32_t** digests, uint8_t** dup,
                      double** mu, double** var, double** score, int64_t* ld);
+/* for tests: copy, on ctx's stream, the per-candidate score bounds [m] (device
+ * doubles: +inf where the f32 pass had no usable bound, -inf on duplicates,
+ * NaN after a failed fit) and exact flags [m] (device bytes: 1 = the bound is
+ * the candidate's exact score) of the last ut_gp_topk_pruned /
+ * ut_score_round_de_pruned call into caller-provided device arrays (either
+ * may be NULL).  They are kept when that call fell back to the dense variance.
+ * UT_EINVAL while no pruned call has computed bounds, or if m is not that
+ * call's m. */
+int ut_gp_prune_bounds(ut_ctx* ctx, double* ub_out, uint8_t* exact_out, int64_t m);
 /* Dense DE rounds (ut_score_round_de) are lazy when K', the smallest power of
  * two >= 2k, is at most 1024 and less than m: only the K' best-scoring
  * candidates are hashed and deduplicated, which selects what hashing all m

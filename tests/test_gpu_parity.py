@@ -29,6 +29,7 @@ def _require_gpu():
         pytest.skip("no GPU")
 
 
+import _prune_oracle as po  # noqa: E402
 from _spaces import oracle_space, to_manip  # noqa: E402
 
 
@@ -45,6 +46,15 @@ def dev(a):
 def hexes(d):
     from uptune_amd.engine import digests_to_hex
     return digests_to_hex(d)
+
+
+def _d2h(ptr, m, dtype=np.float64):
+    import ctypes
+    out = np.empty(m, dtype=dtype)
+    rc = ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr),
+                                                 ctypes.c_size_t(out.nbytes), 2)
+    assert rc == 0, rc
+    return out
 
 
 def mixed_space():
@@ -954,6 +964,10 @@ def test_gp_topk_pruned_equals_dense(acq, bound_rows, prune_pass):
     want = [5 + i for i in sorted(range(m), key=lambda i: (-sc[i], i))[:k]]
     gaps = np.abs(np.diff(np.sort(sc[np.isfinite(sc)])[::-1][:k + 1]))
     _close(top.cpu().numpy(), t2.cpu().numpy(), rtol=1e-9, atol=1e-12)
+    # whatever the gaps: the selection within the band of the k-th best score
+    valid = dup.cpu().numpy() == 0
+    po.band_check(idx.cpu().numpy(), top.cpu().numpy(), score.cpu().numpy(), valid, k, 5, 1e-9, 1e-12)
+    po.band_check(idx.cpu().numpy(), top.cpu().numpy(), sc, valid, k, 5, 1e-5, 1e-8)
     if gaps.min() > 1e-9:
         assert idx.cpu().numpy().tolist() == i2.cpu().numpy().tolist() == want
 
@@ -1015,11 +1029,18 @@ def test_score_round_de_pruned_equals_dense_round():
     e.history_reset(0)
     e.history_add(e.hash(dev(pop[:, :n])))
     a = e.score_round_de(8192, 48, round_=3, cand_base=100, cr=0.3)
+    e.sync()
+    dense_score = _d2h(e.round_buffers()[0][6], 8192)   # every candidate's score (unmasked if the round was lazy)
     b = e.score_round_de_pruned(8192, 48, round_=3, cand_base=100, cr=0.3, bound_rows=128)
     st = b[4]
     assert 0 < st["survivors"] < 8192 and not st["dense"]
     sa, sb = a[1].cpu().numpy(), b[1].cpu().numpy()
     _close(sb, sa, rtol=1e-9, atol=1e-12)
+    # whatever the gaps: the selection within the band of the k-th best dense score
+    e.sync()
+    pdup = e.round_buffers()[0][3]
+    assert pdup, "a pruned round keeps its dup mask"
+    po.band_check(b[0].cpu().numpy(), sb, dense_score, _d2h(pdup, 8192, np.uint8) == 0, 48, 100, 1e-9, 1e-12)
     if np.abs(np.diff(sa)).min() > 1e-9:
         assert a[0].cpu().numpy().tolist() == b[0].cpu().numpy().tolist()
         assert hexes(a[2]) == hexes(b[2])

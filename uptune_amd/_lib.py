@@ -156,6 +156,7 @@ SIGNATURES = {
     "ut_round_lazy_stats": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ut_round_buffers": (C.c_int, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
                                    C.POINTER(P), C.POINTER(P), C.POINTER(I64)]),
+    "ut_gp_prune_bounds": (C.c_int, [P, P, P, I64]),
     "ut_comm_unique_id": (C.c_int, [P]),
     "ut_comm_init": (C.c_int, [P, I32, I32, P]),
     "ut_comm_destroy": (C.c_int, [P]),

@@ -1193,6 +1193,17 @@ int ut_round_buffers(ut_ctx* c, double** values, double** features, uint32_t** d
   return 0;
 }
 
+int ut_gp_prune_bounds(ut_ctx* c, double* ub_out, uint8_t* exact_out, int64_t m) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, c->pr_m > 0, UT_EINVAL, "gp_prune_bounds: no pruned call yet");
+  UT_CHECK(c, m == c->pr_m, UT_EINVAL, "gp_prune_bounds: m is not the last pruned call's m");
+  if (ub_out)
+    UT_HIP(c, hipMemcpyAsync(ub_out, c->pr_ub.p, sizeof(double) * m, hipMemcpyDeviceToDevice, c->stream));
+  if (exact_out)
+    UT_HIP(c, hipMemcpyAsync(exact_out, c->pr_exact.p, sizeof(uint8_t) * m, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
 int ut_round_lazy_stats(ut_ctx* c, int64_t* lazy_rounds, int64_t* fallback_rounds) {
   if (!c) return UT_EINVAL;
   if (lazy_rounds) *lazy_rounds = c->lazy_rounds;

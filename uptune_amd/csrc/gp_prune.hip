@@ -201,13 +201,17 @@ __global__ void k_prune_exact(int64_t n, const int64_t* __restrict__ idx, int64_
 // wave; tau and its index are device scalars).  An exact candidate (its
 // stored score is its exact score) survives iff (score, -index) >= (tau,
 // -tau_index), the k-th best pair of the threshold set -- a lower bound on the
-// k-th best pair overall; any other survives iff its bound >= tau.
+// k-th best pair overall; any other survives iff its bound >= tau.  A threshold
+// set with fewer than k valid entries (m < k, or nearly every candidate a
+// duplicate) has no k-th best pair: its slot is an invalid entry (index < 0)
+// whose stored score means nothing (0 for the sort's padding, -inf for a
+// duplicate), so tau is -inf and nothing is pruned.
 __global__ void k_prune_survivors(int64_t m, const double* __restrict__ ub, const double* __restrict__ tau_p,
                                   const int64_t* __restrict__ tau_idx_p, const uint8_t* __restrict__ exact,
                                   int64_t cand_base, int64_t* __restrict__ out, unsigned long long* __restrict__ count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const double tau = *tau_p;
   const int64_t tau_g = *tau_idx_p;
+  const double tau = tau_g < 0 ? -1.0 / 0.0 : *tau_p;
   bool keep = false;
   if (i < m) {
     const double b = ub[i];
@@ -227,6 +231,7 @@ __global__ void k_fill(double* __restrict__ p, int64_t n, double v) {
 int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
                         int64_t cand_base, int32_t k, int32_t bound_rows, int64_t* out_idx, double* out_score,
                         ut_prune_stats* stats, hipEvent_t dup_ready, bool feat_ours) {
+  c->pr_m = 0;   // (set again once this call's bounds are enqueued)
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_topk_pruned: call ut_gp_fit first");
   UT_CHECK(c, c->gp_fit_prec == 64, UT_EINVAL, "gp_topk_pruned: needs an fp64 fit (ut_gp_set_precision 64)");
   UT_CHECK(c, acq->kind == UT_ACQ_EI || (acq->kind == UT_ACQ_UCB && acq->kappa >= 0.0), UT_EINVAL,
@@ -350,6 +355,7 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
     hipLaunchKernelGGL(k_prune_bound, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, c->mu_part.p, R,
                        c->var_part.p, ldk, pa, dup, c->pr_mu.p, c->pr_ub.p, c->pr_k2.p, c->pr_f2.p, c->pr_exact.p);
   UT_LAUNCH_CHECK(c);
+  c->pr_m = m;   // pr_ub / pr_exact hold this call's bounds (ut_gp_prune_bounds)
   // 3. threshold: exact scores of the best 1024 bounds, tau = their k-th best
   const int32_t kp = (int32_t)(m < 1024 ? m : 1024);
   int64_t* tset = c->pr_idx.p + ldk;                   // [1024] threshold set (global indices)
@@ -375,11 +381,13 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
                      tk_i + (k - 1), c->pr_exact.p, cand_base, c->pr_idx.p,
                      reinterpret_cast<unsigned long long*>(c->pr_count.p));
   UT_LAUNCH_CHECK(c);
-  int64_t ns = 0;
+  int64_t ns = 0, tau_g = -1;
   double tau = 0.0;
   UT_HIP(c, hipMemcpyAsync(&ns, c->pr_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   UT_HIP(c, hipMemcpyAsync(&tau, tk_s + (k - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  UT_HIP(c, hipMemcpyAsync(&tau_g, tk_i + (k - 1), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   UT_HIP(c, hipStreamSynchronize(c->stream));
+  if (tau_g < 0) tau = -1.0 / 0.0;   // no k-th best pair (k_prune_survivors)
   mark(c, "prune");
   const bool dense = ns * 2 > m;
   if (dense) {

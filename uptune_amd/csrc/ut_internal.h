@@ -383,6 +383,7 @@ struct ut_ctx {
   ut::DevBuf<double> pr_gmu;                   // [RT][ldc] fp64 mean partials of recomputed columns (f32 pass)
   int32_t prune_pass = 32;                     // ut_gp_set_prune_pass: the bound pass in f32 or fp64
   ut::DevBuf<uint8_t> pr_exact;                // [ld] the stored score is the exact score
+  int64_t pr_m = 0;                            // the last pruned call's m (ut_gp_prune_bounds); 0 = none yet
   int64_t r_ld = 0;
   int64_t r_m = 0;
   bool r_feat_valid = false;        // r_feat holds the last round's features (pruned rounds only)

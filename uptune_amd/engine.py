@@ -599,6 +599,14 @@ class BatchEngine:
         return idx, top, dig, vals, {"survivors": st.survivors, "bound_rows": st.bound_rows, "dense": bool(st.dense),
                                      "threshold": st.threshold, "m": m}
 
+    def gp_prune_bounds(self, m: int):
+        """ut_gp_prune_bounds (for tests): the last pruned call's per-candidate
+        score bounds [m] (float64) and exact flags [m] (uint8) -> (ub, exact)"""
+        ub = self._empty(int(m))
+        exact = self._empty(int(m), dtype=torch.uint8)
+        L.check(self.ctx, self.lib.ut_gp_prune_bounds(self.ctx, _ptr(ub), _ptr(exact), int(m)), "ut_gp_prune_bounds")
+        return ub, exact
+
     def round_lazy_stats(self) -> Tuple[int, int]:
         """(lazy dense DE rounds, those of them that fell back to hashing every
         candidate) since the context was created; waits for the stream"""
