@@ -501,6 +501,66 @@ int ut_gp_feas_prob(ut_ctx* ctx, const double* values, const double* features, i
 /* what is loaded: the row count (0: nothing) and the parameters as given (either may be NULL) */
 int ut_gp_feas_info(ut_ctx* ctx, int32_t* nf, ut_feas_params* p);
 
+/* ---- constrained EI ------------------------------------------------------ */
+/* The reference's ThresholdAccuracyMinimizeTime (objective.py:246-298) minimises
+ * time among the results whose accuracy reaches a target.  A constraint that is
+ * MEASURED on every run is a GP target like the objective, on the same inputs,
+ * kernel and hyperparameters, so it shares the fit's factor L and needs only a
+ * weight vector of its own (Gardner et al. 2014, constrained EI).
+ *
+ * Up to UT_CONS_MAX constraints c_j(x) <= t_j (a >= constraint: negate both on
+ * the host).  For the current fit -- n rows X, lengthscales, sigma_f2,
+ * sigma_n2 + jitter, L, the standardised objective ys -- and values C [n][nc]
+ * row-aligned with the fit's rows:
+ *   m_j, s_j   = mean, std (ddof 0; std 0 -> 1) of column j  (the fit's own rule for y)
+ *   chat_j     = (C[:, j] - m_j) / s_j        tau_j = (t_j - m_j) / s_j
+ *   alpha_j    = K^-1 chat_j = L^-T (L^-1 chat_j)
+ *   mu_cj(u)   = k*(u) . alpha_j              (k* with sigma_f2, the K* the fit scores with)
+ *   P_j(u)     = Phi((tau_j - mu_cj(u)) / sqrt(var(u)));  var(u) == 0: mu_cj(u) <= tau_j ? 1 : 0
+ *   P(u)       = prod_j P_j(u)                (j ascending)
+ *   F          = { r : C[r, j] <= t_j for every j }   (compared on the raw values)
+ *   f_best_c   = min_{r in F} ys[r]
+ *   score(u)   = EI(mu(u), var(u); f_best_c, xi) P(u)   if F is not empty
+ *              = P(u)                                    if F is empty
+ * var(u) is the objective's own posterior variance (the latent constraint: no
+ * sigma_n2 is added), EI the acquisition of ut_gp_score with f_best_c in place
+ * of the fit's f_best.  -inf (a duplicate) and NaN (a failed fit) pass through;
+ * mu and var are never changed.  With every row feasible and P = 1 the result
+ * is bitwise the unconstrained score.  All sums run in a fixed order: two calls
+ * return the same bits. */
+#define UT_CONS_MAX 4
+/* Load (replace) the constraint values of the fit that is current at the call
+ * (objective.py:246-298): C_host [n][nc], threshold_host [nc]; nc = 0 clears
+ * (both pointers may then be NULL).  A fit staged by ut_gp_fit_async counts as
+ * current and is not waited for.  Synchronous on the host side (the caller's
+ * buffers are free on return).  The values belong to that fit: after any later
+ * fit every scoring call that would apply them returns UT_EINVAL, naming the
+ * stale fit, until ut_gp_cons_set is called again or the constraints are
+ * cleared.
+ * While constraints are loaded the rule above applies to ut_gp_score,
+ * ut_gp_score_values, ut_score_round_de and ut_score_round_ga at every
+ * precision, after the dense posterior and before the feasibility weight
+ * (score = EI(f_best_c) P p^gamma when both are loaded); a scoring call with
+ * UT_ACQ_UCB returns UT_EUNSUPPORTED, and so do ut_gp_topk_pruned,
+ * ut_score_round_de_pruned and ut_gp_select_batch.
+ * UT_EINVAL (what was loaded before stays loaded): no fit, n not the fit's n,
+ * nc < 0 or nc > UT_CONS_MAX, a NULL pointer with nc > 0, a non-finite value,
+ * a NaN threshold (+-inf thresholds are allowed). */
+int ut_gp_cons_set(ut_ctx* ctx, const double* C_host, int32_t n, int32_t nc, const double* threshold_host);
+/* P (p_out [m], required) and optionally the standardised constraint means
+ * mu_cj (mu_c_out [nc][ld], may be NULL) of m candidates under the loaded
+ * constraints (objective.py:246-298); none loaded: P = 1.  Exactly one of values
+ * ([ncols][ld], raw values: the K* the fit scores with) and features ([d][ld]:
+ * the dense contraction over every feature) is non-NULL.  Runs the objective's
+ * posterior for var(u) first.  Device outputs; stream-ordered, no host wait. */
+int ut_gp_cons_prob(ut_ctx* ctx, const double* values, const double* features, int64_t ld, int64_t m,
+                    double* p_out, double* mu_c_out);
+/* What is loaded (objective.py:246-298): the row count, the constraint count
+ * (0: nothing), the size of F and f_best_c (NaN when F is empty or nothing is
+ * loaded).  Any pointer may be NULL.  Waits for the fit when either of the
+ * last two is asked for; UT_EINVAL then if the values belong to an earlier fit. */
+int ut_gp_cons_info(ut_ctx* ctx, int32_t* n, int32_t* nc, int32_t* n_feasible, double* f_best_c);
+
 /* ---- selection ---------------------------------------------------------- */
 /* k largest scores, ties -> smallest global index; entries with dup[i]!=0 or
  * NaN score are never selected; missing slots get index -1. */

@@ -282,9 +282,10 @@ int ut_ctx_destroy(ut_ctx* c) {
   if (c->stream) ut::sync_all(c);
   ut::comm_release(c);
   for (auto& m : c->timing.marks) hipEventDestroy(m.ev);
-  for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_fit, c->ev_prefit, c->ev_fit_x})
+  for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_fit, c->ev_prefit, c->ev_fit_x, c->cs_ev})
     if (e) hipEventDestroy(e);
   if (c->fit_host) hipHostFree(c->fit_host);
+  if (c->cs_host) hipHostFree(c->cs_host);
   if (c->flag_host) hipHostFree(c->flag_host);
   if (c->lml_host) hipHostFree(c->lml_host);
   for (hipStream_t st : {c->own_stream, c->side, c->fit_stream})
@@ -751,6 +752,9 @@ int ut_gp_topk_pruned(ut_ctx* c, const double* feat, int64_t ld, int64_t m, cons
   UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
            "gp_topk_pruned: failed rows are loaded (ut_gp_feas_set) and the pruning bound does not know the "
            "feasibility weight");
+  UT_CHECK(c, c->cs_nc == 0, UT_EUNSUPPORTED,
+           "gp_topk_pruned: constraint values are loaded (ut_gp_cons_set) and the pruning bound does not know the "
+           "constraint weight");
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
   int rc = gp_topk_pruned_impl(c, feat, ld, m, acq, dup, cand_base, k, bound_rows, out_idx, out_score, stats);
@@ -843,6 +847,9 @@ int ut_gp_select_batch(ut_ctx* c, const double* values, int64_t ld, int32_t p, c
   UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
            "gp_select_batch: failed rows are loaded (ut_gp_feas_set) and the per-pick acquisition does not know the "
            "feasibility weight");
+  UT_CHECK(c, c->cs_nc == 0, UT_EUNSUPPORTED,
+           "gp_select_batch: constraint values are loaded (ut_gp_cons_set) and the per-pick acquisition does not know the "
+           "constraint weight");
   // a stand-alone call is a timing round of its own (stages bs_kstar, bs_v, bs_sigma, bs_loop)
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
@@ -874,6 +881,30 @@ int ut_gp_feas_info(ut_ctx* c, int32_t* nf, ut_feas_params* p) {
   if (nf) *nf = c->fs_n;
   if (p) *p = c->fs_par;
   return 0;
+}
+
+int ut_gp_cons_set(ut_ctx* c, const double* C_host, int32_t n, int32_t nc, const double* threshold_host) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_cons_set_impl(c, C_host, n, nc, threshold_host);
+}
+
+int ut_gp_cons_prob(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
+                    double* mu_c_out) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  // a stand-alone call is a timing round of its own (stages encode / cnorm, kstar, var, finalize, cons)
+  const bool own = c->timing.on && !c->timing.in_round;
+  if (own) timing_begin(c);
+  const int rc = gp_cons_prob_impl(c, values, features, ld, m, p_out, mu_c_out);
+  if (own) timing_end(c);
+  return rc;
+}
+
+int ut_gp_cons_info(ut_ctx* c, int32_t* n, int32_t* nc, int32_t* n_feasible, double* f_best_c) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_cons_info_impl(c, n, nc, n_feasible, f_best_c);
 }
 
 int ut_gp_kstar_mode(ut_ctx* c, int32_t* categorical) {
@@ -921,6 +952,9 @@ int ut_score_round_de_pruned(ut_ctx* c, const ut_de_params* de, const ut_acq* ac
   UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
            "score_round_de_pruned: failed rows are loaded (ut_gp_feas_set) and the pruning bound does not know the "
            "feasibility weight");
+  UT_CHECK(c, c->cs_nc == 0, UT_EUNSUPPORTED,
+           "score_round_de_pruned: constraint values are loaded (ut_gp_cons_set) and the pruning bound does not know the "
+           "constraint weight");
   return score_round_de_impl(c, de, acq, round_, cand_base, m, k, out, bound_rows, stats);
 }
 
@@ -933,6 +967,8 @@ static int score_round_de_impl(ut_ctx* c, const ut_de_params* de, const ut_acq* 
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "score_round: call ut_gp_fit first");
   UT_CHECK(c, c->gp_d == c->space.n_feat, UT_EINVAL, "score_round: GP feature width != space feature width");
   UT_CHECK(c, m >= 1 && de && acq, UT_EINVAL, "score_round: bad arguments");
+  // (constraint values of an earlier fit: refused before the round enqueues anything)
+  if (int rs = ut::cons_stale(c, "score_round")) return rs;
   const int64_t ld = ((m + 127) / 128) * 128;
   const int32_t NC = c->space.ncols;
   int rc;
@@ -1117,6 +1153,7 @@ int ut_score_round_ga(ut_ctx* c, const ut_ga_params* ga, const double* parent1, 
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "score_round: call ut_gp_fit first");
   UT_CHECK(c, c->gp_d == c->space.n_feat, UT_EINVAL, "score_round: GP feature width != space feature width");
   UT_CHECK(c, m >= 1 && ga && acq && cand_base >= 0 && k >= 1, UT_EINVAL, "score_round_ga: bad arguments");
+  if (int rs = ut::cons_stale(c, "score_round_ga")) return rs;
   UT_CHECK(c, ga->max_retries >= 1 && ga->max_retries <= 15, UT_EINVAL, "propose_ga: max_retries must be in [1, 15]");
   UT_CHECK(c, ga->must_mutate_count >= 0 && ga->must_mutate_count <= c->space.P, UT_EINVAL,
            "propose_ga: must_mutate_count out of range");

@@ -1,0 +1,502 @@
+// gp_cons.hip -- constrained EI (uthot.h "constrained EI"): up to UT_CONS_MAX
+// measured constraints c_j(x) <= t_j as further GP targets on the fit's own
+// factor.  With the same inputs, kernel and hyperparameters a second target
+// shares L and L^-1; it needs only
+//   alpha_j = K^-1 chat_j = L^-T (L^-1 chat_j)
+// and its posterior mean mu_cj(u) = k*(u) . alpha_j is the K* contraction over
+// the training rows with a weighted epilogue; its variance is the objective's.
+//   P(u)     = prod_j Phi((tau_j - mu_cj(u)) / sqrt(var(u)))
+//   score(u) = EI(mu, var; f_best_c, xi) P(u),  f_best_c = min ys over the feasible rows
+// (P(u) alone when no row is feasible).  The operands (chat, beta, alpha, tau,
+// f_best_c) are a per-fit cache built by small fp64 kernels after the whole fit;
+// the hot kernel is k_cons_means.
+#include "gp_kstar_tile.h"
+#include "gp_post.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace ut {
+
+constexpr int CS_INFO = 4 * UT_CONS_MAX;   // cs_stats[CS_INFO] = f_best_c, [CS_INFO + 1] = n_feasible
+
+// k_feas_sums' contraction (gp_feas.hip: k_gp_kstar<double>'s 128 x 128 items,
+// v_mfma_f64_16x16x4f64, the 2-stage glds ring, per-XCD tickets, two 256-thread
+// workgroups per CU, the int8 code stages first when CAT) over one row set, the
+// fit's training operand, with a weighted epilogue:
+//   1. the item's alpha_j[row0 .. row0 + 127], j < NC, go to LDS beside rowop;
+//   2. each element's k feeds NC accumulators s_j[col] += k alpha_j[row];
+//   3. no K* is stored;
+//   4. part [RT][NC][ldk] gets the tile's column sums per j (sigma_f2 = 1 in the
+//      exp table: k_cons_apply multiplies).
+// Padding rows (>= n) and columns (>= m) contribute exactly 0: their half-norm
+// is -1e300, the clamp at KSTAR_T_MIN is where 2^k' underflows to 0, and alpha
+// is 0 on padding rows.
+template <bool CAT, int NC>
+__global__ __launch_bounds__(K_NT, 2) void k_cons_means(const double* __restrict__ AT, const double* __restrict__ xnorm,
+                                                        const int8_t* __restrict__ acat, int32_t n, int32_t npad,
+                                                        int32_t RT, const double* __restrict__ alpha,
+                                                        const double* __restrict__ B, int64_t ldb, int32_t dpad,
+                                                        int32_t CT, const double* __restrict__ cnorm, int64_t m,
+                                                        int32_t* __restrict__ ticket, double* __restrict__ part,
+                                                        const int8_t* __restrict__ bcat, int32_t nkc, double cat_c0,
+                                                        double cat_c1) {
+  constexpr int MAIN = 2 * K_STAGE;
+  static_assert(K_NT == 2 * K_BM && K_BM == K_BN, "one thread per epilogue operand (rowop)");
+  static_assert(NC >= 1 && NC <= UT_CONS_MAX, "constraints per launch");
+  // the ring, the exp table, the ticket slot, the item's |row|^2 and |u_c|^2, its alpha_j rows
+  __shared__ __attribute__((aligned(16))) double lds[MAIN + EXP_TAB + 2 + (2 + NC) * K_BM];
+  double* etab = lds + MAIN;
+  int32_t& s_item = *reinterpret_cast<int32_t*>(lds + MAIN + EXP_TAB);
+  double* const rowop = lds + MAIN + EXP_TAB + 2;   // [norm 128][cnorm 128][alpha_j 128] x NC
+  const double* const al = rowop + 2 * K_BM;
+  const int t = threadIdx.x, lane0 = t & 63;
+  if (t < EXP_TAB) etab[t] = exp2((double)t / EXP_TAB);   // published by the first ticket barrier
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wm = w >> 1, wn = w & 1;
+  const int32_t xcd = blockIdx.x & 7;
+  const int32_t nk_full = dpad / K_BK, k_rem = (dpad % K_BK) / 4;
+  const int32_t nk = nk_full + (k_rem ? 1 : 0);
+  const int32_t ncs = CAT ? nkc : 0;          // int8 stages first, then the fp64 ones
+  const int32_t ntot = ncs + nk;
+  // the i8 MFMA's row rho of A is tile row sigma(rho) (gp_gemm.hip "Categorical K*")
+  const int sig = ((lane0 & 15) >> 2) + 4 * (lane0 & 3);
+  const int arow = lane0 & 15;
+
+  int32_t nxt = 0;
+  if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+  for (;;) {
+    if (t == 0) s_item = nxt;
+    __syncthreads();
+    // the lane index afresh per item: the per-lane glds addresses derived from a loop
+    // invariant are hoisted to kernel entry and, beside the 128 accumulator registers,
+    // spilled around the item loop
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int32_t j = __builtin_amdgcn_readfirstlane(s_item);
+    const int32_t ct = (j / RT) * 8 + xcd;
+    if (ct >= CT) break;
+    if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+    const int32_t rt = j % RT;
+    const int64_t col0 = (int64_t)ct * K_BN;
+    const int32_t row0 = rt * K_BM;
+
+    auto issue_stage = [&](int32_t s2, double* st) {
+      if (CAT && s2 < ncs)
+        kcat_issue(acat + ((int64_t)s2 * npad + row0) * 128, bcat + ((int64_t)s2 * ldb + col0) * 128, st, w, lane);
+      else
+        kstar_issue(AT, npad, B, ldb, row0, col0, (s2 - ncs) * K_BK, st, w, lane, dpad);
+    };
+    if (ntot > 0) issue_stage(0, lds);
+    // one 1-KiB glds per epilogue operand: the norms, then alpha_j (rows < npad, columns < ldk are in range)
+#pragma unroll
+    for (int op = 0; op < 2 + NC; ++op) {
+      if ((op & 3) != w) continue;
+      const double* src = op == 0 ? xnorm + row0 : op == 1 ? cnorm + col0 : alpha + (int64_t)(op - 2) * npad + row0;
+      __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + op * K_BM), 16,
+                                       0, 0);
+    }
+    kd4 acc[4][4];
+    if constexpr (CAT) {
+      ki4 iacc[4][4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) iacc[i][jj] = (ki4){0, 0, 0, 0};
+      for (int32_t s2 = 0; s2 < ncs; ++s2) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
+        asm volatile("" ::: "memory");
+        if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
+        const int8_t* as8 = reinterpret_cast<const int8_t*>(lds + (s2 & 1) * K_STAGE);
+        const int8_t* bs8 = as8 + K_SA * 8;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          const int c16 = (lane >> 4) + 4 * kk;
+          ki4 af[4], bf[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int row = wm * 64 + i * 16 + sig;
+            af[i] = *reinterpret_cast<const ki4*>(as8 + row * 128 + ((c16 ^ (row & 7)) << 4));
+          }
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int col = wn * 64 + jj * 16 + (lane & 15);
+            bf[jj] = *reinterpret_cast<const ki4*>(bs8 + col * 128 + ((c16 ^ (col & 7)) << 4));
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+              iacc[i][jj] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[jj], iacc[i][jj], 0, 0, 0);
+        }
+      }
+      // c0 + c1 M, in t units (see the launch)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[i][jj][r] = __builtin_fma((double)iacc[i][jj][r], cat_c1, cat_c0);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (kd4){0.0, 0.0, 0.0, 0.0};
+    }
+    for (int32_t s2 = ncs; s2 < ntot; ++s2) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
+      asm volatile("" ::: "memory");
+      if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
+      const double* as = lds + (s2 & 1) * K_STAGE;
+      const int32_t kt = s2 - ncs;
+      const double* bs = as + K_SA;
+      // the last stage of a dpad that is not a multiple of 16 has k_rem k4 steps
+      const int nks = kt < nk_full ? K_BK / 4 : k_rem;
+#pragma unroll
+      for (int ks = 0; ks < K_BK / 4; ++ks) {
+        if (ks >= nks) break;
+        const int kr = ks * 4 + (lane >> 4);
+        double af[4], bf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = as[kr * K_BM + wm * 64 + i * 16 + arow];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) bf[jj] = bs[kr * K_BN + wn * 64 + jj * 16 + (lane & 15)];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj)
+            acc[i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[jj], acc[i][jj], 0, 0, 0);
+      }
+    }
+    if (ntot == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the epilogue operands
+
+    __syncthreads();  // ring free: reuse as the column reduction buffer
+    // the item's half-norms once per item: -1e300 for a padding row (>= n) or column
+    // (>= m), whose k is then exactly 0 without a select in the element code
+    {
+      const double hv = (-0.5 * KSTAR_T_SCALE) * rowop[t];
+      const bool in = t < K_BM ? row0 + t < n : col0 + (t - K_BM) < m;
+      rowop[t] = in ? hv : -1e300;
+    }
+    __syncthreads();
+    double* red = lds;  // [NC][2][128]
+    double hc[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int cl = wn * 64 + jj * 16 + (lane & 15);
+      hc[jj] = rowop[K_BM + cl];
+    }
+    double s[NC][4];
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) s[q][jj] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rl = wm * 64 + i * 16 + (lane >> 4) + 4 * r;
+        const double hx = rowop[rl];
+        double a[NC];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) a[q] = al[q * K_BM + rl];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          // t = (C - |x|^2/2 - |u|^2/2) * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]
+          const double x = __builtin_fmax(__builtin_fmin((acc[i][jj][r] + hx) + hc[jj], 0.0), KSTAR_T_MIN);
+          const double k = sf2_exp2t_nonpos(x, etab);
+#pragma unroll
+          for (int q = 0; q < NC; ++q) s[q][jj] = __builtin_fma(k, a[q], s[q][jj]);
+        }
+      }
+    }
+    // every sum is complete here: without this the optimizer sinks column group jj's
+    // whole chain of exps below the lane test of group jj - 1's reduction, every row's
+    // LDS operands stay live across all four, and the kernel spills
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) asm volatile("" : "+v"(s[q][jj]));
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int cl = wn * 64 + jj * 16 + (lane & 15);
+        double a = s[q][jj];
+        a += __shfl_xor(a, 16);
+        a += __shfl_xor(a, 32);
+        if ((lane >> 4) == 0) red[(q * 2 + wm) * K_BN + cl] = a;
+      }
+    __syncthreads();
+    if (t < K_BN) {
+      const int64_t col = col0 + t;
+      if (col < m) {
+#pragma unroll
+        for (int q = 0; q < NC; ++q)
+          part[((int64_t)rt * NC + q) * ldb + col] = red[(q * 2) * K_BN + t] + red[(q * 2 + 1) * K_BN + t];
+      }
+    }
+  }
+}
+
+// One lane per candidate: mu_cj = sigma_f2 * its partials tile 0 upward, P_j, P
+// (j ascending); the outputs asked for; a finite score becomes
+// EI(mu, var; f_best_c, xi) P, or P when no row is feasible.
+// st: cs_stats -- [4 j + 3] = tau_j, [CS_INFO] = f_best_c, [CS_INFO + 1] = n_feasible
+__global__ void k_cons_apply(int64_t m, int32_t RT, int32_t nc, const double* __restrict__ part, int64_t ldp,
+                             double sf2, const double* __restrict__ st, const double* __restrict__ mu,
+                             const double* __restrict__ var, double xi, double* __restrict__ p_out,
+                             double* __restrict__ mu_c_out, int64_t ldo, double* __restrict__ score) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const double v = var[i];
+  const double sigma = sqrt(v);
+  double P = 1.0;
+  for (int32_t j = 0; j < nc; ++j) {
+    const double mc = sf2 * part_sum(part + (int64_t)j * ldp, RT, (int64_t)nc * ldp, i);
+    const double tau = st[4 * j + 3];
+    double pj;
+    if (v == 0.0) {
+      pj = mc <= tau ? 1.0 : 0.0;
+    } else {
+      const double z = (tau - mc) / sigma;
+      pj = 0.5 * erfc(-z * 0.70710678118654752440);
+    }
+    P *= pj;
+    if (mu_c_out) mu_c_out[(int64_t)j * ldo + i] = mc;
+  }
+  if (p_out) p_out[i] = P;
+  if (score) {
+    const double sc = score[i];
+    // -inf (a duplicate) and NaN (a failed fit) pass through
+    if (__builtin_isfinite(sc))
+      score[i] = st[CS_INFO + 1] > 0.0 ? acq_score(UT_ACQ_EI, mu[i], v, st[CS_INFO], xi, 0.0) * P : P;
+  }
+}
+
+// tau_j = (t_j - m_j) / s_j beside column j's stats; the feasible rows (every
+// raw value <= its threshold): their count and the smallest standardised
+// objective among them (NaN when there is none).  One workgroup.
+__global__ __launch_bounds__(256) void k_cons_scan(const double* __restrict__ C, const double* __restrict__ thr,
+                                                   int32_t n, int32_t npad, int32_t nc, const double* __restrict__ ys,
+                                                   double* __restrict__ st) {
+  __shared__ double rmin[256];
+  __shared__ int32_t rcnt[256];
+  const int t = threadIdx.x;
+  double mn = 1.0 / 0.0;
+  int32_t cnt = 0;
+  for (int32_t r = t; r < n; r += 256) {
+    bool ok = true;
+    for (int32_t j = 0; j < nc; ++j) ok = ok && C[(int64_t)j * npad + r] <= thr[j];
+    if (ok) {
+      ++cnt;
+      const double v = ys[r];
+      mn = v < mn ? v : mn;
+    }
+  }
+  rmin[t] = mn;
+  rcnt[t] = cnt;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      rmin[t] = rmin[t + w] < rmin[t] ? rmin[t + w] : rmin[t];
+      rcnt[t] += rcnt[t + w];
+    }
+    __syncthreads();
+  }
+  if (t < nc) st[4 * t + 3] = (thr[t] - st[4 * t + 1]) / st[4 * t + 2];
+  if (t == 0) {
+    st[CS_INFO] = rcnt[0] > 0 ? rmin[0] : __builtin_nan("");
+    st[CS_INFO + 1] = (double)rcnt[0];
+  }
+}
+
+int cons_stale(ut_ctx* c, const char* who) {
+  UT_CHECK(c, c->cs_nc == 0 || c->cs_fit == c->fit_gen, UT_EINVAL,
+           std::string(who) + ": the constraint values were loaded for fit " + std::to_string(c->cs_fit) +
+               " and fit " + std::to_string(c->fit_gen) +
+               " is current (stale: call ut_gp_cons_set again after every fit, or clear them)");
+  return 0;
+}
+
+// The per-fit operands of the loaded values: standardised columns (the fit's
+// own k_gp_ystats), beta_j = L^-1 chat_j and alpha_j = L^-T beta_j (the fit's
+// own mat-vecs over the explicit inverse), tau_j, the feasible-row scan.
+// Rebuilt when the fit changed (fit_gen) or the values did (ut_gp_cons_set
+// zeroes cs_gen).  On c->stream, after the whole fit: it reads L^-1 and ys.
+static int cons_operands(ut_ctx* c) {
+  if (c->cs_nc == 0 || c->cs_gen == c->fit_gen) return 0;
+  int rc;
+  if ((rc = gp_fit_flush(c))) return rc;
+  if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));
+  const int32_t n = c->cs_n, nc = c->cs_nc, npad = gp_npad(n);
+  UT_CHECK(c, n == c->gp_n && npad == c->gp_npad_fit, UT_EINVAL, "gp_cons: the values are not the fit's rows");
+  const size_t cols = (size_t)nc * npad;
+  if ((rc = ensure(c, c->cs_C, cols + UT_CONS_MAX))) return rc;
+  if ((rc = ensure(c, c->cs_chat, cols))) return rc;
+  if ((rc = ensure(c, c->cs_beta, cols))) return rc;
+  if ((rc = ensure(c, c->cs_alpha, cols))) return rc;
+  if ((rc = ensure(c, c->cs_stats, (size_t)CS_INFO + 2))) return rc;
+  UT_HIP(c, hipMemcpyAsync(c->cs_C.p, c->cs_host, sizeof(double) * (cols + UT_CONS_MAX), hipMemcpyHostToDevice,
+                           c->stream));
+  UT_HIP(c, hipEventRecord(c->cs_ev, c->stream));
+  for (int32_t j = 0; j < nc; ++j) {
+    const int64_t o = (int64_t)j * npad;
+    if ((rc = launch_gp_ystats(c, c->cs_C.p + o, n, npad, c->cs_chat.p + o, c->cs_stats.p + 4 * j))) return rc;
+    if ((rc = launch_gp_lower_mv(c, c->cs_chat.p + o, c->cs_beta.p + o))) return rc;
+    if ((rc = launch_gp_upper_mv(c, c->cs_beta.p + o, c->cs_alpha.p + o))) return rc;
+  }
+  hipLaunchKernelGGL(k_cons_scan, dim3(1), dim3(256), 0, c->stream, c->cs_C.p, c->cs_C.p + cols, n, npad, nc,
+                     c->gp_y.p, c->cs_stats.p);
+  UT_LAUNCH_CHECK(c);
+  c->cs_gen = c->fit_gen;
+  return 0;
+}
+
+template <bool CAT>
+static void launch_cons_means(ut_ctx* c, int32_t nc, int32_t nb, const KstarTrain& tr, const ScoreShape& s, int32_t CT,
+                              int64_t m) {
+  const double* xn = tr.xnorm ? tr.xnorm : c->gp_xnorm.p;
+  const double c0 = tr.cat.c0 * KSTAR_T_SCALE, c1 = tr.cat.c1 * KSTAR_T_SCALE;
+#define UT_CONS_LAUNCH(NC)                                                                                            \
+  hipLaunchKernelGGL((k_cons_means<CAT, NC>), dim3(nb), dim3(K_NT), 0, c->stream, tr.XsT, xn, tr.cat.acat, s.n,       \
+                     s.npad, s.RT, c->cs_alpha.p, c->ucand.p, s.ldk, s.dpad, CT, c->cnorm.p, m, c->gp_ctr.p + 8,      \
+                     c->cs_part.p, tr.cat.bcat, tr.cat.nkc, c0, c1)
+  switch (nc) {
+    case 1: UT_CONS_LAUNCH(1); break;
+    case 2: UT_CONS_LAUNCH(2); break;
+    case 3: UT_CONS_LAUNCH(3); break;
+    default: UT_CONS_LAUNCH(4); break;
+  }
+#undef UT_CONS_LAUNCH
+}
+
+// The constraint means of the m candidates whose K* operands (shape s) are in
+// c->ucand / c->cnorm / c->bcat, then k_cons_apply on their posterior mu / var
+// with the given outputs.
+static int cons_tail(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const double* mu, const double* var,
+                     double* p_out, double* mu_c_out, int64_t ldo, double* score) {
+  const int32_t nc = c->cs_nc;
+  const int64_t ldk = s.ldk;
+  UT_CHECK(c, s.npad % K_BM == 0 && s.dpad % 4 == 0 && ldk % K_BN == 0 && ldk >= m, UT_EINVAL, "gp_cons: bad padding");
+  int rc;
+  if ((rc = cons_stale(c, "gp_cons"))) return rc;
+  if ((rc = cons_operands(c))) return rc;
+  if (nc > 0) {
+    if ((rc = ensure(c, c->cs_part, (size_t)s.RT * nc * ldk))) return rc;
+    const KstarTrain tr = kstar_train(c, s.cat, c->bcat.p);
+    const bool has_cat = tr.cat.nkc > 0;
+    UT_CHECK(c, s.dpad >= 4 || has_cat, UT_EINVAL, "gp_cons: bad padding");
+    UT_CHECK(c, !has_cat || (tr.cat.acat && tr.cat.bcat), UT_EINVAL, "gp_cons: categorical operands missing");
+    const int32_t CT = (int32_t)(ldk / K_BN);
+    const int64_t items = (int64_t)s.RT * CT;
+    // CUs left to an in-flight fit, as launch_gemm_kstar leaves them
+    const bool fit_in_flight = c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
+    const int32_t spare = fit_in_flight ? KSTAR_SPARE_PER_XCD : 0;
+    int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
+    if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
+    UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
+    if (has_cat)
+      launch_cons_means<true>(c, nc, nb, tr, s, CT, m);
+    else
+      launch_cons_means<false>(c, nc, nb, tr, s, CT, m);
+    UT_LAUNCH_CHECK(c);
+  }
+  hipLaunchKernelGGL(k_cons_apply, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, s.RT, nc, c->cs_part.p, ldk,
+                     c->gp_sf2, c->cs_stats.p, mu, var, xi, p_out, mu_c_out, ldo, score);
+  UT_LAUNCH_CHECK(c);
+  mark(c, "cons");
+  return 0;
+}
+
+int cons_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const double* mu, const double* var,
+                double* score) {
+  return cons_tail(c, s, m, xi, mu, var, nullptr, nullptr, 0, score);
+}
+
+int gp_cons_prob_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
+                      double* mu_c_out) {
+  UT_CHECK(c, m >= 0 && ld >= m && (values != nullptr) != (features != nullptr) && (p_out || m == 0), UT_EINVAL,
+           "gp_cons_prob: bad arguments (exactly one of values and features, p_out required)");
+  UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_cons_prob: call ut_gp_fit first");
+  if (m == 0) return 0;
+  int rc;
+  if ((rc = cons_stale(c, "gp_cons_prob"))) return rc;
+  if (values) {
+    UT_CHECK(c, c->has_space, UT_ENOSPACE, "space not defined");
+    UT_CHECK(c, c->gp_d == c->space.n_feat, UT_EINVAL, "gp_cons_prob: GP feature width != space feature width");
+    if ((rc = gp_encode_scaled(c, values, ld, m))) return rc;
+    mark(c, "encode");
+  }
+  // the objective's posterior, for var(u): no score, so nothing is weighted in there
+  const int64_t ldk = gp_ldk(m);
+  if ((rc = ensure(c, c->cs_mu, (size_t)ldk))) return rc;
+  if ((rc = ensure(c, c->cs_var, (size_t)ldk))) return rc;
+  const ut_acq ei{UT_ACQ_EI, 0, 0.0, 0.0};
+  if ((rc = gp_score_impl(c, features, ld, m, &ei, nullptr, c->cs_mu.p, c->cs_var.p, nullptr))) return rc;
+  return cons_tail(c, score_shape(c, m, !features && c->cat_on && c->ucand_cat), m, 0.0, c->cs_mu.p, c->cs_var.p, p_out,
+                   mu_c_out, ld, nullptr);
+}
+
+int gp_cons_info_impl(ut_ctx* c, int32_t* n, int32_t* nc, int32_t* n_feasible, double* f_best_c) {
+  if (n) *n = c->cs_n;
+  if (nc) *nc = c->cs_nc;
+  if (n_feasible) *n_feasible = 0;
+  if (f_best_c) *f_best_c = std::nan("");
+  if (c->cs_nc == 0 || (!n_feasible && !f_best_c)) return 0;   // (the counts alone: no wait)
+  int rc;
+  if ((rc = gp_wait_fit(c))) return rc;
+  if ((rc = cons_stale(c, "gp_cons_info"))) return rc;
+  if ((rc = cons_operands(c))) return rc;
+  double st[2];
+  UT_HIP(c, hipMemcpyAsync(st, c->cs_stats.p + CS_INFO, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  UT_HIP(c, hipStreamSynchronize(c->stream));
+  if (n_feasible) *n_feasible = (int32_t)st[1];
+  if (f_best_c) *f_best_c = st[0];
+  return 0;
+}
+
+int gp_cons_set_impl(ut_ctx* c, const double* C, int32_t n, int32_t nc, const double* thr) {
+  UT_CHECK(c, nc >= 0 && nc <= UT_CONS_MAX, UT_EINVAL,
+           "gp_cons_set: nc = " + std::to_string(nc) + " is not in [0, " + std::to_string(UT_CONS_MAX) + "]");
+  if (nc == 0) {
+    // nothing is weighted from here on (the device arrays stay: a kernel may still be reading them)
+    c->cs_n = 0, c->cs_nc = 0, c->cs_fit = 0, c->cs_gen = 0;
+    return 0;
+  }
+  UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_cons_set: call ut_gp_fit first (the values belong to a fit)");
+  UT_CHECK(c, C != nullptr && thr != nullptr, UT_EINVAL, "gp_cons_set: C_host or threshold_host is NULL");
+  UT_CHECK(c, n == c->gp_n, UT_EINVAL,
+           "gp_cons_set: n = " + std::to_string(n) + ", the fit has " + std::to_string(c->gp_n) + " rows");
+  for (int32_t j = 0; j < nc; ++j)
+    UT_CHECK(c, !std::isnan(thr[j]), UT_EINVAL, "gp_cons_set: threshold " + std::to_string(j) + " is NaN");
+  for (size_t e = 0; e < (size_t)n * nc; ++e)
+    UT_CHECK(c, std::isfinite(C[e]), UT_EINVAL,
+             "gp_cons_set: row " + std::to_string(e / nc) + " has a non-finite value");
+  // Staged in pinned memory as the device layout, C^T [nc][npad] then the
+  // thresholds: cons_operands copies it on the scoring stream, after the fit,
+  // so this call neither touches the device nor waits for a staged or in-flight
+  // fit.  Only a copy of the previous values still queued is waited for.
+  const int32_t npad = gp_npad(n);
+  const size_t need = (size_t)UT_CONS_MAX * npad + UT_CONS_MAX;
+  if (!c->cs_ev) UT_HIP(c, hipEventCreateWithFlags(&c->cs_ev, hipEventDisableTiming));
+  UT_HIP(c, hipEventSynchronize(c->cs_ev));
+  if (c->cs_host_n < need) {
+    double* q = nullptr;
+    const size_t cap = need + need / 4;
+    UT_HIP(c, hipHostMalloc((void**)&q, sizeof(double) * cap, hipHostMallocDefault));
+    if (c->cs_host) (void)hipHostFree(c->cs_host);
+    c->cs_host = q;
+    c->cs_host_n = cap;
+  }
+  std::memset(c->cs_host, 0, sizeof(double) * ((size_t)nc * npad + UT_CONS_MAX));
+  for (int32_t r = 0; r < n; ++r)
+    for (int32_t j = 0; j < nc; ++j) c->cs_host[(size_t)j * npad + r] = C[(size_t)r * nc + j];
+  for (int32_t j = 0; j < nc; ++j) c->cs_host[(size_t)nc * npad + j] = thr[j];
+  c->cs_n = n, c->cs_nc = nc, c->cs_fit = c->fit_gen, c->cs_gen = 0;
+  return 0;
+}
+
+}  // namespace ut

@@ -890,6 +890,23 @@ int gp_ensure_linvt(ut_ctx* c) {
   return 0;
 }
 
+// the fit's two mat-vecs on another right-hand side (gp_cons.hip: a further
+// target on the same factor), on c->stream after the whole fit:
+// out = L^-1 v, and out = L^-T v through (L^-1)^T
+int launch_gp_lower_mv(ut_ctx* c, const double* v, double* out) {
+  const int32_t npad = c->gp_npad_fit;
+  hipLaunchKernelGGL(k_lower_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_Linv.p, npad, v, out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+int launch_gp_upper_mv(ut_ctx* c, const double* v, double* out) {
+  if (int rc = gp_ensure_linvt(c)) return rc;
+  const int32_t npad = c->gp_npad_fit;
+  hipLaunchKernelGGL(k_upper_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_LinvT.p, npad, v, out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 // Host work over the training rows in 8 threads when it is large (C4: 3,680
 // rows x 707 features, 20.8 MB to stage and every one-hot block to check:
 // ~2-3 ms on one thread, most of it with the device idle between rounds)

@@ -302,16 +302,35 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
 // recompute paths).  While failed rows are loaded (ut_gp_feas_set) the scores
 // the dense body wrote are weighted by the feasibility vote (gp_feas.hip) over
 // the K* operands it left in c->ucand / c->cnorm / c->bcat, categorical
-// exactly when its K* was.  With nothing loaded: no launch, no wait.
+// exactly when its K* was.  While constraint values are loaded
+// (ut_gp_cons_set) the constrained-EI tail (gp_cons.hip) rewrites the scores
+// first, from the posterior the dense body wrote (into context scratch where
+// the caller asked for no mu or var): dense, constraint tail, vote.  With
+// nothing loaded: no launch, no wait.
 int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
                   double* mu, double* var, double* score, hipEvent_t dup_ready) {
   const bool weigh = c->fs_n > 0 && score != nullptr;
+  const bool cons = c->cs_nc > 0 && score != nullptr;
   UT_CHECK(c, !(weigh && acq && acq->kind == UT_ACQ_UCB), UT_EUNSUPPORTED,
            "gp_score: failed rows are loaded (ut_gp_feas_set) and the feasibility weight is defined for EI only: "
            "a UCB score can be negative");
-  const int rc = gp_score_dense(c, feat, ld, m, acq, dup, mu, var, score, dup_ready);
-  if (rc || !weigh || m <= 0) return rc;
-  return feas_weight(c, score_shape(c, m, !feat && c->cat_on && c->ucand_cat), m, score);
+  UT_CHECK(c, !(cons && acq && acq->kind == UT_ACQ_UCB), UT_EUNSUPPORTED,
+           "gp_score: constraint values are loaded (ut_gp_cons_set) and the constraint weight is defined for EI "
+           "only: a UCB score can be negative");
+  int rc;
+  if (cons && m > 0) {
+    if ((rc = cons_stale(c, "gp_score"))) return rc;
+    const int64_t ldk = gp_ldk(m);
+    if (!mu && (rc = ensure(c, c->cs_mu, (size_t)ldk))) return rc;
+    if (!var && (rc = ensure(c, c->cs_var, (size_t)ldk))) return rc;
+    if (!mu) mu = c->cs_mu.p;
+    if (!var) var = c->cs_var.p;
+  }
+  rc = gp_score_dense(c, feat, ld, m, acq, dup, mu, var, score, dup_ready);
+  if (rc || !(weigh || cons) || m <= 0) return rc;
+  const ScoreShape s = score_shape(c, m, !feat && c->cat_on && c->ucand_cat);
+  if (cons && (rc = cons_weight(c, s, m, acq->xi, mu, var, score))) return rc;
+  return weigh ? feas_weight(c, s, m, score) : 0;
 }
 
 }  // namespace ut

@@ -455,6 +455,22 @@ struct ut_ctx {
   ut::DevBuf<double> fs_XsT_num, fs_norm_num;   // the numeric block [dpad_num][nfpad] and its norms (categorical fits)
   ut::DevBuf<int8_t> fs_acat;              // [cat_k / 128][nfpad][128] weighted one-hot codes
   ut::DevBuf<double> fs_part;              // [RT + RT_fail][ldk] column partials of sum k
+  // constrained EI (gp_cons.hip): the measured constraint values of the fit's
+  // rows, and their per-fit operands on the shared factor -- a per-fit cache
+  // like the failed rows' above, but the values themselves belong to one fit
+  double* cs_host = nullptr;               // pinned: C^T [cs_nc][cs_n], then the thresholds [cs_nc]
+  size_t cs_host_n = 0;
+  hipEvent_t cs_ev = nullptr;              // the last copy out of cs_host (recorded on the stream it ran on)
+  int32_t cs_n = 0, cs_nc = 0;             // cs_nc = 0: nothing loaded, no score is weighted
+  uint64_t cs_fit = 0;                     // the fit (fit_gen) the values were loaded for
+  uint64_t cs_gen = 0;                     // the fit the operands below were built from; 0 = stale
+  ut::DevBuf<double> cs_C;                 // [cs_nc][npad] raw values (then the thresholds [UT_CONS_MAX])
+  ut::DevBuf<double> cs_chat;              // [cs_nc][npad] standardised, zero on padding rows
+  ut::DevBuf<double> cs_beta;              // [cs_nc][npad] L^-1 chat_j
+  ut::DevBuf<double> cs_alpha;             // [cs_nc][npad] K^-1 chat_j, zero on padding rows
+  ut::DevBuf<double> cs_stats;             // [UT_CONS_MAX][4] ystats of column j, [3] = tau_j; then f_best_c, n_feasible
+  ut::DevBuf<double> cs_part;              // [RT][cs_nc][ldk] column partials of sum k alpha_j
+  ut::DevBuf<double> cs_mu, cs_var;        // [ldk] the posterior of a call that asked for neither
   int32_t dbg_fail_alloc = 0;             // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
@@ -594,6 +610,9 @@ int gp_fit_prefit(ut_ctx* c);
 int launch_gp_prep_train(ut_ctx* c, const double* X, int32_t n, int32_t npad, int32_t d, const double* inv_ell,
                          double* Xs, double* xnorm);
 int launch_gp_ystats(ut_ctx* c, const double* y, int32_t n, int32_t npad, double* ys, double* stats);
+// ... and its mat-vecs over the current factor: out = L^-1 v, out = L^-T v ([npad] each)
+int launch_gp_lower_mv(ut_ctx* c, const double* v, double* out);
+int launch_gp_upper_mv(ut_ctx* c, const double* v, double* out);
 // gp_lml.hip: the log marginal likelihood of the fit in place / at g hyperparameter points
 int gp_lml_impl(ut_ctx* c, double* lml_host);
 int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
@@ -611,6 +630,16 @@ int gp_feas_set_impl(ut_ctx* c, const double* X, int32_t nf, int32_t d, const ut
 int gp_feas_prob_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
                       double* s_ok_out, double* s_fail_out);
 int feas_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double* score);
+// gp_cons.hip: constrained EI.  cons_weight: score[i] = EI(mu_i, var_i; f_best_c, xi) P_i (P_i when no row is
+// feasible) for the m candidates whose K* operands (of shape s) are in c->ucand / c->cnorm / c->bcat and whose
+// posterior the dense body left in mu / var; cons_stale: UT_EINVAL when the loaded values belong to an earlier fit
+int gp_cons_set_impl(ut_ctx* c, const double* C, int32_t n, int32_t nc, const double* thr);
+int gp_cons_prob_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
+                      double* mu_c_out);
+int gp_cons_info_impl(ut_ctx* c, int32_t* n, int32_t* nc, int32_t* n_feasible, double* f_best_c);
+int cons_stale(ut_ctx* c, const char* who);
+int cons_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const double* mu, const double* var,
+                double* score);
 // gp_batch.hip: k picks from a shortlist of p, each conditioned on the picks before it
 int gp_select_batch_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
                          const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);

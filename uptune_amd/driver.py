@@ -51,13 +51,19 @@ class Configuration:
 
 class Result:
     """resultsdb/models.py Result: the measured objective of a configuration"""
-    __slots__ = ("id", "configuration", "time", "was_new_best", "requestor", "state", "tuning_run")
+    # accuracy, energy, size, confidence: the reference Result's other measured
+    # columns, None unless the evaluator reports them; nothing reads them
+    # unless asked (an objective below, SharedModel(constraints=...))
+    __slots__ = ("id", "configuration", "time", "was_new_best", "requestor", "state", "tuning_run", "accuracy",
+                 "energy", "size", "confidence")
 
     def __init__(self, configuration: Optional[Configuration] = None, time: float = float("inf"),
-                 requestor: str = "", state: str = "OK", id: int = -1, tuning_run=None):
+                 requestor: str = "", state: str = "OK", id: int = -1, tuning_run=None, accuracy=None):
         self.id = id
         self.configuration = configuration
         self.time = float(time)
+        self.accuracy = accuracy
+        self.energy = self.size = self.confidence = None
         self.was_new_best = None
         self.requestor = requestor
         self.state = state
@@ -103,6 +109,37 @@ class MinimizeTime:
 
     def limit_from_config(self, config):
         return None
+
+
+class ThresholdAccuracyMinimizeTime(MinimizeTime):
+    """objective.py:246-298: minimise time among the results whose accuracy
+    reaches the target; below it, the more accurate result is the better one.
+    Results compare by (-min(target, accuracy), time).  The surrogate's side of
+    it is SharedModel(constraints=[("accuracy", ">=", accuracy_target)])."""
+
+    def __init__(self, accuracy_target: float):
+        self.accuracy_target = float(accuracy_target)
+
+    def _key(self, r: Result):
+        acc = r.accuracy if r.accuracy is not None else float("-inf")
+        return (-min(self.accuracy_target, acc), r.time)
+
+    def lt(self, a: Result, b: Result) -> bool:
+        return self._key(a) < self._key(b)
+
+    def lte(self, a: Result, b: Result) -> bool:
+        return self._key(a) <= self._key(b)
+
+    def is_acceptable(self, result: Result) -> bool:
+        return result.accuracy is not None and result.accuracy >= self.accuracy_target
+
+
+def _measured(value):
+    """what an evaluator returned -> (time, {further named measurements}): a
+    float, or a mapping with "time" and e.g. "accuracy" """
+    if isinstance(value, dict):
+        return value["time"], {k: v for k, v in value.items() if k != "time"}
+    return value, {}
 
 
 class SearchDriver:
@@ -279,9 +316,17 @@ class SearchDriver:
         return [dr for dr in self._todo if dr.state == "REQUESTED"]
 
     def report(self, dr: DesiredResult, time: float, requestor: Optional[str] = None) -> Result:
-        """measurement_driver.report_result: the Result row of a request"""
+        """measurement_driver.report_result: the Result row of a request; time:
+        the objective, or a mapping with "time" and further named measurements,
+        which become attributes of the Result (accuracy, energy, size, confidence)"""
+        time, extra = _measured(time)
         r = Result(dr.configuration, time, requestor or dr.requestor, id=len(self._results),
                    tuning_run=self.tuning_run)
+        for name, v in extra.items():
+            if name not in ("accuracy", "energy", "size", "confidence"):
+                raise ValueError(f"report: a Result has no measurement {name!r} "
+                                 "(time, accuracy, energy, size, confidence)")
+            setattr(r, name, v)
         self._results.append(r)
         dr.result = r
         dr.state = "COMPLETE"

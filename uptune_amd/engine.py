@@ -493,6 +493,66 @@ class BatchEngine:
         return {"nf": int(nf.value), "prior": float(par.prior) if par.prior > 0.0 else None,
                 "strength": float(par.strength), "ell_scale": float(par.ell_scale), "power": float(par.power)}
 
+    # -- constrained EI -------------------------------------------------------
+    def gp_cons_set(self, C_values, thresholds):
+        """ut_gp_cons_set: load (replace) the measured constraint values
+        C [n][nc] of the current fit's rows, in the fit's row order, and the
+        thresholds [nc] of c_j <= t_j (a >= constraint: negate both).  While
+        loaded every dense EI score becomes EI(f_best over the feasible rows) *
+        prod_j P(c_j <= t_j) under GPs on the fit's own factor.  The values
+        belong to that fit: call again after every gp_fit (scoring raises
+        UT_EINVAL until then).  Does not wait for a fit in flight."""
+        Cv = np.ascontiguousarray(C_values, dtype=np.float64)
+        if Cv.ndim == 1:
+            Cv = Cv.reshape(-1, 1)
+        if Cv.ndim != 2:
+            raise ValueError("gp_cons_set: C must be [n][nc]")
+        thr = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+        n, nc = Cv.shape
+        if thr.shape != (nc,):
+            raise ValueError("gp_cons_set: one threshold per constraint column")
+        L.check(self.ctx, self.lib.ut_gp_cons_set(self.ctx, Cv.ctypes.data if nc else None, n, nc,
+                                                  thr.ctypes.data if nc else None), "ut_gp_cons_set")
+
+    def gp_cons_clear(self):
+        """no constraints: every call scores as it did before any were loaded"""
+        L.check(self.ctx, self.lib.ut_gp_cons_set(self.ctx, None, 0, 0, None), "ut_gp_cons_set")
+
+    def gp_cons_prob(self, values: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None,
+                     m: Optional[int] = None):
+        """ut_gp_cons_prob: (P [m], mu_c [nc][m]) of candidates given as raw values
+        [ncols][m] (the K* the fit scores with) or as features [F][m] (the dense
+        contraction): the probability that every constraint holds and the
+        standardised constraint means; stream-ordered, no host wait"""
+        if (values is None) == (features is None):
+            raise ValueError("gp_cons_prob: exactly one of values and features")
+        x = values if values is not None else features
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        m = x.shape[1] if m is None else int(m)
+        nc = self._cons_counts()[1]
+        ld = x.stride(0)
+        p = self._empty(m)
+        mu_c = torch.empty((max(nc, 1), ld), dtype=torch.float64, device=p.device)
+        L.check(self.ctx, self.lib.ut_gp_cons_prob(self.ctx, _ptr(x) if values is not None else None,
+                                                   _ptr(x) if values is None else None, ld, m, _ptr(p),
+                                                   _ptr(mu_c) if nc else None), "ut_gp_cons_prob")
+        return p, mu_c[:nc, :m]
+
+    def _cons_counts(self) -> Tuple[int, int]:
+        n, nc = C.c_int32(), C.c_int32()
+        L.check(self.ctx, self.lib.ut_gp_cons_info(self.ctx, C.byref(n), C.byref(nc), None, None), "ut_gp_cons_info")
+        return int(n.value), int(nc.value)
+
+    def gp_cons_info(self) -> Dict[str, Any]:
+        """what is loaded: {"n": rows, "nc": constraints (0: nothing), "n_feasible":
+        rows with every value within its threshold, "f_best_c": the smallest
+        standardised objective among them (NaN: none)}; waits for the fit"""
+        n, nc, nf, fb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        L.check(self.ctx, self.lib.ut_gp_cons_info(self.ctx, C.byref(n), C.byref(nc), C.byref(nf), C.byref(fb)),
+                "ut_gp_cons_info")
+        return {"n": int(n.value), "nc": int(nc.value), "n_feasible": int(nf.value), "f_best_c": float(fb.value)}
+
     def gp_topk_pruned(self, feat: torch.Tensor, k: int, m: Optional[int] = None, acq: Optional[L.Acq] = None,
                        dup: Optional[torch.Tensor] = None, cand_base: int = 0, bound_rows: int = 256):
         """ut_gp_topk_pruned: the top-k of the GP score, selection-exact, with the

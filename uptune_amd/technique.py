@@ -274,7 +274,7 @@ class SharedModel:
     def __init__(self, device: int = 0, seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4,
                  precision: int = 64, sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 1e-8,
                  engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40,
-                 feasibility: Union[bool, Dict[str, Any]] = False):
+                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -319,6 +319,17 @@ class SharedModel:
         # in arrival order, and every EI score is weighted by the kernel vote of
         # the training rows against them.  n_failed is how many are loaded.
         self.feasibility = _feas_setting(feasibility)
+        # constraints: [(attr, op, threshold), ...], op "<=" or ">=", at most 4:
+        # measurements every result carries as an attribute (accuracy, energy,
+        # size, ...; the reference's ThresholdAccuracyMinimizeTime, objective.py:246-298,
+        # is [("accuracy", ">=", target)]).  fit() gathers them for the training
+        # rows, in the fit's row order, and loads them after every gp_fit
+        # (engine.gp_cons_set; ">=" negated): EI then counts only improvement on
+        # the best FEASIBLE result, times the probability that every constraint
+        # holds under a GP on the fit's own factor.  A result whose attribute is
+        # missing, None or not finite is not usable (neither trained on nor
+        # failed).  n_feasible_ is the feasible training rows of the last fit.
+        self.constraints = _cons_setting(constraints)
         self._reset()
         self.slots: Dict[str, int] = {}
 
@@ -361,6 +372,11 @@ class SharedModel:
         self._fail_k = 0
         self._fail_sent = 0
         self.n_failed = 0
+        # constraints: the training rows' signed values (c <= t form), arrival
+        # order and the fit's order, beside _ya / _yf
+        self._Ca = np.zeros((0, 0))
+        self._Cf = np.zeros((0, 0))
+        self.n_feasible_ = None
 
     def __deepcopy__(self, memo):
         # techniques (and so their shared model) are deep-copied per driver
@@ -408,10 +424,22 @@ class SharedModel:
         """(re)fit the GP iff the driver's results changed since the last fit;
         the new training rows are encoded on the device (ut_encode_features)
         and the fit is enqueued without a host wait (ut_gp_fit_async)"""
+        cons = self.constraints
+
+        def measured(r):   # (constraints) every constrained measurement is there and finite
+            for attr, _, _ in cons:
+                v = getattr(r, attr, None)
+                if v is None or not math.isfinite(v):
+                    return False
+            return True
+
         def usable(r):
-            return getattr(r, "state", "OK") == "OK" and r.time is not None and math.isfinite(r.time)
+            return (getattr(r, "state", "OK") == "OK" and r.time is not None and math.isfinite(r.time)
+                    and (not cons or measured(r)))
 
         def failed(r):   # (feasibility) a result that is not usable but says where it failed
+            if cons and getattr(r, "state", "OK") == "OK" and r.time is not None and math.isfinite(r.time):
+                return False   # it ran: only a constrained measurement is missing
             return self.feasibility is not None and getattr(r, "configuration", None) is not None
 
         res = driver.results_query()
@@ -464,6 +492,10 @@ class SharedModel:
             self._Xa, self._ya = _rows_room(self._Xa, self._ya, k, n, self.engine.spec.n_features)
             self._Xa[k:n] = self._features(new)
             self._ya[k:n] = [float(r.time) for r in new]
+            if cons:
+                self._Ca = _cols_room(self._Ca, k, n, len(cons))
+                self._Ca[k:n] = [[(-1.0 if op == ">=" else 1.0) * float(getattr(r, attr)) for attr, op, _ in cons]
+                                 for r in new]
             self._n = n
             self._res_ids = list(ids)   # a copy: the scan list keeps growing
         # Row order.  The GP posterior does not depend on it, but the EI bound of
@@ -478,14 +510,20 @@ class SharedModel:
         n = self._n
         npad = -(-n // 128) * 128
         self._Xf, self._yf = _rows_room(self._Xf, self._yf, self._nf, n, self._Xa.shape[1])
+        if cons:
+            self._Cf = _cols_room(self._Cf, self._nf, n, len(cons))
         if self._nf == 0 or npad != self._perm_npad or self._nf > n:
             perm = np.argsort(self._ya[:n], kind="stable")
             self._Xf[:n] = self._Xa[perm]
             self._yf[:n] = self._ya[perm]
+            if cons:   # (re-gathered with the rows)
+                self._Cf[:n] = self._Ca[perm]
             self._perm_npad = npad
         else:
             self._Xf[self._nf:n] = self._Xa[self._nf:n]
             self._yf[self._nf:n] = self._ya[self._nf:n]
+            if cons:
+                self._Cf[self._nf:n] = self._Ca[self._nf:n]
         self._nf = n
         y = self._yf[:n]
         if self.y_transform == "rank":
@@ -505,6 +543,12 @@ class SharedModel:
                 self._ell_npad = npad
             ell = self.lengthscale_
         self.engine.gp_fit(self._Xf[:n], y, lengthscale=ell, wait=False, **self.hyper)
+        if cons:
+            # the values belong to this fit (the last one, after any of the
+            # lengthscale selection's own); no host wait in between
+            thr = [(-1.0 if op == ">=" else 1.0) * float(t) for _, op, t in cons]
+            self.engine.gp_cons_set(self._Cf[:n], thr)
+            self.n_feasible_ = int(np.all(self._Cf[:n] <= np.asarray(thr), axis=1).sum())
         self._fit_key = key
         self._fit_unverified = True
         self.fits += 1
@@ -654,6 +698,34 @@ def _feas_setting(feasibility) -> Optional[Dict[str, Any]]:
     return dict(feasibility)
 
 
+def _cons_setting(constraints) -> List[Any]:
+    """constraints= as a list of (attr, op, threshold); [] = off"""
+    if not constraints:
+        return []
+    out = []
+    for c in constraints:
+        if not isinstance(c, (tuple, list)) or len(c) != 3 or not isinstance(c[0], str) or c[1] not in ("<=", ">="):
+            raise ValueError("constraints: a list of (attribute, '<=' or '>=', threshold)")
+        t = float(c[2])
+        if math.isnan(t):
+            raise ValueError("constraints: a threshold is NaN")
+        out.append((c[0], c[1], t))
+    if len(out) > 4:
+        raise ValueError("constraints: at most 4 (UT_CONS_MAX)")
+    return out
+
+
+def _cols_room(Cm, used, n, nc):
+    """Cm with room for n rows of nc constraint values, the first `used` rows kept"""
+    if Cm.shape[0] >= n and Cm.shape[1] == nc:
+        return Cm
+    C2 = np.empty((max(n + n // 2, 256), nc))
+    used = min(used, n, Cm.shape[0])
+    if used and Cm.shape[1] == nc:
+        C2[:used] = Cm[:used]
+    return C2
+
+
 def _rows_room(X, y, used, n, d):
     """(X, y) with room for n rows of d features, the first `used` rows kept"""
     if X.shape[0] >= n and X.shape[1] == d:
@@ -683,8 +755,20 @@ class GpuBatchTechnique(SearchTechnique):
                  seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4, acq: str = "ei",
                  group=None, surrogate=None, shared: Optional[SharedModel] = None, engine_factory=None,
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
-                 feasibility: Union[bool, Dict[str, Any]] = False, *pargs, **kwargs):
+                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
+        # constraints (SharedModel): EI over the best feasible result times the
+        # probability that every measured constraint holds.  A shared model
+        # carries its own setting; the rule is defined for the dense EI score only
+        if shared.constraints if shared is not None else _cons_setting(constraints):
+            if int(prune_rows) > 0:
+                raise ValueError("constraints weight every candidate's score: not with prune_rows")
+            if int(diversify) > 0:
+                raise ValueError("constraints are not known to the per-pick acquisition: not with diversify")
+            if acq == "ucb":
+                raise ValueError("constraints multiply a score that is >= 0: EI, not acq='ucb'")
+            if surrogate is not None:
+                raise ValueError("constraints weight the GP's EI: not with a tree surrogate")
         # feasibility (SharedModel): EI times the estimated probability that the
         # candidate does not fail.  A shared model carries its own setting; the
         # weight is defined for the dense EI score only
@@ -726,7 +810,8 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    precision=precision,
                                                                    engine_factory=engine_factory,
                                                                    y_transform=y_transform,
-                                                                   feasibility=feasibility)
+                                                                   feasibility=feasibility,
+                                                                   constraints=constraints)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -1030,7 +1115,7 @@ def _shared_model(kw) -> SharedModel:
     return SharedModel(device=kw.get("device", 0), seed=kw.get("seed", 0), lengthscale=kw.get("lengthscale", 0.3),
                        min_train=kw.get("min_train", 4), precision=kw.get("precision", 64),
                        engine_factory=kw.pop("engine_factory", None), y_transform=kw.get("y_transform"),
-                       feasibility=kw.get("feasibility", False))
+                       feasibility=kw.get("feasibility", False), constraints=kw.get("constraints"))
 
 
 def pso_ga_de_bandit(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
