@@ -23,6 +23,7 @@ import numpy as np
 from scipy.linalg import solve_triangular
 from scipy.special import erfc
 
+from _ard_cases import ell_vector
 from oracle import gp as ogp
 
 NPAD = 128   # the device's row tile (gp_npad)
@@ -110,6 +111,9 @@ def restate(gp, U, acq, k, bound_rows, dup=None):
 #   flat_ei0 dense / dense (4948), flat_repeat dense / dense (2000), few_a_ucb dense / dense (10),
 #   few_b_ucb dense / dense (2000), few_c_ucb dense / dense (2000), few_a_ei dense / dense (10),
 #   few_b_ei dense / dense (2000), outlier 36 / 28 (28)
+# One lengthscale per feature (the ard_* cases): the f32 pass stays within 5 % of the restated set.
+#   ard_d64_ei 644 / 622 (622), ard_d64_ucb 290 / 279 (279), ard_d33_short_sf2_37 366 / 350 (350),
+#   ard_d33_late dense / dense (4672)
 OUTLIERS = (3, 500, 501, 777, 1024, 1500, 1998, 1999)
 
 
@@ -171,6 +175,13 @@ CASES = [
     _c("few_b_ei", "few_valid", 6, 640, 0.6, 2000, 16, 256, dup="all_but_10", recipe="worst", seed=28),
     # -- candidates the f32 pass cannot bound (rho >= 1/2)
     _c("outlier", "prunes", 16, 256, 0.1, 2000, 16, 128, dup="none", recipe="outlier", seed=30),
+    # -- one lengthscale per feature (tests/_ard_cases.py): the f32 pass widens each bound
+    # by roundings derived from the |x / ell| norms, which a scalar ell scales as one
+    _c("ard_d64_ei", "prunes", 64, 1000, ell_vector("spread", 64), 5000, 64, 256, seed=60),
+    _c("ard_d64_ucb", "prunes", 64, 1000, ell_vector("spread", 64), 5000, 64, 256, kind="ucb", kappa=2.0, seed=61),
+    _c("ard_d33_short_sf2_37", "prunes", 33, 600, ell_vector("one_short_last", 33, 2.0), 5000, 64, 256, sf2=37.0,
+       seed=62),
+    _c("ard_d33_late", "dense", 33, 600, ell_vector("spread", 33), 5000, 16, 128, sf2=37.0, recipe="late", seed=63),
 ]
 
 

@@ -32,6 +32,13 @@ def test_case_table_covers_the_edges():
     assert any(c["acq"]["xi"] == 0.1 for c in C) and any(c["sn2"] == 1e-2 * c["sf2"] for c in C)
     assert {"prunes", "dense", "flat", "few_valid"} == {c["regime"] for c in C}
     assert all(c["n"] <= 1024 and c["m"] <= 5000 for c in C)
+    # one lengthscale per feature: EI and UCB over ARD's whole box, a short last feature at
+    # sf2 = 37, and a case that falls back to dense
+    ard = [c for c in C if np.ndim(c["ell"]) == 1]
+    assert {("ei", 64), ("ucb", 64), ("ei", 33)} <= {(c["acq"]["kind"], c["d"]) for c in ard}
+    assert any(c["sf2"] == 37.0 and c["ell"][-1] == c["ell"].min() < c["ell"][0] for c in ard)
+    assert any(c["regime"] == "dense" for c in ard)
+    assert all(len(set(np.atleast_1d(c["ell"]).tolist())) > 1 for c in ard)
 
 
 def test_posterior_is_the_oracles(case):

@@ -1101,7 +1101,7 @@ static int score_round_de_impl(ut_ctx* c, const ut_de_params* de, const ut_acq* 
     // pruned: only candidates whose score bound reaches the threshold get the
     // full variance (the bound kernel joins the dup mask first)
     if ((rc = gp_topk_pruned_impl(c, nullptr, ld, m, acq, c->r_dup.p, cand_base, k, prune_rows, c->r_topk_idx.p,
-                                  c->r_topk_score.p, stats, c->ev_join, true)))
+                                  c->r_topk_score.p, stats, c->ev_join)))
       return rc;
   } else {
     // the variance GEMM joins the side stream's hash + dedup (they share the

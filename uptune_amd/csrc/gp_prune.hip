@@ -230,7 +230,7 @@ __global__ void k_fill(double* __restrict__ p, int64_t n, double v) {
 
 int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
                         int64_t cand_base, int32_t k, int32_t bound_rows, int64_t* out_idx, double* out_score,
-                        ut_prune_stats* stats, hipEvent_t dup_ready, bool feat_ours) {
+                        ut_prune_stats* stats, hipEvent_t dup_ready) {
   c->pr_m = 0;   // (set again once this call's bounds are enqueued)
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_topk_pruned: call ut_gp_fit first");
   UT_CHECK(c, c->gp_fit_prec == 64, UT_EINVAL, "gp_topk_pruned: needs an fp64 fit (ut_gp_set_precision 64)");
@@ -244,8 +244,9 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   // critical path, scripts/ab/r04ad_prep_early.sh)
   if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit_x, 0));
   // feat == nullptr: the K* operands are already in c->ucand / c->cnorm (/ c->bcat),
-  // from gp_encode_scaled (a scoring round's fused encode)
-  const bool cat = feat ? feat_ours && c->cat_on : c->ucand_cat;   // the categorical K* (ut's encoder)
+  // from gp_encode_scaled (a scoring round's fused encode, the only maker of the
+  // categorical K*'s operands); a feature matrix takes the dense contraction
+  const bool cat = !feat && c->ucand_cat;
   const ScoreShape s = score_shape(c, m, cat);
   const int32_t n = s.n, npad = s.npad, dpad = s.dpad, RT = s.RT;
   const int64_t ldk = s.ldk;
@@ -274,12 +275,8 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   if ((rc = ensure(c, c->pr_exact, (size_t)ldk))) return rc;
   // 1. K* with the mean in its epilogue, 2. the first R row tiles of L^-1 K*^T
   if (feat) {
-    if (cat) {
-      if ((rc = launch_prep_cand_cat(c, feat, ld, m, c->ucand.p, dpad, ldk, c->cnorm.p, c->bcat.p))) return rc;
-    } else if ((rc = launch_prep_cand(c, feat, ld, m, s.d, dpad, c->ucand.p, ldk, c->cnorm.p))) {
-      return rc;
-    }
-    c->ucand_cat = cat;
+    if ((rc = launch_prep_cand(c, feat, ld, m, s.d, dpad, c->ucand.p, ldk, c->cnorm.p))) return rc;
+    c->ucand_cat = false;
     mark(c, "prep");
   }
   if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));   // K* takes mu = k* . alpha

@@ -718,11 +718,9 @@ int topk_impl(ut_ctx* c, const double* score, const uint8_t* dup, int64_t m, int
               int64_t* out_idx, double* out_score);
 int topk_pairs_impl(ut_ctx* c, const double* score, const int64_t* idx, int64_t n, int32_t k, int64_t* out_idx,
                     double* out_score);
-// feat_ours: the features come from ut's own encoder (one-hot ENUM blocks),
-// so the categorical K* may read them as codes
 int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
                         int64_t cand_base, int32_t k, int32_t bound_rows, int64_t* out_idx, double* out_score,
-                        ut_prune_stats* stats, hipEvent_t dup_ready = nullptr, bool feat_ours = false);
+                        ut_prune_stats* stats, hipEvent_t dup_ready = nullptr);
 // prec: 64 (fp64 MFMA), 32 (fp32 MFMA), 16 (f16x3: fp16 hi/lo split operands,
 // three fp16 MFMA products, f32 accumulate -- see gp_gemm.hip), 8 (the fp64
 // tier on the int8 MFMA: six-digit planes, a per-candidate error bound and an
@@ -811,8 +809,7 @@ int launch_prep_cand(ut_ctx* c, const double* feat, int64_t ld, int64_t m, int32
                      int64_t ldu, double* cn);
 // categorical K*: the K* operands of the candidate side when the fit is in
 // categorical mode -- numeric features / ell (dpad_num rows), their norms, and
-// one-hot codes into c->bcat (from values, or from features made by ut's own
-// encoder); cat_dpad(c) rows
+// one-hot codes into c->bcat, from the values; cat_dpad(c) rows
 // the candidates' 128-byte code rows of one 256-candidate workgroup, written
 // coalesced: each thread sets its codes as bits in LDS (bits [256][stride],
 // stride = cat_k / 32 + 1 dwords), then every 128-column block is expanded to
@@ -843,8 +840,6 @@ __device__ inline void store_code_rows(const uint32_t* bits, int32_t stride, int
 inline size_t code_rows_lds(int32_t cat_k) { return sizeof(uint32_t) * 256 * ((cat_k / 32 + 1) + 33); }
 int launch_encode_scaled_cat(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* u, int32_t dpad,
                              int64_t ldu, double* cn, int8_t* bcat);
-int launch_prep_cand_cat(ut_ctx* c, const double* feat, int64_t ld, int64_t m, double* u, int32_t dpad, int64_t ldu,
-                         double* cn, int8_t* bcat);
 int launch_xs_t(ut_ctx* c, const double* Xs, int32_t npad, int32_t d, int32_t dpad, double* XsT);
 int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const void* kst, int64_t ldk, int32_t npad,
                     int64_t m, double* part, const double* beta, double* mpart);
