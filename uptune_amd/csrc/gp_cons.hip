@@ -20,10 +20,8 @@ namespace ut {
 
 constexpr int CS_INFO = 4 * UT_CONS_MAX;   // cs_stats[CS_INFO] = f_best_c, [CS_INFO + 1] = n_feasible
 
-// k_feas_sums' contraction (gp_feas.hip: k_gp_kstar<double>'s 128 x 128 items,
-// v_mfma_f64_16x16x4f64, the 2-stage glds ring, per-XCD tickets, two 256-thread
-// workgroups per CU, the int8 code stages first when CAT) over one row set, the
-// fit's training operand, with a weighted epilogue:
+// The K* contraction (gp_kstar_tile.h) over one row set, the fit's training
+// operand, with a weighted epilogue:
 //   1. the item's alpha_j[row0 .. row0 + 127], j < NC, go to LDS beside rowop;
 //   2. each element's k feeds NC accumulators s_j[col] += k alpha_j[row];
 //   3. no K* is stored;
@@ -33,14 +31,10 @@ constexpr int CS_INFO = 4 * UT_CONS_MAX;   // cs_stats[CS_INFO] = f_best_c, [CS_
 // is -1e300, the clamp at KSTAR_T_MIN is where 2^k' underflows to 0, and alpha
 // is 0 on padding rows.
 template <bool CAT, int NC>
-__global__ __launch_bounds__(K_NT, 2) void k_cons_means(const double* __restrict__ AT, const double* __restrict__ xnorm,
-                                                        const int8_t* __restrict__ acat, int32_t n, int32_t npad,
-                                                        int32_t RT, const double* __restrict__ alpha,
-                                                        const double* __restrict__ B, int64_t ldb, int32_t dpad,
+__global__ __launch_bounds__(K_NT, 2) void k_cons_means(KstarOperands<double> o, const double* __restrict__ xnorm,
+                                                        int32_t n, int32_t RT, const double* __restrict__ alpha,
                                                         int32_t CT, const double* __restrict__ cnorm, int64_t m,
-                                                        int32_t* __restrict__ ticket, double* __restrict__ part,
-                                                        const int8_t* __restrict__ bcat, int32_t nkc, double cat_c0,
-                                                        double cat_c1) {
+                                                        int32_t* __restrict__ ticket, double* __restrict__ part) {
   constexpr int MAIN = 2 * K_STAGE;
   static_assert(K_NT == 2 * K_BM && K_BM == K_BN, "one thread per epilogue operand (rowop)");
   static_assert(NC >= 1 && NC <= UT_CONS_MAX, "constraints per launch");
@@ -55,24 +49,14 @@ __global__ __launch_bounds__(K_NT, 2) void k_cons_means(const double* __restrict
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = w >> 1, wn = w & 1;
   const int32_t xcd = blockIdx.x & 7;
-  const int32_t nk_full = dpad / K_BK, k_rem = (dpad % K_BK) / 4;
-  const int32_t nk = nk_full + (k_rem ? 1 : 0);
-  const int32_t ncs = CAT ? nkc : 0;          // int8 stages first, then the fp64 ones
-  const int32_t ntot = ncs + nk;
-  // the i8 MFMA's row rho of A is tile row sigma(rho) (gp_gemm.hip "Categorical K*")
-  const int sig = ((lane0 & 15) >> 2) + 4 * (lane0 & 3);
-  const int arow = lane0 & 15;
+  const KstarRows rows = kstar_rows_f64(lane0);
 
   int32_t nxt = 0;
   if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
   for (;;) {
     if (t == 0) s_item = nxt;
     __syncthreads();
-    // the lane index afresh per item: the per-lane glds addresses derived from a loop
-    // invariant are hoisted to kernel entry and, beside the 128 accumulator registers,
-    // spilled around the item loop
-    int lane = lane0;
-    asm volatile("" : "+v"(lane));
+    const int lane = kstar_item_lane(lane0);
     const int32_t j = __builtin_amdgcn_readfirstlane(s_item);
     const int32_t ct = (j / RT) * 8 + xcd;
     if (ct >= CT) break;
@@ -81,96 +65,17 @@ __global__ __launch_bounds__(K_NT, 2) void k_cons_means(const double* __restrict
     const int64_t col0 = (int64_t)ct * K_BN;
     const int32_t row0 = rt * K_BM;
 
-    auto issue_stage = [&](int32_t s2, double* st) {
-      if (CAT && s2 < ncs)
-        kcat_issue(acat + ((int64_t)s2 * npad + row0) * 128, bcat + ((int64_t)s2 * ldb + col0) * 128, st, w, lane);
-      else
-        kstar_issue(AT, npad, B, ldb, row0, col0, (s2 - ncs) * K_BK, st, w, lane, dpad);
-    };
-    if (ntot > 0) issue_stage(0, lds);
     // one 1-KiB glds per epilogue operand: the norms, then alpha_j (rows < npad, columns < ldk are in range)
+    const KstarAcc<double> acc = kstar_contract<double, CAT>(o, rows, row0, col0, lds, w, lane, [=] {
 #pragma unroll
-    for (int op = 0; op < 2 + NC; ++op) {
-      if ((op & 3) != w) continue;
-      const double* src = op == 0 ? xnorm + row0 : op == 1 ? cnorm + col0 : alpha + (int64_t)(op - 2) * npad + row0;
-      __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + op * K_BM), 16,
-                                       0, 0);
-    }
-    kd4 acc[4][4];
-    if constexpr (CAT) {
-      ki4 iacc[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) iacc[i][jj] = (ki4){0, 0, 0, 0};
-      for (int32_t s2 = 0; s2 < ncs; ++s2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
-        asm volatile("" ::: "memory");
-        if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-        const int8_t* as8 = reinterpret_cast<const int8_t*>(lds + (s2 & 1) * K_STAGE);
-        const int8_t* bs8 = as8 + K_SA * 8;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int c16 = (lane >> 4) + 4 * kk;
-          ki4 af[4], bf[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int row = wm * 64 + i * 16 + sig;
-            af[i] = *reinterpret_cast<const ki4*>(as8 + row * 128 + ((c16 ^ (row & 7)) << 4));
-          }
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int col = wn * 64 + jj * 16 + (lane & 15);
-            bf[jj] = *reinterpret_cast<const ki4*>(bs8 + col * 128 + ((c16 ^ (col & 7)) << 4));
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              iacc[i][jj] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[jj], iacc[i][jj], 0, 0, 0);
-        }
+      for (int op = 0; op < 2 + NC; ++op) {
+        if ((op & 3) != w) continue;
+        const double* src =
+            op == 0 ? xnorm + row0 : op == 1 ? cnorm + col0 : alpha + (int64_t)(op - 2) * o.npad_a + row0;
+        __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + op * K_BM),
+                                         16, 0, 0);
       }
-      // c0 + c1 M, in t units (see the launch)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][jj][r] = __builtin_fma((double)iacc[i][jj][r], cat_c1, cat_c0);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (kd4){0.0, 0.0, 0.0, 0.0};
-    }
-    for (int32_t s2 = ncs; s2 < ntot; ++s2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
-      asm volatile("" ::: "memory");
-      if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-      const double* as = lds + (s2 & 1) * K_STAGE;
-      const int32_t kt = s2 - ncs;
-      const double* bs = as + K_SA;
-      // the last stage of a dpad that is not a multiple of 16 has k_rem k4 steps
-      const int nks = kt < nk_full ? K_BK / 4 : k_rem;
-#pragma unroll
-      for (int ks = 0; ks < K_BK / 4; ++ks) {
-        if (ks >= nks) break;
-        const int kr = ks * 4 + (lane >> 4);
-        double af[4], bf[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = as[kr * K_BM + wm * 64 + i * 16 + arow];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) bf[jj] = bs[kr * K_BN + wn * 64 + jj * 16 + (lane & 15)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj)
-            acc[i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[jj], acc[i][jj], 0, 0, 0);
-      }
-    }
-    if (ntot == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the epilogue operands
+    });
 
     __syncthreads();  // ring free: reuse as the column reduction buffer
     // the item's half-norms once per item: -1e300 for a padding row (>= n) or column
@@ -181,7 +86,6 @@ __global__ __launch_bounds__(K_NT, 2) void k_cons_means(const double* __restrict
       rowop[t] = in ? hv : -1e300;
     }
     __syncthreads();
-    double* red = lds;  // [NC][2][128]
     double hc[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -205,39 +109,18 @@ __global__ __launch_bounds__(K_NT, 2) void k_cons_means(const double* __restrict
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
           // t = (C - |x|^2/2 - |u|^2/2) * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]
-          const double x = __builtin_fmax(__builtin_fmin((acc[i][jj][r] + hx) + hc[jj], 0.0), KSTAR_T_MIN);
+          const double x = __builtin_fmax(__builtin_fmin((acc.a[i][jj][r] + hx) + hc[jj], 0.0), KSTAR_T_MIN);
           const double k = sf2_exp2t_nonpos(x, etab);
 #pragma unroll
           for (int q = 0; q < NC; ++q) s[q][jj] = __builtin_fma(k, a[q], s[q][jj]);
         }
       }
     }
-    // every sum is complete here: without this the optimizer sinks column group jj's
-    // whole chain of exps below the lane test of group jj - 1's reduction, every row's
-    // LDS operands stay live across all four, and the kernel spills
-#pragma unroll
-    for (int q = 0; q < NC; ++q)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) asm volatile("" : "+v"(s[q][jj]));
-#pragma unroll
-    for (int q = 0; q < NC; ++q)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int cl = wn * 64 + jj * 16 + (lane & 15);
-        double a = s[q][jj];
-        a += __shfl_xor(a, 16);
-        a += __shfl_xor(a, 32);
-        if ((lane >> 4) == 0) red[(q * 2 + wm) * K_BN + cl] = a;
-      }
-    __syncthreads();
-    if (t < K_BN) {
+    kstar_sums_done(s);
+    kstar_colsums<NC>(s, lds, lane, w, [=](int q, double v) {   // red [NC][2][128]
       const int64_t col = col0 + t;
-      if (col < m) {
-#pragma unroll
-        for (int q = 0; q < NC; ++q)
-          part[((int64_t)rt * NC + q) * ldb + col] = red[(q * 2) * K_BN + t] + red[(q * 2 + 1) * K_BN + t];
-      }
-    }
+      if (col < m) part[((int64_t)rt * NC + q) * o.ldb + col] = v;
+    });
   }
 }
 
@@ -359,11 +242,12 @@ template <bool CAT>
 static void launch_cons_means(ut_ctx* c, int32_t nc, int32_t nb, const KstarTrain& tr, const ScoreShape& s, int32_t CT,
                               int64_t m) {
   const double* xn = tr.xnorm ? tr.xnorm : c->gp_xnorm.p;
-  const double c0 = tr.cat.c0 * KSTAR_T_SCALE, c1 = tr.cat.c1 * KSTAR_T_SCALE;
-#define UT_CONS_LAUNCH(NC)                                                                                            \
-  hipLaunchKernelGGL((k_cons_means<CAT, NC>), dim3(nb), dim3(K_NT), 0, c->stream, tr.XsT, xn, tr.cat.acat, s.n,       \
-                     s.npad, s.RT, c->cs_alpha.p, c->ucand.p, s.ldk, s.dpad, CT, c->cnorm.p, m, c->gp_ctr.p + 8,      \
-                     c->cs_part.p, tr.cat.bcat, tr.cat.nkc, c0, c1)
+  const KstarOperands<double> o{tr.XsT,      c->ucand.p,  s.npad, s.ldk,      s.dpad,
+                                tr.cat.acat, tr.cat.bcat, s.npad, tr.cat.nkc, tr.cat.c0 * KSTAR_T_SCALE,
+                                tr.cat.c1 * KSTAR_T_SCALE};
+#define UT_CONS_LAUNCH(NC)                                                                                   \
+  hipLaunchKernelGGL((k_cons_means<CAT, NC>), dim3(nb), dim3(K_NT), 0, c->stream, o, xn, s.n, s.RT, c->cs_alpha.p, \
+                     CT, c->cnorm.p, m, c->gp_ctr.p + 8, c->cs_part.p)
   switch (nc) {
     case 1: UT_CONS_LAUNCH(1); break;
     case 2: UT_CONS_LAUNCH(2); break;
@@ -391,13 +275,8 @@ static int cons_tail(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const
     UT_CHECK(c, s.dpad >= 4 || has_cat, UT_EINVAL, "gp_cons: bad padding");
     UT_CHECK(c, !has_cat || (tr.cat.acat && tr.cat.bcat), UT_EINVAL, "gp_cons: categorical operands missing");
     const int32_t CT = (int32_t)(ldk / K_BN);
-    const int64_t items = (int64_t)s.RT * CT;
-    // CUs left to an in-flight fit, as launch_gemm_kstar leaves them
-    const bool fit_in_flight = c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
-    const int32_t spare = fit_in_flight ? KSTAR_SPARE_PER_XCD : 0;
-    int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
-    if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-    UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
+    int32_t nb;
+    if ((rc = kstar_grid(c, (int64_t)s.RT * CT, true, &nb))) return rc;
     if (has_cat)
       launch_cons_means<true>(c, nc, nb, tr, s, CT, m);
     else

@@ -4,7 +4,7 @@
 //   k(a, u) = exp(-1/2 |(a - u) / ell|^2 / s^2)
 //   S_ok(u) = sum_{r < n} k(x_r, u),  S_fail(u) = sum_{q < nf} k(f_q, u)
 //   p(u)    = (S_ok + lambda p0) / (S_ok + S_fail + lambda),   score <- score p^gamma
-// Both sums are the K* contraction of gp_gemm.hip with another epilogue, over
+// Both sums are the K* contraction (gp_kstar_tile.h) with another epilogue, over
 // operands the scoring call already has: the fit's scaled training operand
 // (Xs^T, or its numeric block and the one-hot codes), the candidates' U', norms
 // and codes in c->ucand / c->cnorm / c->bcat.  The failed rows get the same
@@ -24,9 +24,7 @@ struct FeasRows {
   int32_t n, npad;       // rows, padded to 128
 };
 
-// k_gp_kstar<double, MU>'s tiling (128 x 128 items, v_mfma_f64_16x16x4f64, the
-// 2-stage glds ring, per-XCD tickets, two 256-thread workgroups per CU, the int8
-// code stages first when CAT) with another epilogue:
+// The K* contraction (gp_kstar_tile.h) with another epilogue:
 //   1. one launch covers both row sets: item j of an XCD group is row tile
 //      j % (RT_ok + RT_fail) -- the training operand's tiles, then the failed one's;
 //   2. the exponent is scaled by 1 / s^2 (the categorical c0 + c1 M start with
@@ -39,13 +37,13 @@ struct FeasRows {
 // Padding rows (row >= n of their set) and columns (>= m) contribute exactly
 // 0: their half-norm is -1e300, and the clamp at KSTAR_T_MIN is where the
 // table's 2^k' underflows to 0.
+// o: what both row sets share (B, ldb, dpad, bcat, nkc, c0, c1); the item's set fills in the rest
 template <bool CAT>
 __global__ __launch_bounds__(K_NT, 2) void k_feas_sums(FeasRows ok, FeasRows fail, int32_t RT_ok, int32_t RT_fail,
-                                                       const double* __restrict__ B, int64_t ldb, int32_t dpad,
-                                                       int32_t CT, const double* __restrict__ cnorm, int64_t m,
+                                                       KstarOperands<double> o, int32_t CT,
+                                                       const double* __restrict__ cnorm, int64_t m,
                                                        int32_t* __restrict__ ticket, double* __restrict__ part,
-                                                       const int8_t* __restrict__ bcat, int32_t nkc, double cat_c0,
-                                                       double cat_c1, double inv_s2) {
+                                                       double inv_s2) {
   constexpr int MAIN = 2 * K_STAGE;
   static_assert(K_NT == 2 * K_BM && K_BM == K_BN, "one thread per epilogue operand (rowop)");
   // the ring, the exp table, the ticket slot, the item's |row|^2 and |u_c|^2
@@ -53,25 +51,20 @@ __global__ __launch_bounds__(K_NT, 2) void k_feas_sums(FeasRows ok, FeasRows fai
   double* etab = lds + MAIN;
   int32_t& s_item = *reinterpret_cast<int32_t*>(lds + MAIN + EXP_TAB);
   double* const rowop = lds + MAIN + EXP_TAB + 2;   // [norm 128][cnorm 128]
-  const int t = threadIdx.x, lane = t & 63;
+  const int t = threadIdx.x, lane0 = t & 63;
   if (t < EXP_TAB) etab[t] = exp2((double)t / EXP_TAB);   // published by the first ticket barrier
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = w >> 1, wn = w & 1;
   const int32_t xcd = blockIdx.x & 7;
-  const int32_t nk_full = dpad / K_BK, k_rem = (dpad % K_BK) / 4;
-  const int32_t nk = nk_full + (k_rem ? 1 : 0);
-  const int32_t ncs = CAT ? nkc : 0;          // int8 stages first, then the fp64 ones
-  const int32_t ntot = ncs + nk;
   const int32_t RTt = RT_ok + RT_fail;
-  // the i8 MFMA's row rho of A is tile row sigma(rho) (gp_gemm.hip "Categorical K*")
-  const int sig = ((lane & 15) >> 2) + 4 * (lane & 3);
-  const int arow = lane & 15;
+  const KstarRows rows = kstar_rows_f64(lane0);
 
   int32_t nxt = 0;
   if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
   for (;;) {
     if (t == 0) s_item = nxt;
     __syncthreads();
+    const int lane = kstar_item_lane(lane0);
     const int32_t j = __builtin_amdgcn_readfirstlane(s_item);   // uniform: the row set's pointers stay scalar
     const int32_t ct = (j / RTt) * 8 + xcd;
     if (ct >= CT) break;
@@ -80,99 +73,20 @@ __global__ __launch_bounds__(K_NT, 2) void k_feas_sums(FeasRows ok, FeasRows fai
     const bool second = rtt >= RT_ok;
     const FeasRows& R = second ? fail : ok;
     const int32_t rt = second ? rtt - RT_ok : rtt;
-    const double* AT = R.AT;
-    const int8_t* acat = R.acat;
-    const int32_t npad_a = R.npad, nrows = R.n;
+    const int32_t nrows = R.n;
     const int64_t col0 = (int64_t)ct * K_BN;
     const int32_t row0 = rt * K_BM;
+    KstarOperands<double> oi = o;
+    oi.AT = R.AT, oi.lda = R.npad, oi.acat = R.acat, oi.npad_a = R.npad;
+    const double* const norm = R.norm;
 
-    auto issue_stage = [&](int32_t s2, double* st) {
-      if (CAT && s2 < ncs)
-        kcat_issue(acat + ((int64_t)s2 * npad_a + row0) * 128, bcat + ((int64_t)s2 * ldb + col0) * 128, st, w, lane);
-      else
-        kstar_issue(AT, npad_a, B, ldb, row0, col0, (s2 - ncs) * K_BK, st, w, lane, dpad);
-    };
-    if (ntot > 0) issue_stage(0, lds);
-    if (w < 2) {  // one 1-KiB glds per operand (rows < npad, columns < ldk are in range)
-      const double* src = w == 0 ? R.norm + row0 : cnorm + col0;
-      __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + w * K_BM), 16,
-                                       0, 0);
-    }
-    kd4 acc[4][4];
-    if constexpr (CAT) {
-      ki4 iacc[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) iacc[i][jj] = (ki4){0, 0, 0, 0};
-      for (int32_t s2 = 0; s2 < ncs; ++s2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
-        asm volatile("" ::: "memory");
-        if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-        const int8_t* as8 = reinterpret_cast<const int8_t*>(lds + (s2 & 1) * K_STAGE);
-        const int8_t* bs8 = as8 + K_SA * 8;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int c16 = (lane >> 4) + 4 * kk;
-          ki4 af[4], bf[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int row = wm * 64 + i * 16 + sig;
-            af[i] = *reinterpret_cast<const ki4*>(as8 + row * 128 + ((c16 ^ (row & 7)) << 4));
-          }
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int col = wn * 64 + jj * 16 + (lane & 15);
-            bf[jj] = *reinterpret_cast<const ki4*>(bs8 + col * 128 + ((c16 ^ (col & 7)) << 4));
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              iacc[i][jj] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[jj], iacc[i][jj], 0, 0, 0);
-        }
+    const KstarAcc<double> acc = kstar_contract<double, CAT>(oi, rows, row0, col0, lds, w, lane, [=] {
+      if (w < 2) {  // one 1-KiB glds per operand (rows < npad, columns < ldk are in range)
+        const double* src = w == 0 ? norm + row0 : cnorm + col0;
+        __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + w * K_BM),
+                                         16, 0, 0);
       }
-      // c0 + c1 M, in t units (see the launch); scaled by 1 / s^2 in the epilogue with the rest
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][jj][r] = __builtin_fma((double)iacc[i][jj][r], cat_c1, cat_c0);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (kd4){0.0, 0.0, 0.0, 0.0};
-    }
-    for (int32_t s2 = ncs; s2 < ntot; ++s2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
-      asm volatile("" ::: "memory");
-      if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-      const double* as = lds + (s2 & 1) * K_STAGE;
-      const int32_t kt = s2 - ncs;
-      const double* bs = as + K_SA;
-      // the last stage of a dpad that is not a multiple of 16 has k_rem k4 steps
-      const int nks = kt < nk_full ? K_BK / 4 : k_rem;
-#pragma unroll
-      for (int ks = 0; ks < K_BK / 4; ++ks) {
-        if (ks >= nks) break;
-        const int kr = ks * 4 + (lane >> 4);
-        double af[4], bf[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = as[kr * K_BM + wm * 64 + i * 16 + arow];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) bf[jj] = bs[kr * K_BN + wn * 64 + jj * 16 + (lane & 15)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj)
-            acc[i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[jj], acc[i][jj], 0, 0, 0);
-      }
-    }
-    if (ntot == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the epilogue operands
+    });
 
     __syncthreads();  // ring free: reuse as the column reduction buffer
     // the item's half-norms once per item, not once per element (as k_gp_kstar<int8_t> keeps
@@ -184,14 +98,13 @@ __global__ __launch_bounds__(K_NT, 2) void k_feas_sums(FeasRows ok, FeasRows fai
       rowop[t] = in ? hv : -1e300;
     }
     __syncthreads();
-    double* red = lds;  // [2][128]
     double hc[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int cl = wn * 64 + jj * 16 + (lane & 15);
       hc[jj] = rowop[K_BM + cl];
     }
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    double s[1][4] = {{0.0, 0.0, 0.0, 0.0}};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -201,24 +114,16 @@ __global__ __launch_bounds__(K_NT, 2) void k_feas_sums(FeasRows ok, FeasRows fai
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
           // t = (C - |x|^2/2 - |u|^2/2) / s^2 * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]
-          const double x = __builtin_fmax(__builtin_fmin((acc[i][jj][r] * inv_s2 + hx) + hc[jj], 0.0), KSTAR_T_MIN);
-          s[jj] += sf2_exp2t_nonpos(x, etab);
+          const double x = __builtin_fmax(__builtin_fmin((acc.a[i][jj][r] * inv_s2 + hx) + hc[jj], 0.0), KSTAR_T_MIN);
+          s[0][jj] += sf2_exp2t_nonpos(x, etab);
         }
       }
     }
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int cl = wn * 64 + jj * 16 + (lane & 15);
-      double a = s[jj];
-      a += __shfl_xor(a, 16);
-      a += __shfl_xor(a, 32);
-      if ((lane >> 4) == 0) red[wm * K_BN + cl] = a;
-    }
-    __syncthreads();
-    if (t < K_BN) {
+    kstar_sums_done(s);
+    kstar_colsums<1>(s, lds, lane, w, [=](int, double v) {   // red [2][128]
       const int64_t col = col0 + t;
-      if (col < m) part[(int64_t)rtt * ldb + col] = red[t] + red[K_BN + t];
-    }
+      if (col < m) part[(int64_t)rtt * o.ldb + col] = v;
+    });
   }
 }
 
@@ -295,18 +200,16 @@ static int feas_vote(ut_ctx* c, const ScoreShape& s, int64_t m, double* p_out, d
   const FeasRows fail = s.cat ? FeasRows{c->fs_XsT_num.p, c->fs_norm_num.p, c->fs_acat.p, nf, nfpad}
                               : FeasRows{c->fs_XsT.p, c->fs_norm.p, nullptr, nf, nfpad};
   const int32_t CT = (int32_t)(ldk / K_BN);
-  const int64_t items = (int64_t)(RT_ok + RT_fail) * CT;
-  // CUs left to an in-flight fit, as launch_gemm_kstar leaves them
-  const bool fit_in_flight = c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
-  const int32_t spare = fit_in_flight ? KSTAR_SPARE_PER_XCD : 0;
-  int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
-  if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
+  int32_t nb;
+  if ((rc = kstar_grid(c, (int64_t)(RT_ok + RT_fail) * CT, true, &nb))) return rc;
   const ut_feas_params& fp = c->fs_par;
   const double inv_s2 = 1.0 / (fp.ell_scale * fp.ell_scale);
-  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
+  // (AT, lda, acat, npad_a: each item's row set)
+  const KstarOperands<double> o{nullptr, c->ucand.p,  0, ldk,        s.dpad,
+                                nullptr, tr.cat.bcat, 0, tr.cat.nkc, tr.cat.c0 * KSTAR_T_SCALE,
+                                tr.cat.c1 * KSTAR_T_SCALE};
   hipLaunchKernelGGL(has_cat ? k_feas_sums<true> : k_feas_sums<false>, dim3(nb), dim3(K_NT), 0, c->stream, ok, fail,
-                     RT_ok, RT_fail, c->ucand.p, ldk, s.dpad, CT, c->cnorm.p, m, c->gp_ctr.p + 8, c->fs_part.p,
-                     tr.cat.bcat, tr.cat.nkc, tr.cat.c0 * KSTAR_T_SCALE, tr.cat.c1 * KSTAR_T_SCALE, inv_s2);
+                     RT_ok, RT_fail, o, CT, c->cnorm.p, m, c->gp_ctr.p + 8, c->fs_part.p, inv_s2);
   UT_LAUNCH_CHECK(c);
   // the prior success rate: as given, or the share of successes among the rows in use
   const double p0 = fp.prior > 0.0 ? fp.prior : (double)s.n / (double)(s.n + nf);

@@ -55,7 +55,7 @@ __global__ void k_gp_prep_train(const double* __restrict__ X, int32_t n, int32_t
   xnorm[j] = s;
 }
 
-// categorical K* operands of the training rows (gp_gemm.hip "Categorical K*"):
+// categorical K* operands of the training rows (gp_kstar_tile.h "Categorical K*"):
 // XsT_num [dpad_num][npad] = the numeric features of Xs, transposed, and their
 // norms in feature order; one thread per row
 __global__ void k_gp_num_train(const double* __restrict__ Xs, int32_t npad, int32_t d,

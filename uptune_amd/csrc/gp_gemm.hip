@@ -9,8 +9,6 @@
 //
 //   fp64: v_mfma_f64_16x16x4_f64   (C/D: col = lane&15, row = (lane>>4) + 4r)
 //   fp32: v_mfma_f32_32x32x2_f32   (C/D: col = lane&31, row = (r&3) + 8(r>>2) + 4(lane>>5))
-#include <type_traits>
-
 #include "gp_kstar_tile.h"
 #include "ut_internal.h"
 
@@ -43,7 +41,7 @@ __global__ void k_to_f32(const double* __restrict__ src, float* __restrict__ dst
 //   A = Xs^T [dpad][npad] (rows >= d zero), B = U' [dpad][ldk] (rows >= d and
 //   columns >= m zero; written by k_gp_prep_cand)
 // ---------------------------------------------------------------------------
-// (K_NT, K_BM, K_BN, K_BK, KSTAR_SPARE_PER_XCD, kstar_issue, kcat_issue: gp_kstar_tile.h)
+// (the tile, the contraction and the column reduction: gp_kstar_tile.h)
 
 // f16x3 operand layout (k_gp_var_h3): 256-row x 32-k blocks of 16 KiB per
 // plane, pre-swizzled into the variance kernel's LDS image
@@ -58,65 +56,176 @@ __device__ __forceinline__ int64_t h3_blk_off(int64_t r, int32_t k, int32_t K) {
   const int rr = (int)(r & (H3_BM - 1)), c = (k & (H3_BK - 1)) >> 3;
   return ((r >> 8) * (K / H3_BK) + (k >> 5)) * H3_BLK + rr * H3_BK + ((c ^ ((rr >> 2) & 3)) << 3) + (k & 7);
 }
-  // CUs left to an in-flight GP fit (launch_gemm_kstar)
 
 // (sf2_exp2t_nonpos, EXP_TAB, KSTAR_T_MIN: ut_internal.h)
 
-// Categorical K* (CAT): ENUM and BOOL params are one-hot blocks of the GP
-// features (SURVEY.md §8 GP spec: Enum one-hot, Bool {0, 1}), and with one
-// lengthscale ell over those blocks a block contributes to |x - u|^2 exactly
-//   2 / ell^2 (ENUM) or 1 / ell^2 (BOOL)  when the two configurations' options
-//   differ, and 0 when they match.
-// So -|x - u|^2 / 2 over the categorical features is c0 + c1 * M with
-//   M = sum_j w_j [opt_x(j) == opt_u(j)],  w_j = 2 (ENUM), 1 (BOOL),
-//   c1 = 1 / (2 ell^2),  c0 = -c1 * sum_j w_j,
-// and M is the integer dot product of the training rows' weighted one-hot
-// codes with the candidates' 0/1 codes (ENUM: n_opt columns, BOOL: 2).  That
-// product runs on v_mfma_i32_16x16x64_i8 (exact int32, 4x the fp64 MFMA's
-// rate per instruction at 16x the K), ahead of the fp64 contraction over the
-// remaining ("numeric") features, and c0 + c1 M starts the fp64 accumulator.
-// At C3 (HPL-64: 79 of 119 features one-hot / 0-1) the fp64 contraction's K
-// drops 120 -> 40, at C4 (gcc: 552 of 707) 708 -> 156.
-//   int8 stage: 128 code columns x 128 rows (A) / candidates (B) = 16 KiB per
-//   operand, the fp64 stage's footprint; global layout [k / 128][row][128 B],
-//   LDS row r's 16-B chunk c at position c ^ (r & 7) (swizzled through the
-//   glds source address: the fragment reads are at most 2-way conflicted).
-//   The i8 MFMA's C/D rows are 4 (l >> 4) + q where the fp64 MFMA's are
-//   (l >> 4) + 4 q, so the A fragment of MFMA row rho loads tile row
-//   sigma(rho) = (rho >> 2) + 4 (rho & 3): iacc[i][jj][q] then sits where
-//   acc[i][jj][q] does (scripts/exp/i8_mfma_probe.hip checks both maps).
+// An item in its epilogue: where the lane sits, and the item's operands in LDS
+// (landed with the first K stage): rowop = [|x_r|^2 128][alpha_r 128][|u_c|^2 128],
+// hc = the lane's four columns' half-norms.  Padding rows / columns get a huge
+// negative half-norm, so their k* is exactly 0 without a select.
+// (every LDS read is unconditional and the padding goes in by a select:
+// a branch around a read splits the epilogue into basic blocks and each
+// read's wait then stalls the wave instead of overlapping other elements)
+struct KstarItem {
+  int lane, wm, wn;
+  int32_t row0, n;
+  int64_t col0;
+  const double *rowop, *etab;
+  double hc[4];
+};
+
+// t = (C - |x|^2/2 - |u|^2/2) * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]; k* = sf2 2^(t/256)
+__device__ __forceinline__ double kstar_elem(double c, double hx, double hc, const double* etab) {
+  return sf2_exp2t_nonpos(__builtin_fmax(__builtin_fmin((c + hx) + hc, 0.0), KSTAR_T_MIN), etab);
+}
+
+// fp64 / fp32: K*^T [row][ldk] as TS and, MU, the lane's partials of sum_r alpha_r k*_r
+// (s[0]) and sum_r k*_r^2 (s[1]).  STORE: this tile's rows are stored (pruned scoring
+// stores the bound rows only); decided once per item, so the element code has no branch
+template <typename TS, bool MU, bool STORE>
+__device__ __forceinline__ void kstar_epi_store(const KstarAcc<double>& acc, const KstarItem& it, TS* __restrict__ kst,
+                                                int64_t ldk, double (&s)[2][4]) {
+  const int lane = it.lane;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rl = it.wm * 64 + i * 16 + (lane >> 4) + 4 * r;
+      const int32_t row = it.row0 + rl;
+      const double hv = (-0.5 * KSTAR_T_SCALE) * it.rowop[rl];
+      const double hx = row < it.n ? hv : -1e300;
+      double al = 0.0;
+      if constexpr (MU) al = it.rowop[K_BM + rl];
+      TS* kp = kst + (int64_t)row * ldk + it.col0 + it.wn * 64 + (lane & 15);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const double ks = kstar_elem(acc.a[i][jj][r], hx, it.hc[jj], it.etab);
+        if constexpr (STORE) kp[jj * 16] = (TS)ks;
+        // (fused: the build contracts nothing by itself)
+        if constexpr (MU) s[0][jj] = __builtin_fma(al, ks, s[0][jj]);
+        if constexpr (MU) s[1][jj] = __builtin_fma(ks, ks, s[1][jj]);
+      }
+    }
+  }
+}
+
+// h3 (precision 16): ks = k* * kscale (the exp table carries the power-of-two
+// kscale) split into fp16 hi + lo, stored candidate-major in the blocked layout
+// of k_gp_var_h3 (K = npad; ldk % 256 == 0); the lo plane starts lo_off elements
+// after the hi plane.  Under kstar_rows_perm a lane's four accumulator rows are
+// four consecutive k of one candidate, 8 contiguous bytes per plane, stored
+// straight from registers (round 3 transposed the tile through LDS with 128
+// ds_write_b16 per lane per item).  The mean's alpha is divided by kscale: the
+// product is unchanged bit for bit.
+__device__ __forceinline__ void kstar_epi_h3(const KstarAcc<double>& acc, const KstarItem& it, double ikscale,
+                                             _Float16* __restrict__ kst, int64_t lo_off, int32_t npad,
+                                             double (&s)[2][4]) {
+  const int lane = it.lane;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    // the four rows of this lane in row group i: training rows 4 (l >> 4) + r
+    const int rl0 = it.wm * 64 + i * 16 + 4 * (lane >> 4);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int64_t col = it.col0 + it.wn * 64 + jj * 16 + (lane & 15);
+      uint32_t hpk[2] = {0u, 0u}, lpk[2] = {0u, 0u};   // the four rows' fp16 hi / lo, packed
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double hv = (-0.5 * KSTAR_T_SCALE) * it.rowop[rl0 + r];
+        const double hx = it.row0 + rl0 + r < it.n ? hv : -1e300;
+        const double ks = kstar_elem(acc.a[i][jj][r], hx, it.hc[jj], it.etab);
+        // ks = k* * kscale (< 2^15): hi = fp16(ks), lo = fp16 of the rest,
+        // the rest taken in f32 (exact there: hi is within 2^-11 of xf)
+        const float xf = (float)ks;
+        const _Float16 hi = (_Float16)xf;
+        const uint32_t hb = __builtin_bit_cast(uint16_t, hi);
+        const uint32_t lb = __builtin_bit_cast(uint16_t, (_Float16)(xf - (float)hi));
+        hpk[r >> 1] |= (r & 1) ? hb << 16 : hb;
+        lpk[r >> 1] |= (r & 1) ? lb << 16 : lb;
+        s[0][jj] += (it.rowop[K_BM + rl0 + r] * ikscale) * ks;
+      }
+      // rows 4 (l >> 4) .. + 3 of this column: 8 bytes per plane in the blocked layout
+      const int64_t o = h3_blk_off(col, it.row0 + rl0, npad);
+      *reinterpret_cast<uint2*>(kst + o) = make_uint2(hpk[0], hpk[1]);
+      *reinterpret_cast<uint2*>(kst + lo_off + o) = make_uint2(lpk[0], lpk[1]);
+    }
+  }
+}
+
+// precision 8: y = k* * kscale (<= 0.49) as six balanced digit planes of the
+// int8 variance contraction (gp_i8.hip), four consecutive training rows of a
+// candidate per dword (kstar_rows_perm, as h3); lo_off: bytes per plane.
+// it.rowop holds the rows' half-norms (padding: -1e300) and alpha / kscale.
+// Per column group: the four row groups' digit dwords (lane row R = l >> 4
+// holds rows 16 i + 4 R .. + 3 of its column for i = 0..3), transposed
+// over (R, i) by two v_permlane32_swap + two v_permlane16_swap per plane
+// so that lane row R holds rows 16 R .. 16 R + 15: one 16-byte store per
+// plane, the 32-byte pieces of 16 consecutive candidates written whole
+// (four 4-byte stores per plane left pieces half written per instruction:
+// 1.4x the planes' bytes reached HBM)
+__device__ __forceinline__ void kstar_epi_i8(const KstarAcc<double>& acc, const KstarItem& it, int8_t* __restrict__ kst,
+                                             int64_t ldk, int64_t lo_off, double (&s)[2][4]) {
+  const int lane = it.lane;
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+    const int64_t col = it.col0 + it.wn * 64 + jj * 16 + (lane & 15);
+    uint32_t pw[I8_S][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int rl0 = it.wm * 64 + i * 16 + 4 * (lane >> 4);   // this lane's training rows rl0 .. rl0 + 3
+      uint32_t lo[4], hi[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double ks = kstar_elem(acc.a[i][jj][r], it.rowop[rl0 + r], it.hc[jj], it.etab);   // y = k* 2^-eb
+        s[0][jj] = __builtin_fma(it.rowop[K_BM + rl0 + r], ks, s[0][jj]);
+        const uint64_t b = i8_biased(ks);
+        lo[r] = (uint32_t)b;
+        hi[r] = (uint32_t)(b >> 32);
+      }
+      uint32_t pl[I8_S];
+      i8_planes(lo, hi, pl);
+#pragma unroll
+      for (int p = 0; p < I8_S; ++p) pw[p][i] = pl[p];
+    }
+#pragma unroll
+    for (int p = 0; p < I8_S; ++p) {
+      const auto a0 = __builtin_amdgcn_permlane32_swap(pw[p][0], pw[p][2], false, false);
+      const auto a1 = __builtin_amdgcn_permlane32_swap(pw[p][1], pw[p][3], false, false);
+      const auto b0 = __builtin_amdgcn_permlane16_swap(a0[0], a1[0], false, false);
+      const auto b1 = __builtin_amdgcn_permlane16_swap(a0[1], a1[1], false, false);
+      pw[p][0] = b0[0];
+      pw[p][1] = b0[1];
+      pw[p][2] = b1[0];
+      pw[p][3] = b1[1];
+    }
+    int8_t* dst = kst + i8_off(col, it.row0 + it.wm * 64 + 16 * (lane >> 4), ldk);
+#pragma unroll
+    for (int p = 0; p < I8_S; ++p)
+      *reinterpret_cast<uint4*>(dst + p * lo_off) = make_uint4(pw[p][0], pw[p][1], pw[p][2], pw[p][3]);
+  }
+}
+
+// TS = double / float: K*^T stored as TS.  TS = _Float16 (h3) and int8_t
+// (precision 8): k* * kscale in the variance kernels' operand layouts
+// (kstar_epi_h3, kstar_epi_i8), the tile's training rows permuted over the MFMA
+// rows (kstar_rows_perm).
 // MU: also the column partial of the mean, sum_r alpha_r k*_r (fp32 scoring;
-// fp64 takes the mean from the variance epilogue instead)
+// fp64 takes the mean from the variance epilogue instead), and with part2 (fp64
+// / fp32 only; pruned scoring) the column partial sum_r k*_r^2 as well, for the
+// tail bound of the variance (gp_prune.hip k_prune_bound).
+// RTe <= RT: the items' row tiles (RT sizes the operands' layout).
 template <typename TS, bool MU, bool CAT>
-__global__ __launch_bounds__(K_NT, 2) void k_gp_kstar(const double* __restrict__ AT, int64_t lda,
-                                                      const double* __restrict__ B, int64_t ldb, int32_t dpad,
-                                                      int32_t RT, int32_t CT, const double* __restrict__ xnorm,
+__global__ __launch_bounds__(K_NT, 2) void k_gp_kstar(KstarOperands<double> o, int32_t RT, int32_t CT,
+                                                      const double* __restrict__ xnorm,
                                                       const double* __restrict__ cnorm,
                                                       const double* __restrict__ alpha, double sf2, int32_t n,
                                                       int64_t m, int32_t* __restrict__ ticket, TS* __restrict__ kst,
                                                       int64_t ldk, double* __restrict__ part, double kscale,
                                                       int64_t lo_off, int32_t store_rt, double* __restrict__ part2,
-                                                      const int8_t* __restrict__ acat, const int8_t* __restrict__ bcat,
-                                                      int32_t nkc, double cat_c0, double cat_c1, int32_t RTe) {
-  // part2 (MU, fp64/fp32 only; pruned scoring): the column partial sum_r k*_r^2
-  // as well, for the tail bound of the variance (gp_prune.hip k_prune_bound)
-  // TS = _Float16 (h3): k* * kscale split into fp16 hi + lo, stored candidate-major
-  // in the blocked layout of k_gp_var_h3 (K = npad = RT * K_BM; ldk % 256 == 0);
-  // the lo plane starts lo_off elements after the hi plane.  h3 permutes the
-  // tile's training rows over the MFMA rows, pi(rho) = 4 (rho & 3) + (rho >> 2),
-  // so that a lane's four accumulator rows (l >> 4) + 4 r hold the training
-  // rows 4 (l >> 4) + r: four consecutive k of one candidate, 8 contiguous bytes
-  // per plane in the blocked layout, stored straight from registers (round 3
-  // transposed the tile through LDS with 128 ds_write_b16 per lane per item)
-  constexpr bool H3 = sizeof(TS) == 2;
-  // TS = int8_t (precision 8): y = k* * kscale (<= 0.49) as six balanced digit
-  // planes of the int8 variance contraction (gp_i8.hip), four consecutive
-  // training rows of a candidate per dword: the row permutation of h3
-  constexpr bool I8 = sizeof(TS) == 1;
-  constexpr bool PERM = H3 || I8;
+                                                      int32_t RTe) {
+  constexpr bool H3 = sizeof(TS) == 2, I8 = sizeof(TS) == 1, PERM = H3 || I8;
   // one __shared__ object (see k_gp_var): the 2-stage ring, the exp table,
   // then the ticket slot
-  constexpr int RED_OFF = 0;
   constexpr int MAIN = 2 * K_STAGE;
   // + the item's epilogue operands, staged by glds with its first K stage:
   // |x_r|^2 and alpha_r of its 128 rows, |u_c|^2 of its 128 columns (read from
@@ -127,25 +236,13 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar(const double* __restrict__
   int32_t& s_item = *reinterpret_cast<int32_t*>(lds + MAIN + EXP_TAB);
   double* const rowop = lds + MAIN + EXP_TAB + 2;   // [xnorm 128][alpha 128][cnorm 128]
   const int t = threadIdx.x, lane = t & 63;
-  // h3: the table carries the split's power-of-two scale, so ks below is
-  // k* * kscale exactly (and the mean's alpha is divided by it: the product is
-  // unchanged bit for bit)
+  // h3 / precision 8: the table carries the power-of-two kscale, so ks is k* * kscale exactly
   if (t < EXP_TAB) etab[t] = (sf2 * exp2((double)t / EXP_TAB)) * (PERM ? kscale : 1.0);  // published by the first ticket barrier
   const double ikscale = 1.0 / kscale;   // a power of two
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = w >> 1, wn = w & 1;
   const int32_t xcd = blockIdx.x & 7;
-  // dpad % 4 == 0: whole 16-k stages, then one stage of k_rem k4 steps
-  const int32_t nk_full = dpad / K_BK, k_rem = (dpad % K_BK) / 4;
-  const int32_t nk = nk_full + (k_rem ? 1 : 0);
-  const int32_t ncs = CAT ? nkc : 0;          // int8 stages first, then the fp64 ones
-  const int32_t ntot = ncs + nk;
-  const int npad_a = RT * K_BM;
-  // the i8 MFMA's row rho of A is tile row sigma(rho) (see above); h3: the
-  // f64 MFMA's row rho is tile row pi(rho), and the i8 one's row rho itself
-  const int sig = PERM ? (lane & 15) : ((lane & 15) >> 2) + 4 * (lane & 3);
-  const int arow = PERM ? 4 * (lane & 3) + ((lane & 15) >> 2) : (lane & 15);
-  typedef kd4 d4;
+  const KstarRows rows = PERM ? kstar_rows_perm(lane) : kstar_rows_f64(lane);
+  const bool want2 = !PERM && MU && part2 != nullptr;
 
   // the next item's ticket is taken at the start of the current one, so its
   // atomic round trip overlaps the item's first K stage instead of sitting
@@ -156,267 +253,50 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar(const double* __restrict__
     if (t == 0) s_item = nxt;
     __syncthreads();
     const int32_t j = s_item;
-    // (RTe <= RT: the item's row tiles; RT sizes the operands' layout)
     const int32_t ct = (j / RTe) * 8 + xcd;
     if (ct >= CT) break;
     if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
     const int32_t rt = j % RTe;
-    const int64_t col0 = (int64_t)ct * K_BN;
-    const int32_t row0 = rt * K_BM;
+    KstarItem it{lane, w >> 1, w & 1, rt * K_BM, n, (int64_t)ct * K_BN, rowop, etab, {}};
 
-    auto issue_stage = [&](int32_t s2, double* st) {
-      if (CAT && s2 < ncs)
-        kcat_issue(acat + ((int64_t)s2 * npad_a + row0) * 128, bcat + ((int64_t)s2 * ldb + col0) * 128, st, w, lane);
-      else
-        kstar_issue(AT, lda, B, ldb, row0, col0, (s2 - ncs) * K_BK, st, w, lane, dpad);
-    };
-    if (ntot > 0) issue_stage(0, lds);
-    {  // one 1-KiB glds per operand (rows < npad, columns < ldk are in range)
-      const double* src = w == 0 ? xnorm + row0 : (w == 1 ? alpha + row0 : cnorm + col0);
+    const KstarAcc<double> acc = kstar_contract<double, CAT>(o, rows, it.row0, it.col0, lds, w, lane, [=] {
+      // one 1-KiB glds per operand (rows < npad, columns < ldk are in range)
+      const double* src = w == 0 ? xnorm + it.row0 : (w == 1 ? alpha + it.row0 : cnorm + it.col0);
       if (w < 3 && (MU || w != 1))
         __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + w * K_BM),
                                          16, 0, 0);
-    }
-    d4 acc[4][4];
-    if constexpr (CAT) {
-      // the int8 stages: M into int32 accumulators (dead once acc is started)
-      ki4 iacc[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) iacc[i][jj] = (ki4){0, 0, 0, 0};
-      for (int32_t s2 = 0; s2 < ncs; ++s2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
-        asm volatile("" ::: "memory");
-        if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-        const int8_t* as8 = reinterpret_cast<const int8_t*>(lds + (s2 & 1) * K_STAGE);
-        const int8_t* bs8 = as8 + K_SA * 8;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int c16 = (lane >> 4) + 4 * kk;
-          ki4 af[4], bf[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int row = wm * 64 + i * 16 + sig;
-            af[i] = *reinterpret_cast<const ki4*>(as8 + row * 128 + ((c16 ^ (row & 7)) << 4));
-          }
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int col = wn * 64 + jj * 16 + (lane & 15);
-            bf[jj] = *reinterpret_cast<const ki4*>(bs8 + col * 128 + ((c16 ^ (col & 7)) << 4));
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              iacc[i][jj] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[jj], iacc[i][jj], 0, 0, 0);
-        }
-      }
-      // c0 + c1 M starts the fp64 accumulators
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            acc[i][jj][r] = __builtin_fma((double)iacc[i][jj][r], cat_c1, cat_c0);   // (in t units: see the launch)
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (d4){0.0, 0.0, 0.0, 0.0};
-    }
-    for (int32_t s2 = ncs; s2 < ntot; ++s2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // stage s2 landed everywhere; stage s2-1 fully read
-      asm volatile("" ::: "memory");
-      if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-      const double* as = lds + (s2 & 1) * K_STAGE;
-      const int32_t kt = s2 - ncs;
-      const double* bs = as + K_SA;
-      // the last stage of a dpad that is not a multiple of 16 has k_rem k4 steps
-      const int nks = kt < nk_full ? K_BK / 4 : k_rem;
-#pragma unroll
-      for (int ks = 0; ks < K_BK / 4; ++ks) {
-        if (ks >= nks) break;
-        const int kr = ks * 4 + (lane >> 4);
-        double af[4], bf[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = as[kr * K_BM + wm * 64 + i * 16 + arow];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) bf[jj] = bs[kr * K_BN + wn * 64 + jj * 16 + (lane & 15)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj)
-            acc[i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[jj], acc[i][jj], 0, 0, 0);
-      }
-    }
-    if (ntot == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the epilogue operands
+    });
 
-    __syncthreads();  // ring free: reuse as the column reduction buffer (and the h3 image)
+    __syncthreads();  // ring free: reuse as the column reduction buffer
     if constexpr (I8) {
       // the rows' epilogue operands once per item instead of once per column
       // group: the half-norm with the padding rows' -1e300, alpha / kscale
       if (t < K_BM) {
         const double hv = (-0.5 * KSTAR_T_SCALE) * rowop[t];
-        rowop[t] = row0 + t < n ? hv : -1e300;
+        rowop[t] = it.row0 + t < n ? hv : -1e300;
         rowop[K_BM + t] = rowop[K_BM + t] * ikscale;
       }
       __syncthreads();
     }
-    double* red = lds + RED_OFF;  // [2][128]
-    // epilogue operands from the LDS copies (landed with the first K stage).
-    // Padding rows / columns get a huge negative half-norm, so their k* is
-    // exactly 0 without a select.
-    // (every LDS read is unconditional and the padding goes in by a select:
-    // a branch around a read splits the epilogue into basic blocks and each
-    // read's wait then stalls the wave instead of overlapping other elements)
-    double hc[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
-      const int cl = wn * 64 + jj * 16 + (lane & 15);
+      const int cl = it.wn * 64 + jj * 16 + (lane & 15);
       const double hv = (-0.5 * KSTAR_T_SCALE) * rowop[2 * K_BM + cl];
-      hc[jj] = col0 + cl < m ? hv : -1e300;
+      it.hc[jj] = it.col0 + cl < m ? hv : -1e300;
     }
-    const bool want2 = !PERM && MU && part2 != nullptr;
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-    if constexpr (H3) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        // the four rows of this lane in row group i: training rows 4 (l >> 4) + r
-        const int rl0 = wm * 64 + i * 16 + 4 * (lane >> 4);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const int64_t col = col0 + wn * 64 + jj * 16 + (lane & 15);
-          uint32_t hpk[2] = {0u, 0u}, lpk[2] = {0u, 0u};   // the four rows' fp16 hi / lo, packed
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const double hv = (-0.5 * KSTAR_T_SCALE) * rowop[rl0 + r];
-            const double hx = row0 + rl0 + r < n ? hv : -1e300;
-            const double x = __builtin_fmax(__builtin_fmin((acc[i][jj][r] + hx) + hc[jj], 0.0), KSTAR_T_MIN);
-            const double ks = sf2_exp2t_nonpos(x, etab);
-            // ks = k* * kscale (< 2^15): hi = fp16(ks), lo = fp16 of the rest,
-            // the rest taken in f32 (exact there: hi is within 2^-11 of xf)
-            const float xf = (float)ks;
-            const _Float16 hi = (_Float16)xf;
-            const uint32_t hb = __builtin_bit_cast(uint16_t, hi);
-            const uint32_t lb = __builtin_bit_cast(uint16_t, (_Float16)(xf - (float)hi));
-            hpk[r >> 1] |= (r & 1) ? hb << 16 : hb;
-            lpk[r >> 1] |= (r & 1) ? lb << 16 : lb;
-            s[jj] += (rowop[K_BM + rl0 + r] * ikscale) * ks;
-          }
-          // rows 4 (l >> 4) .. + 3 of this column: 8 bytes per plane in the blocked layout
-          const int64_t o = h3_blk_off(col, row0 + rl0, RT * K_BM);
-          *reinterpret_cast<uint2*>(kst + o) = make_uint2(hpk[0], hpk[1]);
-          *reinterpret_cast<uint2*>(kst + lo_off + o) = make_uint2(lpk[0], lpk[1]);
-        }
-      }
-    } else if constexpr (I8) {
-      // per column group: the four row groups' digit dwords (lane row R = l >> 4
-      // holds rows 16 i + 4 R .. + 3 of its column for i = 0..3), transposed
-      // over (R, i) by two v_permlane32_swap + two v_permlane16_swap per plane
-      // so that lane row R holds rows 16 R .. 16 R + 15: one 16-byte store per
-      // plane, the 32-byte pieces of 16 consecutive candidates written whole
-      // (four 4-byte stores per plane left pieces half written per instruction:
-      // 1.4x the planes' bytes reached HBM)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int64_t col = col0 + wn * 64 + jj * 16 + (lane & 15);
-        uint32_t pw[I8_S][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int rl0 = wm * 64 + i * 16 + 4 * (lane >> 4);   // this lane's training rows rl0 .. rl0 + 3
-          uint32_t lo[4], hi[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const double x = __builtin_fmax(__builtin_fmin((acc[i][jj][r] + rowop[rl0 + r]) + hc[jj], 0.0), KSTAR_T_MIN);
-            const double ks = sf2_exp2t_nonpos(x, etab);   // y = k* 2^-eb
-            s[jj] = __builtin_fma(rowop[K_BM + rl0 + r], ks, s[jj]);
-            const uint64_t b = i8_biased(ks);
-            lo[r] = (uint32_t)b;
-            hi[r] = (uint32_t)(b >> 32);
-          }
-          uint32_t pl[I8_S];
-          i8_planes(lo, hi, pl);
-#pragma unroll
-          for (int p = 0; p < I8_S; ++p) pw[p][i] = pl[p];
-        }
-#pragma unroll
-        for (int p = 0; p < I8_S; ++p) {
-          const auto a0 = __builtin_amdgcn_permlane32_swap(pw[p][0], pw[p][2], false, false);
-          const auto a1 = __builtin_amdgcn_permlane32_swap(pw[p][1], pw[p][3], false, false);
-          const auto b0 = __builtin_amdgcn_permlane16_swap(a0[0], a1[0], false, false);
-          const auto b1 = __builtin_amdgcn_permlane16_swap(a0[1], a1[1], false, false);
-          pw[p][0] = b0[0];
-          pw[p][1] = b0[1];
-          pw[p][2] = b1[0];
-          pw[p][3] = b1[1];
-        }
-        // lo_off: bytes per plane
-        int8_t* dst = reinterpret_cast<int8_t*>(kst) + i8_off(col, row0 + wm * 64 + 16 * (lane >> 4), ldk);
-#pragma unroll
-        for (int p = 0; p < I8_S; ++p)
-          *reinterpret_cast<uint4*>(dst + p * lo_off) = make_uint4(pw[p][0], pw[p][1], pw[p][2], pw[p][3]);
-      }
-    } else {
-      // STORE: this tile's rows are stored (pruned scoring stores the bound
-      // rows only); decided once per item, so the element code has no branch
-      auto epi = [&](auto store_c) {
-        constexpr bool STORE = decltype(store_c)::value;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int rl = wm * 64 + i * 16 + (lane >> 4) + 4 * r;
-            const int32_t row = row0 + rl;
-            const double hv = (-0.5 * KSTAR_T_SCALE) * rowop[rl];
-            const double hx = row < n ? hv : -1e300;
-            double al = 0.0;
-            if constexpr (MU) al = rowop[K_BM + rl];
-            TS* kp = kst + (int64_t)row * ldk + col0 + wn * 64 + (lane & 15);
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-              // t = (C - |x|^2/2 - |u|^2/2) * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]
-              const double x = __builtin_fmax(__builtin_fmin((acc[i][jj][r] + hx) + hc[jj], 0.0), KSTAR_T_MIN);
-              const double ks = sf2_exp2t_nonpos(x, etab);
-              if constexpr (STORE) kp[jj * 16] = (TS)ks;
-              // (fused: the build contracts nothing by itself)
-              if constexpr (MU) s[jj] = __builtin_fma(al, ks, s[jj]);
-              if constexpr (MU) s2[jj] = __builtin_fma(ks, ks, s2[jj]);
-            }
-          }
-        }
+    double s[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    if constexpr (H3) kstar_epi_h3(acc, it, ikscale, kst, lo_off, RT * K_BM, s);
+    else if constexpr (I8) kstar_epi_i8(acc, it, kst, ldk, lo_off, s);
+    else if (rt < store_rt) kstar_epi_store<TS, MU, true>(acc, it, kst, ldk, s);
+    else kstar_epi_store<TS, MU, false>(acc, it, kst, ldk, s);
+    if constexpr (MU) {
+      auto out = [=](int q, double v) {
+        const int64_t col = it.col0 + t;
+        if (col < m) (q ? part2 : part)[(int64_t)rt * ldk + col] = v;
       };
-      if (rt < store_rt) epi(std::integral_constant<bool, true>{});
-      else epi(std::integral_constant<bool, false>{});
-    }
-    if constexpr (MU) {
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int cl = wn * 64 + jj * 16 + (lane & 15);
-        double a = s[jj];
-        a += __shfl_xor(a, 16);
-        a += __shfl_xor(a, 32);
-        if ((lane >> 4) == 0) red[wm * K_BN + cl] = a;
-        if (want2) {
-          double b = s2[jj];
-          b += __shfl_xor(b, 16);
-          b += __shfl_xor(b, 32);
-          if ((lane >> 4) == 0) red[2 * K_BN + wm * K_BN + cl] = b;
-        }
-      }
-    }
-    if constexpr (MU) __syncthreads();
-    if constexpr (MU) {
-      if (t < K_BN) {
-        const int64_t col = col0 + t;
-        if (col < m) {
-          part[(int64_t)rt * ldk + col] = red[t] + red[K_BN + t];
-          if (want2) part2[(int64_t)rt * ldk + col] = red[2 * K_BN + t] + red[3 * K_BN + t];
-        }
-      }
+      if constexpr (H3) kstar_sums_done(s);   // (h3 alone spills without it)
+      if (want2) kstar_colsums<2>(s, lds, lane, w, out);   // red [2][2][128]
+      else kstar_colsums<1>(s, lds, lane, w, out);
     }
   }
 }
@@ -437,37 +317,14 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar(const double* __restrict__
 // (2 |c0| + |x|^2 + |u|^2) (units of t; K the contraction length: products
 // and sums rounded to f32, hx / hc rounded once, two adds).
 // ---------------------------------------------------------------------------
-typedef float kf4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void kstar_issue_f32(const float* __restrict__ AT, int64_t lda, const float* __restrict__ B,
-                                                int64_t ldb, int32_t row0, int64_t col0, int32_t k0, float* st, int w,
-                                                int lane, int32_t dpad) {
-  // 8 KiB of A and 8 KiB of B per 16-k stage: wave w loads k rows 4w .. 4w+3,
-  // two 512-B rows per 1-KiB glds (lanes 0-31 row q, 32-63 row q + 1)
-  if (k0 + 4 * w >= dpad) return;
-  const int rr = lane >> 5, cc = (lane & 31) * 4;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int q = 4 * w + 2 * u;
-    __builtin_amdgcn_global_load_lds(AT + (int64_t)(k0 + q + rr) * lda + row0 + cc,
-                                     (__attribute__((address_space(3))) void*)(st + q * 128), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(B + (int64_t)(k0 + q + rr) * ldb + col0 + cc,
-                                     (__attribute__((address_space(3))) void*)(st + K_SA + q * 128), 16, 0, 0);
-  }
-}
-
 template <bool CAT>
-__global__ __launch_bounds__(K_NT, 2) void k_gp_kstar_f32c(const float* __restrict__ AT, int64_t lda,
-                                                           const float* __restrict__ B, int64_t ldb, int32_t dpad,
-                                                           int32_t rt0, int32_t RT, int32_t CT,
+__global__ __launch_bounds__(K_NT, 2) void k_gp_kstar_f32c(KstarOperands<float> o, int32_t rt0, int32_t RT, int32_t CT,
                                                            const double* __restrict__ xnorm,
                                                            const double* __restrict__ cnorm,
                                                            const double* __restrict__ alpha, double sf2, int32_t n,
                                                            int64_t m, int32_t* __restrict__ ticket, int64_t ldk,
                                                            double* __restrict__ part, double* __restrict__ part2,
-                                                           double* __restrict__ part3, const int8_t* __restrict__ acat,
-                                                           const int8_t* __restrict__ bcat, int32_t nkc, float cat_c0,
-                                                           float cat_c1) {
+                                                           double* __restrict__ part3) {
   // the ring (sized as k_gp_kstar's: the int8 stages fill it, the f32 ones half),
   // the ticket slot, the item's row / column operands
   __shared__ __attribute__((aligned(16))) double lds[2 * K_STAGE + 2 + 3 * K_BM];
@@ -477,12 +334,8 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar_f32c(const float* __restri
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = w >> 1, wn = w & 1;
   const int32_t xcd = blockIdx.x & 7;
-  const int32_t nk_full = dpad / K_BK, k_rem = (dpad % K_BK) / 4;
-  const int32_t nk = nk_full + (k_rem ? 1 : 0);
-  const int32_t ncs = CAT ? nkc : 0;
-  const int32_t ntot = ncs + nk;
-  const int npad_a = RT * K_BM;
   const int32_t RTe = RT - rt0;
+  const KstarRows rows = kstar_rows_f32(lane);
   int32_t nxt = 0;
   if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
   for (;;) {
@@ -495,94 +348,13 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar_f32c(const float* __restri
     const int32_t rt = rt0 + j % RTe;
     const int64_t col0 = (int64_t)ct * K_BN;
     const int32_t row0 = rt * K_BM;
-    auto issue_stage = [&](int32_t s2, double* st) {
-      if (CAT && s2 < ncs)
-        kcat_issue(acat + ((int64_t)s2 * npad_a + row0) * 128, bcat + ((int64_t)s2 * ldb + col0) * 128, st, w, lane);
-      else
-        kstar_issue_f32(AT, lda, B, ldb, row0, col0, (s2 - ncs) * K_BK, reinterpret_cast<float*>(st), w, lane, dpad);
-    };
-    if (ntot > 0) issue_stage(0, lds);
-    {
+    const KstarAcc<float> acc = kstar_contract<float, CAT>(o, rows, row0, col0, lds, w, lane, [=] {
       const double* src = w == 0 ? xnorm + row0 : (w == 1 ? alpha + row0 : cnorm + col0);
       if (w < 3)
         __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + w * K_BM),
                                          16, 0, 0);
-    }
-    kf4 acc[4][4];
-    if constexpr (CAT) {
-      ki4 iacc[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) iacc[i][jj] = (ki4){0, 0, 0, 0};
-      for (int32_t s2 = 0; s2 < ncs; ++s2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-        const int8_t* as8 = reinterpret_cast<const int8_t*>(lds + (s2 & 1) * K_STAGE);
-        const int8_t* bs8 = as8 + K_SA * 8;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int c16 = (lane >> 4) + 4 * kk;
-          ki4 af[4], bf[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int row = wm * 64 + i * 16 + (lane & 15);   // the f32 MFMA's rows are the i8 one's
-            af[i] = *reinterpret_cast<const ki4*>(as8 + row * 128 + ((c16 ^ (row & 7)) << 4));
-          }
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int col = wn * 64 + jj * 16 + (lane & 15);
-            bf[jj] = *reinterpret_cast<const ki4*>(bs8 + col * 128 + ((c16 ^ (col & 7)) << 4));
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              iacc[i][jj] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[i], bf[jj], iacc[i][jj], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][jj][r] = __builtin_fmaf((float)iacc[i][jj][r], cat_c1, cat_c0);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (kf4){0.f, 0.f, 0.f, 0.f};
-    }
-    for (int32_t s2 = ncs; s2 < ntot; ++s2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (s2 + 1 < ntot) issue_stage(s2 + 1, lds + ((s2 + 1) & 1) * K_STAGE);
-      const float* as = reinterpret_cast<const float*>(lds + (s2 & 1) * K_STAGE);
-      const float* bs = as + K_SA;
-      const int32_t kt = s2 - ncs;
-      const int nks = kt < nk_full ? K_BK / 4 : k_rem;
-#pragma unroll
-      for (int ks = 0; ks < K_BK / 4; ++ks) {
-        if (ks >= nks) break;
-        const int kr = ks * 4 + (lane >> 4);
-        float af[4], bf[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = as[kr * K_BM + wm * 64 + i * 16 + (lane & 15)];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) bf[jj] = bs[kr * K_BN + wn * 64 + jj * 16 + (lane & 15)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj)
-            acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bf[jj], acc[i][jj], 0, 0, 0);
-      }
-    }
-    if (ntot == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    });
     __syncthreads();   // ring free: the column reduction buffer
-    double* red = lds;   // [6][128]
     float hc[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -600,39 +372,41 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar_f32c(const float* __restri
         const float aa = __builtin_fabsf(al);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-          const float kf = __builtin_amdgcn_exp2f(((acc[i][jj][r] + hx) + hc[jj]) * 0x1p-8f);
+          const float kf = __builtin_amdgcn_exp2f(((acc.a[i][jj][r] + hx) + hc[jj]) * 0x1p-8f);
           fs[jj] = __builtin_fmaf(al, kf, fs[jj]);
           fa[jj] = __builtin_fmaf(aa, kf, fa[jj]);
           f2[jj] = __builtin_fmaf(kf, kf, f2[jj]);
         }
       }
     }
+    double s[3][4];   // k* alpha, k*^2, k* |alpha|
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int cl = wn * 64 + jj * 16 + (lane & 15);
-      double a = fs[jj], b = f2[jj], q = fa[jj];
-      a += __shfl_xor(a, 16);
-      a += __shfl_xor(a, 32);
-      b += __shfl_xor(b, 16);
-      b += __shfl_xor(b, 32);
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      if ((lane >> 4) == 0) {
-        red[wm * K_BN + cl] = a;
-        red[2 * K_BN + wm * K_BN + cl] = b;
-        red[4 * K_BN + wm * K_BN + cl] = q;
-      }
-    }
-    __syncthreads();
-    if (t < K_BN) {
+    for (int jj = 0; jj < 4; ++jj) s[0][jj] = fs[jj], s[1][jj] = f2[jj], s[2][jj] = fa[jj];
+    kstar_colsums<3>(s, lds, lane, w, [=](int q, double v) {   // red [3][2][128]
       const int64_t col = col0 + t;
-      if (col < m) {
-        part[(int64_t)rt * ldk + col] = red[t] + red[K_BN + t];
-        part2[(int64_t)rt * ldk + col] = (red[2 * K_BN + t] + red[3 * K_BN + t]) * (sf2 * sf2);
-        part3[(int64_t)rt * ldk + col] = red[4 * K_BN + t] + red[5 * K_BN + t];
-      }
-    }
+      if (col < m) (q == 0 ? part : q == 1 ? part2 : part3)[(int64_t)rt * ldk + col] = q == 1 ? v * (sf2 * sf2) : v;
+    });
   }
+}
+
+// The persistent grid of a K* launch.  Two K* workgroups fill a CU's VGPRs, so
+// a full persistent grid leaves no slot for the GP fit running beside it on the
+// fit stream, and the fit's serial chain of small kernels then stalls the
+// variance GEMM that waits for it.  While a fit is in flight, 2 CUs per XCD are
+// left to it (C2: the round with a refit 30.2 -> 29.6 ms, the same as without a
+// refit; K* alone 3% slower).
+constexpr int KSTAR_SPARE_PER_XCD = 2;
+
+int32_t kstar_blocks(ut_ctx* c, int64_t items, bool leave_for_fit) {
+  const bool fit_in_flight = leave_for_fit && c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
+  const int32_t nb = 2 * (c->n_cu / 8 - (fit_in_flight ? KSTAR_SPARE_PER_XCD : 0)) * 8;
+  return items < nb ? (int32_t)(((items + 7) / 8) * 8) : nb;
+}
+
+int kstar_grid(ut_ctx* c, int64_t items, bool leave_for_fit, int32_t* nb) {
+  *nb = kstar_blocks(c, items, leave_for_fit);
+  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
+  return 0;
 }
 
 int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, int32_t npad, const KstarArgs& a) {
@@ -646,15 +420,15 @@ int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, 
   const int32_t RT = npad / K_BM;
   UT_CHECK(c, a.rt0 >= 0 && a.rt0 < RT, UT_EINVAL, "gemm_kstar_f32c: bad first row tile");
   const int32_t CT = (int32_t)(ldk / K_BN);
-  const int64_t items = (int64_t)(RT - a.rt0) * CT;
-  int32_t nb = 2 * (c->n_cu / 8) * 8;
-  if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
-  const float c0 = (float)(cat.c0 * KSTAR_T_SCALE), c1 = (float)(cat.c1 * KSTAR_T_SCALE);
-  hipLaunchKernelGGL(has_cat ? k_gp_kstar_f32c<true> : k_gp_kstar_f32c<false>, dim3(nb), dim3(K_NT), 0, c->stream,
-                     XsT_f, (int64_t)npad, ucand_f, ldk, a.dpad, a.rt0, RT, CT,
-                     a.train.xnorm ? a.train.xnorm : c->gp_xnorm.p, a.cn ? a.cn : c->cnorm.p, c->gp_alpha.p, c->gp_sf2,
-                     c->gp_n, m, c->gp_ctr.p + 8, ldk, a.part, a.part2, a.part3, cat.acat, cat.bcat, cat.nkc, c0, c1);
+  int32_t nb;
+  int rc;
+  if ((rc = kstar_grid(c, (int64_t)(RT - a.rt0) * CT, false, &nb))) return rc;
+  const KstarOperands<float> o{XsT_f,    ucand_f,  npad, ldk,     a.dpad,
+                               cat.acat, cat.bcat, npad, cat.nkc, (float)(cat.c0 * KSTAR_T_SCALE),
+                               (float)(cat.c1 * KSTAR_T_SCALE)};
+  hipLaunchKernelGGL(has_cat ? k_gp_kstar_f32c<true> : k_gp_kstar_f32c<false>, dim3(nb), dim3(K_NT), 0, c->stream, o,
+                     a.rt0, RT, CT, a.train.xnorm ? a.train.xnorm : c->gp_xnorm.p, a.cn ? a.cn : c->cnorm.p,
+                     c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, ldk, a.part, a.part2, a.part3);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -682,24 +456,18 @@ int launch_gemm_kstar(ut_ctx* c, int prec, int32_t npad, const KstarArgs& a) {
   // fp64: only the first store_rows rows of K* are written (the mean still
   // sums every row); the other precisions always store everything
   const int32_t store_rt = store_rows < 0 ? RT : (store_rows + K_BM - 1) / K_BM;
-  const int64_t items = (int64_t)RTe * CT;
-  // Two K* workgroups fill a CU's VGPRs, so a full persistent grid leaves no
-  // slot for the GP fit running beside it on the fit stream, and the fit's
-  // serial chain of small kernels then stalls the variance GEMM that waits for
-  // it.  While a fit is in flight, 2 CUs per XCD are left to it (C2: the round
-  // with a refit 30.2 -> 29.6 ms, the same as without a refit; K* alone 3% slower).
-  const bool fit_in_flight = c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
-  const int32_t spare = fit_in_flight ? KSTAR_SPARE_PER_XCD : 0;
-  int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
-  if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
-  UT_HIP(c, hipMemsetAsync(c->gp_ctr.p + 8, 0, sizeof(int32_t) * 8, c->stream));
+  int32_t nb;
+  int rc;
+  if ((rc = kstar_grid(c, (int64_t)RTe * CT, true, &nb))) return rc;
   const double* xnorm = a.train.xnorm ? a.train.xnorm : c->gp_xnorm.p;
   const double* cnorm = a.cn ? a.cn : c->cnorm.p;
-#define UT_KSTAR_LAUNCH(TS, MU, CAT, KST, PART, KSCALE, LOOFF, SRT, PART2)                                         \
-  hipLaunchKernelGGL((k_gp_kstar<TS, MU, CAT>), dim3(nb), dim3(K_NT), 0, c->stream, XsT, (int64_t)npad, ucand, ldk, \
-                     dpad, RT, CT, xnorm, cnorm, c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, KST, ldk, PART, \
-                     KSCALE, LOOFF, SRT, PART2, cat.acat, cat.bcat, cat.nkc, cat.c0 * KSTAR_T_SCALE,        \
-                     cat.c1 * KSTAR_T_SCALE, RTe)
+  const KstarOperands<double> o{XsT,      ucand,    npad, ldk,     dpad,
+                                cat.acat, cat.bcat, npad, cat.nkc, cat.c0 * KSTAR_T_SCALE,
+                                cat.c1 * KSTAR_T_SCALE};
+#define UT_KSTAR_LAUNCH(TS, MU, CAT, KST, PART, KSCALE, LOOFF, SRT, PART2)                                      \
+  hipLaunchKernelGGL((k_gp_kstar<TS, MU, CAT>), dim3(nb), dim3(K_NT), 0, c->stream, o, RT, CT, xnorm, cnorm,    \
+                     c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, KST, ldk, PART, KSCALE, LOOFF, SRT, \
+                     PART2, RTe)
 #define UT_KSTAR_BOTH(TS, MU, ...)                   \
   do {                                               \
     if (has_cat) UT_KSTAR_LAUNCH(TS, MU, true, __VA_ARGS__); \

@@ -502,11 +502,7 @@ int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m,
   UT_LAUNCH_CHECK(c);
   const int32_t RT = npad / Q_BM;
   const int32_t CT = (int32_t)(ldk / Q_BN);
-  const int64_t items = (int64_t)RT * CT;
-  const bool fit_in_flight = c->fit_pending && hipEventQuery(c->ev_fit) == hipErrorNotReady;
-  const int32_t spare = fit_in_flight ? 2 : 0;   // as launch_gemm_kstar
-  int32_t nb = 2 * (c->n_cu / 8 - spare) * 8;
-  if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
+  const int32_t nb = kstar_blocks(c, (int64_t)RT * CT, true);   // (no tickets: its items are static)
   const double kscale = ldexp(1.0, -i8_kstar_exp(c->gp_sf2));
 #define UT_KQ_LAUNCH(PAIR)                                                                                     \
   hipLaunchKernelGGL((k_gp_kstar_q<int8_t, false, false, PAIR>), dim3(nb), dim3(Q_NT), 0, c->stream, xd.p, npad,    \

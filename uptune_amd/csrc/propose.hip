@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256) void k_encode_scaled(const DevParam* __restric
   cn[i] = s;
 }
 
-// the categorical K*'s candidate operands in one pass (gp_gemm.hip
+// the categorical K*'s candidate operands in one pass (gp_kstar_tile.h
 // "Categorical K*"): U'[k][i] = numeric feature k / ell (0 past n_num and for
 // the padding columns), cnorm[i] = |u'_i|^2 over the numeric features in
 // feature order, and the one-hot codes bcat[(q >> 7)][i][q & 127] = 1 at code

@@ -794,6 +794,11 @@ struct KstarArgs {
   int32_t rt0 = 0;                 // f32c: the first row tile
   const double* cn = nullptr;      // candidate norms (nullptr: c->cnorm)
 };
+// The persistent grid of a K* launch over `items` work items: two workgroups
+// per CU, a multiple of 8 (one ticket per XCD), CUs left to an in-flight fit if
+// asked; kstar_grid also zeroes the eight tickets at c->gp_ctr + 8 on c->stream.
+int32_t kstar_blocks(ut_ctx* c, int64_t items, bool leave_for_fit);
+int kstar_grid(ut_ctx* c, int64_t items, bool leave_for_fit, int32_t* nb);
 int launch_gemm_kstar(ut_ctx* c, int prec, int32_t npad, const KstarArgs& a);
 int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, int32_t npad, const KstarArgs& a);
 // gp_kq.hip: K* of a numeric precision-8 fit as the distance contraction on
