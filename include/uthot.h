@@ -337,6 +337,31 @@ int ut_gp_set_precision(ut_ctx* ctx, int32_t bits);
  * (mean k* . alpha), so the selection is the dense one.  64: the bound pass in
  * fp64 (its mean exact and reused for the survivors). */
 int ut_gp_set_prune_pass(ut_ctx* ctx, int32_t bits);
+/* Weighted pruning (off by default).  With enable = 0, ut_gp_topk_pruned and
+ * ut_score_round_de_pruned return UT_EUNSUPPORTED while failed rows
+ * (ut_gp_feas_set) or constraint values (ut_gp_cons_set) are loaded.  With
+ * enable = 1 both accept them with UT_ACQ_EI and return the k best
+ * (S, -index) pairs among the valid candidates of the dense weighted score
+ *   S(u) = (E(u) P(u)) p(u)^gamma,
+ * E the EI at f_best_c (1 when values are loaded and no row is feasible), P the
+ * constraint weight (1 with no values), p the feasibility vote (p^gamma = 1
+ * with no rows): the dense path's factors in its order.  Every factor lies in
+ * [0, 1], so the bound of the first bound_rows rows stays a bound; the
+ * constraint weight is bounded per candidate as well,
+ *   ub(u)  = ub_E(u) prod_j Pub_j(u),
+ *   Pub_j  = 1 where tau_j - mu_cj(u) >= 0, else Phi((tau_j - mu_cj(u)) / sqrt(var_ub(u)))
+ * (Phi of a negative ratio rises with sigma, and var <= var_ub), with ub_E at
+ * f_best_c (1 with no feasible row) and mu_cj exact for every candidate (one
+ * fp64 pass of the constraint means per call, at either bound pass).  The vote
+ * gets no bound.  A bound is flagged exact (ut_gp_prune_bounds) only when the
+ * pass pins the variance and the EI argument and no failed rows are loaded:
+ * with failed rows no bound is exact, and a flat posterior then runs the dense
+ * branch.  ut_gp_prune_bounds returns the weighted bounds; ut_prune_stats is
+ * unchanged.  Still refused with enable = 1: UT_ACQ_UCB while anything is
+ * loaded (UT_EUNSUPPORTED, the dense path's message), constraint values of an
+ * earlier fit (UT_EINVAL), failed rows the categorical K* cannot read
+ * (UT_EINVAL).  With nothing loaded the switch changes no bit of any result. */
+int ut_gp_set_prune_weighted(ut_ctx* ctx, int32_t enable);
 /* precision 8: the largest accepted relative error of a candidate's variance
  * (default 2^-20); 0 recomputes every candidate in fp64 */
 int ut_gp_set_i8_tol(ut_ctx* ctx, double tol);
@@ -478,8 +503,9 @@ typedef struct ut_feas_params {
  * ut_score_round_de and ut_score_round_ga at every precision, and, as it is
  * defined for EI only (a UCB score can be negative), a scoring call with
  * UT_ACQ_UCB returns UT_EUNSUPPORTED; so do ut_gp_topk_pruned and
- * ut_score_round_de_pruned (their bound does not know the weight) and
- * ut_gp_select_batch (its per-pick acquisition does not either).  A fit that
+ * ut_score_round_de_pruned unless ut_gp_set_prune_weighted is on (their
+ * weighted bound is opt-in) and ut_gp_select_batch (its per-pick acquisition
+ * does not know the weight).  A fit that
  * scores with the categorical K* needs failed rows that are one-hot in the
  * ENUM blocks and 0 / 1 in the BOOL columns: otherwise the scoring call returns
  * UT_EINVAL naming the first row that is not.
@@ -541,8 +567,9 @@ int ut_gp_feas_info(ut_ctx* ctx, int32_t* nf, ut_feas_params* p);
  * ut_gp_score_values, ut_score_round_de and ut_score_round_ga at every
  * precision, after the dense posterior and before the feasibility weight
  * (score = EI(f_best_c) P p^gamma when both are loaded); a scoring call with
- * UT_ACQ_UCB returns UT_EUNSUPPORTED, and so do ut_gp_topk_pruned,
- * ut_score_round_de_pruned and ut_gp_select_batch.
+ * UT_ACQ_UCB returns UT_EUNSUPPORTED, and so do ut_gp_select_batch and, unless
+ * ut_gp_set_prune_weighted is on, ut_gp_topk_pruned and
+ * ut_score_round_de_pruned.
  * UT_EINVAL (what was loaded before stays loaded): no fit, n not the fit's n,
  * nc < 0 or nc > UT_CONS_MAX, a NULL pointer with nc > 0, a non-finite value,
  * a NaN threshold (+-inf thresholds are allowed). */

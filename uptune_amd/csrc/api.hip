@@ -749,10 +749,10 @@ int ut_gp_topk_pruned(ut_ctx* c, const double* feat, int64_t ld, int64_t m, cons
   if (!c) return UT_EINVAL;
   UT_CHECK(c, m >= 1 && feat && ld >= m && acq && out_idx && out_score && cand_base >= 0, UT_EINVAL,
            "gp_topk_pruned: bad arguments");
-  UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
+  UT_CHECK(c, c->fs_n == 0 || c->prune_weighted, UT_EUNSUPPORTED,
            "gp_topk_pruned: failed rows are loaded (ut_gp_feas_set) and the pruning bound does not know the "
            "feasibility weight");
-  UT_CHECK(c, c->cs_nc == 0, UT_EUNSUPPORTED,
+  UT_CHECK(c, c->cs_nc == 0 || c->prune_weighted, UT_EUNSUPPORTED,
            "gp_topk_pruned: constraint values are loaded (ut_gp_cons_set) and the pruning bound does not know the "
            "constraint weight");
   const bool own = c->timing.on && !c->timing.in_round;
@@ -775,6 +775,12 @@ int ut_gp_set_prune_pass(ut_ctx* c, int32_t bits) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, bits == 32 || bits == 64, UT_EINVAL, "prune pass must be 32 or 64");
   c->prune_pass = bits;
+  return 0;
+}
+
+int ut_gp_set_prune_weighted(ut_ctx* c, int32_t enable) {
+  if (!c) return UT_EINVAL;
+  c->prune_weighted = enable ? 1 : 0;
   return 0;
 }
 
@@ -949,10 +955,10 @@ int ut_score_round_de_pruned(ut_ctx* c, const ut_de_params* de, const ut_acq* ac
                              ut_prune_stats* stats) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, bound_rows >= 1, UT_EINVAL, "score_round_pruned: bound_rows must be >= 1");
-  UT_CHECK(c, c->fs_n == 0, UT_EUNSUPPORTED,
+  UT_CHECK(c, c->fs_n == 0 || c->prune_weighted, UT_EUNSUPPORTED,
            "score_round_de_pruned: failed rows are loaded (ut_gp_feas_set) and the pruning bound does not know the "
            "feasibility weight");
-  UT_CHECK(c, c->cs_nc == 0, UT_EUNSUPPORTED,
+  UT_CHECK(c, c->cs_nc == 0 || c->prune_weighted, UT_EUNSUPPORTED,
            "score_round_de_pruned: constraint values are loaded (ut_gp_cons_set) and the pruning bound does not know the "
            "constraint weight");
   return score_round_de_impl(c, de, acq, round_, cand_base, m, k, out, bound_rows, stats);

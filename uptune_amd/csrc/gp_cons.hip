@@ -18,8 +18,6 @@
 
 namespace ut {
 
-constexpr int CS_INFO = 4 * UT_CONS_MAX;   // cs_stats[CS_INFO] = f_best_c, [CS_INFO + 1] = n_feasible
-
 // The K* contraction (gp_kstar_tile.h) over one row set, the fit's training
 // operand, with a weighted epilogue:
 //   1. the item's alpha_j[row0 .. row0 + 127], j < NC, go to LDS beside rowop;
@@ -140,14 +138,7 @@ __global__ void k_cons_apply(int64_t m, int32_t RT, int32_t nc, const double* __
   for (int32_t j = 0; j < nc; ++j) {
     const double mc = sf2 * part_sum(part + (int64_t)j * ldp, RT, (int64_t)nc * ldp, i);
     const double tau = st[4 * j + 3];
-    double pj;
-    if (v == 0.0) {
-      pj = mc <= tau ? 1.0 : 0.0;
-    } else {
-      const double z = (tau - mc) / sigma;
-      pj = 0.5 * erfc(-z * 0.70710678118654752440);
-    }
-    P *= pj;
+    P *= cons_prob1(mc, tau, v, sigma);
     if (mu_c_out) mu_c_out[(int64_t)j * ldo + i] = mc;
   }
   if (p_out) p_out[i] = P;
@@ -257,11 +248,11 @@ static void launch_cons_means(ut_ctx* c, int32_t nc, int32_t nb, const KstarTrai
 #undef UT_CONS_LAUNCH
 }
 
-// The constraint means of the m candidates whose K* operands (shape s) are in
-// c->ucand / c->cnorm / c->bcat, then k_cons_apply on their posterior mu / var
-// with the given outputs.
-static int cons_tail(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const double* mu, const double* var,
-                     double* p_out, double* mu_c_out, int64_t ldo, double* score) {
+// The constraint-mean partials (c->cs_part) of the m candidates whose K*
+// operands (shape s) are in c->ucand / c->cnorm / c->bcat, after the per-fit
+// operands.  A column's sums do not depend on its neighbours, so pruned
+// scoring reads a gathered candidate's means at its own index.
+int cons_means(ut_ctx* c, const ScoreShape& s, int64_t m) {
   const int32_t nc = c->cs_nc;
   const int64_t ldk = s.ldk;
   UT_CHECK(c, s.npad % K_BM == 0 && s.dpad % 4 == 0 && ldk % K_BN == 0 && ldk >= m, UT_EINVAL, "gp_cons: bad padding");
@@ -283,6 +274,16 @@ static int cons_tail(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const
       launch_cons_means<false>(c, nc, nb, tr, s, CT, m);
     UT_LAUNCH_CHECK(c);
   }
+  return 0;
+}
+
+// cons_means, then k_cons_apply on the candidates' posterior mu / var with the
+// given outputs.
+static int cons_tail(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const double* mu, const double* var,
+                     double* p_out, double* mu_c_out, int64_t ldo, double* score) {
+  if (int rc = cons_means(c, s, m)) return rc;
+  const int32_t nc = c->cs_nc;
+  const int64_t ldk = s.ldk;
   hipLaunchKernelGGL(k_cons_apply, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, s.RT, nc, c->cs_part.p, ldk,
                      c->gp_sf2, c->cs_stats.p, mu, var, xi, p_out, mu_c_out, ldo, score);
   UT_LAUNCH_CHECK(c);

@@ -144,7 +144,7 @@ __global__ void k_feas_apply(int64_t m, int32_t RT_ok, int32_t RT_fail, const do
   if (score) {
     const double sc = score[i];
     // -inf (a duplicate) and NaN (a failed fit) pass through
-    if (__builtin_isfinite(sc)) score[i] = sc * (gamma == 1.0 ? p : pow(p, gamma));
+    if (__builtin_isfinite(sc)) score[i] = sc * feas_factor(p, gamma);
   }
 }
 
@@ -176,23 +176,27 @@ static int feas_operands(ut_ctx* c) {
 }
 
 // The vote over the m candidates whose K* operands (shape s) are in c->ucand /
-// c->cnorm / c->bcat, then k_feas_apply with the given outputs.
+// c->cnorm / c->bcat -- or, given ops, in its arrays (pruned scoring's gathered
+// columns; only the candidate padding differs from s) -- then k_feas_apply with
+// the given outputs.
 static int feas_vote(ut_ctx* c, const ScoreShape& s, int64_t m, double* p_out, double* s_ok_out, double* s_fail_out,
-                     double* score) {
+                     double* score, const CandOps* ops = nullptr) {
+  const CandOps own{c->ucand.p, c->cnorm.p, c->bcat.p, s.ldk};
+  const CandOps& u = ops ? *ops : own;
   const int32_t nf = c->fs_n;
   UT_CHECK(c, nf == 0 || c->fs_d == s.d, UT_EINVAL,
            "gp_feas: the failed rows have " + std::to_string(c->fs_d) + " features, the fit " + std::to_string(s.d));
   UT_CHECK(c, !(s.cat && nf > 0 && c->fs_bad_row >= 0), UT_EINVAL,
            "gp_feas: the fit scores with the categorical K* and failed row " + std::to_string(c->fs_bad_row) +
                " is not one-hot in an ENUM block / 0-1 in a BOOL column");
-  const int64_t ldk = s.ldk;
+  const int64_t ldk = u.ld;
   UT_CHECK(c, s.npad % K_BM == 0 && s.dpad % 4 == 0 && ldk % K_BN == 0 && ldk >= m, UT_EINVAL, "gp_feas: bad padding");
   int rc;
   if ((rc = feas_operands(c))) return rc;
   const int32_t nfpad = nf > 0 ? gp_npad(nf) : 0;
   const int32_t RT_ok = s.RT, RT_fail = nfpad / K_BM;
   if ((rc = ensure(c, c->fs_part, (size_t)(RT_ok + RT_fail) * ldk))) return rc;
-  const KstarTrain tr = kstar_train(c, s.cat, c->bcat.p);
+  const KstarTrain tr = kstar_train(c, s.cat, u.bcat);
   const bool has_cat = tr.cat.nkc > 0;
   UT_CHECK(c, s.dpad >= 4 || has_cat, UT_EINVAL, "gp_feas: bad padding");
   UT_CHECK(c, !has_cat || (tr.cat.acat && tr.cat.bcat), UT_EINVAL, "gp_feas: categorical operands missing");
@@ -205,11 +209,11 @@ static int feas_vote(ut_ctx* c, const ScoreShape& s, int64_t m, double* p_out, d
   const ut_feas_params& fp = c->fs_par;
   const double inv_s2 = 1.0 / (fp.ell_scale * fp.ell_scale);
   // (AT, lda, acat, npad_a: each item's row set)
-  const KstarOperands<double> o{nullptr, c->ucand.p,  0, ldk,        s.dpad,
+  const KstarOperands<double> o{nullptr, u.ucand,     0, ldk,        s.dpad,
                                 nullptr, tr.cat.bcat, 0, tr.cat.nkc, tr.cat.c0 * KSTAR_T_SCALE,
                                 tr.cat.c1 * KSTAR_T_SCALE};
   hipLaunchKernelGGL(has_cat ? k_feas_sums<true> : k_feas_sums<false>, dim3(nb), dim3(K_NT), 0, c->stream, ok, fail,
-                     RT_ok, RT_fail, o, CT, c->cnorm.p, m, c->gp_ctr.p + 8, c->fs_part.p, inv_s2);
+                     RT_ok, RT_fail, o, CT, u.cnorm, m, c->gp_ctr.p + 8, c->fs_part.p, inv_s2);
   UT_LAUNCH_CHECK(c);
   // the prior success rate: as given, or the share of successes among the rows in use
   const double p0 = fp.prior > 0.0 ? fp.prior : (double)s.n / (double)(s.n + nf);
@@ -222,6 +226,10 @@ static int feas_vote(ut_ctx* c, const ScoreShape& s, int64_t m, double* p_out, d
 
 int feas_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double* score) {
   return feas_vote(c, s, m, nullptr, nullptr, nullptr, score);
+}
+
+int feas_prob_cols(ut_ctx* c, const ScoreShape& s, const CandOps& ops, int64_t m, double* p_out) {
+  return feas_vote(c, s, m, p_out, nullptr, nullptr, nullptr, &ops);
 }
 
 int gp_feas_prob_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,

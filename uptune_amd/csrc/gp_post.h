@@ -32,6 +32,24 @@ inline Acq make_acq(const ut_ctx* c, const ut_acq* a) {
   return Acq{c->gp_sf2, c->gp_stats.p, c->gp_flag.p, a->kind, a->xi, a->kappa};
 }
 
+// ... with f_best read from the loaded constraint values' scan (gp_cons.hip:
+// f_best_c, the best feasible standardised y; NaN when no row is feasible --
+// the score is then P alone and this EI is never evaluated)
+inline Acq make_acq_cons(const ut_ctx* c, const ut_acq* a) {
+  return Acq{c->gp_sf2, c->cs_stats.p + CS_INFO, c->gp_flag.p, a->kind, a->xi, a->kappa};
+}
+
+// P_j of one constraint (uthot.h "constrained EI"): Phi((tau - mu_c) / sigma),
+// sigma = sqrt(v); v == 0: mu_c <= tau ? 1 : 0.  The one place it is computed:
+// k_cons_apply, the pruning bound and pruned scoring's exact stage.
+__device__ __forceinline__ double cons_prob1(double mc, double tau, double v, double sigma) {
+  if (v == 0.0) return mc <= tau ? 1.0 : 0.0;
+  const double z = (tau - mc) / sigma;
+  return 0.5 * erfc(-z * 0.70710678118654752440);
+}
+// the feasibility vote's factor p^gamma (k_feas_apply, pruned scoring's exact stage)
+__device__ __forceinline__ double feas_factor(double p, double gamma) { return gamma == 1.0 ? p : pow(p, gamma); }
+
 // column i's sum of the first RT row-tile partials, tile 0 upward, one call per
 // quantity: the pruning proof (gp_prune.hip) needs the first R partial sums
 // bitwise those of the full sum
@@ -40,6 +58,49 @@ __device__ __forceinline__ double part_sum(const double* __restrict__ part, int3
   for (int32_t r = 0; r < RT; ++r) s += part[(int64_t)r * ld + i];
   return s;
 }
+
+// What pruned scoring needs of the loaded weights, by value (nc == 0 and no
+// vote: nothing is loaded, every kernel takes its unweighted path).
+//   part: cs_part [RT][nc][ldp], the constraint-mean partials of EVERY candidate
+//   of the call by its own index (k_cons_means); st: cs_stats.
+struct PruneW {
+  int32_t nc, RT;
+  const double* part;
+  int64_t ldp;
+  const double* st;
+  double sf2;
+  int32_t vote;   // failed rows are loaded: the exact score carries p^gamma, no bound is exact
+  double gamma;
+  int32_t pub;    // 0: the constraint weight gets no bound either (UT_PRUNE_WEIGHT_BOUND=0, measurements only)
+  __device__ __forceinline__ bool on() const { return nc > 0 || vote != 0; }
+  // values are loaded and no row is feasible: the score is P alone (k_cons_apply)
+  __device__ __forceinline__ bool no_ei() const { return nc > 0 && !(st[CS_INFO + 1] > 0.0); }
+  // P = prod_j P_j (j ascending) of candidate i at variance v.  UB: every
+  // factor's upper bound over variances <= v instead -- 1 where tau_j - mu_cj
+  // >= 0, else P_j at v itself (Phi of a negative ratio rises with sigma; v == 0
+  // gives 0, as cons_prob1 does for mu_cj > tau_j)
+  template <bool UB>
+  __device__ __forceinline__ double P(int64_t i, double v) const {
+    const double sigma = sqrt(v);
+    double p = 1.0;
+    for (int32_t j = 0; j < nc; ++j) {
+      const double mc = sf2 * part_sum(part + (int64_t)j * ldp, RT, (int64_t)nc * ldp, i);
+      const double tau = st[4 * j + 3];
+      p *= UB && mc <= tau ? 1.0 : cons_prob1(mc, tau, v, sigma);
+    }
+    return p;
+  }
+  // E P of candidate i in the dense order (k_cons_apply): E its EI at f_best_c
+  // (a: make_acq_cons), dropped when no row is feasible
+  __device__ __forceinline__ double EP(double E, int64_t i, double v) const {
+    const double p = P<false>(i, v);
+    return no_ei() ? p : E * p;
+  }
+  // ... and its bound from a bound ub_E on E and v >= the candidate's variance
+  __device__ __forceinline__ double EP_ub(double ub_E, int64_t i, double v) const {
+    return (no_ei() ? 1.0 : ub_E) * (pub ? P<true>(i, v) : 1.0);
+  }
+};
 
 // var = max(sf2 - |L^-1 k*|^2, 0)
 __device__ __forceinline__ double clamped_var(double sf2, double vs) {

@@ -8,8 +8,28 @@
 //   tiles, same k order) and fp addition of non-negative terms and sf2 - x are
 //   monotone, so var_exact <= var_bound holds in floating point too; the score
 //   bound gets a 1e-12 relative margin for the acquisition's own rounding.
+//
+// Weighted (ut_gp_set_prune_weighted, with failed rows and / or constraint
+// values loaded; EI only).  The score is S = (E P) p^gamma, E the EI at f_best_c
+// (1 when no row is feasible), P = prod_j Phi((tau_j - mu_cj) / sigma), p the
+// feasibility vote.  Every factor lies in [0, 1], and per candidate
+//   ub_w  = ub_E prod_j Pub_j,
+//   Pub_j = 1 where tau_j - mu_cj >= 0, else Phi((tau_j - mu_cj) / sqrt(var_ub))
+// bounds S: Phi of a negative ratio rises with sigma and var <= var_ub holds
+// bitwise (above); the vote gets no bound (factor 1).  mu_cj is exact for every
+// candidate: k_cons_means runs once over the round's K* operands (fp64, at both
+// passes) and the exact stage reads the same partials at the candidate's own
+// index.  erfc is only nearly monotone in floating point, so the 1e-12 / 1e-300
+// margin goes on after the product.  A bound keeps its exact flag only when the
+// pass's own test pins var and the EI argument AND no failed rows are loaded;
+// the stored double is then E P by the exact stage's own device function
+// (PruneW::EP).  With failed rows loaded no candidate is flagged exact, so a
+// flat GP (every score one double) keeps every candidate and falls back to the
+// dense branch, which ends with cons_weight then feas_weight as gp_score_impl.
 // ---------------------------------------------------------------------------
 #include "gp_post.h"
+
+#include <cstdlib>
 
 namespace ut {
 
@@ -43,7 +63,7 @@ __global__ void k_prune_bound(int64_t m, int32_t RTm, const double* __restrict__
                               const double* __restrict__ var_part, int64_t ldp, Acq a,
                               const uint8_t* __restrict__ dup, double* __restrict__ mu_out,
                               double* __restrict__ ub_out, const double* __restrict__ k2_part,
-                              const double* __restrict__ linv_f2, uint8_t* __restrict__ exact_out) {
+                              const double* __restrict__ linv_f2, uint8_t* __restrict__ exact_out, PruneW w) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const double mu = part_sum(mu_part, RTm, ldp, i);
@@ -59,6 +79,10 @@ __global__ void k_prune_bound(int64_t m, int32_t RTm, const double* __restrict__
     exact = tail == tail && var_lo == var;   // (NaN tail: not exact)
   } else if (RTv >= RTm) {
     exact = true;   // the bound GEMM covered every row
+  }
+  if (w.on()) {
+    exact = exact && !w.vote;
+    ub = exact ? w.EP(ub, i, var) : w.EP_ub(ub, i, var);
   }
   if (!exact) ub = ub + fabs(ub) * 1e-12 + 1e-300;
   mu_out[i] = *a.fit_flag != 0 ? __builtin_nan("") : mu;
@@ -96,7 +120,7 @@ __global__ void k_prune_bound32(int64_t m, int32_t RTm, const double* __restrict
                                 const uint8_t* __restrict__ dup,
                                 const double* __restrict__ cst, double* __restrict__ ub_out,
                                 uint8_t* __restrict__ exact_out, int32_t Kc, double c0abs,
-                                const double* __restrict__ cnorm) {
+                                const double* __restrict__ cnorm, PruneW w) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const double sf2 = a.sf2;
@@ -124,11 +148,15 @@ __global__ void k_prune_bound32(int64_t m, int32_t RTm, const double* __restrict
   const double var_lo = clamped_var(sf2, (vs + tail) * (1.0 + 0x1p-36));
   double ub = a.score(mu - dmu, var_ub);
   bool exact = var_lo == var_ub && dmu == dmu;
-  if (exact) {
+  if (exact && !w.no_ei()) {   // (no feasible row: the score has no EI factor to pin)
     if (a.kind == UT_ACQ_UCB)
       exact = ub == a.score(mu + dmu, var_lo);
     else
       exact = (a.stats[0] - (mu - dmu) - a.xi) == (a.stats[0] - (mu + dmu) - a.xi);
+  }
+  if (w.on()) {   // (the constraint means are fp64 and exact: no error term of this pass)
+    exact = exact && !w.vote;
+    ub = exact ? w.EP(ub, i, var_ub) : w.EP_ub(ub, i, var_ub);
   }
   if (!exact) ub = ub + fabs(ub) * 1e-12 + 1e-300;
   if (!(rho < 0.5)) {   // no usable bound: the candidate survives
@@ -178,10 +206,12 @@ __global__ __launch_bounds__(256) void k_sumsq_final(const double* __restrict__ 
 // mu_full: the bound pass's exact mean by global index; or (nullptr) the fp64
 // mean partials k* . alpha of these columns' K* (gather_kstar_cols: the f32
 // bound pass has no exact mean)
+// w: the weighted form, S = (E P) p^gamma in the dense order -- the constraint
+// means by global index as mu_full, p_vote[j] the vote of gathered column j
 __global__ void k_prune_exact(int64_t n, const int64_t* __restrict__ idx, int64_t base, int32_t RT,
                               const double* __restrict__ var_part, int64_t ldp, const double* __restrict__ mu_full,
                               Acq a, double* __restrict__ compact, double* __restrict__ full,
-                              const double* __restrict__ mu_part) {
+                              const double* __restrict__ mu_part, PruneW w, const double* __restrict__ p_vote) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const int64_t q = idx[j];
@@ -191,7 +221,12 @@ __global__ void k_prune_exact(int64_t n, const int64_t* __restrict__ idx, int64_
   }
   const double vs = part_sum(var_part, RT, ldp, j);
   const double mu = mu_full ? mu_full[q - base] : part_sum(mu_part, RT, ldp, j);
-  double sc = a.score(mu, clamped_var(a.sf2, vs));
+  const double var = clamped_var(a.sf2, vs);
+  double sc = a.score(mu, var);
+  if (w.on()) {
+    sc = w.EP(sc, q - base, var);
+    if (w.vote) sc = sc * feas_factor(p_vote[j], w.gamma);
+  }
   if (*a.fit_flag != 0) sc = __builtin_nan("");
   if (compact) compact[j] = sc;
   if (full) full[q - base] = sc;
@@ -237,6 +272,11 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   UT_CHECK(c, acq->kind == UT_ACQ_EI || (acq->kind == UT_ACQ_UCB && acq->kappa >= 0.0), UT_EINVAL,
            "gp_topk_pruned: the score must increase with sigma (EI, or UCB with kappa >= 0)");
   UT_CHECK(c, k >= 1 && k <= 1024, UT_EINVAL, "gp_topk_pruned: k must be in [1, 1024]");
+  // the weighted form (ut_gp_set_prune_weighted; the entry points refuse loaded rows / values without it)
+  const bool wv = c->prune_weighted && c->fs_n > 0, wc = c->prune_weighted && c->cs_nc > 0;
+  if (int rc0 = weights_refuse_ucb(c, acq, wv, wc)) return rc0;
+  if (wc)
+    if (int rc0 = cons_stale(c, "gp_topk_pruned")) return rc0;
   if (int rc0 = gp_fit_flush(c)) return rc0;
   // the candidates' K* operands need only the fit's scaled inputs (1/ell):
   // they are prepared while the factorisation still runs, and K* then waits
@@ -252,8 +292,9 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   const int64_t ldk = s.ldk;
   int32_t R = gp_npad(bound_rows) / NPAD;
   R = R < 1 ? 1 : (R > RT ? RT : R);
-  const Acq pa = make_acq(c, acq);
+  Acq pa = make_acq(c, acq);
   int rc;
+  if (wv && (rc = ensure(c, c->pr_p, (size_t)ldk))) return rc;
   if ((rc = ensure(c, c->kst, (size_t)npad * ldk))) return rc;
   if ((rc = ensure(c, c->mu_part, (size_t)RT * ldk))) return rc;
   if ((rc = ensure(c, c->var_part, (size_t)RT * ldk))) return rc;
@@ -341,16 +382,29 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
     c->pr_ab_gen = c->fit_gen;
   }
   mark(c, "kstar");
+  if (wc) {   // mu_cj of every candidate, once, over the same operands (fp64 at both passes)
+    if ((rc = cons_means(c, s, m))) return rc;
+    mark(c, "cons");
+    pa = make_acq_cons(c, acq);   // (f_best_c lives in cs_stats, which cons_means may just have allocated)
+  }
+  // UT_PRUNE_WEIGHT_BOUND=0 (scripts/prune_weight_bench.py): Pub_j = 1, the EI bound alone -- still a bound
+  const char* pub_env = getenv("UT_PRUNE_WEIGHT_BOUND");
+  const PruneW pw{wc ? c->cs_nc : 0, RT, c->cs_part.p, ldk, c->cs_stats.p, c->gp_sf2, wv ? 1 : 0, c->fs_par.power,
+                  pub_env && atoi(pub_env) == 0 ? 0 : 1};
+  // the vote of gathered columns (threshold set, survivors), from their gathered operands
+  auto vote = [&](int64_t cnt, int64_t ldc) -> int {
+    return wv ? feas_prob_cols(c, s, CandOps{c->pr_ucand.p, c->pr_cnorm.p, c->pr_bcat.p, ldc}, cnt, c->pr_p.p) : 0;
+  };
   if ((rc = launch_gemm_var64(c, npad, c->kst.p, ldk, R * NPAD, m, c->var_part.p))) return rc;
   mark(c, "bound");
   if (dup_ready) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));   // the dup mask (side stream)
   if (f32)
     hipLaunchKernelGGL(k_prune_bound32, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, c->mu_part.p,
                        c->pr_sa.p, c->pr_k2.p, R, c->var_part.p, ldk, pa, n, dup, c->pr_f2.p, c->pr_ub.p,
-                       c->pr_exact.p, dpad + (cat ? 1 : 0), cat ? fabs(c->cat_c0) : 0.0, c->cnorm.p);
+                       c->pr_exact.p, dpad + (cat ? 1 : 0), cat ? fabs(c->cat_c0) : 0.0, c->cnorm.p, pw);
   else
     hipLaunchKernelGGL(k_prune_bound, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT, c->mu_part.p, R,
-                       c->var_part.p, ldk, pa, dup, c->pr_mu.p, c->pr_ub.p, c->pr_k2.p, c->pr_f2.p, c->pr_exact.p);
+                       c->var_part.p, ldk, pa, dup, c->pr_mu.p, c->pr_ub.p, c->pr_k2.p, c->pr_f2.p, c->pr_exact.p, pw);
   UT_LAUNCH_CHECK(c);
   c->pr_m = m;   // pr_ub / pr_exact hold this call's bounds (ut_gp_prune_bounds)
   // 3. threshold: exact scores of the best 1024 bounds, tau = their k-th best
@@ -364,9 +418,10 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   const int64_t ldt = gp_ldk(kp);
   if ((rc = gather_kstar_cols(c, s, tset, cand_base, kp, ldt, gmu))) return rc;
   if ((rc = launch_gemm_var64(c, npad, c->pr_kst.p, ldt, npad, kp, c->pr_vpart.p))) return rc;
+  if ((rc = vote(kp, ldt))) return rc;
   const double* mu_full = f32 ? nullptr : c->pr_mu.p;
   hipLaunchKernelGGL(k_prune_exact, dim3(grid1(kp, 256)), dim3(256), 0, c->stream, (int64_t)kp, tset, cand_base, RT,
-                     c->pr_vpart.p, ldt, mu_full, pa, tex, nullptr, gmu);
+                     c->pr_vpart.p, ldt, mu_full, pa, tex, nullptr, gmu, pw, c->pr_p.p);
   UT_LAUNCH_CHECK(c);
   int64_t* tk_i = out_idx;   // the caller's [k] outputs hold tau's top-k for now
   double* tk_s = out_score;
@@ -391,9 +446,15 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
     // most candidates survive: the whole K* (this time every row) and the dense variance
     if ((rc = launch_gemm_kstar(c, 64, npad, ka))) return rc;
     if ((rc = launch_gemm_var64(c, npad, c->kst.p, ldk, npad, m, c->var_part.p))) return rc;
-    if ((rc = launch_gp_finalize(c, m, RT, RT, c->mu_part.p, c->var_part.p, ldk, pa, dup, nullptr, nullptr,
-                                 c->pr_score.p)))
+    // (weighted: the plain EI first, then the dense path's own tails in its order)
+    if (wc && (rc = ensure(c, c->cs_mu, (size_t)ldk))) return rc;
+    if (wc && (rc = ensure(c, c->cs_var, (size_t)ldk))) return rc;
+    if ((rc = launch_gp_finalize(c, m, RT, RT, c->mu_part.p, c->var_part.p, ldk, make_acq(c, acq), dup,
+                                 wc ? c->cs_mu.p : nullptr, wc ? c->cs_var.p : nullptr, c->pr_score.p)))
       return rc;
+    if (wc || wv) mark(c, "var");   // (the tails mark their own stages: cons, feas)
+    if (wc && (rc = cons_weight(c, s, m, acq->xi, c->cs_mu.p, c->cs_var.p, c->pr_score.p))) return rc;
+    if (wv && (rc = feas_weight(c, s, m, c->pr_score.p))) return rc;
   } else {
     // 5. the full variance for the survivors only, their exact scores into a -inf array
     hipLaunchKernelGGL(k_fill, dim3(grid1(m, 256)), dim3(256), 0, c->stream, c->pr_score.p, m, -1.0 / 0.0);
@@ -402,8 +463,9 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
       const int64_t lds = gp_ldk(ns);
       if ((rc = gather_kstar_cols(c, s, c->pr_idx.p, 0, ns, lds, gmu))) return rc;
       if ((rc = launch_gemm_var64(c, npad, c->pr_kst.p, lds, npad, ns, c->pr_vpart.p))) return rc;
+      if ((rc = vote(ns, lds))) return rc;
       hipLaunchKernelGGL(k_prune_exact, dim3(grid1(ns, 256)), dim3(256), 0, c->stream, ns, c->pr_idx.p, (int64_t)0,
-                         RT, c->pr_vpart.p, lds, mu_full, pa, nullptr, c->pr_score.p, gmu);
+                         RT, c->pr_vpart.p, lds, mu_full, pa, nullptr, c->pr_score.p, gmu, pw, c->pr_p.p);
       UT_LAUNCH_CHECK(c);
     }
   }

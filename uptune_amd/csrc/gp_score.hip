@@ -297,6 +297,17 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
   return 0;
 }
 
+// the weights are defined for EI only (dense scoring, and pruned scoring under ut_gp_set_prune_weighted)
+int weights_refuse_ucb(ut_ctx* c, const ut_acq* acq, bool feas, bool cons) {
+  UT_CHECK(c, !(feas && acq && acq->kind == UT_ACQ_UCB), UT_EUNSUPPORTED,
+           "gp_score: failed rows are loaded (ut_gp_feas_set) and the feasibility weight is defined for EI only: "
+           "a UCB score can be negative");
+  UT_CHECK(c, !(cons && acq && acq->kind == UT_ACQ_UCB), UT_EUNSUPPORTED,
+           "gp_score: constraint values are loaded (ut_gp_cons_set) and the constraint weight is defined for EI "
+           "only: a UCB score can be negative");
+  return 0;
+}
+
 // The single choke point of dense scoring (ut_gp_score, ut_gp_score_values,
 // the DE and GA rounds, every precision tier and both of precision 8's
 // recompute paths).  While failed rows are loaded (ut_gp_feas_set) the scores
@@ -311,13 +322,8 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
                   double* mu, double* var, double* score, hipEvent_t dup_ready) {
   const bool weigh = c->fs_n > 0 && score != nullptr;
   const bool cons = c->cs_nc > 0 && score != nullptr;
-  UT_CHECK(c, !(weigh && acq && acq->kind == UT_ACQ_UCB), UT_EUNSUPPORTED,
-           "gp_score: failed rows are loaded (ut_gp_feas_set) and the feasibility weight is defined for EI only: "
-           "a UCB score can be negative");
-  UT_CHECK(c, !(cons && acq && acq->kind == UT_ACQ_UCB), UT_EUNSUPPORTED,
-           "gp_score: constraint values are loaded (ut_gp_cons_set) and the constraint weight is defined for EI "
-           "only: a UCB score can be negative");
   int rc;
+  if ((rc = weights_refuse_ucb(c, acq, weigh, cons))) return rc;
   if (cons && m > 0) {
     if ((rc = cons_stale(c, "gp_score"))) return rc;
     const int64_t ldk = gp_ldk(m);

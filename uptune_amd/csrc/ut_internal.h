@@ -383,6 +383,8 @@ struct ut_ctx {
   ut::DevBuf<double> pr_gmu;                   // [RT][ldc] fp64 mean partials of recomputed columns (f32 pass)
   int32_t prune_pass = 32;                     // ut_gp_set_prune_pass: the bound pass in f32 or fp64
   ut::DevBuf<uint8_t> pr_exact;                // [ld] the stored score is the exact score
+  int32_t prune_weighted = 0;                  // ut_gp_set_prune_weighted: pruned scoring takes loaded rows / values
+  ut::DevBuf<double> pr_p;                     // [ldc] the vote p of the gathered candidates (weighted pruning)
   int64_t pr_m = 0;                            // the last pruned call's m (ut_gp_prune_bounds); 0 = none yet
   int64_t r_ld = 0;
   int64_t r_m = 0;
@@ -630,6 +632,16 @@ int gp_feas_set_impl(ut_ctx* c, const double* X, int32_t nf, int32_t d, const ut
 int gp_feas_prob_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* p_out,
                       double* s_ok_out, double* s_fail_out);
 int feas_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double* score);
+// the candidates' K* operands of a vote: the context's own (c->ucand / c->cnorm / c->bcat, padded to s.ldk)
+// unless given -- pruned scoring's gathered columns (c->pr_ucand / c->pr_cnorm / c->pr_bcat, padded to ld)
+struct CandOps {
+  const double* ucand;
+  const double* cnorm;
+  const int8_t* bcat;
+  int64_t ld;
+};
+// ... p_out[j] = p of the m columns of ops (no score is touched)
+int feas_prob_cols(ut_ctx* c, const ScoreShape& s, const CandOps& ops, int64_t m, double* p_out);
 // gp_cons.hip: constrained EI.  cons_weight: score[i] = EI(mu_i, var_i; f_best_c, xi) P_i (P_i when no row is
 // feasible) for the m candidates whose K* operands (of shape s) are in c->ucand / c->cnorm / c->bcat and whose
 // posterior the dense body left in mu / var; cons_stale: UT_EINVAL when the loaded values belong to an earlier fit
@@ -640,6 +652,12 @@ int gp_cons_info_impl(ut_ctx* c, int32_t* n, int32_t* nc, int32_t* n_feasible, d
 int cons_stale(ut_ctx* c, const char* who);
 int cons_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const double* mu, const double* var,
                 double* score);
+// ... its first half alone: the per-fit operands (cs_alpha, cs_stats) and the constraint-mean partials of the m
+// candidates in c->ucand / c->cnorm / c->bcat into c->cs_part [RT][cs_nc][s.ldk] (k_cons_means)
+int cons_means(ut_ctx* c, const ScoreShape& s, int64_t m);
+constexpr int CS_INFO = 4 * UT_CONS_MAX;   // cs_stats[CS_INFO] = f_best_c, [CS_INFO + 1] = n_feasible
+// gp_score.hip: UT_EUNSUPPORTED for a UCB score while rows (feas) or values (cons) would weight it
+int weights_refuse_ucb(ut_ctx* c, const ut_acq* acq, bool feas, bool cons);
 // gp_batch.hip: k picks from a shortlist of p, each conditioned on the picks before it
 int gp_select_batch_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
                          const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);

@@ -290,6 +290,13 @@ class BatchEngine:
         """gp_topk_pruned's bound pass: 32 (default, f32 k* with bounded rounding) or 64 (fp64)"""
         L.check(self.ctx, self.lib.ut_gp_set_prune_pass(self.ctx, int(bits)), "ut_gp_set_prune_pass")
 
+    def gp_set_prune_weighted(self, on: bool):
+        """ut_gp_set_prune_weighted: with True, gp_topk_pruned and
+        score_round_de_pruned accept loaded failed rows / constraint values (EI
+        only) and select by the dense weighted score; False (default): they
+        raise UT_EUNSUPPORTED meanwhile"""
+        L.check(self.ctx, self.lib.ut_gp_set_prune_weighted(self.ctx, 1 if on else 0), "ut_gp_set_prune_weighted")
+
     def gp_set_i8_tol(self, tol: float):
         """precision 8: largest accepted relative variance error (0: recompute all in fp64)"""
         L.check(self.ctx, self.lib.ut_gp_set_i8_tol(self.ctx, float(tol)), "ut_gp_set_i8_tol")
@@ -454,7 +461,8 @@ class BatchEngine:
         p^power, p = (S_ok + strength p0) / (S_ok + S_fail + strength) the kernel
         vote of the fit's rows against these (the GP's kernel, lengthscales times
         ell_scale); prior=None: p0 = n / (n + nf) of the fit in use.  UCB scoring,
-        pruned scoring and gp_select_batch raise UT_EUNSUPPORTED meanwhile."""
+        gp_select_batch and, unless gp_set_prune_weighted(True), pruned scoring
+        raise UT_EUNSUPPORTED meanwhile."""
         X = np.ascontiguousarray(X_fail, dtype=np.float64)
         if X.ndim != 2:
             raise ValueError("gp_feas_set: X_fail must be [nf][n_features]")

@@ -274,7 +274,7 @@ class SharedModel:
     def __init__(self, device: int = 0, seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4,
                  precision: int = 64, sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 1e-8,
                  engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40,
-                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None):
+                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -330,6 +330,11 @@ class SharedModel:
         # missing, None or not finite is not usable (neither trained on nor
         # failed).  n_feasible_ is the feasible training rows of the last fit.
         self.constraints = _cons_setting(constraints)
+        # prune_weighted: the engine's pruned rounds accept the loaded failed
+        # rows / constraint values and select by the weighted score
+        # (engine.gp_set_prune_weighted); False: they refuse, and a technique
+        # with prune_rows > 0 cannot use this model's feasibility / constraints
+        self.prune_weighted = bool(prune_weighted)
         self._reset()
         self.slots: Dict[str, int] = {}
 
@@ -399,6 +404,8 @@ class SharedModel:
             else:
                 self.engine = self.engine_factory(tech.manipulator, self.device, self.seed)
             self.engine.gp_set_precision(self.precision)
+            if self.prune_weighted:
+                self.engine.gp_set_prune_weighted(True)
             self.engine.history_reset(1024)
         self.engine.population_select(self.slot(tech))
         return self.engine
@@ -755,13 +762,17 @@ class GpuBatchTechnique(SearchTechnique):
                  seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4, acq: str = "ei",
                  group=None, surrogate=None, shared: Optional[SharedModel] = None, engine_factory=None,
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
-                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, *pargs, **kwargs):
+                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
+                 *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
+        # prune_weighted (SharedModel): pruned rounds under constraints / feasibility,
+        # by the weighted bound of ut_gp_set_prune_weighted.  A shared model carries its own
+        weighted = shared.prune_weighted if shared is not None else bool(prune_weighted)
         # constraints (SharedModel): EI over the best feasible result times the
         # probability that every measured constraint holds.  A shared model
         # carries its own setting; the rule is defined for the dense EI score only
         if shared.constraints if shared is not None else _cons_setting(constraints):
-            if int(prune_rows) > 0:
+            if int(prune_rows) > 0 and not weighted:
                 raise ValueError("constraints weight every candidate's score: not with prune_rows")
             if int(diversify) > 0:
                 raise ValueError("constraints are not known to the per-pick acquisition: not with diversify")
@@ -773,7 +784,7 @@ class GpuBatchTechnique(SearchTechnique):
         # candidate does not fail.  A shared model carries its own setting; the
         # weight is defined for the dense EI score only
         if (shared.feasibility if shared is not None else _feas_setting(feasibility)) is not None:
-            if int(prune_rows) > 0:
+            if int(prune_rows) > 0 and not weighted:
                 raise ValueError("feasibility weights every candidate's score: not with prune_rows")
             if int(diversify) > 0:
                 raise ValueError("feasibility is not known to the per-pick acquisition: not with diversify")
@@ -811,7 +822,8 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    engine_factory=engine_factory,
                                                                    y_transform=y_transform,
                                                                    feasibility=feasibility,
-                                                                   constraints=constraints)
+                                                                   constraints=constraints,
+                                                                   prune_weighted=prune_weighted)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -1115,7 +1127,8 @@ def _shared_model(kw) -> SharedModel:
     return SharedModel(device=kw.get("device", 0), seed=kw.get("seed", 0), lengthscale=kw.get("lengthscale", 0.3),
                        min_train=kw.get("min_train", 4), precision=kw.get("precision", 64),
                        engine_factory=kw.pop("engine_factory", None), y_transform=kw.get("y_transform"),
-                       feasibility=kw.get("feasibility", False), constraints=kw.get("constraints"))
+                       feasibility=kw.get("feasibility", False), constraints=kw.get("constraints"),
+                       prune_weighted=kw.get("prune_weighted", False))
 
 
 def pso_ga_de_bandit(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
