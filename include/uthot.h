@@ -639,6 +639,22 @@ int ut_round_buffers(ut_ctx* ctx, double** values, double** features, uint32_t**
  * UT_EINVAL while no pruned call has computed bounds, or if m is not that
  * call's m. */
 int ut_gp_prune_bounds(ut_ctx* ctx, double* ub_out, uint8_t* exact_out, int64_t m);
+/* for tests: the K* that the last dense scoring call (ut_gp_score,
+ * ut_gp_score_values, a dense round) on ctx left in its scratch, element by
+ * element: k_out [npad][nc] (device doubles, written on ctx's stream) gets
+ * k*[r][c] for every training row 0 <= r < npad and candidate column
+ * c0 <= c < c0 + nc <= ldk, the padding (r >= n, c >= m: exact zeros)
+ * included.  *npad, *ldk: that call's padded sizes; *format: 64 when the
+ * scratch holds fp64 rows (copied: an fp64 fit, or a precision-8 call whose
+ * whole round fell back to fp64 and rewrote K*), 8 when it holds precision 8's
+ * six digit planes (decoded exactly: a 48-bit integer times 2^(eb - 48)).
+ * k_out may be NULL (the sizes and the format only); so may the other three.
+ * Nothing is launched or recorded on the scoring paths for this.
+ * UT_EUNSUPPORTED after a dense call of an fp32 or f16x3 fit; UT_EINVAL when no
+ * dense call has completed since the last fit (a fit, a pruned call and a failed
+ * dense call each leave nothing to read) or for columns outside [0, ldk]. */
+int ut_gp_kstar_read(ut_ctx* ctx, double* k_out, int64_t c0, int64_t nc, int32_t* npad, int64_t* ldk,
+                     int32_t* format);
 /* Dense DE rounds (ut_score_round_de) are lazy when K', the smallest power of
  * two >= 2k, is at most 1024 and less than m: only the K' best-scoring
  * candidates are hashed and deduplicated, which selects what hashing all m

@@ -5,8 +5,12 @@ contraction's own, gp_kq.hip), so every candidate's mean and variance agree to
 1e-9 relative (1e-10 absolute) and the dense rounds select the same
 candidates, at the padded sizes 1024 / 2048 (sf2 far from 1 too: the round-5
 fault case, npad 2048 and sf2 1e-3).  A categorical fit keeps the fp64-MFMA K*
-(bit-identical with and without UT_KSTAR_Q).  Both are held to
-oracle/gp.py by test_gpu_i8.py / test_gpu_parity.py."""
+(bit-identical with and without UT_KSTAR_Q), so the "cat" half never reaches
+k_gp_kstar_q.  This file compares two device kernels that share the exp
+table, the norms and the clamp: an error in the shared part cancels here.
+test_gpu_i8.py / test_gpu_parity.py hold both kernels' posterior, not their K*,
+to oracle/gp.py at 1e-5; K* itself is held element by element to an
+extended-precision reference by test_gpu_kstar_elements.py."""
 import ctypes
 import os
 import sys

@@ -161,6 +161,7 @@ SIGNATURES = {
     "ut_round_buffers": (C.c_int, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
                                    C.POINTER(P), C.POINTER(P), C.POINTER(I64)]),
     "ut_gp_prune_bounds": (C.c_int, [P, P, P, I64]),
+    "ut_gp_kstar_read": (C.c_int, [P, P, I64, I64, C.POINTER(I32), C.POINTER(I64), C.POINTER(I32)]),
     "ut_comm_unique_id": (C.c_int, [P]),
     "ut_comm_init": (C.c_int, [P, I32, I32, P]),
     "ut_comm_destroy": (C.c_int, [P]),

@@ -1247,6 +1247,24 @@ int ut_gp_prune_bounds(ut_ctx* c, double* ub_out, uint8_t* exact_out, int64_t m)
   return 0;
 }
 
+int ut_gp_kstar_read(ut_ctx* c, double* k_out, int64_t c0, int64_t nc, int32_t* npad, int64_t* ldk,
+                     int32_t* format) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, c->kst_fmt >= 0, UT_EUNSUPPORTED, "gp_kstar_read: the fp32 and f16x3 K* formats are not read out");
+  UT_CHECK(c, c->kst_fmt != 0 && c->kst.p, UT_EINVAL, "gp_kstar_read: no dense scoring call since the last fit");
+  UT_CHECK(c, c0 >= 0 && nc >= 0 && c0 + nc <= c->kst_ldk, UT_EINVAL, "gp_kstar_read: columns outside [0, ldk]");
+  if (npad) *npad = c->kst_npad;
+  if (ldk) *ldk = c->kst_ldk;
+  if (format) *format = c->kst_fmt;
+  if (!k_out || nc == 0) return 0;
+  if (c->kst_fmt == 8)
+    return launch_kstar_decode_i8(c, reinterpret_cast<const int8_t*>(c->kst.p), c->kst_npad, c->kst_ldk, c0, nc,
+                                  k_out);
+  UT_HIP(c, hipMemcpy2DAsync(k_out, sizeof(double) * nc, c->kst.p + c0, sizeof(double) * c->kst_ldk,
+                             sizeof(double) * nc, (size_t)c->kst_npad, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
 int ut_round_lazy_stats(ut_ctx* c, int64_t* lazy_rounds, int64_t* fallback_rounds) {
   if (!c) return UT_EINVAL;
   if (lazy_rounds) *lazy_rounds = c->lazy_rounds;

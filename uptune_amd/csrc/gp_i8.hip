@@ -315,4 +315,33 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
   return 0;
 }
 
+// (for tests: ut_gp_kstar_read) K*'s digit planes back to doubles: element
+// (training row r, candidate col) has digit p at kst8[p npad ldk + i8_off(col,
+// r, ldk)], plane 0 the most significant; k* = (sum_p d_p 256^(5-p)) scale
+// with scale = 2^(eb - 48): a 48-bit integer times a power of two, exact.
+// out [npad][nc], columns c0 .. c0 + nc - 1.
+__global__ __launch_bounds__(256) void k_i8_kstar_decode(const int8_t* __restrict__ kst8, int32_t npad, int64_t ldk,
+                                                         int64_t c0, int64_t nc, double scale,
+                                                         double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)npad * nc) return;
+  const int32_t r = (int32_t)(e / nc);
+  const int64_t j = e - (int64_t)r * nc;
+  const int64_t plane = (int64_t)npad * ldk, off = i8_off(c0 + j, r, ldk);
+  int64_t v = 0;
+#pragma unroll
+  for (int p = 0; p < I8_S; ++p) v = v * 256 + (int64_t)kst8[p * plane + off];
+  out[e] = (double)v * scale;
+}
+
+int launch_kstar_decode_i8(ut_ctx* c, const int8_t* kst8, int32_t npad, int64_t ldk, int64_t c0, int64_t nc,
+                           double* out) {
+  UT_CHECK(c, npad % 32 == 0 && c0 >= 0 && nc >= 0 && c0 + nc <= ldk, UT_EINVAL, "kstar_decode_i8: bad range");
+  if (nc == 0) return 0;
+  hipLaunchKernelGGL(k_i8_kstar_decode, dim3(grid1((int64_t)npad * nc, 256)), dim3(256), 0, c->stream, kst8, npad,
+                     ldk, c0, nc, ldexp(1.0, i8_kstar_exp(c->gp_sf2) - 48), out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 }  // namespace ut

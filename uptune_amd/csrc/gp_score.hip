@@ -183,6 +183,7 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_score: call ut_gp_fit first");
   UT_CHECK(c, acq != nullptr, UT_EINVAL, "gp_score: acq is NULL");
   if (m <= 0) return 0;
+  c->kst_fmt = 0;   // (ut_gp_kstar_read: set again where this call returns with K* in c->kst)
   if (int rc0 = gp_fit_flush(c)) return rc0;
   const int prec = c->gp_fit_prec;
   const bool fp32 = prec != 64;  // fp32, h3 (f16x3) and i8: K* stores a reduced-precision K*
@@ -288,12 +289,15 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
         return rc;
     }
     mark(c, "recompute");
+    // the digit planes, or the fp64 rows the whole-round fallback wrote over them
+    c->kst_fmt = c->i8_recomputed == -1 ? 64 : 8, c->kst_npad = npad, c->kst_ldk = ldk;
     return 0;
   }
   // h3's variance partials come per 256-row tile
   const int32_t RTv = prec == 16 ? (npad + 255) / 256 : RT;
   if ((rc = launch_gp_finalize(c, m, RT, RTv, c->mu_part.p, c->var_part.p, ldk, pa, dup, mu, var, score))) return rc;
   mark(c, "finalize");
+  c->kst_fmt = prec == 64 ? 64 : -1, c->kst_npad = npad, c->kst_ldk = ldk;
   return 0;
 }
 

@@ -338,6 +338,11 @@ struct ut_ctx {
 
   // scratch for GP scoring / round pipeline
   ut::DevBuf<double> kst;        // [n][ld]
+  // what the last dense scoring call left in kst (ut_gp_kstar_read): 64 = fp64
+  // rows [npad][ldk], 8 = six digit planes, -1 = the fp32 / f16x3 formats,
+  // 0 = nothing of the current fit (a fit, a pruned call or a failed dense call since)
+  int32_t kst_fmt = 0, kst_npad = 0;
+  int64_t kst_ldk = 0;
   ut::DevBuf<double> mu_part;    // [RT][ld]
   ut::DevBuf<double> var_part;   // [RT][ld]
   ut::DevBuf<double> cnorm;      // [ld]
@@ -921,6 +926,9 @@ int launch_split_i8(ut_ctx* c, int32_t n, int32_t npad);
 // part / mpart: per 64-row tile the column sums of v^2 and of v beta (the mean)
 int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk, int64_t m, double* part,
                        double* mpart);
+// (for tests) columns c0 .. c0 + nc - 1 of K*'s digit planes as doubles, out [npad][nc]
+int launch_kstar_decode_i8(ut_ctx* c, const int8_t* kst8, int32_t npad, int64_t ldk, int64_t c0, int64_t nc,
+                           double* out);
 // L^-1 [row][k] (n x n, fp64) -> scaled fp16 hi/lo planes, blocked (h3 A operand, rows padded to 256);
 // the scale exponent is derived on the device from max|L^-1| (kept in gp_ctr[16..17])
 int launch_split_h3(ut_ctx* c, const double* Linv, int32_t n, _Float16* dst);

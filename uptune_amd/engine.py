@@ -675,6 +675,20 @@ class BatchEngine:
         L.check(self.ctx, self.lib.ut_gp_prune_bounds(self.ctx, _ptr(ub), _ptr(exact), int(m)), "ut_gp_prune_bounds")
         return ub, exact
 
+    def gp_kstar_read(self, c0: int = 0, nc: Optional[int] = None):
+        """ut_gp_kstar_read (for tests): the K* the last dense scoring call left
+        behind, k*[r][c] for every padded training row r < npad and the columns
+        c0 <= c < c0 + nc (nc None: up to ldk), padding included
+        -> (k [npad][nc] float64 on the device, npad, ldk, format 64 | 8)"""
+        npad, ldk, fmt = C.c_int32(), C.c_int64(), C.c_int32()
+        L.check(self.ctx, self.lib.ut_gp_kstar_read(self.ctx, None, int(c0), 0, C.byref(npad), C.byref(ldk),
+                                                    C.byref(fmt)), "ut_gp_kstar_read")
+        nc = ldk.value - int(c0) if nc is None else int(nc)
+        k = self._empty(npad.value, max(nc, 0))
+        L.check(self.ctx, self.lib.ut_gp_kstar_read(self.ctx, _ptr(k), int(c0), nc, None, None, None),
+                "ut_gp_kstar_read")
+        return k, int(npad.value), int(ldk.value), int(fmt.value)
+
     def round_lazy_stats(self) -> Tuple[int, int]:
         """(lazy dense DE rounds, those of them that fell back to hashing every
         candidate) since the context was created; waits for the stream"""
