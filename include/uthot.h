@@ -655,6 +655,41 @@ int ut_gp_prune_bounds(ut_ctx* ctx, double* ub_out, uint8_t* exact_out, int64_t 
  * dense call each leave nothing to read) or for columns outside [0, ldk]. */
 int ut_gp_kstar_read(ut_ctx* ctx, double* k_out, int64_t c0, int64_t nc, int32_t* npad, int64_t* ldk,
                      int32_t* format);
+/* for tests: one operand of the last fit, as doubles.  Waits for that fit
+ * (a staged one is enqueued first), then copies, on ctx's stream, into out
+ * (caller-provided device doubles; may be NULL: the info only).  *info (may be
+ * NULL) is always filled once the fit is known to be positive definite.
+ *   UT_FIT_L         [npad][npad]: the lower triangle of the factor, zeros above
+ *                    the diagonal.  info->l_rows: the leading rows whose
+ *                    off-diagonal entries are L's -- npad after a refit; after
+ *                    appends the first appended block row times 64 (their B
+ *                    lives in scratch; the diagonal blocks beyond stay valid).
+ *   UT_FIT_LINV      [npad][npad]: L^-1 as stored, upper triangle included.
+ *   UT_FIT_LINVT     [npad][npad]: (L^-1)^T;  UT_FIT_ALPHA [npad].  While
+ *                    info->stale is set (a precision-8 refit leaves both to
+ *                    their first reader) nothing is copied and nothing computed.
+ *   UT_FIT_BETA, UT_FIT_YS   [npad]: L^-1 ys and the standardised targets.
+ *   UT_FIT_LINVT_F32 [npad][npad]: the f32 copy of (L^-1)^T, widened
+ *                    (precision-32 fits; UT_EUNSUPPORTED otherwise).
+ *   UT_FIT_I8A       [npad][npad] in (row, k) order: the six digit planes of
+ *                    L^-1 decoded exactly to sum_p a_p 256^(5-p);
+ *   UT_FIT_I8RS      [2 npad + 2]: [rs | e2 | E | Emu]  (precision-8 fits;
+ *                    UT_EUNSUPPORTED otherwise).
+ *   UT_FIT_H3        the f16x3 planes: always UT_EUNSUPPORTED.
+ * Nothing is launched or recorded on the fit or scoring paths for this.
+ * UT_EINVAL with no fit or an unknown operand; UT_ENOTPD after a fit that was
+ * not positive definite. */
+enum {
+  UT_FIT_L = 0, UT_FIT_LINV = 1, UT_FIT_LINVT = 2, UT_FIT_ALPHA = 3, UT_FIT_BETA = 4, UT_FIT_YS = 5,
+  UT_FIT_LINVT_F32 = 6, UT_FIT_I8A = 7, UT_FIT_I8RS = 8, UT_FIT_H3 = 9
+};
+typedef struct ut_gp_fit_info {
+  int32_t n, npad;     /* training rows and their padded count */
+  int32_t precision;   /* 64, 32, 16 or 8: the fit's */
+  int32_t l_rows;      /* see UT_FIT_L */
+  int32_t stale;       /* 1: (L^-1)^T and alpha are not written for this factor yet */
+} ut_gp_fit_info;
+int ut_gp_fit_read(ut_ctx* ctx, int32_t what, double* out, ut_gp_fit_info* info);
 /* Dense DE rounds (ut_score_round_de) are lazy when K', the smallest power of
  * two >= 2k, is at most 1024 and less than m: only the K' best-scoring
  * candidates are hashed and deduplicated, which selects what hashing all m

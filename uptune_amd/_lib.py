@@ -74,6 +74,16 @@ class GpHyper(C.Structure):
                 ("lengthscale_host", C.c_void_p)]
 
 
+class GpFitInfo(C.Structure):
+    _fields_ = [("n", C.c_int32), ("npad", C.c_int32), ("precision", C.c_int32), ("l_rows", C.c_int32),
+                ("stale", C.c_int32)]
+
+
+# ut_gp_fit_read's operands (uthot.h UT_FIT_*)
+FIT_OPERANDS = {"L": 0, "LINV": 1, "LINVT": 2, "ALPHA": 3, "BETA": 4, "YS": 5, "LINVT_F32": 6, "I8A": 7, "I8RS": 8,
+                "H3": 9}
+
+
 class Acq(C.Structure):
     _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("xi", C.c_double), ("kappa", C.c_double)]
 
@@ -162,6 +172,7 @@ SIGNATURES = {
                                    C.POINTER(P), C.POINTER(P), C.POINTER(I64)]),
     "ut_gp_prune_bounds": (C.c_int, [P, P, P, I64]),
     "ut_gp_kstar_read": (C.c_int, [P, P, I64, I64, C.POINTER(I32), C.POINTER(I64), C.POINTER(I32)]),
+    "ut_gp_fit_read": (C.c_int, [P, I32, P, C.POINTER(GpFitInfo)]),
     "ut_comm_unique_id": (C.c_int, [P]),
     "ut_comm_init": (C.c_int, [P, I32, I32, P]),
     "ut_comm_destroy": (C.c_int, [P]),

@@ -1265,6 +1265,40 @@ int ut_gp_kstar_read(ut_ctx* c, double* k_out, int64_t c0, int64_t nc, int32_t* 
   return 0;
 }
 
+int ut_gp_fit_read(ut_ctx* c, int32_t what, double* out, ut_gp_fit_info* info) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, what >= UT_FIT_L && what <= UT_FIT_H3, UT_EINVAL, "gp_fit_read: unknown operand");
+  UT_CHECK(c, c->gp_npad_fit > 0 && c->gp_K.p, UT_EINVAL, "gp_fit_read: no fit");
+  // gp_fit_flush, then the fit stream and its flag (UT_ENOTPD)
+  if (int rc = gp_wait_fit(c)) return rc;
+  const int32_t npad = c->gp_npad_fit, prec = c->gp_fit_prec;
+  const bool stale = c->gp_linvt_stale;
+  if (info) *info = ut_gp_fit_info{c->gp_n, npad, prec, c->gp_l_rows, stale ? 1 : 0};
+  UT_CHECK(c, what != UT_FIT_H3, UT_EUNSUPPORTED, "gp_fit_read: the f16x3 planes are not read out");
+  UT_CHECK(c, what != UT_FIT_LINVT_F32 || prec == 32, UT_EUNSUPPORTED, "gp_fit_read: not a precision-32 fit");
+  UT_CHECK(c, (what != UT_FIT_I8A && what != UT_FIT_I8RS) || prec == 8, UT_EUNSUPPORTED,
+           "gp_fit_read: not a precision-8 fit");
+  if (!out) return 0;
+  const size_t nn = (size_t)npad * npad;
+  const double* src = nullptr;
+  size_t cnt = 0;
+  switch (what) {
+    case UT_FIT_L: return launch_fit_read_lower(c, c->gp_K.p, npad, out);
+    case UT_FIT_LINVT_F32: return launch_fit_read_f32(c, c->gp_LinvT_f.p, (int64_t)nn, out);
+    case UT_FIT_I8A: return launch_linv_decode_i8(c, npad, out);
+    case UT_FIT_LINV: src = c->gp_Linv.p, cnt = nn; break;
+    case UT_FIT_LINVT: if (stale) return 0; src = c->gp_LinvT.p, cnt = nn; break;
+    case UT_FIT_ALPHA: if (stale) return 0; src = c->gp_alpha.p, cnt = npad; break;
+    case UT_FIT_BETA: src = c->gp_beta.p, cnt = npad; break;
+    case UT_FIT_YS: src = c->gp_y.p, cnt = npad; break;
+    default:
+      UT_CHECK(c, c->gp_i8rs.p && c->gp_i8rs.n >= (size_t)2 * npad + 2, UT_EINVAL, "gp_fit_read: no int8 row scales");
+      src = c->gp_i8rs.p, cnt = (size_t)2 * npad + 2;
+  }
+  UT_HIP(c, hipMemcpyAsync(out, src, sizeof(double) * cnt, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
 int ut_round_lazy_stats(ut_ctx* c, int64_t* lazy_rounds, int64_t* fallback_rounds) {
   if (!c) return UT_EINVAL;
   if (lazy_rounds) *lazy_rounds = c->lazy_rounds;

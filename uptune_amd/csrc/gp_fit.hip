@@ -907,6 +907,33 @@ int launch_gp_upper_mv(ut_ctx* c, const double* v, double* out) {
   return 0;
 }
 
+// (for tests: ut_gp_fit_read) the factor without what gp_K keeps above its
+// diagonal, and the f32 operand widened
+__global__ __launch_bounds__(256) void k_fit_read_lower(const double* __restrict__ src, int32_t npad,
+                                                        double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)npad * npad) return;
+  out[e] = e % npad <= e / npad ? src[e] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_fit_read_f32(const float* __restrict__ src, int64_t n,
+                                                      double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) out[e] = (double)src[e];
+}
+
+int launch_fit_read_lower(ut_ctx* c, const double* src, int32_t npad, double* out) {
+  hipLaunchKernelGGL(k_fit_read_lower, dim3(grid1((int64_t)npad * npad, 256)), dim3(256), 0, c->stream, src, npad, out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
+int launch_fit_read_f32(ut_ctx* c, const float* src, int64_t n, double* out) {
+  hipLaunchKernelGGL(k_fit_read_f32, dim3(grid1(n, 256)), dim3(256), 0, c->stream, src, n, out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 // Host work over the training rows in 8 threads when it is large (C4: 3,680
 // rows x 707 features, 20.8 MB to stage and every one-hot block to check:
 // ~2-3 ms on one thread, most of it with the device idle between rounds)
@@ -1050,6 +1077,7 @@ int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32
   c->gp_diag_fit = diag;
   c->gp_sn2_fit = h->sigma_n2;
   c->gp_fit_kind = app ? 1 : 0;
+  c->gp_l_rows = app ? std::min(c->gp_l_rows, n0 / NB * NB) : npad;
   c->gp_ready = true;
   ut_ctx::FitJob& j = c->fit_job;
   j.n = n, j.n0 = n0, j.d = d, j.npad = npad, j.dpn = dpn, j.xr0 = xr0;

@@ -344,4 +344,28 @@ int launch_kstar_decode_i8(ut_ctx* c, const int8_t* kst8, int32_t npad, int64_t 
   return 0;
 }
 
+// (for tests: ut_gp_fit_read) L^-1's digit planes back to integers: element
+// (row r, k) has digit p at A[p npad^2 + i8_off(r, k, npad)], plane 0 the most
+// significant; out [npad][npad] = sum_p d_p 256^(5-p), below 2^47 in magnitude: exact
+__global__ __launch_bounds__(256) void k_i8_linv_decode(const int8_t* __restrict__ A, int32_t npad,
+                                                        double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)npad * npad) return;
+  const int32_t r = (int32_t)(e / npad), k = (int32_t)(e - (int64_t)r * npad);
+  const int64_t plane = (int64_t)npad * npad, off = i8_off(r, k, npad);
+  int64_t v = 0;
+#pragma unroll
+  for (int p = 0; p < I8_S; ++p) v = v * 256 + (int64_t)A[p * plane + off];
+  out[e] = (double)v;
+}
+
+int launch_linv_decode_i8(ut_ctx* c, int32_t npad, double* out) {
+  UT_CHECK(c, npad % 32 == 0 && c->gp_i8a.p && c->gp_i8a.n >= (size_t)I8_S * npad * npad, UT_EINVAL,
+           "linv_decode_i8: the fit has no int8 planes");
+  hipLaunchKernelGGL(k_i8_linv_decode, dim3(grid1((int64_t)npad * npad, 256)), dim3(256), 0, c->stream, c->gp_i8a.p,
+                     npad, out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 }  // namespace ut

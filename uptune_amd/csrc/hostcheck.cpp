@@ -27,6 +27,7 @@ long long uthc_sizeof(int which) {
     case 6: return (long long)sizeof(ut_ga_params);
     case 7: return (long long)sizeof(ut_tree_node);
     case 8: return (long long)sizeof(ut_prune_stats);
+    case 9: return (long long)sizeof(ut_gp_fit_info);
     default: return -1;
   }
 }

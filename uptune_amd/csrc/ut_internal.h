@@ -296,6 +296,7 @@ struct ut_ctx {
   double gp_diag_fit = 0.0;    // its sigma_n2 + jitter
   double gp_sn2_fit = 0.0;     // ... and its sigma_n2 alone (the LML gradient's noise component)
   int32_t gp_fit_kind = 0;     // 0 = the last fit refactored, 1 = it appended rows
+  int32_t gp_l_rows = 0;       // leading rows of gp_K whose off-diagonal entries are L's (appends keep B in gp_T)
   bool gp_linvt_stale = false; // gp_LinvT / gp_alpha not yet written for the current factor (gp_ensure_linvt)
   int32_t* flag_host = nullptr;  // pinned readback of the previous fit's flag
   ut::DevBuf<float> gp_Xs_f;    // fp32 copies for the fp32 MFMA path
@@ -929,6 +930,11 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
 // (for tests) columns c0 .. c0 + nc - 1 of K*'s digit planes as doubles, out [npad][nc]
 int launch_kstar_decode_i8(ut_ctx* c, const int8_t* kst8, int32_t npad, int64_t ldk, int64_t c0, int64_t nc,
                            double* out);
+// (for tests) L^-1's digit planes as the integers sum_p a_p 256^(5-p), out [npad][npad] in (row, k) order
+int launch_linv_decode_i8(ut_ctx* c, int32_t npad, double* out);
+// (for tests, gp_fit.hip) out [npad][npad] = the lower triangle of src, zeros above; out [n] = (double)src [n]
+int launch_fit_read_lower(ut_ctx* c, const double* src, int32_t npad, double* out);
+int launch_fit_read_f32(ut_ctx* c, const float* src, int64_t n, double* out);
 // L^-1 [row][k] (n x n, fp64) -> scaled fp16 hi/lo planes, blocked (h3 A operand, rows padded to 256);
 // the scale exponent is derived on the device from max|L^-1| (kept in gp_ctr[16..17])
 int launch_split_h3(ut_ctx* c, const double* Linv, int32_t n, _Float16* dst);

@@ -689,6 +689,25 @@ class BatchEngine:
                 "ut_gp_kstar_read")
         return k, int(npad.value), int(ldk.value), int(fmt.value)
 
+    def gp_fit_read(self, what: str):
+        """ut_gp_fit_read (for tests): one operand of the last fit, after waiting
+        for it.  what: a key of _lib.FIT_OPERANDS ("L", "LINV", "LINVT", "ALPHA",
+        "BETA", "YS", "LINVT_F32", "I8A", "I8RS", "H3")
+        -> (float64 tensor on the device, [npad][npad], [npad] or [2 npad + 2];
+        None while info["stale"] is set for LINVT / ALPHA, info: n, npad,
+        precision, l_rows, stale)"""
+        w = L.FIT_OPERANDS[what]
+        fi = L.GpFitInfo()
+        L.check(self.ctx, self.lib.ut_gp_fit_read(self.ctx, w, None, C.byref(fi)), "ut_gp_fit_read")
+        info = {k: int(getattr(fi, k)) for k, _ in L.GpFitInfo._fields_}
+        if what in ("LINVT", "ALPHA") and info["stale"]:
+            return None, info
+        npad = info["npad"]
+        out = self._empty(*{"ALPHA": (npad,), "BETA": (npad,), "YS": (npad,), "I8RS": (2 * npad + 2,)}.get(
+            what, (npad, npad)))
+        L.check(self.ctx, self.lib.ut_gp_fit_read(self.ctx, w, _ptr(out), None), "ut_gp_fit_read")
+        return out, info
+
     def round_lazy_stats(self) -> Tuple[int, int]:
         """(lazy dense DE rounds, those of them that fell back to hashing every
         candidate) since the context was created; waits for the stream"""
