@@ -6,13 +6,13 @@ Every step runs in a child process of its own under `timeout`, in a fixed
 order, and the first one that fails ends the script (nothing more is started
 on the device after a fault or a hang).  The steps:
 
-  c2_n1024_nc1, c2_n1024_nc4   stage `cons` (k_cons_means + k_cons_apply) of
+  c2_n1024_nc1, c2_n1024_nc4   stage `cons` (k_kstar_sums + k_cons_apply) of
   c2_n4096_nc1, c2_n4096_nc4   ut_gp_cons_prob at the C2 shape (m = 2^20 candidates,
                                d = 64, the bench's data and lengthscale) with 1,024
                                and 4,096 training rows; and, in the same process, the
                                yardstick: stage `feas` of ut_gp_feas_prob with ONE
-                               failed row loaded -- k_feas_sums, the kernel this one
-                               was derived from, over the same training row tiles
+                               failed row loaded -- the same kernel without weights,
+                               over the same training row tiles
                                plus one tile of 128
   c2_round                     the bench's DE round (precision 8, an asynchronous
                                refit per round, no history growth) with and without
@@ -157,8 +157,8 @@ def main():
             return 1
         recs.append(json.loads(line[-1][len("CONS_REC "):]))
         print(json.dumps(recs[-1]), flush=True)
-    res = dict(what="constrained EI's tail (k_cons_means + k_cons_apply, stage `cons`) by device events inside "
-                    "ut_gp_cons_prob, against the feasibility vote with one failed row (k_feas_sums over the same "
+    res = dict(what="constrained EI's tail (k_kstar_sums + k_cons_apply, stage `cons`) by device events inside "
+                    "ut_gp_cons_prob, against the feasibility vote with one failed row (the same kernel over the same "
                     "training row tiles + 1) in the same process; the bench's C2 round by the host clock around "
                     "round + synchronise, alternating one constraint loaded / nothing loaded (medians)",
                steps=recs)

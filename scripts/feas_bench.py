@@ -193,7 +193,7 @@ def main():
             return 1
         recs.append(json.loads(line[-1][len("FEAS_REC "):]))
         print(json.dumps(recs[-1]), flush=True)
-    res = dict(what="the feasibility vote (k_feas_sums + k_feas_apply, stage `feas`) by device events: alone "
+    res = dict(what="the feasibility vote (k_kstar_sums + k_feas_apply, stage `feas`) by device events: alone "
                     "(ut_gp_feas_prob) and inside the bench's rounds; rounds by the host clock around round + "
                     "synchronise, alternating loaded / not loaded (medians)",
                steps=recs)

@@ -16,7 +16,7 @@ a hang).  The steps, at bound passes 32 and 64:
                       regression check: this tree's runs inside the parent's spread
   cons_pNN_qQ         one constraint c = x . w + 0.05 N <= its Q-quantile over the
                       training rows (Q = 0.5, 0.05), reloaded after every fit: the
-                      weighted pruned round, its stage `cons` (k_cons_means over every
+                      weighted pruned round, its stage `cons` (k_kstar_sums over every
                       candidate), survivors and dense flag; the survivors of the same
                       round with the constraint-weight bound switched off
                       (UT_PRUNE_WEIGHT_BOUND=0: the EI bound at f_best_c alone, for
@@ -195,7 +195,7 @@ def main():
     res = dict(what="the bench's C3 pruned round (HPL-64, m = 2^21, n = 4096, k = 256, bound_rows = 256) by the host "
                     "clock around round + synchronise: with nothing loaded on this tree and on the parent commit "
                     "(one process per run, alternating), and with one constraint loaded under "
-                    "ut_gp_set_prune_weighted (stage `cons` = k_cons_means over every candidate, by device events), "
+                    "ut_gp_set_prune_weighted (stage `cons` = k_kstar_sums over every candidate, by device events), "
                     "against the dense constrained fp64 round in the same process",
                regression=reg, steps=recs)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -4,123 +4,21 @@
 // shares L and L^-1; it needs only
 //   alpha_j = K^-1 chat_j = L^-T (L^-1 chat_j)
 // and its posterior mean mu_cj(u) = k*(u) . alpha_j is the K* contraction over
-// the training rows with a weighted epilogue; its variance is the objective's.
+// the training rows with a weighted epilogue (the column-sum K* kernel,
+// gp_kstar_sums.hip, with alpha_j as the rows' weights); its variance is the
+// objective's.
 //   P(u)     = prod_j Phi((tau_j - mu_cj(u)) / sqrt(var(u)))
 //   score(u) = EI(mu, var; f_best_c, xi) P(u),  f_best_c = min ys over the feasible rows
 // (P(u) alone when no row is feasible).  The operands (chat, beta, alpha, tau,
 // f_best_c) are a per-fit cache built by small fp64 kernels after the whole fit;
-// the hot kernel is k_cons_means.
-#include "gp_kstar_tile.h"
+// the hot kernel is k_kstar_sums.
 #include "gp_post.h"
+#include "ut_internal.h"
 
 #include <cmath>
 #include <cstring>
 
 namespace ut {
-
-// The K* contraction (gp_kstar_tile.h) over one row set, the fit's training
-// operand, with a weighted epilogue:
-//   1. the item's alpha_j[row0 .. row0 + 127], j < NC, go to LDS beside rowop;
-//   2. each element's k feeds NC accumulators s_j[col] += k alpha_j[row];
-//   3. no K* is stored;
-//   4. part [RT][NC][ldk] gets the tile's column sums per j (sigma_f2 = 1 in the
-//      exp table: k_cons_apply multiplies).
-// Padding rows (>= n) and columns (>= m) contribute exactly 0: their half-norm
-// is -1e300, the clamp at KSTAR_T_MIN is where 2^k' underflows to 0, and alpha
-// is 0 on padding rows.
-template <bool CAT, int NC>
-__global__ __launch_bounds__(K_NT, 2) void k_cons_means(KstarOperands<double> o, const double* __restrict__ xnorm,
-                                                        int32_t n, int32_t RT, const double* __restrict__ alpha,
-                                                        int32_t CT, const double* __restrict__ cnorm, int64_t m,
-                                                        int32_t* __restrict__ ticket, double* __restrict__ part) {
-  constexpr int MAIN = 2 * K_STAGE;
-  static_assert(K_NT == 2 * K_BM && K_BM == K_BN, "one thread per epilogue operand (rowop)");
-  static_assert(NC >= 1 && NC <= UT_CONS_MAX, "constraints per launch");
-  // the ring, the exp table, the ticket slot, the item's |row|^2 and |u_c|^2, its alpha_j rows
-  __shared__ __attribute__((aligned(16))) double lds[MAIN + EXP_TAB + 2 + (2 + NC) * K_BM];
-  double* etab = lds + MAIN;
-  int32_t& s_item = *reinterpret_cast<int32_t*>(lds + MAIN + EXP_TAB);
-  double* const rowop = lds + MAIN + EXP_TAB + 2;   // [norm 128][cnorm 128][alpha_j 128] x NC
-  const double* const al = rowop + 2 * K_BM;
-  const int t = threadIdx.x, lane0 = t & 63;
-  if (t < EXP_TAB) etab[t] = exp2((double)t / EXP_TAB);   // published by the first ticket barrier
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = w >> 1, wn = w & 1;
-  const int32_t xcd = blockIdx.x & 7;
-  const KstarRows rows = kstar_rows_f64(lane0);
-
-  int32_t nxt = 0;
-  if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
-  for (;;) {
-    if (t == 0) s_item = nxt;
-    __syncthreads();
-    const int lane = kstar_item_lane(lane0);
-    const int32_t j = __builtin_amdgcn_readfirstlane(s_item);
-    const int32_t ct = (j / RT) * 8 + xcd;
-    if (ct >= CT) break;
-    if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
-    const int32_t rt = j % RT;
-    const int64_t col0 = (int64_t)ct * K_BN;
-    const int32_t row0 = rt * K_BM;
-
-    // one 1-KiB glds per epilogue operand: the norms, then alpha_j (rows < npad, columns < ldk are in range)
-    const KstarAcc<double> acc = kstar_contract<double, CAT>(o, rows, row0, col0, lds, w, lane, [=] {
-#pragma unroll
-      for (int op = 0; op < 2 + NC; ++op) {
-        if ((op & 3) != w) continue;
-        const double* src =
-            op == 0 ? xnorm + row0 : op == 1 ? cnorm + col0 : alpha + (int64_t)(op - 2) * o.npad_a + row0;
-        __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + op * K_BM),
-                                         16, 0, 0);
-      }
-    });
-
-    __syncthreads();  // ring free: reuse as the column reduction buffer
-    // the item's half-norms once per item: -1e300 for a padding row (>= n) or column
-    // (>= m), whose k is then exactly 0 without a select in the element code
-    {
-      const double hv = (-0.5 * KSTAR_T_SCALE) * rowop[t];
-      const bool in = t < K_BM ? row0 + t < n : col0 + (t - K_BM) < m;
-      rowop[t] = in ? hv : -1e300;
-    }
-    __syncthreads();
-    double hc[4];
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int cl = wn * 64 + jj * 16 + (lane & 15);
-      hc[jj] = rowop[K_BM + cl];
-    }
-    double s[NC][4];
-#pragma unroll
-    for (int q = 0; q < NC; ++q)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) s[q][jj] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rl = wm * 64 + i * 16 + (lane >> 4) + 4 * r;
-        const double hx = rowop[rl];
-        double a[NC];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) a[q] = al[q * K_BM + rl];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          // t = (C - |x|^2/2 - |u|^2/2) * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]
-          const double x = __builtin_fmax(__builtin_fmin((acc.a[i][jj][r] + hx) + hc[jj], 0.0), KSTAR_T_MIN);
-          const double k = sf2_exp2t_nonpos(x, etab);
-#pragma unroll
-          for (int q = 0; q < NC; ++q) s[q][jj] = __builtin_fma(k, a[q], s[q][jj]);
-        }
-      }
-    }
-    kstar_sums_done(s);
-    kstar_colsums<NC>(s, lds, lane, w, [=](int q, double v) {   // red [NC][2][128]
-      const int64_t col = col0 + t;
-      if (col < m) part[((int64_t)rt * NC + q) * o.ldb + col] = v;
-    });
-  }
-}
 
 // One lane per candidate: mu_cj = sigma_f2 * its partials tile 0 upward, P_j, P
 // (j ascending); the outputs asked for; a finite score becomes
@@ -229,52 +127,21 @@ static int cons_operands(ut_ctx* c) {
   return 0;
 }
 
-template <bool CAT>
-static void launch_cons_means(ut_ctx* c, int32_t nc, int32_t nb, const KstarTrain& tr, const ScoreShape& s, int32_t CT,
-                              int64_t m) {
-  const double* xn = tr.xnorm ? tr.xnorm : c->gp_xnorm.p;
-  const KstarOperands<double> o{tr.XsT,      c->ucand.p,  s.npad, s.ldk,      s.dpad,
-                                tr.cat.acat, tr.cat.bcat, s.npad, tr.cat.nkc, tr.cat.c0 * KSTAR_T_SCALE,
-                                tr.cat.c1 * KSTAR_T_SCALE};
-#define UT_CONS_LAUNCH(NC)                                                                                   \
-  hipLaunchKernelGGL((k_cons_means<CAT, NC>), dim3(nb), dim3(K_NT), 0, c->stream, o, xn, s.n, s.RT, c->cs_alpha.p, \
-                     CT, c->cnorm.p, m, c->gp_ctr.p + 8, c->cs_part.p)
-  switch (nc) {
-    case 1: UT_CONS_LAUNCH(1); break;
-    case 2: UT_CONS_LAUNCH(2); break;
-    case 3: UT_CONS_LAUNCH(3); break;
-    default: UT_CONS_LAUNCH(4); break;
-  }
-#undef UT_CONS_LAUNCH
-}
-
-// The constraint-mean partials (c->cs_part) of the m candidates whose K*
-// operands (shape s) are in c->ucand / c->cnorm / c->bcat, after the per-fit
-// operands.  A column's sums do not depend on its neighbours, so pruned
-// scoring reads a gathered candidate's means at its own index.
-int cons_means(ut_ctx* c, const ScoreShape& s, int64_t m) {
+// The constraint-mean partials (c->cs_part [RT][nc][ld]) of the m candidates
+// whose K* operands (shape s) are in c->ucand / c->cnorm / c->bcat -- or, given
+// ops, in its arrays -- after the per-fit operands.  A column's sums do not
+// depend on its neighbours, so pruned scoring reads a gathered candidate's
+// means at its own index.
+int cons_means(ut_ctx* c, const ScoreShape& s, int64_t m, const CandOps* ops) {
+  const CandOps own{c->ucand.p, c->cnorm.p, c->bcat.p, s.ldk};
+  const CandOps& u = ops ? *ops : own;
   const int32_t nc = c->cs_nc;
-  const int64_t ldk = s.ldk;
-  UT_CHECK(c, s.npad % K_BM == 0 && s.dpad % 4 == 0 && ldk % K_BN == 0 && ldk >= m, UT_EINVAL, "gp_cons: bad padding");
   int rc;
   if ((rc = cons_stale(c, "gp_cons"))) return rc;
   if ((rc = cons_operands(c))) return rc;
-  if (nc > 0) {
-    if ((rc = ensure(c, c->cs_part, (size_t)s.RT * nc * ldk))) return rc;
-    const KstarTrain tr = kstar_train(c, s.cat, c->bcat.p);
-    const bool has_cat = tr.cat.nkc > 0;
-    UT_CHECK(c, s.dpad >= 4 || has_cat, UT_EINVAL, "gp_cons: bad padding");
-    UT_CHECK(c, !has_cat || (tr.cat.acat && tr.cat.bcat), UT_EINVAL, "gp_cons: categorical operands missing");
-    const int32_t CT = (int32_t)(ldk / K_BN);
-    int32_t nb;
-    if ((rc = kstar_grid(c, (int64_t)s.RT * CT, true, &nb))) return rc;
-    if (has_cat)
-      launch_cons_means<true>(c, nc, nb, tr, s, CT, m);
-    else
-      launch_cons_means<false>(c, nc, nb, tr, s, CT, m);
-    UT_LAUNCH_CHECK(c);
-  }
-  return 0;
+  if (nc == 0) return 0;
+  if ((rc = ensure(c, c->cs_part, (size_t)s.RT * nc * u.ld))) return rc;
+  return launch_kstar_sums(c, "gp_cons", s, u, m, c->cs_alpha.p, nc, KstarRowSet{}, 1.0, c->cs_part.p);
 }
 
 // cons_means, then k_cons_apply on the candidates' posterior mu / var with the

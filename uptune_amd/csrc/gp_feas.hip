@@ -4,128 +4,20 @@
 //   k(a, u) = exp(-1/2 |(a - u) / ell|^2 / s^2)
 //   S_ok(u) = sum_{r < n} k(x_r, u),  S_fail(u) = sum_{q < nf} k(f_q, u)
 //   p(u)    = (S_ok + lambda p0) / (S_ok + S_fail + lambda),   score <- score p^gamma
-// Both sums are the K* contraction (gp_kstar_tile.h) with another epilogue, over
-// operands the scoring call already has: the fit's scaled training operand
-// (Xs^T, or its numeric block and the one-hot codes), the candidates' U', norms
-// and codes in c->ucand / c->cnorm / c->bcat.  The failed rows get the same
-// operands, built by the fit's own kernels once per fit (feas_operands).
-#include "gp_kstar_tile.h"
+// Both sums are one launch of the column-sum K* kernel (gp_kstar_sums.hip: no
+// weights, the exponent scaled by 1 / s^2, the failed rows as its second row
+// set), over operands the scoring call already has: the fit's scaled training
+// operand (Xs^T, or its numeric block and the one-hot codes), the candidates'
+// U', norms and codes in c->ucand / c->cnorm / c->bcat.  The failed rows get
+// the same operands, built by the fit's own kernels once per fit
+// (feas_operands).  part [RT_ok + RT_fail][ldk]: the training tiles' sums, then
+// the failed ones'.
 #include "gp_post.h"
+#include "ut_internal.h"
 
 #include <cmath>
 
 namespace ut {
-
-// one row set of the vote: the A operand of the contraction and what goes with it
-struct FeasRows {
-  const double* AT;      // [dpad][npad] scaled rows, transposed, times KSTAR_T_SCALE
-  const double* norm;    // [npad] |row / ell|^2 over the operand's features
-  const int8_t* acat;    // [nkc][npad][128] weighted one-hot codes (categorical)
-  int32_t n, npad;       // rows, padded to 128
-};
-
-// The K* contraction (gp_kstar_tile.h) with another epilogue:
-//   1. one launch covers both row sets: item j of an XCD group is row tile
-//      j % (RT_ok + RT_fail) -- the training operand's tiles, then the failed one's;
-//   2. the exponent is scaled by 1 / s^2 (the categorical c0 + c1 M start with
-//      it: s scales every lengthscale).  Each of its three terms is scaled, not
-//      their sum, so that a padding row's or column's -1e300 stays what it is
-//      whatever s (inv_s2 == 1: the same bits as K*'s (acc + hx) + hc);
-//   3. no K* is stored;
-//   4. part [RT_ok + RT_fail][ldk] gets the tile's column sums of k (no alpha,
-//      no second moment, sigma_f2 = 1 in the exp table).
-// Padding rows (row >= n of their set) and columns (>= m) contribute exactly
-// 0: their half-norm is -1e300, and the clamp at KSTAR_T_MIN is where the
-// table's 2^k' underflows to 0.
-// o: what both row sets share (B, ldb, dpad, bcat, nkc, c0, c1); the item's set fills in the rest
-template <bool CAT>
-__global__ __launch_bounds__(K_NT, 2) void k_feas_sums(FeasRows ok, FeasRows fail, int32_t RT_ok, int32_t RT_fail,
-                                                       KstarOperands<double> o, int32_t CT,
-                                                       const double* __restrict__ cnorm, int64_t m,
-                                                       int32_t* __restrict__ ticket, double* __restrict__ part,
-                                                       double inv_s2) {
-  constexpr int MAIN = 2 * K_STAGE;
-  static_assert(K_NT == 2 * K_BM && K_BM == K_BN, "one thread per epilogue operand (rowop)");
-  // the ring, the exp table, the ticket slot, the item's |row|^2 and |u_c|^2
-  __shared__ __attribute__((aligned(16))) double lds[MAIN + EXP_TAB + 2 + 2 * K_BM];
-  double* etab = lds + MAIN;
-  int32_t& s_item = *reinterpret_cast<int32_t*>(lds + MAIN + EXP_TAB);
-  double* const rowop = lds + MAIN + EXP_TAB + 2;   // [norm 128][cnorm 128]
-  const int t = threadIdx.x, lane0 = t & 63;
-  if (t < EXP_TAB) etab[t] = exp2((double)t / EXP_TAB);   // published by the first ticket barrier
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = w >> 1, wn = w & 1;
-  const int32_t xcd = blockIdx.x & 7;
-  const int32_t RTt = RT_ok + RT_fail;
-  const KstarRows rows = kstar_rows_f64(lane0);
-
-  int32_t nxt = 0;
-  if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
-  for (;;) {
-    if (t == 0) s_item = nxt;
-    __syncthreads();
-    const int lane = kstar_item_lane(lane0);
-    const int32_t j = __builtin_amdgcn_readfirstlane(s_item);   // uniform: the row set's pointers stay scalar
-    const int32_t ct = (j / RTt) * 8 + xcd;
-    if (ct >= CT) break;
-    if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
-    const int32_t rtt = j % RTt;              // the partial's row in `part`
-    const bool second = rtt >= RT_ok;
-    const FeasRows& R = second ? fail : ok;
-    const int32_t rt = second ? rtt - RT_ok : rtt;
-    const int32_t nrows = R.n;
-    const int64_t col0 = (int64_t)ct * K_BN;
-    const int32_t row0 = rt * K_BM;
-    KstarOperands<double> oi = o;
-    oi.AT = R.AT, oi.lda = R.npad, oi.acat = R.acat, oi.npad_a = R.npad;
-    const double* const norm = R.norm;
-
-    const KstarAcc<double> acc = kstar_contract<double, CAT>(oi, rows, row0, col0, lds, w, lane, [=] {
-      if (w < 2) {  // one 1-KiB glds per operand (rows < npad, columns < ldk are in range)
-        const double* src = w == 0 ? norm + row0 : cnorm + col0;
-        __builtin_amdgcn_global_load_lds(src + lane * 2, (__attribute__((address_space(3))) void*)(rowop + w * K_BM),
-                                         16, 0, 0);
-      }
-    });
-
-    __syncthreads();  // ring free: reuse as the column reduction buffer
-    // the item's half-norms once per item, not once per element (as k_gp_kstar<int8_t> keeps
-    // its rows'): scaled by 1 / s^2, and -1e300 for a padding row (>= n of its set) or column
-    // (>= m), whose k is then exactly 0 without a select in the element code
-    {
-      const double hv = ((-0.5 * KSTAR_T_SCALE) * rowop[t]) * inv_s2;
-      const bool in = t < K_BM ? row0 + t < nrows : col0 + (t - K_BM) < m;
-      rowop[t] = in ? hv : -1e300;
-    }
-    __syncthreads();
-    double hc[4];
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int cl = wn * 64 + jj * 16 + (lane & 15);
-      hc[jj] = rowop[K_BM + cl];
-    }
-    double s[1][4] = {{0.0, 0.0, 0.0, 0.0}};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rl = wm * 64 + i * 16 + (lane >> 4) + 4 * r;
-        const double hx = rowop[rl];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          // t = (C - |x|^2/2 - |u|^2/2) / s^2 * 256 / ln 2, clamped to [-1000 * 256 / ln 2, 0]
-          const double x = __builtin_fmax(__builtin_fmin((acc.a[i][jj][r] * inv_s2 + hx) + hc[jj], 0.0), KSTAR_T_MIN);
-          s[0][jj] += sf2_exp2t_nonpos(x, etab);
-        }
-      }
-    }
-    kstar_sums_done(s);
-    kstar_colsums<1>(s, lds, lane, w, [=](int, double v) {   // red [2][128]
-      const int64_t col = col0 + t;
-      if (col < m) part[(int64_t)rtt * o.ldb + col] = v;
-    });
-  }
-}
 
 // One lane per candidate: the OK partials tile 0 upward, then the failed
 // ones; p; the outputs asked for; a finite score times p^gamma.
@@ -190,31 +82,17 @@ static int feas_vote(ut_ctx* c, const ScoreShape& s, int64_t m, double* p_out, d
            "gp_feas: the fit scores with the categorical K* and failed row " + std::to_string(c->fs_bad_row) +
                " is not one-hot in an ENUM block / 0-1 in a BOOL column");
   const int64_t ldk = u.ld;
-  UT_CHECK(c, s.npad % K_BM == 0 && s.dpad % 4 == 0 && ldk % K_BN == 0 && ldk >= m, UT_EINVAL, "gp_feas: bad padding");
   int rc;
   if ((rc = feas_operands(c))) return rc;
   const int32_t nfpad = nf > 0 ? gp_npad(nf) : 0;
-  const int32_t RT_ok = s.RT, RT_fail = nfpad / K_BM;
+  const int32_t RT_ok = s.RT, RT_fail = nfpad / NPAD;
   if ((rc = ensure(c, c->fs_part, (size_t)(RT_ok + RT_fail) * ldk))) return rc;
-  const KstarTrain tr = kstar_train(c, s.cat, u.bcat);
-  const bool has_cat = tr.cat.nkc > 0;
-  UT_CHECK(c, s.dpad >= 4 || has_cat, UT_EINVAL, "gp_feas: bad padding");
-  UT_CHECK(c, !has_cat || (tr.cat.acat && tr.cat.bcat), UT_EINVAL, "gp_feas: categorical operands missing");
-  const FeasRows ok{tr.XsT, tr.xnorm ? tr.xnorm : c->gp_xnorm.p, tr.cat.acat, s.n, s.npad};
-  const FeasRows fail = s.cat ? FeasRows{c->fs_XsT_num.p, c->fs_norm_num.p, c->fs_acat.p, nf, nfpad}
-                              : FeasRows{c->fs_XsT.p, c->fs_norm.p, nullptr, nf, nfpad};
-  const int32_t CT = (int32_t)(ldk / K_BN);
-  int32_t nb;
-  if ((rc = kstar_grid(c, (int64_t)(RT_ok + RT_fail) * CT, true, &nb))) return rc;
+  const KstarRowSet fail = s.cat ? KstarRowSet{c->fs_XsT_num.p, c->fs_norm_num.p, c->fs_acat.p, nullptr, nf, nfpad}
+                                 : KstarRowSet{c->fs_XsT.p, c->fs_norm.p, nullptr, nullptr, nf, nfpad};
   const ut_feas_params& fp = c->fs_par;
-  const double inv_s2 = 1.0 / (fp.ell_scale * fp.ell_scale);
-  // (AT, lda, acat, npad_a: each item's row set)
-  const KstarOperands<double> o{nullptr, u.ucand,     0, ldk,        s.dpad,
-                                nullptr, tr.cat.bcat, 0, tr.cat.nkc, tr.cat.c0 * KSTAR_T_SCALE,
-                                tr.cat.c1 * KSTAR_T_SCALE};
-  hipLaunchKernelGGL(has_cat ? k_feas_sums<true> : k_feas_sums<false>, dim3(nb), dim3(K_NT), 0, c->stream, ok, fail,
-                     RT_ok, RT_fail, o, CT, u.cnorm, m, c->gp_ctr.p + 8, c->fs_part.p, inv_s2);
-  UT_LAUNCH_CHECK(c);
+  if ((rc = launch_kstar_sums(c, "gp_feas", s, u, m, nullptr, 0, fail, 1.0 / (fp.ell_scale * fp.ell_scale),
+                              c->fs_part.p)))
+    return rc;
   // the prior success rate: as given, or the share of successes among the rows in use
   const double p0 = fp.prior > 0.0 ? fp.prior : (double)s.n / (double)(s.n + nf);
   hipLaunchKernelGGL(k_feas_apply, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, RT_ok, RT_fail, c->fs_part.p, ldk,
@@ -250,10 +128,7 @@ int gp_feas_prob_impl(ut_ctx* c, const double* values, const double* features, i
   if ((rc = gp_fit_flush(c))) return rc;
   if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit_x, 0));
   const ScoreShape s = score_shape(c, m, false);
-  if ((rc = ensure(c, c->cnorm, (size_t)s.ldk))) return rc;
-  if ((rc = ensure(c, c->ucand, s.urows() * s.ldk))) return rc;
-  if ((rc = launch_prep_cand(c, features, ld, m, s.d, s.dpad, c->ucand.p, s.ldk, c->cnorm.p))) return rc;
-  c->ucand_cat = false;
+  if ((rc = prep_cand_features(c, s, features, ld, m))) return rc;
   mark(c, "cnorm");
   return feas_vote(c, s, m, p_out, s_ok_out, s_fail_out, nullptr);
 }

@@ -244,18 +244,13 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar(KstarOperands<double> o, i
   const KstarRows rows = PERM ? kstar_rows_perm(lane) : kstar_rows_f64(lane);
   const bool want2 = !PERM && MU && part2 != nullptr;
 
-  // the next item's ticket is taken at the start of the current one, so its
-  // atomic round trip overlaps the item's first K stage instead of sitting
-  // between two items (one ticket past the end per workgroup is drawn and unused)
   int32_t nxt = 0;
-  if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+  kstar_draw(nxt, ticket, xcd);
   for (;;) {
-    if (t == 0) s_item = nxt;
-    __syncthreads();
-    const int32_t j = s_item;
-    const int32_t ct = (j / RTe) * 8 + xcd;
+    int32_t j;
+    const int32_t ct = kstar_item(nxt, s_item, xcd, RTe, j);
     if (ct >= CT) break;
-    if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+    kstar_draw(nxt, ticket, xcd);
     const int32_t rt = j % RTe;
     KstarItem it{lane, w >> 1, w & 1, rt * K_BM, n, (int64_t)ct * K_BN, rowop, etab, {}};
 
@@ -337,14 +332,12 @@ __global__ __launch_bounds__(K_NT, 2) void k_gp_kstar_f32c(KstarOperands<float> 
   const int32_t RTe = RT - rt0;
   const KstarRows rows = kstar_rows_f32(lane);
   int32_t nxt = 0;
-  if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+  kstar_draw(nxt, ticket, xcd);
   for (;;) {
-    if (t == 0) s_item = nxt;
-    __syncthreads();
-    const int32_t j = s_item;
-    const int32_t ct = (j / RTe) * 8 + xcd;
+    int32_t j;
+    const int32_t ct = kstar_item(nxt, s_item, xcd, RTe, j);
     if (ct >= CT) break;
-    if (t == 0) nxt = atomicAdd(&ticket[xcd], 1);
+    kstar_draw(nxt, ticket, xcd);
     const int32_t rt = rt0 + j % RTe;
     const int64_t col0 = (int64_t)ct * K_BN;
     const int32_t row0 = rt * K_BM;
@@ -413,19 +406,15 @@ int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, 
   const KstarCat& cat = a.train.cat;
   const int64_t m = a.m, ldk = a.ldk;
   const bool has_cat = cat.nkc > 0;
-  UT_CHECK(c, npad % K_BM == 0 && a.dpad % 4 == 0 && (a.dpad >= 4 || has_cat) && ldk % K_BN == 0 && ldk >= m,
-           UT_EINVAL, "gemm_kstar_f32c: bad padding");
-  UT_CHECK(c, !has_cat || (cat.acat && cat.bcat), UT_EINVAL, "gemm_kstar_f32c: categorical operands missing");
+  int rc;
+  if ((rc = kstar_check(c, "gemm_kstar_f32c", npad, a.dpad, ldk, m, cat))) return rc;
   UT_CHECK(c, a.part && a.part2 && a.part3, UT_EINVAL, "gemm_kstar_f32c: partial outputs missing");
   const int32_t RT = npad / K_BM;
   UT_CHECK(c, a.rt0 >= 0 && a.rt0 < RT, UT_EINVAL, "gemm_kstar_f32c: bad first row tile");
   const int32_t CT = (int32_t)(ldk / K_BN);
   int32_t nb;
-  int rc;
   if ((rc = kstar_grid(c, (int64_t)(RT - a.rt0) * CT, false, &nb))) return rc;
-  const KstarOperands<float> o{XsT_f,    ucand_f,  npad, ldk,     a.dpad,
-                               cat.acat, cat.bcat, npad, cat.nkc, (float)(cat.c0 * KSTAR_T_SCALE),
-                               (float)(cat.c1 * KSTAR_T_SCALE)};
+  const KstarOperands<float> o = kstar_operands<float>(XsT_f, ucand_f, cat, npad, ldk, a.dpad);
   hipLaunchKernelGGL(has_cat ? k_gp_kstar_f32c<true> : k_gp_kstar_f32c<false>, dim3(nb), dim3(K_NT), 0, c->stream, o,
                      a.rt0, RT, CT, a.train.xnorm ? a.train.xnorm : c->gp_xnorm.p, a.cn ? a.cn : c->cnorm.p,
                      c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, ldk, a.part, a.part2, a.part3);
@@ -443,9 +432,8 @@ int launch_gemm_kstar(ut_ctx* c, int prec, int32_t npad, const KstarArgs& a) {
   void* kst = a.kst;
   double *part = a.part, *part2 = a.part2;
   const bool has_cat = cat.nkc > 0;
-  UT_CHECK(c, npad % K_BM == 0 && dpad % 4 == 0 && (dpad >= 4 || has_cat) && ldk % K_BN == 0 && ldk >= m, UT_EINVAL,
-           "gemm_kstar: bad padding");
-  UT_CHECK(c, !has_cat || (cat.acat && cat.bcat), UT_EINVAL, "gemm_kstar: categorical operands missing");
+  int rc;
+  if ((rc = kstar_check(c, "gemm_kstar", npad, dpad, ldk, m, cat))) return rc;
   UT_CHECK(c, prec == 64 || prec == 32 || prec == 16 || prec == 8, UT_EINVAL, "gemm_kstar: bad precision");
   UT_CHECK(c, part != nullptr || prec == 64 || prec == 8, UT_EINVAL,
            "gemm_kstar: fp32 / h3 mode takes the mean partial here");
@@ -457,13 +445,10 @@ int launch_gemm_kstar(ut_ctx* c, int prec, int32_t npad, const KstarArgs& a) {
   // sums every row); the other precisions always store everything
   const int32_t store_rt = store_rows < 0 ? RT : (store_rows + K_BM - 1) / K_BM;
   int32_t nb;
-  int rc;
   if ((rc = kstar_grid(c, (int64_t)RTe * CT, true, &nb))) return rc;
   const double* xnorm = a.train.xnorm ? a.train.xnorm : c->gp_xnorm.p;
   const double* cnorm = a.cn ? a.cn : c->cnorm.p;
-  const KstarOperands<double> o{XsT,      ucand,    npad, ldk,     dpad,
-                                cat.acat, cat.bcat, npad, cat.nkc, cat.c0 * KSTAR_T_SCALE,
-                                cat.c1 * KSTAR_T_SCALE};
+  const KstarOperands<double> o = kstar_operands<double>(XsT, ucand, cat, npad, ldk, dpad);
 #define UT_KSTAR_LAUNCH(TS, MU, CAT, KST, PART, KSCALE, LOOFF, SRT, PART2)                                      \
   hipLaunchKernelGGL((k_gp_kstar<TS, MU, CAT>), dim3(nb), dim3(K_NT), 0, c->stream, o, RT, CT, xnorm, cnorm,    \
                      c->gp_alpha.p, c->gp_sf2, c->gp_n, m, c->gp_ctr.p + 8, KST, ldk, PART, KSCALE, LOOFF, SRT, \
@@ -507,11 +492,14 @@ __global__ void k_gp_prep_cand(const double* __restrict__ feat, int64_t ld, int6
   cn[i] = s;
 }
 
-int launch_prep_cand(ut_ctx* c, const double* feat, int64_t ld, int64_t m, int32_t d, int32_t dpad, double* u,
-                     int64_t ldu, double* cn) {
-  hipLaunchKernelGGL(k_gp_prep_cand, dim3(grid1(ldu, 256)), dim3(256), 0, c->stream, feat, ld, m, d, dpad,
-                     c->gp_inv_ell.p, u, ldu, cn);
+int prep_cand_features(ut_ctx* c, const ScoreShape& s, const double* feat, int64_t ld, int64_t m) {
+  int rc;
+  if ((rc = ensure(c, c->cnorm, (size_t)s.ldk))) return rc;
+  if ((rc = ensure(c, c->ucand, s.urows() * s.ldk))) return rc;
+  hipLaunchKernelGGL(k_gp_prep_cand, dim3(grid1(s.ldk, 256)), dim3(256), 0, c->stream, feat, ld, m, s.d, s.dpad,
+                     c->gp_inv_ell.p, c->ucand.p, s.ldk, c->cnorm.p);
   UT_LAUNCH_CHECK(c);
+  c->ucand_cat = false;
   return 0;
 }
 

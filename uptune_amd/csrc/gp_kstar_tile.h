@@ -1,9 +1,11 @@
 // gp_kstar_tile.h -- the K* distance contraction, once: the tile's sizes and
 // vector types, the glds stage loaders, one item's contraction (int8 code
-// stages, then the fp64 or f32 ones, through the 2-stage ring) and the column
-// reduction of an item's sums.  k_gp_kstar / k_gp_kstar_f32c (gp_gemm.hip),
-// k_feas_sums (gp_feas.hip) and k_cons_means (gp_cons.hip) keep their LDS
-// layout, their ticket arithmetic and their epilogue.
+// stages, then the fp64 or f32 ones, through the 2-stage ring), the ticket draw
+// of its persistent kernels, the column reduction of an item's sums, and the
+// host side's operand struct and padding check.  Its kernels are k_gp_kstar /
+// k_gp_kstar_f32c (gp_gemm.hip: K* stored, or the f32 bound pass) and
+// k_kstar_sums (gp_kstar_sums.hip: column sums alone, for the failure vote and
+// the constraint means); each keeps its LDS layout and its epilogue.
 //   256-thread workgroups (2 x 2 waves of 64 x 64) on 128 x 128 tiles, K in
 //   steps of 16, a 2-stage glds ring (64 KiB) so two workgroups share a CU
 #pragma once
@@ -130,6 +132,47 @@ struct KstarOperands {
   int32_t npad_a, nkc;
   T c0, c1;
 };
+// ... of a launch over npad training rows (AT [dpad][npad]) and ldk candidates (B [dpad][ldk])
+template <typename T>
+inline KstarOperands<T> kstar_operands(const T* AT, const T* B, const KstarCat& cat, int32_t npad, int64_t ldk,
+                                       int32_t dpad) {
+  return {AT,       B,        npad, ldk,     dpad,
+          cat.acat, cat.bcat, npad, cat.nkc, (T)(cat.c0 * KSTAR_T_SCALE),
+          (T)(cat.c1 * KSTAR_T_SCALE)};
+}
+// ... and the padding it relies on: whole row and column tiles, whole k4 steps, something to contract
+inline int kstar_check(ut_ctx* c, const char* who, int32_t npad, int32_t dpad, int64_t ldk, int64_t m,
+                       const KstarCat& cat) {
+  const bool has_cat = cat.nkc > 0;
+  UT_CHECK(c, npad % K_BM == 0 && dpad % 4 == 0 && (dpad >= 4 || has_cat) && ldk % K_BN == 0 && ldk >= m, UT_EINVAL,
+           std::string(who) + ": bad padding");
+  UT_CHECK(c, !has_cat || (cat.acat && cat.bcat), UT_EINVAL, std::string(who) + ": categorical operands missing");
+  return 0;
+}
+
+// The ticket draw of a persistent K* kernel: the items of XCD group xcd are
+// ticket[xcd]'s values j = 0, 1, ..., item j being row tile j % RTe of column
+// tile ct = (j / RTe) * 8 + xcd, until ct >= CT.  The next item's ticket is
+// taken at the start of the current one, so its atomic round trip overlaps the
+// item's first K stage instead of sitting between two items (one ticket past
+// the end per workgroup is drawn and unused).  The barrier that publishes the
+// item through s_item (LDS) also publishes the exp table built before the loop.
+// kstar_draw takes a ticket (thread 0 holds it); kstar_item publishes it as the
+// current item j and returns its column tile; the loop is
+//   kstar_draw(nxt, ...);
+//   for (;;) { ct = kstar_item(nxt, ..., j); if (ct >= CT) break; kstar_draw(nxt, ...); ... }
+// UNIFORM: j through readfirstlane, where per-item pointers chosen by it are to
+// stay scalar.
+__device__ __forceinline__ void kstar_draw(int32_t& nxt, int32_t* __restrict__ ticket, int32_t xcd) {
+  if (threadIdx.x == 0) nxt = atomicAdd(&ticket[xcd], 1);
+}
+template <bool UNIFORM = false>
+__device__ __forceinline__ int32_t kstar_item(int32_t nxt, int32_t& s_item, int32_t xcd, int32_t RTe, int32_t& j) {
+  if (threadIdx.x == 0) s_item = nxt;
+  __syncthreads();
+  j = UNIFORM ? __builtin_amdgcn_readfirstlane(s_item) : s_item;
+  return (j / RTe) * 8 + xcd;
+}
 
 // the 64 x 64 outputs of a wave, [i][jj][r]: row group i, column group jj, C/D row r
 template <typename T>
@@ -147,9 +190,9 @@ __device__ __forceinline__ kf4 kstar_mfma(float a, float b, kf4 c) {
 
 // The lane index afresh for an item.  The per-lane glds addresses derived from a
 // loop-invariant lane index are hoisted to kernel entry; where the epilogue leaves
-// no registers for them beside the 128 accumulator registers (k_feas_sums,
-// k_cons_means) they are spilled around the item loop, and recomputing them per
-// item from this opaque copy is the cheaper end.
+// no registers for them beside the 128 accumulator registers (k_kstar_sums)
+// they are spilled around the item loop, and recomputing them per item from
+// this opaque copy is the cheaper end.
 __device__ __forceinline__ int kstar_item_lane(int lane) {
   asm volatile("" : "+v"(lane));
   return lane;
@@ -167,7 +210,7 @@ __device__ __forceinline__ int kstar_item_lane(int lane) {
 // the kernel then has no scratch (k_gp_kstar, k_gp_kstar_f32c: the hoisted glds
 // addresses fit and cost nothing per item), and kstar_item_lane of it, taken
 // once per item and used by the epilogue too, where it otherwise spills
-// (k_feas_sums, k_cons_means).  The accumulators are a local array copied into the
+// (k_kstar_sums).  The accumulators are a local array copied into the
 // value returned: taken by reference, or built in the returned struct, the
 // kernels without code stages spill 108-116 B/lane.
 template <typename T, bool CAT, typename First>
@@ -278,7 +321,7 @@ __device__ __forceinline__ KstarAcc<T> kstar_contract(const KstarOperands<T>& o,
 // Every sum of an item's epilogue is complete here.  Without this the optimizer
 // sinks column group jj's whole chain of exps below the lane test of group
 // jj - 1's reduction, every row's LDS operands stay live across all four, and
-// k_feas_sums / k_cons_means / k_gp_kstar<_Float16> spill.  The other k_gp_kstar
+// k_kstar_sums / k_gp_kstar<_Float16> spill.  The other k_gp_kstar
 // and k_gp_kstar_f32c do not spill without it and lose 1 % of the pruned round
 // with it: they do not call it.
 template <int NA>

@@ -62,7 +62,7 @@ __device__ __forceinline__ double part_sum(const double* __restrict__ part, int3
 // What pruned scoring needs of the loaded weights, by value (nc == 0 and no
 // vote: nothing is loaded, every kernel takes its unweighted path).
 //   part: cs_part [RT][nc][ldp], the constraint-mean partials of EVERY candidate
-//   of the call by its own index (k_cons_means); st: cs_stats.
+//   of the call by its own index (cons_means); st: cs_stats.
 struct PruneW {
   int32_t nc, RT;
   const double* part;

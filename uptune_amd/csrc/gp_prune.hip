@@ -17,7 +17,7 @@
 //   Pub_j = 1 where tau_j - mu_cj >= 0, else Phi((tau_j - mu_cj) / sqrt(var_ub))
 // bounds S: Phi of a negative ratio rises with sigma and var <= var_ub holds
 // bitwise (above); the vote gets no bound (factor 1).  mu_cj is exact for every
-// candidate: k_cons_means runs once over the round's K* operands (fp64, at both
+// candidate: k_kstar_sums runs once over the round's K* operands (fp64, at both
 // passes) and the exact stage reads the same partials at the candidate's own
 // index.  erfc is only nearly monotone in floating point, so the 1e-12 / 1e-300
 // margin goes on after the product.  A bound keeps its exact flag only when the
@@ -300,8 +300,6 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   if ((rc = ensure(c, c->mu_part, (size_t)RT * ldk))) return rc;
   if ((rc = ensure(c, c->var_part, (size_t)RT * ldk))) return rc;
   if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldk))) return rc;
-  if ((rc = ensure(c, c->cnorm, (size_t)ldk))) return rc;
-  if ((rc = ensure(c, c->ucand, s.urows() * ldk))) return rc;
   if (cat && (rc = ensure(c, c->bcat, (size_t)c->space.cat_k * ldk))) return rc;
   if ((rc = ensure(c, c->pr_mu, (size_t)ldk))) return rc;
   if ((rc = ensure(c, c->pr_ub, (size_t)ldk))) return rc;
@@ -317,8 +315,7 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   if ((rc = ensure(c, c->pr_exact, (size_t)ldk))) return rc;
   // 1. K* with the mean in its epilogue, 2. the first R row tiles of L^-1 K*^T
   if (feat) {
-    if ((rc = launch_prep_cand(c, feat, ld, m, s.d, dpad, c->ucand.p, ldk, c->cnorm.p))) return rc;
-    c->ucand_cat = false;
+    if ((rc = prep_cand_features(c, s, feat, ld, m))) return rc;
     mark(c, "prep");
   }
   if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));   // K* takes mu = k* . alpha

@@ -209,16 +209,13 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
   // (i8: the variance and mean partials come per 64-row tile)
   if ((rc = ensure(c, c->mu_part, (size_t)(i8 ? 2 * RT : RT) * ldk))) return rc;
   if ((rc = ensure(c, c->var_part, (size_t)(i8 ? 2 * RT : RT) * ldk))) return rc;
-  if ((rc = ensure(c, c->cnorm, (size_t)ldk))) return rc;
-  if ((rc = ensure(c, c->ucand, s.urows() * ldk))) return rc;
   if (i8) {
     UT_CHECK(c, npad <= I8_MAX_K, UT_EINVAL, "gp_score: precision 8 takes at most 16384 training points");
     if ((rc = ensure(c, c->pr_idx, (size_t)ldk))) return rc;
     if ((rc = ensure(c, c->pr_count, 1))) return rc;
   }
   if (feat) {
-    if ((rc = launch_prep_cand(c, feat, ld, m, s.d, s.dpad, c->ucand.p, ldk, c->cnorm.p))) return rc;
-    c->ucand_cat = false;
+    if ((rc = prep_cand_features(c, s, feat, ld, m))) return rc;
     mark(c, "cnorm");
   }
   // every K* of this call: all m candidates from c->ucand / c->cnorm into c->kst

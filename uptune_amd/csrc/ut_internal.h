@@ -646,6 +646,20 @@ struct CandOps {
   const int8_t* bcat;
   int64_t ld;
 };
+// gp_kstar_sums.hip: the K* contraction with a column-sum epilogue, no K* stored.  One row set of a launch: the
+// contraction's A operand and what goes with it
+struct KstarRowSet {
+  const double* AT = nullptr;     // [dpad][npad] scaled rows, transposed, times KSTAR_T_SCALE
+  const double* norm = nullptr;   // [npad] |row / ell|^2 over the operand's features
+  const int8_t* acat = nullptr;   // [nkc][npad][128] weighted one-hot codes (categorical)
+  const double* w = nullptr;      // [nw][npad] the rows' weight vectors (nw > 0; 0 on padding rows)
+  int32_t n = 0, npad = 0;        // rows, padded to 128 (0: an empty set)
+};
+// part [(s.npad + b.npad) / 128][max(nw, 1)][u.ld] = per row tile, the fit's training rows' then b's, the sums over
+// the tile's rows r of k(r, u) (nw = 0, with every lengthscale times 1 / sqrt(inv_s2)) or of k(r, u) w_q[r]
+// (q < nw <= UT_CONS_MAX, w: the training rows' weights; inv_s2 unused), for the m candidates of u (shape s)
+int launch_kstar_sums(ut_ctx* c, const char* who, const ScoreShape& s, const CandOps& u, int64_t m, const double* w,
+                      int32_t nw, const KstarRowSet& b, double inv_s2, double* part);
 // ... p_out[j] = p of the m columns of ops (no score is touched)
 int feas_prob_cols(ut_ctx* c, const ScoreShape& s, const CandOps& ops, int64_t m, double* p_out);
 // gp_cons.hip: constrained EI.  cons_weight: score[i] = EI(mu_i, var_i; f_best_c, xi) P_i (P_i when no row is
@@ -659,8 +673,8 @@ int cons_stale(ut_ctx* c, const char* who);
 int cons_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const double* mu, const double* var,
                 double* score);
 // ... its first half alone: the per-fit operands (cs_alpha, cs_stats) and the constraint-mean partials of the m
-// candidates in c->ucand / c->cnorm / c->bcat into c->cs_part [RT][cs_nc][s.ldk] (k_cons_means)
-int cons_means(ut_ctx* c, const ScoreShape& s, int64_t m);
+// candidates in c->ucand / c->cnorm / c->bcat (or in ops) into c->cs_part [RT][cs_nc][ld] (k_kstar_sums)
+int cons_means(ut_ctx* c, const ScoreShape& s, int64_t m, const CandOps* ops = nullptr);
 constexpr int CS_INFO = 4 * UT_CONS_MAX;   // cs_stats[CS_INFO] = f_best_c, [CS_INFO + 1] = n_feasible
 // gp_score.hip: UT_EUNSUPPORTED for a UCB score while rows (feas) or values (cons) would weight it
 int weights_refuse_ucb(ut_ctx* c, const ut_acq* acq, bool feas, bool cons);
@@ -834,8 +848,9 @@ int alloc_split_x8(ut_ctx* c, int32_t npad, int32_t K);
 int launch_split_x8(ut_ctx* c, const double* XsT, int32_t K, int32_t npad);
 int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m, void* kst, int64_t ldk,
                         DevBuf<int8_t>& u8, DevBuf<double>& scol);
-int launch_prep_cand(ut_ctx* c, const double* feat, int64_t ld, int64_t m, int32_t d, int32_t dpad, double* u,
-                     int64_t ldu, double* cn);
+// a caller's feature matrix feat [s.d][ld] becomes the K* operands of the m candidates of a call of shape s (dense
+// over every feature) in c->ucand / c->cnorm, grown as needed
+int prep_cand_features(ut_ctx* c, const ScoreShape& s, const double* feat, int64_t ld, int64_t m);
 // categorical K*: the K* operands of the candidate side when the fit is in
 // categorical mode -- numeric features / ell (dpad_num rows), their norms, and
 // one-hot codes into c->bcat, from the values; cat_dpad(c) rows
