@@ -655,6 +655,31 @@ int ut_gp_prune_bounds(ut_ctx* ctx, double* ub_out, uint8_t* exact_out, int64_t 
  * dense call each leave nothing to read) or for columns outside [0, ldk]. */
 int ut_gp_kstar_read(ut_ctx* ctx, double* k_out, int64_t c0, int64_t nc, int32_t* npad, int64_t* ldk,
                      int32_t* format);
+/* for tests: the plane-occupancy mask of the digit planes ut_gp_kstar_read
+ * decodes, as k_gp_kstar_q wrote it beside them: mask_out [npad / 32][ldk / 32]
+ * (device bytes, copied on ctx's stream) has bit p of byte [r][c] set iff digit
+ * plane p (0 = most significant) of the 32 training rows x 32 candidates block
+ * (r, c) of K* holds a non-zero digit; the padding's bytes are 0.  The
+ * precision-8 variance contraction skips the zero planes' loads and products
+ * by it while the last call's K* had a zero plane in at least 1 block of 16
+ * (UT_VAR_SKIP, read per call: 0 never, 1 always; both kernels give the same bits).
+ * *rows, *cols (may be NULL): npad / 32 and ldk / 32; mask_out may be NULL (the
+ * sizes only).  Nothing is launched or recorded on the scoring paths for this.
+ * Returns UT_NOMASK (a status, not an error: no message is set) when the planes the last dense call left
+ * have no mask: written by k_gp_kstar<int8_t> (UT_KSTAR_Q=0, categorical fits)
+ * or rewritten as fp64 rows by the whole-round fallback; UT_EINVAL when there
+ * are no precision-8 planes to describe (ut_gp_kstar_read's conditions). */
+#define UT_NOMASK 1
+int ut_gp_kstar_mask_read(ut_ctx* ctx, uint8_t* mask_out, int32_t* rows, int64_t* cols);
+/* for tests: the precision-8 variance contraction's per-tile partials of the
+ * last dense precision-8 call that kept its digit planes (ut_gp_kstar_read's
+ * format 8), copied on ctx's stream: var_part_out and mu_part_out (device
+ * doubles, either may be NULL) get [npad / 64][ldk], row rt the column sums of
+ * v^2 and of v beta over the 64 training rows of tile rt; columns at and past
+ * that call's m are not written by the contraction and hold no meaning.
+ * *rows, *ldk (may be NULL): npad / 64 and ldk.  Nothing is launched or
+ * recorded on the scoring paths for this.  UT_EINVAL otherwise. */
+int ut_gp_i8_parts_read(ut_ctx* ctx, double* var_part_out, double* mu_part_out, int32_t* rows, int64_t* ldk);
 /* for tests: one operand of the last fit, as doubles.  Waits for that fit
  * (a staged one is enqueued first), then copies, on ctx's stream, into out
  * (caller-provided device doubles; may be NULL: the info only).  *info (may be

@@ -22,6 +22,7 @@ UT_X_NONE, UT_X_OX1, UT_X_OX3, UT_X_PX, UT_X_CX, UT_X_PMX = range(6)
 CROSSOVERS = {"op3_cross_OX1": UT_X_OX1, "op3_cross_OX3": UT_X_OX3, "op3_cross_PX": UT_X_PX,
               "op3_cross_CX": UT_X_CX, "op3_cross_PMX": UT_X_PMX}
 
+NOMASK = 1   # UT_NOMASK: ut_gp_kstar_mask_read's "the planes have no mask" status
 ERRORS = {
     -1: "UT_EINVAL", -2: "UT_EHIP", -3: "UT_ENOSPACE", -4: "UT_EUNSUPPORTED", -5: "UT_ENOTPD", -6: "UT_ENOMEM", -7: "UT_ECOMM",
 }
@@ -172,6 +173,8 @@ SIGNATURES = {
                                    C.POINTER(P), C.POINTER(P), C.POINTER(I64)]),
     "ut_gp_prune_bounds": (C.c_int, [P, P, P, I64]),
     "ut_gp_kstar_read": (C.c_int, [P, P, I64, I64, C.POINTER(I32), C.POINTER(I64), C.POINTER(I32)]),
+    "ut_gp_kstar_mask_read": (C.c_int, [P, P, C.POINTER(I32), C.POINTER(I64)]),
+    "ut_gp_i8_parts_read": (C.c_int, [P, P, P, C.POINTER(I32), C.POINTER(I64)]),
     "ut_gp_fit_read": (C.c_int, [P, I32, P, C.POINTER(GpFitInfo)]),
     "ut_comm_unique_id": (C.c_int, [P]),
     "ut_comm_init": (C.c_int, [P, I32, I32, P]),

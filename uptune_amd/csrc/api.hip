@@ -1265,6 +1265,33 @@ int ut_gp_kstar_read(ut_ctx* c, double* k_out, int64_t c0, int64_t nc, int32_t* 
   return 0;
 }
 
+int ut_gp_kstar_mask_read(ut_ctx* c, uint8_t* mask_out, int32_t* rows, int64_t* cols) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, c->kst_fmt == 8 || c->kst_fmt == 64, UT_EINVAL,
+           "gp_kstar_mask_read: no precision-8 dense scoring call since the last fit");
+  if (c->kst_fmt != 8 || !c->kst_masked) return UT_NOMASK;
+  const int32_t r = c->kst_npad / 32;
+  const int64_t cc = c->kst_ldk / 32;
+  if (rows) *rows = r;
+  if (cols) *cols = cc;
+  if (mask_out)
+    UT_HIP(c, hipMemcpyAsync(mask_out, c->kmask.p, (size_t)r * (size_t)cc, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
+int ut_gp_i8_parts_read(ut_ctx* c, double* var_part_out, double* mu_part_out, int32_t* rows, int64_t* ldk) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, c->kst_fmt == 8 && c->var_part.p && c->mu_part.p, UT_EINVAL,
+           "gp_i8_parts_read: no precision-8 dense scoring call that kept its digit planes since the last fit");
+  const int32_t r = c->kst_npad / I8_BM;
+  if (rows) *rows = r;
+  if (ldk) *ldk = c->kst_ldk;
+  const size_t bytes = sizeof(double) * (size_t)r * (size_t)c->kst_ldk;
+  if (var_part_out) UT_HIP(c, hipMemcpyAsync(var_part_out, c->var_part.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (mu_part_out) UT_HIP(c, hipMemcpyAsync(mu_part_out, c->mu_part.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
 int ut_gp_fit_read(ut_ctx* c, int32_t what, double* out, ut_gp_fit_info* info) {
   if (!c) return UT_EINVAL;
   UT_CHECK(c, what >= UT_FIT_L && what <= UT_FIT_H3, UT_EINVAL, "gp_fit_read: unknown operand");

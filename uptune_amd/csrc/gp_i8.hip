@@ -33,15 +33,33 @@
 // accepted only if Emu <= tau * sigma as well.
 //
 // Layouts (bytes): A = [6][npad/32][npad][32] (L^-1 rows), B = [6][npad/32][ldk][32]
-// (written by k_gp_kstar<int8_t>); row / candidate r's 16-byte chunk c of a
-// 32-k piece sits at position c ^ ((r >> 3) & 1), so the 32x32x32 MFMA's
-// fragment reads (32 rows x 2 chunks per ds_read_b128) hit distinct banks.
+// (written by k_gp_kstar_q, gp_kq.hip, for numeric fits; by k_gp_kstar<int8_t>
+// under UT_KSTAR_Q=0 and for categorical fits); row / candidate r's 16-byte
+// chunk c of a 32-k piece sits at position c ^ ((r >> 3) & 1), so the 32x32x32
+// MFMA's fragment reads (32 rows x 2 chunks per ds_read_b128) hit distinct banks.
+// k_gp_kstar_q also writes B's plane-occupancy mask, kmask [npad/32][ldk/32]
+// bytes: bit p set iff plane p of that 32-k x 32-candidate block holds a
+// non-zero digit (one k stage of a 128-candidate strip: one aligned dword).
+// K* has one exponent for the whole fit, so an element below 2^-9 of sf2's
+// scale has a zero top digit and one below 2^-49 six zero digits: far from the
+// data (short lengthscales) whole blocks of planes are zero, and
+// k_gp_var_i8<true> neither loads them nor issues their MFMAs.  A product with
+// an all-zero operand adds exact zeros to an exact int32 sum: no output bit
+// changes, and the error contract above is the unmasked kernel's.  The masked
+// kernel's guarded MFMA groups cost a dense K* about 3 %, so gp_score.hip runs
+// it only while the last call's K* was sparse (ut_ctx::var_skip_hint).
 #include "ut_internal.h"
 
 namespace ut {
 
 constexpr int I8_PL = I8_BM * I8_BK;   // one plane's piece of a stage: 64 rows x 32 k = 2 KiB
 constexpr double I8_C = 3.5 * 0x1p-49;
+
+// a wave-uniform 64-bit value, said so to the compiler (it then stays in SGPRs)
+__device__ __forceinline__ uint64_t i8_uniform64(uint64_t v) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(v >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)v);
+}
 
 template <int N>
 __device__ __forceinline__ void i8_vm_wait() {
@@ -157,15 +175,31 @@ int launch_split_i8(ut_ctx* c, int32_t n, int32_t npad) {
 // triangular): those stages skip their MFMAs.  Probe on random digits
 // (scripts/exp/i8var_probe.hip, n = 1024, m = 2^20): 9.26 ms against 10.0 for
 // 64-candidate tiles with a 3-stage ring.
+//
+// MASK (k_gp_kstar_q's occupancy mask, npad <= I8_MASK_MAX_K): lane l of every
+// wave fetches the strip's mask dword of k stage l once per item (both tiles
+// of the pair share the strip) and ORs its four bytes into a 6-bit stage mask;
+// a ballot gives the live stages as one 64-bit scalar set, and a live stage's
+// mask comes back by readlane, so the loop stays scalar-uniform.  A tile walks
+// its live stages only (ascending, the short tile descending, the next live
+// one prefetched into the other ring slot).  K* is non-negative under one
+// exponent, so a block's zero planes are its leading ones: a stage whose first
+// plane with a digit is q0 loads and multiplies B planes q0 .. 5 only (and the
+// A planes they meet: pa + qb < 6), a stage with q0 = 0 issues the unmasked
+// loads and all 21 products, and a tile with no live stage writes the zeros
+// that zero accumulators give.  (A zero plane behind a non-zero one is loaded
+// and multiplied as the zeros it holds.)
 // ---------------------------------------------------------------------------
 constexpr int I8_WN = 128;                 // candidates per tile
 constexpr int I8_BPL = I8_WN * I8_BK;      // one B plane's piece of a stage (4 KiB)
 
+template <bool MASK>
 __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__ Ad, const int8_t* __restrict__ Bd,
                                                       int32_t npad, int64_t ldk, int32_t RT, int32_t CT, int64_t m,
                                                       int32_t* __restrict__ ticket, const double* __restrict__ rs,
                                                       const double* __restrict__ beta, double* __restrict__ part,
-                                                      double* __restrict__ mpart, int32_t Sg) {
+                                                      double* __restrict__ mpart, int32_t Sg,
+                                                      const uint8_t* __restrict__ kmask) {
   constexpr int STAGE = I8_S * (I8_PL + I8_BPL);
   constexpr int NW = 6 * I8_S / 4;   // glds per wave per stage
   __shared__ __attribute__((aligned(16))) int8_t lds[2 * STAGE + 4 * I8_WN * 8 + 2 * I8_BM * 8 + 16];
@@ -181,24 +215,35 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
 
   // stage kt of tile (row0, col0): A planes 2 KiB (2 pieces), B planes 4 KiB (4 pieces);
   // wave w moves pieces w + 4j
-  auto issue = [&](int32_t row0, int64_t col0, int32_t kt, int8_t* st) {
+  // (all_c false: only the B planes from q0 on, and the A planes pa that meet
+  // one of them in a product, pa + q0 < 6)
+  auto issue = [&](int32_t row0, int64_t col0, int32_t kt, int8_t* st, auto all_c, int q0) {
+    constexpr bool ALL = decltype(all_c)::value;
 #pragma unroll
     for (int j = 0; j < NW; ++j) {
       const int u = w + 4 * j;
       const int8_t* src;
       int8_t* dst;
+      bool need;
       if (u < 2 * I8_S) {
         const int pl = u >> 1, h = u & 1;
         src = Ad + pl * aplane + ((int64_t)kt * npad + row0) * 32 + h * 1024;
         dst = st + pl * I8_PL + h * 1024;
+        need = ALL || pl + q0 < I8_S;
       } else {
         const int v = u - 2 * I8_S, pl = v >> 2, h = v & 3;
         src = Bd + pl * bplane + ((int64_t)kt * ldk + col0) * 32 + h * 1024;
         dst = st + I8_S * I8_PL + pl * I8_BPL + h * 1024;
+        need = ALL || pl >= q0;
       }
-      __builtin_amdgcn_global_load_lds(src + lane * 16, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+      if constexpr (ALL)
+        __builtin_amdgcn_global_load_lds(src + lane * 16, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+      else if (need)
+        __builtin_amdgcn_global_load_lds(src + lane * 16, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
     }
   };
+  constexpr std::integral_constant<bool, true> all_planes{};
+  constexpr std::integral_constant<bool, false> live_planes{};
 
   const int32_t P = (RT + 1) / 2;
   const int c = lane >> 5;
@@ -219,6 +264,15 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
     const int32_t ct = (G * Sg + q / P) * 8 + xcd;
     if (ct >= CT) break;   // uniform: the whole workgroup leaves
     const int nrt = RT - 1 - p == p ? 1 : 2;
+    // lane l: the 6-bit mask of k stage l of this strip (the long tile's stages
+    // include the short tile's); live: the stages with any plane
+    uint32_t m6 = 0;
+    uint64_t live = 0;
+    uint32_t dw = 0;   // (the fetch is issued here and first read in the long tile, below)
+    if constexpr (MASK) {
+      const int32_t nkl = (RT - p) * (I8_BM / I8_BK);   // <= 64
+      if (lane < nkl) dw = *reinterpret_cast<const uint32_t*>(kmask + (int64_t)lane * (ldk >> 5) + ct * 4);
+    }
     for (int ri = 0; ri < nrt; ++ri) {
       if (ri > 0) __syncthreads();   // the previous tile's ring, red and srs are read
       const int32_t rt = __builtin_amdgcn_readfirstlane(ri == 0 ? RT - 1 - p : p);
@@ -227,6 +281,28 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
       const int32_t nk = (row0 + I8_BM) / I8_BK;   // >= 2
       const bool rev = ri > 0;
       auto ktof = [&](int32_t u) -> int32_t { return rev ? nk - 1 - u : u; };
+      uint64_t lv = 0;   // (MASK) the tile's live stages not yet issued
+      if constexpr (MASK) {
+        if (ri == 0) {   // (the fetch's first use: the wave waits for it here)
+          dw |= dw >> 16;
+          m6 = (dw | (dw >> 8)) & 0x3fu;
+          live = i8_uniform64(__builtin_amdgcn_ballot_w64(m6 != 0));
+        }
+        lv = i8_uniform64(live & (nk >= 64 ? ~0ull : (1ull << nk) - 1));
+        if (lv == 0) {
+          // no live stage: what zero accumulators give.  (The barrier: a one-tile
+          // item has none otherwise between reading s_item and the next ticket.)
+          if (ri == 0) __syncthreads();
+          if (t < I8_WN) {
+            const int64_t col = col0 + t;
+            if (col < m) {
+              part[(int64_t)rt * ldk + col] = 0.0;
+              mpart[(int64_t)rt * ldk + col] = 0.0;
+            }
+          }
+          continue;
+        }
+      }
       i8v16 acc[2][I8_S];
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj)
@@ -237,29 +313,87 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
       if (w < 2 && lane < 32)   // 64 row scales / betas: one 512-B glds each, retired with stage 0
         __builtin_amdgcn_global_load_lds((w == 0 ? rs : beta) + row0 + lane * 2,
                                          (__attribute__((address_space(3))) void*)(w == 0 ? srs : sbt), 16, 0, 0);
-      issue(row0, col0, ktof(0), lds);
-      for (int32_t u = 0; u < nk; ++u) {
-        i8_vm_wait<0>();                        // stage u landed (this wave's pieces)
-        __builtin_amdgcn_s_barrier();           // every wave's stage u landed; stage u - 1 fully read
-        asm volatile("" ::: "memory");
-        if (u + 1 < nk) issue(row0, col0, ktof(u + 1), lds + ((u + 1) & 1) * STAGE);
-        const int32_t kt = ktof(u);
-        if (kt * I8_BK >= row0 + 32 * wm + 32) continue;   // rows of this wave: all zero here
-        const int8_t* st = lds + (u & 1) * STAGE;
-        i8v4 af[I8_S];
+      if constexpr (!MASK) {
+        issue(row0, col0, ktof(0), lds, all_planes, 0);
+        for (int32_t u = 0; u < nk; ++u) {
+          i8_vm_wait<0>();                        // stage u landed (this wave's pieces)
+          __builtin_amdgcn_s_barrier();           // every wave's stage u landed; stage u - 1 fully read
+          asm volatile("" ::: "memory");
+          if (u + 1 < nk) issue(row0, col0, ktof(u + 1), lds + ((u + 1) & 1) * STAGE, all_planes, 0);
+          const int32_t kt = ktof(u);
+          if (kt * I8_BK >= row0 + 32 * wm + 32) continue;   // rows of this wave: all zero here
+          const int8_t* st = lds + (u & 1) * STAGE;
+          i8v4 af[I8_S];
 #pragma unroll
-        for (int pp = 0; pp < I8_S; ++pp) af[pp] = *reinterpret_cast<const i8v4*>(st + pp * I8_PL + aoff);
+          for (int pp = 0; pp < I8_S; ++pp) af[pp] = *reinterpret_cast<const i8v4*>(st + pp * I8_PL + aoff);
 #pragma unroll
-        for (int qb = 0; qb < I8_S; ++qb) {
-          i8v4 bf[2];
+          for (int qb = 0; qb < I8_S; ++qb) {
+            i8v4 bf[2];
 #pragma unroll
-          for (int jj = 0; jj < 2; ++jj) bf[jj] = *reinterpret_cast<const i8v4*>(st + qb * I8_BPL + boff[jj]);
-          // digit products of group g = pa + qb (0-based): pairs with (pa + 1) + (qb + 1) <= 7
+            for (int jj = 0; jj < 2; ++jj) bf[jj] = *reinterpret_cast<const i8v4*>(st + qb * I8_BPL + boff[jj]);
+            // digit products of group g = pa + qb (0-based): pairs with (pa + 1) + (qb + 1) <= 7
 #pragma unroll
-          for (int pa = 0; pa + qb < I8_S; ++pa)
+            for (int pa = 0; pa + qb < I8_S; ++pa)
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-              acc[jj][pa + qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[pa], bf[jj], acc[jj][pa + qb], 0, 0, 0);
+              for (int jj = 0; jj < 2; ++jj)
+                acc[jj][pa + qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[pa], bf[jj], acc[jj][pa + qb], 0, 0, 0);
+          }
+        }
+      } else {
+        // the live stages in the tile's order; q0: a stage's first plane with a
+        // digit.  K* is non-negative under one exponent, so a block's zero planes
+        // are its leading ones: planes q0 .. 5 are loaded and multiplied (a zero
+        // plane among them as the zeros it holds), planes 0 .. q0 - 1 neither.
+        auto take = [&]() -> int32_t {
+          const int32_t k = rev ? 63 - __builtin_clzll(lv) : __builtin_ctzll(lv);
+          lv &= ~(1ull << k);
+          return k;
+        };
+        auto issue_live = [&](int32_t k, int8_t* st, int q0) {   // (a dense stage: the unmasked loads)
+          if (q0 == 0) issue(row0, col0, k, st, all_planes, 0);
+          else issue(row0, col0, k, st, live_planes, q0);
+        };
+        int32_t kt = take();
+        int q0 = __builtin_ctz(__builtin_amdgcn_readlane(m6, kt));
+        issue_live(kt, lds, q0);
+        for (int32_t u = 0;; ++u) {
+          i8_vm_wait<0>();                        // this live stage landed (this wave's pieces)
+          __builtin_amdgcn_s_barrier();           // ... in every wave; the one before it fully read
+          asm volatile("" ::: "memory");
+          const bool more = lv != 0;
+          int32_t ktn = 0;
+          int q0n = 0;
+          if (more) {
+            ktn = take();
+            q0n = __builtin_ctz(__builtin_amdgcn_readlane(m6, ktn));
+            issue_live(ktn, lds + ((u + 1) & 1) * STAGE, q0n);
+          }
+          if (kt * I8_BK < row0 + 32 * wm + 32) {   // (else: rows of this wave all zero here)
+            // One body for every q0, its MFMA groups under scalar guards (a second,
+            // unguarded body beside it made the compiler spill the accumulators
+            // inside this loop; reading a plane's fragments ahead of its guard put
+            // a scratch reload into the loads of a partly live stage).  An A plane
+            // that was not loaded is read as stale bytes and meets no product.
+            const int8_t* st = lds + (u & 1) * STAGE;
+            i8v4 af[I8_S];
+#pragma unroll
+            for (int pp = 0; pp < I8_S; ++pp) af[pp] = *reinterpret_cast<const i8v4*>(st + pp * I8_PL + aoff);
+#pragma unroll
+            for (int qb = 0; qb < I8_S; ++qb) {
+              if (qb < q0) continue;   // (scalar)
+              i8v4 bf[2];
+#pragma unroll
+              for (int jj = 0; jj < 2; ++jj) bf[jj] = *reinterpret_cast<const i8v4*>(st + qb * I8_BPL + boff[jj]);
+#pragma unroll
+              for (int pa = 0; pa + qb < I8_S; ++pa)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj)
+                  acc[jj][pa + qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[pa], bf[jj], acc[jj][pa + qb], 0, 0, 0);
+            }
+          }
+          if (!more) break;
+          kt = ktn;
+          q0 = q0n;
         }
       }
       // epilogue: v = 2^-16 (T_2 + 2^-8 (T_3 + ...)) * 2^(ea_row + eb), column sums
@@ -298,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
 }
 
 int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk, int64_t m, double* part,
-                       double* mpart) {
+                       double* mpart, const uint8_t* kmask) {
   UT_CHECK(c, npad % 128 == 0 && npad <= I8_MAX_K && ldk % I8_WN == 0 && ldk >= m, UT_EINVAL,
            "gemm_var_i8: bad padding");
   UT_CHECK(c, c->gp_i8a.p && c->gp_i8rs.p, UT_EINVAL, "gemm_var_i8: the fit has no int8 planes");
@@ -309,8 +443,13 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
   const int32_t W = nb / 8, Sg = W / P > 1 ? W / P : 1;
   UT_HIP(c, hipMemsetAsync(c->gp_ctr.p, 0, sizeof(int32_t) * 8, c->stream));
-  hipLaunchKernelGGL(k_gp_var_i8, dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT, m,
-                     c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg);
+  // (past I8_MASK_MAX_K rows a tile has more than 64 stages: the unmasked kernel)
+  if (kmask && npad <= I8_MASK_MAX_K)
+    hipLaunchKernelGGL(k_gp_var_i8<true>, dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT, m,
+                       c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg, kmask);
+  else
+    hipLaunchKernelGGL(k_gp_var_i8<false>, dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT, m,
+                       c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg, nullptr);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

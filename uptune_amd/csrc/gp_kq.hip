@@ -192,7 +192,7 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
     const double* __restrict__ cnorm, const double* __restrict__ alpha, double sf2, int32_t n, int64_t m,
     TS* __restrict__ kst, double* __restrict__ part, double kscale, int64_t lo_off,
     int32_t store_rt, double* __restrict__ part2, const int8_t* __restrict__ acat, const int8_t* __restrict__ bcat,
-    int32_t nkc, double cat_c0, double cat_c1) {
+    int32_t nkc, double cat_c0, double cat_c1, uint8_t* __restrict__ kmask, int32_t* __restrict__ kcount) {
   constexpr bool I8 = sizeof(TS) == 1;
   constexpr int OPS = 2 * Q_BM + 2 * Q_BN;              // one item's epilogue operands (doubles)
   // a 3-slot ring (80 KiB in all: two workgroups per CU)
@@ -232,6 +232,8 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
   const int32_t Wq = W / RT, Wr = W % RT;    // an item's successor: W items on
   const int ops_n = (MU || w != 1) ? 1 : 0;   // this wave's epilogue-operand load per item
   int32_t cnt = 0;                           // vector-memory instructions issued (counted ones)
+  int32_t nsparse = 0;                       // (I8) blocks of this wave with a zero digit plane
+  int32_t mask_st = 0;                       // (I8) this item stored its mask byte
   int32_t at0 = 0, at1 = 0, at2 = 0;         // cnt just after stage g's loads, slot g mod 3
   // this wave's digit-stage pieces u = 0..5: piece q = w + 4u is half q & 1 of
   // plane (q >> 1) of A (u < 3) or of B (plane (q >> 1) - 6): the plane and
@@ -434,6 +436,20 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
         int8_t* dst = reinterpret_cast<int8_t*>(kst) + p * lo_off + i8_off(col, row0 + wm * 32 + 16 * c, ldk);
         *reinterpret_cast<uint4*>(dst) = make_uint4(a0[0], a0[1], a1[0], a1[1]);
       }
+      // the plane-occupancy byte of this wave's 32-row x 32-candidate block, from
+      // the digits just stored: bit p set iff plane p holds a non-zero digit
+      // (kmask [npad / 32][ldk / 32]: the variance contraction skips the products
+      // of all-zero planes, gp_i8.hip).  The launcher presets every byte to 0x3f,
+      // so a full block stores nothing (a dense K* pays no byte stores: they cost
+      // C2 at ell = 2 about 0.15 ms of its 3.1); any other block's byte is one
+      // lane's store, counted with the plane stores below.
+      uint32_t mk = 0;
+#pragma unroll
+      for (int p = 0; p < I8_S; ++p)
+        if (__builtin_amdgcn_ballot_w64((pw[p][0] | pw[p][1] | pw[p][2] | pw[p][3]) != 0) != 0) mk |= 1u << p;
+      mask_st = mk != 0x3fu ? 1 : 0;   // (scalar)
+      if (mask_st && lane == 0) kmask[(int64_t)((row0 >> 5) + wm) * (ldk >> 5) + (col0 >> 5) + wn] = (uint8_t)mk;
+      nsparse += mask_st;   // (this wave's blocks with a zero plane, added up once below)
     }
     if constexpr (MU) {
       // each wave's 32 rows: one partial per 32-row half tile (no cross-wave
@@ -446,7 +462,7 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
         if (want2) part2[o] = s2v;
       }
     }
-    if constexpr (I8) cnt += I8_S;   // the plane stores
+    if constexpr (I8) cnt += I8_S + mask_st;   // the plane stores and the mask byte, where one was stored
     else if (store) cnt += 16;        // the rows' stores
     cob = cob == 2 ? 0 : cob + 1;
     crt += Wr;
@@ -457,6 +473,9 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
     }
     if (cctq * 8 + xcd >= CT) break;   // (uniform: no next item)
   }
+  // how sparse this K* is, for the host's choice of the next call's variance kernel
+  if constexpr (I8)
+    if (lane == 0 && nsparse != 0) atomicAdd(kcount, nsparse);
 }
 
 // ---------------------------------------------------------------------------
@@ -497,6 +516,10 @@ int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m,
   int rc;
   if ((rc = ensure(c, u8, (size_t)I8_S * (K32 > 0 ? K32 : 1) * 32 * ldk))) return rc;
   if ((rc = ensure(c, scol, (size_t)ldk))) return rc;
+  if ((rc = ensure(c, c->kmask, (size_t)(npad / 32) * (size_t)(ldk / 32)))) return rc;
+  if ((rc = ensure(c, c->kmask_cnt, 1))) return rc;
+  UT_HIP(c, hipMemsetAsync(c->kmask_cnt.p, 0, sizeof(int32_t), c->stream));
+  UT_HIP(c, hipMemsetAsync(c->kmask.p, 0x3f, (size_t)(npad / 32) * (size_t)(ldk / 32), c->stream));
   hipLaunchKernelGGL(k_q_split_u, dim3(grid1(ldk, 256)), dim3(256), 0, c->stream, ucand, dpad, ldk, K32,
                      c->gp_q8.p + 1, pair ? -24 : -16, u8.p, scol.p);
   UT_LAUNCH_CHECK(c);
@@ -507,11 +530,13 @@ int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m,
 #define UT_KQ_LAUNCH(PAIR)                                                                                     \
   hipLaunchKernelGGL((k_gp_kstar_q<int8_t, false, false, PAIR>), dim3(nb), dim3(Q_NT), 0, c->stream, xd.p, npad,    \
                      u8.p, ldk, K32, scol.p, RT, CT, c->gp_xnorm.p, c->cnorm.p, c->gp_alpha.p, c->gp_sf2, c->gp_n, m,     \
-                     (int8_t*)kst, nullptr, kscale, (int64_t)npad * ldk, RT, nullptr, nullptr, nullptr, 0, 0.0, 0.0)
+                     (int8_t*)kst, nullptr, kscale, (int64_t)npad * ldk, RT, nullptr, nullptr, nullptr, 0, 0.0, 0.0,  \
+                     c->kmask.p, c->kmask_cnt.p)
   if (pair) UT_KQ_LAUNCH(true);
   else UT_KQ_LAUNCH(false);
 #undef UT_KQ_LAUNCH
   UT_LAUNCH_CHECK(c);
+  c->kst_masked = true;   // c->kmask describes the planes now in kst (gp_score_dense clears it)
   return 0;
 }
 

@@ -184,6 +184,7 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
   UT_CHECK(c, acq != nullptr, UT_EINVAL, "gp_score: acq is NULL");
   if (m <= 0) return 0;
   c->kst_fmt = 0;   // (ut_gp_kstar_read: set again where this call returns with K* in c->kst)
+  c->kst_masked = false;   // (set by launch_gemm_kstar_q alone: every other writer of kst leaves no mask)
   if (int rc0 = gp_fit_flush(c)) return rc0;
   const int prec = c->gp_fit_prec;
   const bool fp32 = prec != 64;  // fp32, h3 (f16x3) and i8: K* stores a reduced-precision K*
@@ -245,8 +246,16 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
   if (dup_ready && !i8) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));
   mark(c, "var_wait");  // the wait for the fit (and the dup mask) is not variance time
   if (i8) {
+    // K*'s all-zero digit-plane blocks are skipped where k_gp_kstar_q left their
+    // mask (exact: zero products add nothing to an int32 sum).  The masked
+    // kernel's guarded MFMA groups cost a dense K* about 3 % (C2 at ell = 2:
+    // 10.5 -> 10.9 ms), so it runs while the last call's K* had a zero plane in
+    // at least 1 block of 16 (c->var_skip_hint, from the count read back below).
+    // UT_VAR_SKIP (read per call): 0 keeps the unmasked kernel, 1 the masked one.
+    const char* vs_env = getenv("UT_VAR_SKIP");
+    const bool vskip = c->kst_masked && (vs_env ? atoi(vs_env) != 0 : c->var_skip_hint);
     if ((rc = launch_gemm_var_i8(c, npad, reinterpret_cast<const int8_t*>(c->kst.p), ldk, m, c->var_part.p,
-                                 c->mu_part.p)))
+                                 c->mu_part.p, vskip ? c->kmask.p : nullptr)))
       return rc;
   } else if ((rc = launch_gemm_var(c, prec, fp32 ? (const void*)c->gp_LinvT_f.p : (const void*)c->gp_LinvT.p, npad,
                                    c->kst.p, ldk, npad, m, c->var_part.p, fp32 ? nullptr : c->gp_beta.p,
@@ -265,13 +274,18 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
     mark(c, "finalize");
     int64_t nf = 0;
     UT_HIP(c, hipMemcpyAsync(&nf, c->pr_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    int32_t nsparse = 0;
+    if (c->kst_masked)
+      UT_HIP(c, hipMemcpyAsync(&nsparse, c->kmask_cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     UT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->kst_masked) c->var_skip_hint = (int64_t)nsparse * 16 >= (int64_t)(npad / 32) * (ldk / 32);
     c->i8_recomputed = nf;
     if (nf > 0 && (rc = gp_ensure_linvt(c))) return rc;   // (the fp64 contraction reads (L^-1)^T)
     if (nf * 2 > m) {
       // most candidates need fp64: the whole K* (fp64, over the planes) and the
       // fp64 contraction, with the mean from its epilogue
       c->i8_recomputed = -1;
+      c->kst_masked = false;   // (kst becomes fp64 rows)
       if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldk))) return rc;
       if ((rc = launch_gemm_kstar(c, 64, npad, ka))) return rc;
       if ((rc = launch_gemm_var64(c, npad, c->kst.p, ldk, npad, m, c->var_part.p))) return rc;

@@ -326,7 +326,24 @@ struct ut_ctx {
   ut::DevBuf<int8_t> gp_x8, u8;
   ut::DevBuf<int64_t> gp_q8;
   ut::DevBuf<double> scol;
-  int32_t kstar_q = 1;   // UT_KSTAR_Q=0: precision-8 K* on k_gp_kstar<int8_t> (the fp64 MFMA)
+  // k_gp_kstar_q's plane-occupancy mask [npad / 32][ldk / 32]: bit p of a byte is
+  // set iff plane p of that 32-row x 32-candidate block of K* holds a non-zero
+  // digit (the four bytes of a 128-candidate variance strip at one k stage: one
+  // aligned dword).  kst_masked: it describes the planes now in kst -- set by
+  // launch_gemm_kstar_q, cleared at the start of every dense call and where the
+  // whole-round fp64 fallback rewrites kst; k_gp_kstar<int8_t> (UT_KSTAR_Q=0,
+  // categorical fits) writes none, and its planes take the dense variance path.
+  ut::DevBuf<uint8_t> kmask;
+  bool kst_masked = false;
+  // kmask_cnt [1]: the blocks of the last k_gp_kstar_q whose mask is not 0x3f
+  // (padding included), read back with each precision-8 call's recompute count.
+  // var_skip_hint: the last such call had enough of them (1 in 16) for the masked
+  // variance kernel to pay; a dense K* (long lengthscales) runs the unmasked
+  // kernel from the next call on.  Both kernels give the same bits, so a stale
+  // hint costs time only.  UT_VAR_SKIP=1 forces the masked kernel, 0 the unmasked.
+  ut::DevBuf<int32_t> kmask_cnt;
+  bool var_skip_hint = true;
+  int32_t kstar_q = 1;  // UT_KSTAR_Q=0: precision-8 K* on k_gp_kstar<int8_t> (the fp64 MFMA)
   int32_t gp_i8_eb = 0;          // K* digit scale: y = k* 2^-eb <= 0.49
   double i8_tol = 0x1p-20;       // accepted relative variance error (ut_gp_set_i8_tol)
   int64_t i8_recomputed = 0;     // candidates of the last score recomputed in fp64 (-1: all, dense)
@@ -843,7 +860,8 @@ int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, 
 // the int8 MFMA (digit planes of the training operand from the fit, of the
 // candidates' operand per call into u8 / scol), stored as the six digit planes
 // the int8 variance reads (no mean partial, no one-hot codes; norms in
-// c->gp_xnorm / c->cnorm).
+// c->gp_xnorm / c->cnorm).  launch_gemm_kstar_q also writes the planes'
+// occupancy mask into c->kmask and sets c->kst_masked.
 int alloc_split_x8(ut_ctx* c, int32_t npad, int32_t K);
 int launch_split_x8(ut_ctx* c, const double* XsT, int32_t K, int32_t npad);
 int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m, void* kst, int64_t ldk,
@@ -940,8 +958,11 @@ int launch_split_i8(ut_ctx* c, int32_t n, int32_t npad);
 // the variance contraction from K*'s digit planes (kst8, [6][npad/32][ldk][32]):
 // part [npad / 64][ldk] column partials of |v|^2
 // part / mpart: per 64-row tile the column sums of v^2 and of v beta (the mean)
+// kmask: the planes' occupancy mask [npad / 32][ldk / 32] (k_gp_kstar_q's), whose
+// all-zero blocks are neither loaded nor multiplied; nullptr: no mask
+constexpr int32_t I8_MASK_MAX_K = 2048;   // the masked kernel keeps a tile's live stages in one 64-bit set
 int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk, int64_t m, double* part,
-                       double* mpart);
+                       double* mpart, const uint8_t* kmask);
 // (for tests) columns c0 .. c0 + nc - 1 of K*'s digit planes as doubles, out [npad][nc]
 int launch_kstar_decode_i8(ut_ctx* c, const int8_t* kst8, int32_t npad, int64_t ldk, int64_t c0, int64_t nc,
                            double* out);

@@ -689,6 +689,34 @@ class BatchEngine:
                 "ut_gp_kstar_read")
         return k, int(npad.value), int(ldk.value), int(fmt.value)
 
+    def gp_kstar_mask_read(self):
+        """ut_gp_kstar_mask_read (for tests): the plane-occupancy mask of the digit
+        planes the last dense precision-8 call left, bit p of byte [r][c] set iff
+        plane p of the 32-row x 32-candidate block (r, c) of K* holds a non-zero digit
+        -> uint8 tensor [npad / 32][ldk / 32] on the device, or None when those
+        planes have no mask (UT_NOMASK)"""
+        rows, cols = C.c_int32(), C.c_int64()
+        rc = self.lib.ut_gp_kstar_mask_read(self.ctx, None, C.byref(rows), C.byref(cols))
+        if rc == L.NOMASK:
+            return None
+        L.check(self.ctx, rc, "ut_gp_kstar_mask_read")
+        mk = self._empty(rows.value, cols.value, dtype=torch.uint8)
+        L.check(self.ctx, self.lib.ut_gp_kstar_mask_read(self.ctx, _ptr(mk), None, None), "ut_gp_kstar_mask_read")
+        return mk
+
+    def gp_i8_parts_read(self):
+        """ut_gp_i8_parts_read (for tests): the precision-8 variance contraction's
+        per-64-row-tile column sums of the last dense call that kept its planes
+        -> (var_part, mu_part), float64 [npad / 64][ldk] on the device (columns at
+        and past that call's m hold no meaning)"""
+        rows, ldk = C.c_int32(), C.c_int64()
+        L.check(self.ctx, self.lib.ut_gp_i8_parts_read(self.ctx, None, None, C.byref(rows), C.byref(ldk)),
+                "ut_gp_i8_parts_read")
+        vp, mp = self._empty(rows.value, ldk.value), self._empty(rows.value, ldk.value)
+        L.check(self.ctx, self.lib.ut_gp_i8_parts_read(self.ctx, _ptr(vp), _ptr(mp), None, None),
+                "ut_gp_i8_parts_read")
+        return vp, mp
+
     def gp_fit_read(self, what: str):
         """ut_gp_fit_read (for tests): one operand of the last fit, after waiting
         for it.  what: a key of _lib.FIT_OPERANDS ("L", "LINV", "LINVT", "ALPHA",
