@@ -648,6 +648,10 @@ int ut_gp_prune_bounds(ut_ctx* ctx, double* ub_out, uint8_t* exact_out, int64_t 
  * scratch holds fp64 rows (copied: an fp64 fit, or a precision-8 call whose
  * whole round fell back to fp64 and rewrote K*), 8 when it holds precision 8's
  * six digit planes (decoded exactly: a 48-bit integer times 2^(eb - 48)).
+ * Where those planes have a plane-occupancy mask (ut_gp_kstar_mask_read), a
+ * digit of a plane whose mask bit is clear is decoded as 0: true by the mask's
+ * definition, and necessary after a screened call (ut_gp_kstar_screen_stats),
+ * which does not write the planes of the units it certified as all-zero.
  * k_out may be NULL (the sizes and the format only); so may the other three.
  * Nothing is launched or recorded on the scoring paths for this.
  * UT_EUNSUPPORTED after a dense call of an fp32 or f16x3 fit; UT_EINVAL when no
@@ -671,6 +675,21 @@ int ut_gp_kstar_read(ut_ctx* ctx, double* k_out, int64_t c0, int64_t nc, int32_t
  * are no precision-8 planes to describe (ut_gp_kstar_read's conditions). */
 #define UT_NOMASK 1
 int ut_gp_kstar_mask_read(ut_ctx* ctx, uint8_t* mask_out, int32_t* rows, int64_t* cols);
+/* for tests: the K* screen of the last precision-8 dense call.  Before
+ * k_gp_kstar_q a screened call bounds every element's exponent from the
+ * products of the operands' two top digit planes and certifies the units (64
+ * training rows x 128 candidates) whose every element is stored as six zero
+ * digits: their planes are not computed, their mask bytes are 0.  A call
+ * screens when k_gp_kstar_q runs, npad <= 2048, d <= 128, UT_VAR_SKIP is not 0,
+ * and UT_KSTAR_SCREEN (read per call) is 1, or unset while at least half of the
+ * last call's blocks were all-zero.  *screened: 1 / 0; *certified: the certified
+ * units (0 when not screened); *units: (npad / 64) (ldk / 128), 0 when the last
+ * dense call left no masked planes.  UT_KSTAR_STRIPS (read per call): 1 / 0
+ * makes a screened call's variance kernel walk / not walk the screen's list of
+ * strips with a live unit, unset it does when at least 7 blocks in 8 of the
+ * last call were all-zero; the same bits either way.  Host values of the last call's one sync:
+ * nothing is launched or recorded on the scoring paths for this. */
+int ut_gp_kstar_screen_stats(ut_ctx* ctx, int32_t* screened, int64_t* certified, int64_t* units);
 /* for tests: the precision-8 variance contraction's per-tile partials of the
  * last dense precision-8 call that kept its digit planes (ut_gp_kstar_read's
  * format 8), copied on ctx's stream: var_part_out and mu_part_out (device

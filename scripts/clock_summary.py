@@ -18,7 +18,10 @@ import sys
 from collections import defaultdict
 
 KERNELS = {"var": ("void ut::k_gp_var_pp<false>(", "ut::k_gp_var_pp(", "void ut::k_gp_var<double>"),
-           "var8": ("void ut::k_gp_var_i8<false>", "void ut::k_gp_var_i8<true>", "ut::k_gp_var_i8("), "kstar8": ("void ut::k_gp_kstar_q<signed char, false", "void ut::k_gp_kstar<signed char, false, false>",
+           "var8_list": ("void ut::k_gp_var_i8<true, true>",),
+    "var8": ("void ut::k_gp_var_i8<false, false>", "void ut::k_gp_var_i8<true, false>", "void ut::k_gp_var_i8<false>", "void ut::k_gp_var_i8<true>", "ut::k_gp_var_i8("), "screen8": ("ut::k_q_screen(",), "mask_zeros8": ("ut::k_q_mask_zeros(",),
+    "kstar8_list": ("void ut::k_gp_kstar_q<signed char, false, false, true, true>", "void ut::k_gp_kstar_q<signed char, false, false, false, true>"),
+    "kstar8": ("void ut::k_gp_kstar_q<signed char, false, false, true, false>", "void ut::k_gp_kstar_q<signed char, false, false, false, false>", "void ut::k_gp_kstar_q<signed char, false", "void ut::k_gp_kstar<signed char, false, false>",
                      "void ut::k_gp_kstar<signed char, true, false>"), "split_u8": ("ut::k_q_split_u(",),
            "kstar": ("void ut::k_gp_kstar<double, false, false>", "void ut::k_gp_kstar<double, false>"), "inner_pairs": ("ut::k_inner_pairs",),
            "encode": ("ut::k_encode_scaled",),

@@ -33,7 +33,10 @@ STAGES = {  # stage key -> kernel-name prefixes (the first match wins)
     # rocprofv3 leaves the _Float16 instantiations mangled
     "var16": ("_ZN2ut11k_gp_var_h3",), "kstar16": ("_ZN2ut10k_gp_kstarIDF16_",),
     # precision 8 (int8 slices)
-    "var8": ("void ut::k_gp_var_i8<false>", "void ut::k_gp_var_i8<true>", "ut::k_gp_var_i8("), "kstar8": ("void ut::k_gp_kstar_q<signed char, false", "void ut::k_gp_kstar<signed char, false, false>",
+    "var8_list": ("void ut::k_gp_var_i8<true, true>",),
+    "var8": ("void ut::k_gp_var_i8<false, false>", "void ut::k_gp_var_i8<true, false>", "void ut::k_gp_var_i8<false>", "void ut::k_gp_var_i8<true>", "ut::k_gp_var_i8("), "screen8": ("ut::k_q_screen(",), "mask_zeros8": ("ut::k_q_mask_zeros(",),
+    "kstar8_list": ("void ut::k_gp_kstar_q<signed char, false, false, true, true>", "void ut::k_gp_kstar_q<signed char, false, false, false, true>"),
+    "kstar8": ("void ut::k_gp_kstar_q<signed char, false, false, true, false>", "void ut::k_gp_kstar_q<signed char, false, false, false, false>", "void ut::k_gp_kstar_q<signed char, false", "void ut::k_gp_kstar<signed char, false, false>",
                      "void ut::k_gp_kstar<signed char, true, false>"), "split_u8": ("ut::k_q_split_u(",),
     "split8": ("ut::k_split_i8(",), "finalize8": ("ut::k_gp_finalize_i8(",),
     "inner_pairs": ("ut::k_inner_pairs",), "de_diff": ("ut::k_de_diff",), "pop_digests": ("ut::k_pop_digests",),

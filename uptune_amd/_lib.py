@@ -174,6 +174,7 @@ SIGNATURES = {
     "ut_gp_prune_bounds": (C.c_int, [P, P, P, I64]),
     "ut_gp_kstar_read": (C.c_int, [P, P, I64, I64, C.POINTER(I32), C.POINTER(I64), C.POINTER(I32)]),
     "ut_gp_kstar_mask_read": (C.c_int, [P, P, C.POINTER(I32), C.POINTER(I64)]),
+    "ut_gp_kstar_screen_stats": (C.c_int, [P, C.POINTER(I32), C.POINTER(I64), C.POINTER(I64)]),
     "ut_gp_i8_parts_read": (C.c_int, [P, P, P, C.POINTER(I32), C.POINTER(I64)]),
     "ut_gp_fit_read": (C.c_int, [P, I32, P, C.POINTER(GpFitInfo)]),
     "ut_comm_unique_id": (C.c_int, [P]),

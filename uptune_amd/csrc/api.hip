@@ -1259,9 +1259,17 @@ int ut_gp_kstar_read(ut_ctx* c, double* k_out, int64_t c0, int64_t nc, int32_t* 
   if (!k_out || nc == 0) return 0;
   if (c->kst_fmt == 8)
     return launch_kstar_decode_i8(c, reinterpret_cast<const int8_t*>(c->kst.p), c->kst_npad, c->kst_ldk, c0, nc,
-                                  k_out);
+                                  k_out, c->kst_masked ? c->kmask.p : nullptr);
   UT_HIP(c, hipMemcpy2DAsync(k_out, sizeof(double) * nc, c->kst.p + c0, sizeof(double) * c->kst_ldk,
                              sizeof(double) * nc, (size_t)c->kst_npad, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
+int ut_gp_kstar_screen_stats(ut_ctx* c, int32_t* screened, int64_t* certified, int64_t* units) {
+  if (!c) return UT_EINVAL;
+  if (screened) *screened = c->ks_last_screened;
+  if (certified) *certified = c->ks_last_cert;
+  if (units) *units = c->ks_last_units;
   return 0;
 }
 

@@ -48,6 +48,13 @@
 // changes, and the error contract above is the unmasked kernel's.  The masked
 // kernel's guarded MFMA groups cost a dense K* about 3 %, so gp_score.hip runs
 // it only while the last call's K* was sparse (ut_ctx::var_skip_hint).
+// After a screened K* (k_q_screen, gp_kq.hip) the planes behind cleared mask
+// dwords were not written at all: the masked kernel always runs then.  Where
+// the launcher expects few live strips (ut_ctx::kst_list: 7 blocks in 8 of the
+// last call all-zero, or UT_KSTAR_STRIPS=1) it is the instance <true, true>
+// over the screen's list of strips with a live unit (the other strips'
+// partials already hold their zeros); otherwise <true> over every strip, which
+// gives the same bits and is the faster instance per live strip.
 #include "ut_internal.h"
 
 namespace ut {
@@ -193,7 +200,7 @@ int launch_split_i8(ut_ctx* c, int32_t n, int32_t npad) {
 constexpr int I8_WN = 128;                 // candidates per tile
 constexpr int I8_BPL = I8_WN * I8_BK;      // one B plane's piece of a stage (4 KiB)
 
-template <bool MASK>
+template <bool MASK, bool SLIST = false>
 __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__ Ad, const int8_t* __restrict__ Bd,
                                                       int32_t npad, int64_t ldk, int32_t RT, int32_t CT, int64_t m,
                                                       int32_t* __restrict__ ticket, const double* __restrict__ rs,
@@ -256,12 +263,29 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
     boff[jj] = I8_S * I8_PL + cb * 32 + ((c ^ ((cb >> 3) & 1)) << 4);
   }
   for (;;) {
-    if (t == 0) s_item = atomicAdd(&ticket[xcd], 1);
+    if (t == 0) {
+      const int32_t it = atomicAdd(&ticket[xcd], 1);
+      s_item = it;
+      if constexpr (SLIST) {
+        // a strip list (k_q_screen's): the XCD's live strips in the list's order,
+        // the others hold their zeros already; past its end CT, so that the
+        // workgroup leaves (with no live strip after one ticket).  The list sits
+        // behind the mask's bytes, [8 counts][8][ceil(CT / 8)] strips, and thread 0
+        // looks the strip up beside the ticket, in an instance of its own: read
+        // through pointer arguments by every wave it cost the plain masked kernel
+        // 9 more spilled SGPRs and 18 % at ell = 0.5.
+        const int32_t* tail = reinterpret_cast<const int32_t*>(kmask + (int64_t)(npad >> 5) * (ldk >> 5));
+        const int32_t P_ = (RT + 1) / 2;
+        const int32_t si = (it / (P_ * Sg)) * Sg + (it % (P_ * Sg)) / P_;
+        (&s_item)[1] = si < tail[xcd] ? tail[8 + xcd * ((CT + 7) >> 3) + si] : CT;
+      }
+    }
     __syncthreads();
     // (every item quantity scalar: the glds bases and loop bounds in SGPRs)
     const int32_t j = __builtin_amdgcn_readfirstlane(s_item);
     const int32_t G = j / (P * Sg), q = j % (P * Sg), p = q % P;
-    const int32_t ct = (G * Sg + q / P) * 8 + xcd;
+    const int32_t ct =
+        SLIST ? __builtin_amdgcn_readfirstlane((&s_item)[1]) : (G * Sg + q / P) * 8 + xcd;
     if (ct >= CT) break;   // uniform: the whole workgroup leaves
     const int nrt = RT - 1 - p == p ? 1 : 2;
     // lane l: the 6-bit mask of k stage l of this strip (the long tile's stages
@@ -432,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
 }
 
 int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk, int64_t m, double* part,
-                       double* mpart, const uint8_t* kmask) {
+                       double* mpart, const uint8_t* kmask, bool strip_list) {
   UT_CHECK(c, npad % 128 == 0 && npad <= I8_MAX_K && ldk % I8_WN == 0 && ldk >= m, UT_EINVAL,
            "gemm_var_i8: bad padding");
   UT_CHECK(c, c->gp_i8a.p && c->gp_i8rs.p, UT_EINVAL, "gemm_var_i8: the fit has no int8 planes");
@@ -444,7 +468,10 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
   const int32_t W = nb / 8, Sg = W / P > 1 ? W / P : 1;
   UT_HIP(c, hipMemsetAsync(c->gp_ctr.p, 0, sizeof(int32_t) * 8, c->stream));
   // (past I8_MASK_MAX_K rows a tile has more than 64 stages: the unmasked kernel)
-  if (kmask && npad <= I8_MASK_MAX_K)
+  if (kmask && npad <= I8_MASK_MAX_K && strip_list)
+    hipLaunchKernelGGL((k_gp_var_i8<true, true>), dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT,
+                       m, c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg, kmask);
+  else if (kmask && npad <= I8_MASK_MAX_K)
     hipLaunchKernelGGL(k_gp_var_i8<true>, dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT, m,
                        c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg, kmask);
   else
@@ -461,24 +488,27 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
 // out [npad][nc], columns c0 .. c0 + nc - 1.
 __global__ __launch_bounds__(256) void k_i8_kstar_decode(const int8_t* __restrict__ kst8, int32_t npad, int64_t ldk,
                                                          int64_t c0, int64_t nc, double scale,
-                                                         double* __restrict__ out) {
+                                                         double* __restrict__ out,
+                                                         const uint8_t* __restrict__ kmask) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= (int64_t)npad * nc) return;
   const int32_t r = (int32_t)(e / nc);
   const int64_t j = e - (int64_t)r * nc;
   const int64_t plane = (int64_t)npad * ldk, off = i8_off(c0 + j, r, ldk);
   int64_t v = 0;
+  // (a plane whose mask bit is clear holds no digit: after a screened call it was not even written)
+  const uint32_t mk = kmask ? kmask[(int64_t)(r >> 5) * (ldk >> 5) + ((c0 + j) >> 5)] : 0x3fu;
 #pragma unroll
-  for (int p = 0; p < I8_S; ++p) v = v * 256 + (int64_t)kst8[p * plane + off];
+  for (int p = 0; p < I8_S; ++p) v = v * 256 + (((mk >> p) & 1u) ? (int64_t)kst8[p * plane + off] : 0);
   out[e] = (double)v * scale;
 }
 
 int launch_kstar_decode_i8(ut_ctx* c, const int8_t* kst8, int32_t npad, int64_t ldk, int64_t c0, int64_t nc,
-                           double* out) {
+                           double* out, const uint8_t* kmask) {
   UT_CHECK(c, npad % 32 == 0 && c0 >= 0 && nc >= 0 && c0 + nc <= ldk, UT_EINVAL, "kstar_decode_i8: bad range");
   if (nc == 0) return 0;
   hipLaunchKernelGGL(k_i8_kstar_decode, dim3(grid1((int64_t)npad * nc, 256)), dim3(256), 0, c->stream, kst8, npad,
-                     ldk, c0, nc, ldexp(1.0, i8_kstar_exp(c->gp_sf2) - 48), out);
+                     ldk, c0, nc, ldexp(1.0, i8_kstar_exp(c->gp_sf2) - 48), out, kmask);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

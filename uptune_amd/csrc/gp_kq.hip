@@ -39,6 +39,11 @@
 // CU; waves 2 x 2 of 32 x 32 (one MFMA output tile, six group accumulators);
 // stages of 32 k: 6 A + 6 B planes of 2 KiB each in a 3-slot glds ring; each
 // XCD's items dealt round-robin to its workgroups (no ticket atomics).
+//
+// Far from the data whole tiles of K* are six zero planes.  k_q_screen (below)
+// certifies them beforehand from the products of the operands' two top planes;
+// the LIST instances of k_gp_kstar_q then walk the list of the remaining items
+// and the certified tiles' planes are never written (their mask bytes are 0).
 #include "ut_internal.h"
 
 namespace ut {
@@ -185,14 +190,15 @@ __device__ __forceinline__ void q_issue_ops(const double* __restrict__ xnorm, co
 // ---------------------------------------------------------------------------
 // the contraction + epilogue
 // ---------------------------------------------------------------------------
-template <typename TS, bool MU, bool CAT, bool PAIR>
+template <typename TS, bool MU, bool CAT, bool PAIR, bool LIST = false>
 __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
     const int8_t* __restrict__ Xd, int32_t npad, const int8_t* __restrict__ Ud, int64_t ldk, int32_t K32,
     const double* __restrict__ scol, int32_t RT, int32_t CT, const double* __restrict__ xnorm,
     const double* __restrict__ cnorm, const double* __restrict__ alpha, double sf2, int32_t n, int64_t m,
     TS* __restrict__ kst, double* __restrict__ part, double kscale, int64_t lo_off,
     int32_t store_rt, double* __restrict__ part2, const int8_t* __restrict__ acat, const int8_t* __restrict__ bcat,
-    int32_t nkc, double cat_c0, double cat_c1, uint8_t* __restrict__ kmask, int32_t* __restrict__ kcount) {
+    int32_t nkc, double cat_c0, double cat_c1, uint8_t* __restrict__ kmask, int32_t* __restrict__ kcount,
+    const int32_t* __restrict__ litems, const int32_t* __restrict__ lcount) {
   constexpr bool I8 = sizeof(TS) == 1;
   constexpr int OPS = 2 * Q_BM + 2 * Q_BN;              // one item's epilogue operands (doubles)
   // a 3-slot ring (80 KiB in all: two workgroups per CU)
@@ -248,13 +254,24 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
   }
   // the issue cursor: stage is_ of item (row tile irt, column tile ict), ring
   // slot isl, operand buffer iob; iok false past the last item
+  // LIST: the items are the entries b0, b0 + W, ... of this XCD's live-item list
+  // (k_q_screen's: 64 * column tile + row tile, lcount[xcd] of them; uniform
+  // loads), ictq then the column tile itself
+  const int32_t* li = LIST ? litems + (int64_t)xcd * (((CT + 7) >> 3) * RT) : nullptr;
+  const int32_t nli = LIST ? lcount[xcd] : 0;
+  int32_t ii = b0;
   int32_t irt = b0 % RT, ictq = b0 / RT, is_ = 0, isl = 0, iob = 0;
   bool iok = ictq * 8 + xcd < CT;
+  if constexpr (LIST) {
+    iok = ii < nli;
+    const int32_t e_ = iok ? li[ii] : 0;
+    irt = e_ & 63, ictq = e_ >> 6;
+  }
 #define UT_KQ_ISSUE()                                                                                            \
   do {                                                                                                          \
     if (iok) {                                                                                                  \
       const int32_t r0_ = irt * Q_BM;                                                                            \
-      const int64_t c0_ = (int64_t)(ictq * 8 + xcd) * Q_BN;                                                      \
+      const int64_t c0_ = (int64_t)(LIST ? ictq : ictq * 8 + xcd) * Q_BN;                                        \
       int8_t* st_ = lds + isl * Q_STAGE;                                                                         \
       if (CAT && is_ < ncs) {                                                                                    \
         q_issue_cat(acat, bcat, npad, ldk, w, lane, r0_, c0_, is_, st_);                                         \
@@ -279,13 +296,20 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
       if (++is_ == ntot) {                                                                                      \
         is_ = 0;                                                                                                \
         iob = iob == 2 ? 0 : iob + 1;                                                                           \
-        irt += Wr;                                                                                              \
-        ictq += Wq;                                                                                             \
-        if (irt >= RT) {                                                                                        \
-          irt -= RT;                                                                                            \
-          ++ictq;                                                                                               \
+        if constexpr (LIST) {                                                                                   \
+          ii += W;                                                                                              \
+          iok = ii < nli;                                                                                       \
+          const int32_t e_ = iok ? li[ii] : 0;                                                                  \
+          irt = e_ & 63, ictq = e_ >> 6;                                                                        \
+        } else {                                                                                                \
+          irt += Wr;                                                                                            \
+          ictq += Wq;                                                                                           \
+          if (irt >= RT) {                                                                                      \
+            irt -= RT;                                                                                          \
+            ++ictq;                                                                                             \
+          }                                                                                                     \
+          iok = ictq * 8 + xcd < CT;                                                                            \
         }                                                                                                       \
-        iok = ictq * 8 + xcd < CT;                                                                              \
       }                                                                                                         \
     }                                                                                                           \
   } while (0)
@@ -295,9 +319,14 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
   UT_KQ_ISSUE();
   // the consumer: item (row tile crt, column tile cctq), stage slot csl, operand buffer cob
   int32_t crt = b0 % RT, cctq = b0 / RT, csl = 0, cob = 0;
+  int32_t ci = b0;
+  if constexpr (LIST) {
+    const int32_t e_ = li[ci];   // (ci < nli: this workgroup has an item)
+    crt = e_ & 63, cctq = e_ >> 6;
+  }
   for (;;) {
     const int32_t row0 = crt * Q_BM;
-    const int64_t col0 = (int64_t)(cctq * 8 + xcd) * Q_BN;
+    const int64_t col0 = (int64_t)(LIST ? cctq : cctq * 8 + xcd) * Q_BN;
     double* ops = ops0 + cob * OPS;
     double* rx = ops;
     double* ra = ops + Q_BM;
@@ -465,17 +494,187 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
     if constexpr (I8) cnt += I8_S + mask_st;   // the plane stores and the mask byte, where one was stored
     else if (store) cnt += 16;        // the rows' stores
     cob = cob == 2 ? 0 : cob + 1;
-    crt += Wr;
-    cctq += Wq;
-    if (crt >= RT) {
-      crt -= RT;
-      ++cctq;
+    if constexpr (LIST) {
+      ci += W;
+      if (ci >= nli) break;   // (uniform: no next item)
+      const int32_t e_ = li[ci];
+      crt = e_ & 63, cctq = e_ >> 6;
+    } else {
+      crt += Wr;
+      cctq += Wq;
+      if (crt >= RT) {
+        crt -= RT;
+        ++cctq;
+      }
+      if (cctq * 8 + xcd >= CT) break;   // (uniform: no next item)
     }
-    if (cctq * 8 + xcd >= CT) break;   // (uniform: no next item)
   }
   // how sparse this K* is, for the host's choice of the next call's variance kernel
   if constexpr (I8)
     if (lane == 0 && nsparse != 0) atomicAdd(kcount, nsparse);
+}
+
+// ---------------------------------------------------------------------------
+// the screen: which 64-row x 128-candidate units of K* are six zero planes
+// ---------------------------------------------------------------------------
+// (DESIGN.md section 4 has the derivation.)  k_gp_kstar_q's exponent of an element is
+//   t = 2^(ea + eb_c - 16) (T_2 + 2^-8 T_3 + R) + rx_r + hc_c,   R = sum_{g=4..7} 2^(-8 (g - 2)) T_g,
+// and |a_p b_q| <= 2^14 with g - 1 pairs in group g gives |R| <= K 2^14 (3 2^-16
+// + 4 2^-24 + 5 2^-32 + 6 2^-40) < 0.76 K.  T_2 and T_3 are the products of the
+// two top planes (a_1 b_1; a_1 b_2 + a_2 b_1), so with U = 256 T_2 + T_3 (exact
+// in fp64) and s = 2^(ea + eb_c - 24)
+//   t <= t_up = (U + 194.56 K) s + rx_r + hc_c.
+// The kernel stores six zero digits where rint(t) >> 8 <= -49, i.e. t < -12288.5
+// (sf2_exp2t_nonpos: p etab[j] < 1.0014 * 0.98 < 1, so y < 2^-49 and
+// rint(y 2^48) = 0).  Both sides round: every intermediate is at most 2 M with
+// M = max_r |rx_r| + |hc_c| + 194.56 K s (|C| <= |rx| + |hc|), a handful of fp64
+// roundings each side, below 2^-48 M in all; the slack is 1 + 2^-40 M.  A unit
+// whose every element has t_up + slack < -12288.5 is certified: its two mask
+// dwords are cleared (no plane of it is stored, none is read); every other unit
+// is appended, as its two 64 x 64 items, to the K* lists of their XCDs, and its
+// strip to the variance list of the strip's XCD (strips: [8] counts, [8][scap]).  A strip with no live unit gets
+// the zeros in part / mpart that the variance kernel would have written.
+// One workgroup per 128-candidate strip: the strip's B planes 0 and 1 in LDS,
+// wave w takes the row tiles w, w + 4, ... with A fragments straight from Xd.
+constexpr int QS_MAX_K32 = 4;                  // 8 KiB of LDS per 32 k (48 KiB with 2048 rows' norms)
+constexpr double QS_LINE = -12288.5;           // rint(t) <= -49 * 256 + 255 below it
+constexpr double QS_REM = 0.76 * 256.0;        // the remainder bound per k, in units of U
+
+__global__ __launch_bounds__(256, 2) void k_q_screen(
+    const int8_t* __restrict__ Xd, int32_t npad, const int8_t* __restrict__ Ud, int64_t ldk, int32_t K32,
+    const double* __restrict__ scol, double scl, const double* __restrict__ xnorm, const double* __restrict__ cnorm,
+    int32_t n, int64_t m, uint8_t* __restrict__ kmask, int32_t* __restrict__ items, int32_t icap,
+    int32_t* __restrict__ strips, int32_t scap, int32_t CTv, int32_t* __restrict__ cnts, double* __restrict__ vpart,
+    double* __restrict__ mpart) {
+  extern __shared__ __attribute__((aligned(16))) int8_t qs_lds[];
+  int8_t* bl = qs_lds;                                                       // [2][K32][128][32]
+  double* rxs = reinterpret_cast<double*>(qs_lds + (size_t)2 * K32 * 4096);  // [npad] row half-norms (t units)
+  double* red = rxs + npad;                                                  // [4]
+  uint32_t* s_live = reinterpret_cast<uint32_t*>(red + 4);                   // live row tiles (RT <= 32), certified units
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int32_t ct = blockIdx.x, RT = npad / Q_BM;
+  const int64_t col0 = (int64_t)ct * 128;
+  const int64_t xplane = (int64_t)K32 * 32 * npad, uplane = (int64_t)K32 * 32 * ldk;
+  if (t < 2) s_live[t] = 0;
+  for (int32_t j = 0; j < 2 * K32; ++j) {   // plane j / K32, stage j % K32: 4 KiB, contiguous
+    const int8_t* src = Ud + (int64_t)(j / K32) * uplane + ((int64_t)(j % K32) * ldk + col0) * 32;
+    *reinterpret_cast<uint4*>(bl + j * 4096 + t * 16) = *reinterpret_cast<const uint4*>(src + t * 16);
+  }
+  double rmx = 0.0;
+  for (int32_t r = t; r < npad; r += 256) {
+    const double hv = (-0.5 * KSTAR_T_SCALE) * xnorm[r];
+    rxs[r] = r < n ? hv : -1e300;
+    if (r < n) rmx = fmax(rmx, fabs(hv));
+  }
+  for (int o = 32; o > 0; o >>= 1) rmx = fmax(rmx, __shfl_xor(rmx, o));
+  if (lane == 0) red[w] = rmx;
+  __syncthreads();
+  rmx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  const double rem = QS_REM * (double)(K32 * 32);
+  const int c = lane >> 5, l31 = lane & 31;
+  double s24[4], off[4];   // per column: the scale of U; remainder + column half-norm + slack
+  int boff[4];
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+    const int cb = jj * 32 + l31;
+    const int64_t col = col0 + cb;
+    const double hc = col < m ? (-0.5 * KSTAR_T_SCALE) * cnorm[col] : -1e300;
+    s24[jj] = scol[col] * scl;
+    const double rs = rem * s24[jj];
+    off[jj] = (rs + hc) + (1.0 + 0x1p-40 * ((rmx + fabs(hc)) + rs));
+    boff[jj] = cb * 32 + ((c ^ ((cb >> 3) & 1)) << 4);
+  }
+  const int aoff = l31 * 32 + ((c ^ ((l31 >> 3) & 1)) << 4);
+  int32_t ncert = 0;
+  for (int32_t rt = w; rt < RT; rt += 4) {
+    double mx[4];
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const int32_t r0 = rt * Q_BM + h * 32;
+      i8v16 a0[4], a1[4];
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) a0[jj][q] = 0, a1[jj][q] = 0;
+#pragma unroll 1
+      for (int32_t kb = 0; kb < K32; ++kb) {
+        const int8_t* ap = Xd + ((int64_t)kb * npad + r0) * 32 + aoff;
+        const i8v4 af0 = *reinterpret_cast<const i8v4*>(ap);
+        const i8v4 af1 = *reinterpret_cast<const i8v4*>(ap + xplane);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const i8v4 bf0 = *reinterpret_cast<const i8v4*>(bl + kb * 4096 + boff[jj]);
+          const i8v4 bf1 = *reinterpret_cast<const i8v4*>(bl + (K32 + kb) * 4096 + boff[jj]);
+          a0[jj] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af0, bf0, a0[jj], 0, 0, 0);
+          a1[jj] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af0, bf1, a1[jj], 0, 0, 0);
+          a1[jj] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af1, bf0, a1[jj], 0, 0, 0);
+        }
+      }
+      // (C/D map: row (q & 3) + 8 (q >> 2) + 4 (lane >> 5), column lane & 31)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const double rx = rxs[r0 + (q & 3) + 8 * (q >> 2) + 4 * c];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const double u = __builtin_fma((double)a0[jj][q], 256.0, (double)a1[jj][q]);
+          const double e = __builtin_fma(u, s24[jj], rx);
+          mx[jj] = (h == 0 && q == 0) ? e : fmax(mx[jj], e);
+        }
+      }
+    }
+    double tm = fmax(fmax(mx[0] + off[0], mx[1] + off[1]), fmax(mx[2] + off[2], mx[3] + off[3]));
+    for (int o = 32; o > 0; o >>= 1) tm = fmax(tm, __shfl_xor(tm, o));
+    if (tm < QS_LINE) {   // (uniform) certified: rows 2 rt and 2 rt + 1 of the mask, the strip's dword
+      if (lane < 2) *reinterpret_cast<uint32_t*>(kmask + (int64_t)(2 * rt + lane) * (ldk >> 5) + ct * 4) = 0u;
+      ++ncert;
+    } else if (lane == 0) {
+      atomicOr(&s_live[0], 1u << rt);
+    }
+  }
+  if (lane == 0 && ncert) atomicAdd(&s_live[1], (uint32_t)ncert);
+  __syncthreads();
+  const uint32_t live = s_live[0];
+  if (w == 0) {
+    const int32_t nl = __builtin_popcount(live);
+    if (nl) {
+      // one atomic per list: the strip's two column tiles 2 ct and 2 ct + 1 on their XCDs
+      const int32_t xa = (2 * ct) & 7, xb = xa + 1;
+      int32_t ba = 0, bb = 0;
+      if (lane == 0) {
+        ba = atomicAdd(&cnts[xa], nl);
+        bb = atomicAdd(&cnts[xb], nl);
+        if (ct < CTv) strips[8 + (ct & 7) * scap + atomicAdd(&strips[ct & 7], 1)] = ct;
+      }
+      ba = __builtin_amdgcn_readfirstlane(ba), bb = __builtin_amdgcn_readfirstlane(bb);
+      if (lane < 32 && ((live >> lane) & 1u)) {
+        const int32_t pos = __builtin_popcount(live & ((1u << lane) - 1u));
+        items[(int64_t)xa * icap + ba + pos] = (2 * ct) * 64 + lane;
+        items[(int64_t)xb * icap + bb + pos] = (2 * ct + 1) * 64 + lane;
+      }
+    }
+    if (lane == 0 && s_live[1]) atomicAdd(&cnts[16], (int32_t)s_live[1]);
+  }
+  if (live == 0 && t < 128 && col0 + t < m) {   // a strip the variance kernel will not visit
+    for (int32_t rt = 0; rt < RT; ++rt) {
+      vpart[(int64_t)rt * ldk + col0 + t] = 0.0;
+      mpart[(int64_t)rt * ldk + col0 + t] = 0.0;
+    }
+  }
+}
+
+// the all-zero blocks of an unscreened K*'s mask -> cnts[17] (the next call's
+// screen hint); leaves at once unless this K* has a zero plane in 1 block of 16
+__global__ __launch_bounds__(256) void k_q_mask_zeros(const uint8_t* __restrict__ kmask, int64_t ndw,
+                                                      const int32_t* __restrict__ kcount, int32_t* __restrict__ cnts) {
+  if ((int64_t)kcount[0] * 4 < ndw) return;   // (nsparse * 16 < blocks: uniform)
+  int32_t z = 0;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < ndw; e += (int64_t)gridDim.x * 256) {
+    const uint32_t d = reinterpret_cast<const uint32_t*>(kmask)[e];
+    z += ((d & 0xffu) == 0) + ((d & 0xff00u) == 0) + ((d & 0xff0000u) == 0) + ((d & 0xff000000u) == 0);
+  }
+  for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+  if ((threadIdx.x & 63) == 0 && z) atomicAdd(&cnts[17], z);
 }
 
 // ---------------------------------------------------------------------------
@@ -516,26 +715,71 @@ int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m,
   int rc;
   if ((rc = ensure(c, u8, (size_t)I8_S * (K32 > 0 ? K32 : 1) * 32 * ldk))) return rc;
   if ((rc = ensure(c, scol, (size_t)ldk))) return rc;
-  if ((rc = ensure(c, c->kmask, (size_t)(npad / 32) * (size_t)(ldk / 32)))) return rc;
+  // (behind the mask's bytes: the screen's variance-strip list, [8] counts and [8][ceil(strips / 8)] strips)
+  const size_t mask_bytes = (size_t)(npad / 32) * (size_t)(ldk / 32);
+  const int32_t CTv = (int32_t)((m + 127) / 128), scap = (CTv + 7) / 8;
+  if ((rc = ensure(c, c->kmask, mask_bytes + sizeof(int32_t) * (8 + 8 * (size_t)scap)))) return rc;
   if ((rc = ensure(c, c->kmask_cnt, 1))) return rc;
   UT_HIP(c, hipMemsetAsync(c->kmask_cnt.p, 0, sizeof(int32_t), c->stream));
   UT_HIP(c, hipMemsetAsync(c->kmask.p, 0x3f, (size_t)(npad / 32) * (size_t)(ldk / 32), c->stream));
+  const int32_t RT = npad / Q_BM;
+  const int32_t CT = (int32_t)(ldk / Q_BN);
+  // The screen (k_q_screen) runs where the masked variance kernel can follow it
+  // (npad <= I8_MASK_MAX_K, UT_VAR_SKIP not 0: a screened call leaves unwritten
+  // planes behind cleared mask dwords) and its strip's planes fit in LDS;
+  // UT_KSTAR_SCREEN (read per call) 1 / 0 forces it on / off, unset it follows
+  // c->kstar_screen_hint (at least half of the last call's blocks all-zero).
+  const char* vs_env = getenv("UT_VAR_SKIP");
+  const char* ks_env = getenv("UT_KSTAR_SCREEN");
+  const bool can_screen = npad <= I8_MASK_MAX_K && K32 <= QS_MAX_K32 && !(vs_env && atoi(vs_env) == 0);
+  const bool screen = can_screen && (ks_env ? atoi(ks_env) == 1 : c->kstar_screen_hint);
+  const int32_t icap = ((CT + 7) / 8) * RT;
+  int32_t* strips = reinterpret_cast<int32_t*>(c->kmask.p + mask_bytes);
+  c->kst_screened = false, c->kst_counted = false;
+  if (can_screen) {
+    if ((rc = ensure(c, c->ks_cnt, 24))) return rc;
+    UT_HIP(c, hipMemsetAsync(c->ks_cnt.p, 0, sizeof(int32_t) * 24, c->stream));
+  }
+  if (screen) {
+    if ((rc = ensure(c, c->ks_items, (size_t)8 * icap))) return rc;
+    UT_HIP(c, hipMemsetAsync(strips, 0, sizeof(int32_t) * 8, c->stream));
+  }
   hipLaunchKernelGGL(k_q_split_u, dim3(grid1(ldk, 256)), dim3(256), 0, c->stream, ucand, dpad, ldk, K32,
                      c->gp_q8.p + 1, pair ? -24 : -16, u8.p, scol.p);
   UT_LAUNCH_CHECK(c);
-  const int32_t RT = npad / Q_BM;
-  const int32_t CT = (int32_t)(ldk / Q_BN);
   const int32_t nb = kstar_blocks(c, (int64_t)RT * CT, true);   // (no tickets: its items are static)
   const double kscale = ldexp(1.0, -i8_kstar_exp(c->gp_sf2));
-#define UT_KQ_LAUNCH(PAIR)                                                                                     \
-  hipLaunchKernelGGL((k_gp_kstar_q<int8_t, false, false, PAIR>), dim3(nb), dim3(Q_NT), 0, c->stream, xd.p, npad,    \
-                     u8.p, ldk, K32, scol.p, RT, CT, c->gp_xnorm.p, c->cnorm.p, c->gp_alpha.p, c->gp_sf2, c->gp_n, m,     \
-                     (int8_t*)kst, nullptr, kscale, (int64_t)npad * ldk, RT, nullptr, nullptr, nullptr, 0, 0.0, 0.0,  \
-                     c->kmask.p, c->kmask_cnt.p)
-  if (pair) UT_KQ_LAUNCH(true);
-  else UT_KQ_LAUNCH(false);
+#define UT_KQ_LAUNCH(PAIR, LIST, LI, LC)                                                                             \
+  hipLaunchKernelGGL((k_gp_kstar_q<int8_t, false, false, PAIR, LIST>), dim3(nb), dim3(Q_NT), 0, c->stream, xd.p,       \
+                     npad, u8.p, ldk, K32, scol.p, RT, CT, c->gp_xnorm.p, c->cnorm.p, c->gp_alpha.p, c->gp_sf2,         \
+                     c->gp_n, m, (int8_t*)kst, nullptr, kscale, (int64_t)npad * ldk, RT, nullptr, nullptr, nullptr, 0, \
+                     0.0, 0.0, c->kmask.p, c->kmask_cnt.p, LI, LC)
+  if (screen) {
+    UT_CHECK(c, c->var_part.p && c->mu_part.p && c->var_part.n >= (size_t)RT * ldk && c->mu_part.n >= (size_t)RT * ldk,
+             UT_EINVAL, "gemm_kstar_q: the screen needs the variance partials allocated");
+    const size_t lds = (size_t)2 * K32 * 4096 + sizeof(double) * (npad + 4) + 16;
+    hipLaunchKernelGGL(k_q_screen, dim3((unsigned)(ldk / 128)), dim3(256), lds, c->stream, xd.p, npad, u8.p, ldk, K32,
+                       scol.p, pair ? 1.0 : 0x1p-8, c->gp_xnorm.p, c->cnorm.p, c->gp_n, m, c->kmask.p, c->ks_items.p,
+                       icap, strips, scap, CTv, c->ks_cnt.p, c->var_part.p, c->mu_part.p);
+    UT_LAUNCH_CHECK(c);
+    if (pair) UT_KQ_LAUNCH(true, true, c->ks_items.p, c->ks_cnt.p);
+    else UT_KQ_LAUNCH(false, true, c->ks_items.p, c->ks_cnt.p);
+  } else {
+    if (pair) UT_KQ_LAUNCH(true, false, nullptr, nullptr);
+    else UT_KQ_LAUNCH(false, false, nullptr, nullptr);
+  }
 #undef UT_KQ_LAUNCH
   UT_LAUNCH_CHECK(c);
+  c->kst_screened = screen;
+  const char* st_env = getenv("UT_KSTAR_STRIPS");
+  c->kst_list = screen && (st_env ? atoi(st_env) == 1 : c->ks_list_hint);
+  if (can_screen && !screen && !ks_env) {
+    const int64_t ndw = (int64_t)(npad / 32) * (ldk / 32) / 4;
+    hipLaunchKernelGGL(k_q_mask_zeros, dim3(64), dim3(256), 0, c->stream, c->kmask.p, ndw, c->kmask_cnt.p,
+                       c->ks_cnt.p);
+    UT_LAUNCH_CHECK(c);
+    c->kst_counted = true;
+  }
   c->kst_masked = true;   // c->kmask describes the planes now in kst (gp_score_dense clears it)
   return 0;
 }

@@ -253,9 +253,15 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
     // at least 1 block of 16 (c->var_skip_hint, from the count read back below).
     // UT_VAR_SKIP (read per call): 0 keeps the unmasked kernel, 1 the masked one.
     const char* vs_env = getenv("UT_VAR_SKIP");
-    const bool vskip = c->kst_masked && (vs_env ? atoi(vs_env) != 0 : c->var_skip_hint);
+    // A screened K* (k_q_screen) left the planes of its certified units
+    // unwritten: always the masked kernel; over the screen's list of strips with
+    // a live unit (it wrote the other strips' zeros) where the launcher chose so
+    // (c->kst_list: few live strips expected; the kernel over every strip gives
+    // the same bits, and is the faster instance where most strips are live).
+    const bool screened = c->kst_masked && c->kst_screened;
+    const bool vskip = c->kst_masked && (screened || (vs_env ? atoi(vs_env) != 0 : c->var_skip_hint));
     if ((rc = launch_gemm_var_i8(c, npad, reinterpret_cast<const int8_t*>(c->kst.p), ldk, m, c->var_part.p,
-                                 c->mu_part.p, vskip ? c->kmask.p : nullptr)))
+                                 c->mu_part.p, vskip ? c->kmask.p : nullptr, screened && c->kst_list)))
       return rc;
   } else if ((rc = launch_gemm_var(c, prec, fp32 ? (const void*)c->gp_LinvT_f.p : (const void*)c->gp_LinvT.p, npad,
                                    c->kst.p, ldk, npad, m, c->var_part.p, fp32 ? nullptr : c->gp_beta.p,
@@ -277,8 +283,29 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
     int32_t nsparse = 0;
     if (c->kst_masked)
       UT_HIP(c, hipMemcpyAsync(&nsparse, c->kmask_cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // the screen's certified units / the unscreened mask's all-zero bytes, in the same sync
+    int32_t ksc[2] = {0, 0};
+    const bool ks_read = c->kst_masked && (c->kst_screened || c->kst_counted);
+    if (ks_read)
+      UT_HIP(c, hipMemcpyAsync(ksc, c->ks_cnt.p + 16, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     UT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->kst_masked) c->var_skip_hint = (int64_t)nsparse * 16 >= (int64_t)(npad / 32) * (ldk / 32);
+    const int64_t blocks = (int64_t)(npad / 32) * (ldk / 32);
+    c->ks_last_screened = c->kst_masked && c->kst_screened ? 1 : 0;
+    c->ks_last_units = c->kst_masked ? blocks / 8 : 0;
+    c->ks_last_cert = c->ks_last_screened ? ksc[0] : 0;
+    if (c->kst_masked) {
+      // (a certified unit is 8 blocks that k_gp_kstar_q never visited to count)
+      c->var_skip_hint = ((int64_t)nsparse + (c->kst_screened ? 8 * (int64_t)ksc[0] : 0)) * 16 >= blocks;
+      const int64_t zero_blocks = c->kst_screened ? 8 * (int64_t)ksc[0] : (c->kst_counted ? (int64_t)ksc[1] : 0);
+      c->kstar_screen_hint = 2 * zero_blocks >= blocks;
+      // (zero blocks the certificate cannot clear -- k* below 2^-49 of the scale by
+      // less than its remainder bound -- would turn the screen on after every
+      // unscreened call and off after every screened one: a screen that cleared
+      // less than half holds the hint off for the next 8 calls)
+      if (c->kst_screened && !c->kstar_screen_hint) c->ks_backoff = 8;
+      else if (!c->kst_screened && c->ks_backoff > 0) --c->ks_backoff, c->kstar_screen_hint = false;
+      c->ks_list_hint = 8 * zero_blocks >= 7 * blocks;
+    }
     c->i8_recomputed = nf;
     if (nf > 0 && (rc = gp_ensure_linvt(c))) return rc;   // (the fp64 contraction reads (L^-1)^T)
     if (nf * 2 > m) {

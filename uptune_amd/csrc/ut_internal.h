@@ -343,6 +343,36 @@ struct ut_ctx {
   // hint costs time only.  UT_VAR_SKIP=1 forces the masked kernel, 0 the unmasked.
   ut::DevBuf<int32_t> kmask_cnt;
   bool var_skip_hint = true;
+  // The K* screen (k_q_screen, gp_kq.hip): before k_gp_kstar_q it certifies, from
+  // the products of the operands' two top digit planes, the 64-row x
+  // 128-candidate units whose every element the kernel would store as six zero
+  // digits, clears their mask dwords and lists the rest: ks_items [8][icap] the
+  // live 64 x 64 K* items per XCD (64 * column tile + row tile); behind the
+  // mask's bytes in kmask, [8] counts and [8][scap] the variance strips with a
+  // live unit (there, so that the variance kernel needs no further pointer);
+  // ks_cnt [24] = item counts [0, 8), certified units [16], all-zero mask bytes
+  // of an unscreened call [17] (k_q_mask_zeros).  A certified unit's planes are NOT
+  // written: they hold whatever an earlier call left, and every reader goes
+  // through the mask (the masked variance kernel, ut_gp_kstar_read).
+  // kst_screened: this call's K* was screened (the variance kernel must be a
+  // masked one: over the strip list if kst_list, else over every strip); kst_counted: it was not and [17] was counted.
+  // kstar_screen_hint: at least half of the last call's blocks were all-zero
+  // (the certified units of a screened call, [17] of an unscreened one), read
+  // back in the call's one sync; a stale hint costs time only.
+  // ks_list_hint: at least 7 blocks in 8 were; kst_list: this screened call's
+  // variance kernel walks the strip list (the hint, or UT_KSTAR_STRIPS=1).  The
+  // list instance of k_gp_var_i8 is about 18 % slower per live strip than the
+  // plain masked one (C2 at ell = 0.5, screen forced: 7.78 against 6.63 ms), which
+  // visits every strip and gives the same bits: the list pays where nearly all
+  // strips are dead.
+  // UT_KSTAR_SCREEN=1 / 0 (read per call) forces the screen on / off and leaves
+  // the list to its hint; UT_KSTAR_STRIPS=1 / 0 (read per call) forces the list
+  // on / off in a screened call.
+  ut::DevBuf<int32_t> ks_items, ks_cnt;
+  bool kst_screened = false, kst_counted = false, kst_list = false, kstar_screen_hint = false, ks_list_hint = false;
+  int32_t ks_backoff = 0;                 // unscreened calls left before the hint may turn on again
+  int32_t ks_last_screened = 0;           // (ut_gp_kstar_screen_stats) the last precision-8 dense call:
+  int64_t ks_last_cert = 0, ks_last_units = 0;   // screened?, certified units, units
   int32_t kstar_q = 1;  // UT_KSTAR_Q=0: precision-8 K* on k_gp_kstar<int8_t> (the fp64 MFMA)
   int32_t gp_i8_eb = 0;          // K* digit scale: y = k* 2^-eb <= 0.49
   double i8_tol = 0x1p-20;       // accepted relative variance error (ut_gp_set_i8_tol)
@@ -961,11 +991,15 @@ int launch_split_i8(ut_ctx* c, int32_t n, int32_t npad);
 // kmask: the planes' occupancy mask [npad / 32][ldk / 32] (k_gp_kstar_q's), whose
 // all-zero blocks are neither loaded nor multiplied; nullptr: no mask
 constexpr int32_t I8_MASK_MAX_K = 2048;   // the masked kernel keeps a tile's live stages in one 64-bit set
+// strip_list (with kmask): visit only the strips of k_q_screen's list, which sits behind the mask's bytes
+// ([8] counts, [8][ceil(CT / 8)] strips per XCD); every other strip's part / mpart already hold their zeros
 int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk, int64_t m, double* part,
-                       double* mpart, const uint8_t* kmask);
+                       double* mpart, const uint8_t* kmask, bool strip_list = false);
 // (for tests) columns c0 .. c0 + nc - 1 of K*'s digit planes as doubles, out [npad][nc]
+// kmask (nullptr: none): a digit of a plane whose mask bit is clear reads as 0 -- true by the mask's
+// definition, and what a screened call's unwritten planes need
 int launch_kstar_decode_i8(ut_ctx* c, const int8_t* kst8, int32_t npad, int64_t ldk, int64_t c0, int64_t nc,
-                           double* out);
+                           double* out, const uint8_t* kmask = nullptr);
 // (for tests) L^-1's digit planes as the integers sum_p a_p 256^(5-p), out [npad][npad] in (row, k) order
 int launch_linv_decode_i8(ut_ctx* c, int32_t npad, double* out);
 // (for tests, gp_fit.hip) out [npad][npad] = the lower triangle of src, zeros above; out [n] = (double)src [n]

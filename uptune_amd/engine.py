@@ -704,6 +704,15 @@ class BatchEngine:
         L.check(self.ctx, self.lib.ut_gp_kstar_mask_read(self.ctx, _ptr(mk), None, None), "ut_gp_kstar_mask_read")
         return mk
 
+    def gp_kstar_screen_stats(self) -> Tuple[bool, int, int]:
+        """ut_gp_kstar_screen_stats (for tests): the K* screen of the last
+        precision-8 dense call -> (screened, certified units, units of 64
+        training rows x 128 candidates)"""
+        s, nc, nu = C.c_int32(), C.c_int64(), C.c_int64()
+        L.check(self.ctx, self.lib.ut_gp_kstar_screen_stats(self.ctx, C.byref(s), C.byref(nc), C.byref(nu)),
+                "ut_gp_kstar_screen_stats")
+        return bool(s.value), int(nc.value), int(nu.value)
+
     def gp_i8_parts_read(self):
         """ut_gp_i8_parts_read (for tests): the precision-8 variance contraction's
         per-64-row-tile column sums of the last dense call that kept its planes
