@@ -768,6 +768,38 @@ int ut_forest_set(ut_ctx* ctx, int32_t n_trees, const int32_t* roots_host, int64
  * names both numbers), never an answer read from another column. */
 int ut_forest_predict(ut_ctx* ctx, const double* features, int64_t ld, int64_t m, int32_t n_features,
                       const uint8_t* dup, double sign, double* pred, double* score);
+/* Predictive variance and acquisition of an AVERAGED ensemble (base 0, scale 1,
+ * div = n_trees: a random forest, whose trees are samples of one function; the
+ * reference scores its models by their mean alone, src/multi_stage.py:8-22,
+ * plugins/xgbregressor.py:50-63 -- the variance over trees is SMAC's, Hutter,
+ * Hoos & Leyton-Brown 2011).
+ *
+ * ut_forest_leaf_var, after ut_forest_set: the variance of the training
+ * targets in every leaf (var_host[k] for node k; read at leaves only, where it
+ * must be finite and >= 0, else UT_EINVAL and nothing changes; n_nodes must be
+ * the loaded count).  ut_forest_set clears it.  Without it every leaf variance
+ * is 0.  It lives in the leaf records' threshold field on the device, which
+ * ut_forest_predict never reads. */
+int ut_forest_leaf_var(ut_ctx* ctx, const double* var_host, int64_t n_nodes);
+/* Tree t = 0..T-1 of candidate i ends in a leaf of value m_t and variance s_t;
+ * every sum in tree order, in fp64, nothing fused:
+ *   mu    = (base + sum m_t) / div            bitwise ut_forest_predict's pred
+ *   a_t   = m_t - m_0                         shifted by the candidate's own first leaf
+ *   D1 = sum a_t, D2 = sum a_t^2, SV = sum s_t
+ *   var   = max((D2 + SV) / T - (D1 / T)^2, 0)     law of total variance over trees
+ *   score = the acquisition of ut_gp_score at (mu, var, f_best) for the same
+ *           ut_acq (EI: improvement below f_best; UCB: kappa sigma - mu);
+ *           -inf where dup[i] != 0 (dup may be NULL)
+ * mu, var, score [m] device outputs, each may be NULL; features, ld, n_features
+ * and their UT_EINVAL cases as ut_forest_predict (the n_features message names
+ * both numbers); a NULL acq or unknown kind is UT_EINVAL.  UT_EUNSUPPORTED
+ * unless the loaded ensemble is an average (a boosted ensemble's stages are not
+ * samples of one function).  m == 0 returns 0 and launches nothing.  Enqueued
+ * on the context's stream with no host wait; the outputs do not depend on
+ * which of the two kernels runs (UT_FOREST_STATS=lane|staged forces one, read
+ * per call, for measurements). */
+int ut_forest_score(ut_ctx* ctx, const double* features, int64_t ld, int64_t m, int32_t n_features,
+                    const uint8_t* dup, const ut_acq* acq, double f_best, double* mu, double* var, double* score);
 
 /* ---- multi-GPU exchange over RCCL -------------
  * One process per GPU, one communicator per context.  Rank r scores the

@@ -141,6 +141,8 @@ SIGNATURES = {
     "ut_gp_last_fit_kind": (C.c_int, [P, C.POINTER(I32)]),
     "ut_forest_set": (C.c_int, [P, I32, P, I64, P, I32, D, D, D]),
     "ut_forest_predict": (C.c_int, [P, P, I64, I64, I32, P, D, P, P]),
+    "ut_forest_leaf_var": (C.c_int, [P, P, I64]),
+    "ut_forest_score": (C.c_int, [P, P, I64, I64, I32, P, P, D, P, P, P]),
     "ut_gp_score": (C.c_int, [P, P, I64, I64, C.POINTER(Acq), P, P, P, P]),
     "ut_gp_score_values": (C.c_int, [P, P, I64, I64, C.POINTER(Acq), P, P, P, P]),
     "ut_gp_set_precision": (C.c_int, [P, I32]),

@@ -71,12 +71,18 @@ extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_ho
       max_feat = std::max(max_feat, q.feature);
     }
   }
+  // the device's records: a leaf's threshold field (no kernel of the mean reads
+  // it; sklearn leaves carry -2 there) is its variance, 0 until ut_forest_leaf_var
+  std::vector<ut_tree_node> recs(nodes_host, nodes_host + n_nodes);
+  for (ut_tree_node& q : recs)
+    if (q.feature < 0) q.threshold = 0.0;
   UT_HIP(c, hipSetDevice(c->device));
   UT_HIP(c, ut::sync_all(c));
   c->forest_trees = 0;
   UT_HIP(c, c->forest_nodes.alloc((size_t)n_nodes));
   UT_HIP(c, c->forest_roots.alloc((size_t)n_trees));
-  UT_HIP(c, hipMemcpy(c->forest_nodes.p, nodes_host, sizeof(ut_tree_node) * n_nodes, hipMemcpyHostToDevice));
+  UT_HIP(c, hipMemcpy(c->forest_nodes.p, recs.data(), sizeof(ut_tree_node) * n_nodes, hipMemcpyHostToDevice));
+  c->forest_host.swap(recs);
   UT_HIP(c, hipMemcpy(c->forest_roots.p, roots_host, sizeof(int32_t) * n_trees, hipMemcpyHostToDevice));
   c->forest_trees = n_trees;
   c->forest_rule = rule;
@@ -84,6 +90,26 @@ extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_ho
   c->forest_base = base;
   c->forest_scale = scale;
   c->forest_div = div;
+  return 0;
+}
+
+extern "C" int ut_forest_leaf_var(ut_ctx* c, const double* var_host, int64_t n_nodes) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, c->forest_trees > 0, UT_EINVAL, "forest_leaf_var: call ut_forest_set first");
+  UT_CHECK(c, var_host != nullptr, UT_EINVAL, "forest_leaf_var: var is NULL");
+  UT_CHECK(c, n_nodes == (int64_t)c->forest_host.size(), UT_EINVAL,
+           "forest_leaf_var: " + std::to_string(n_nodes) + " values for the " +
+               std::to_string(c->forest_host.size()) + " nodes loaded");
+  for (int64_t k = 0; k < n_nodes; ++k)
+    if (c->forest_host[k].feature < 0)
+      UT_CHECK(c, __builtin_isfinite(var_host[k]) && var_host[k] >= 0.0, UT_EINVAL,
+               "forest_leaf_var: the variance of leaf " + std::to_string(k) + " is not finite and >= 0");
+  for (int64_t k = 0; k < n_nodes; ++k)
+    if (c->forest_host[k].feature < 0) c->forest_host[k].threshold = var_host[k];
+  UT_HIP(c, hipSetDevice(c->device));
+  UT_HIP(c, ut::sync_all(c));   // a scoring kernel still queued reads the old records
+  UT_HIP(c, hipMemcpy(c->forest_nodes.p, c->forest_host.data(), sizeof(ut_tree_node) * n_nodes,
+                      hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -464,6 +464,9 @@ struct ut_ctx {
   int32_t forest_trees = 0, forest_rule = 0;
   int32_t forest_max_feat = -1;   // largest feature index of the loaded ensemble's splits
   double forest_base = 0.0, forest_scale = 1.0, forest_div = 1.0;
+  // the loaded records as the device holds them: every leaf's threshold field
+  // is its variance (0 until ut_forest_leaf_var; forest_score.hip reads it)
+  std::vector<ut_tree_node> forest_host;
 
   // multi-GPU exchange (comm.hip): the RCCL communicator of this context's
   // rank and the packed top-k records of the all-gather / merge

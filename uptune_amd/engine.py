@@ -588,6 +588,9 @@ class BatchEngine:
                                                  nodes.ctypes.data, int(f.rule), float(f.base), float(f.scale),
                                                  float(f.div)), "ut_forest_set")
         self.forest = f
+        if f.leaf_var is not None:
+            lv = np.ascontiguousarray(f.leaf_var, dtype=np.float64)
+            L.check(self.ctx, self.lib.ut_forest_leaf_var(self.ctx, lv.ctypes.data, lv.size), "ut_forest_leaf_var")
 
     def forest_predict(self, feat: torch.Tensor, m: Optional[int] = None, dup: Optional[torch.Tensor] = None,
                        sign: float = -1.0):
@@ -598,6 +601,19 @@ class BatchEngine:
                                                      _ptr(dup), float(sign), _ptr(pred), _ptr(score)),
                 "ut_forest_predict")
         return pred, score
+
+    def forest_score(self, feat: torch.Tensor, acq: Optional[L.Acq] = None, f_best: float = 0.0,
+                     dup: Optional[torch.Tensor] = None, m: Optional[int] = None):
+        """ut_forest_score of the loaded averaged ensemble: -> (mu, var, score), each [m];
+        mu is forest_predict's pred, var the variance over trees plus the mean leaf
+        variance, score the GP's acquisition at (mu, var, f_best), -inf on duplicates"""
+        m = feat.shape[1] if m is None else m
+        acq = acq or self.acq()
+        mu, var, score = self._empty(m), self._empty(m), self._empty(m)
+        L.check(self.ctx, self.lib.ut_forest_score(self.ctx, _ptr(feat), feat.stride(0), m, feat.shape[0],
+                                                   _ptr(dup), C.byref(acq), float(f_best), _ptr(mu), _ptr(var),
+                                                   _ptr(score)), "ut_forest_score")
+        return mu, var, score
 
     # -- selection ---------------------------------------------------------
     def topk(self, score: torch.Tensor, k: int, dup: Optional[torch.Tensor] = None, cand_base: int = 0):

@@ -8,6 +8,11 @@ averages the models and ranks the pool (src/multi_stage.py:8-22 `score`,
 (`ut_tree_node`) and every candidate of a pool walks it on the GPU
 (csrc/forest.hip), on the same features the GP uses.
 
+An averaged ensemble (RandomForest / ExtraTrees) also has a predictive
+variance: the spread of its trees' leaf means plus the mean of the leaves' own
+target variances (`from_sklearn(model, leaf_var=True)`, engine.forest_score,
+csrc/forest_score.hip) -- SMAC's model, scored by the GP's EI / UCB.
+
 Accepted models:
   * scikit-learn DecisionTreeRegressor, RandomForestRegressor,
     ExtraTreesRegressor, GradientBoostingRegressor (squared error) --
@@ -22,7 +27,7 @@ from __future__ import annotations
 
 import json
 from dataclasses import dataclass
-from typing import Any, List, Sequence
+from typing import Any, List, Optional, Sequence
 
 import numpy as np
 
@@ -38,6 +43,10 @@ class Forest:
     base: float
     scale: float
     div: float
+    # the variance of the training targets in every leaf ([n_nodes], read at
+    # leaves only), or None: what engine.forest_score's variance adds to the
+    # spread of the trees' means (ut_forest_leaf_var)
+    leaf_var: Optional[np.ndarray] = None
 
     @property
     def n_trees(self) -> int:
@@ -67,8 +76,20 @@ def _append_sklearn_tree(tree, out: List[np.ndarray], offset: int) -> int:
     return offset + n
 
 
-def from_sklearn(model) -> Forest:
-    """DecisionTree / RandomForest / ExtraTrees / GradientBoosting regressors"""
+def _sklearn_leaf_var(trees) -> np.ndarray:
+    """tree_.impurity of squared-error trees is the variance of the node's
+    training targets; clamped at 0 (ExtraTrees on targets offset by 1e3 gives
+    impurities of about -1e-13: E[y^2] - E[y]^2 in floating point)"""
+    for est in trees:
+        if getattr(est, "criterion", None) not in ("squared_error", "friedman_mse", "mse"):
+            raise TypeError(f"leaf_var: a leaf's impurity is its variance only for squared-error trees, "
+                            f"not criterion={getattr(est, 'criterion', None)!r}")
+    return np.maximum(np.concatenate([np.asarray(est.tree_.impurity, np.float64) for est in trees]), 0.0)
+
+
+def from_sklearn(model, leaf_var: bool = False) -> Forest:
+    """DecisionTree / RandomForest / ExtraTrees / GradientBoosting regressors;
+    leaf_var: also the leaves' training-target variances (Forest.leaf_var)"""
     name = type(model).__name__
     parts: List[np.ndarray] = []
     roots: List[int] = []
@@ -76,13 +97,15 @@ def from_sklearn(model) -> Forest:
     if name == "DecisionTreeRegressor":
         roots.append(off)
         _append_sklearn_tree(model, parts, off)
-        return Forest(np.concatenate(parts), np.array(roots, np.int32), L.UT_SPLIT_LE, 0.0, 1.0, 1.0)
+        return Forest(np.concatenate(parts), np.array(roots, np.int32), L.UT_SPLIT_LE, 0.0, 1.0, 1.0,
+                      _sklearn_leaf_var([model]) if leaf_var else None)
     if name in ("RandomForestRegressor", "ExtraTreesRegressor"):
         for est in model.estimators_:              # ForestRegressor.predict: sum in order, then / T
             roots.append(off)
             off = _append_sklearn_tree(est, parts, off)
         return Forest(np.concatenate(parts), np.array(roots, np.int32), L.UT_SPLIT_LE, 0.0, 1.0,
-                      float(len(model.estimators_)))
+                      float(len(model.estimators_)),
+                      _sklearn_leaf_var(model.estimators_) if leaf_var else None)
     if name == "GradientBoostingRegressor":
         init = model.init_
         if not hasattr(init, "constant_"):
@@ -91,7 +114,8 @@ def from_sklearn(model) -> Forest:
             roots.append(off)
             off = _append_sklearn_tree(est, parts, off)
         return Forest(np.concatenate(parts), np.array(roots, np.int32), L.UT_SPLIT_LE,
-                      float(np.asarray(init.constant_).ravel()[0]), float(model.learning_rate), 1.0)
+                      float(np.asarray(init.constant_).ravel()[0]), float(model.learning_rate), 1.0,
+                      _sklearn_leaf_var(list(model.estimators_[:, 0])) if leaf_var else None)
     raise TypeError(f"unsupported model {name}")
 
 

@@ -274,7 +274,8 @@ class SharedModel:
     def __init__(self, device: int = 0, seed: int = 0, lengthscale: Union[float, str] = 0.3, min_train: int = 4,
                  precision: int = 64, sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 1e-8,
                  engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40,
-                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False):
+                 feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
+                 surrogate: Optional[str] = None, forest_kw: Optional[Dict[str, Any]] = None):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -335,6 +336,21 @@ class SharedModel:
         # (engine.gp_set_prune_weighted); False: they refuse, and a technique
         # with prune_rows > 0 cannot use this model's feasibility / constraints
         self.prune_weighted = bool(prune_weighted)
+        # surrogate: None = the GP; "forest" = a random forest refitted on the
+        # host from the same usable rows, features and y_transform whenever the
+        # GP would refit: RandomForestRegressor(n_estimators=64, min_samples_leaf=3,
+        # random_state=seed, **forest_kw), deterministic for a seed and data (SPMD
+        # replicas agree), loaded with its leaf variances and scored by EI / UCB
+        # on the mean and variance over trees (engine.forest_score; SMAC's
+        # model).  f_best is min(y) in the units fitted, fit_seconds the host
+        # time spent in RandomForestRegressor.fit.  The GP's weights
+        # (feasibility, constraints) and its pruned rounds do not apply.
+        if surrogate not in (None, "forest"):
+            raise ValueError("SharedModel surrogate: None (the GP) or 'forest'")
+        if surrogate is not None and (self.feasibility is not None or self.constraints):
+            raise ValueError("feasibility and constraints weight the GP's EI: not with a tree surrogate")
+        self.surrogate = surrogate
+        self.forest_kw = dict(forest_kw or {})
         self._reset()
         self.slots: Dict[str, int] = {}
 
@@ -363,6 +379,8 @@ class SharedModel:
         self._fit_key = None
         self._fit_unverified = False
         self.fits = 0
+        self.f_best = None          # surrogate="forest": min(y) of the last fit, in the units fitted
+        self.fit_seconds = 0.0      # ... and the host time of its RandomForestRegressor.fit calls
         # list drivers (append-only results table): the usable rows found so
         # far and how far the table has been scanned
         self._scan_n = 0
@@ -427,10 +445,9 @@ class SharedModel:
         if new:
             self.engine.history_add(new)
 
-    def fit(self, driver) -> bool:
-        """(re)fit the GP iff the driver's results changed since the last fit;
-        the new training rows are encoded on the device (ut_encode_features)
-        and the fit is enqueued without a host wait (ut_gp_fit_async)"""
+    def _scan(self, driver):
+        """the driver's results as (usable rows, their ids, failed results), in
+        arrival order: what either surrogate trains on"""
         cons = self.constraints
 
         def measured(r):   # (constraints) every constrained measurement is there and finite
@@ -471,22 +488,13 @@ class SharedModel:
             ids = [getattr(r, "id", i) for i, r in enumerate(rows)]
             bad = [r for r in res if not usable(r) and failed(r)]
             self._fail_k = 0
-        if len(rows) < self.min_train:
-            return False
-        if self._fit_unverified and self._fit_key is not None:
-            # the previous fit ran asynchronously (no host wait when it was
-            # enqueued): a kernel matrix that was not positive definite would
-            # leave every score NaN, so check it once, before reusing it
-            self._fit_unverified = False
-            if not self.engine.gp_fit_ok():
-                self.hyper["jitter"] = max(10.0 * self.hyper.get("jitter", 0.0), 1e-8)
-                log.warning("GP fit on %d results was not positive definite: refitting with jitter %g",
-                            self._fit_key[0], self.hyper["jitter"])
-                self._fit_key = None
-        key = (len(rows), ids[-1])
-        if key == self._fit_key:
-            self._load_failed(bad)      # failures alone do not refit, but they count
-            return True
+        return rows, ids, bad
+
+    def _gather(self, rows, ids) -> None:
+        """_Xa / _ya (and _Ca) := the features, objectives (and signed constraint
+        values) of `rows`, arrival order; only the rows appended since the last
+        call are encoded"""
+        cons = self.constraints
         k = self._n
         if k == 0 or ids[:k] != self._res_ids:      # not an append: re-encode everything
             k = self._n = self._nf = 0
@@ -505,6 +513,68 @@ class SharedModel:
                                  for r in new]
             self._n = n
             self._res_ids = list(ids)   # a copy: the scan list keeps growing
+
+    def _transform(self, y):
+        """what the surrogate is fitted on (y_transform)"""
+        if self.y_transform == "rank":
+            from scipy.special import ndtri
+            from scipy.stats import rankdata
+            # average ranks: tied (repeated) measurements get one normal score,
+            # whatever their row order (ADVICE r5)
+            r = rankdata(y, method="average") - 1.0
+            y = ndtri((r + 0.5) / len(y))
+        return y
+
+    def _fit_forest(self, rows, ids) -> bool:
+        """surrogate="forest": refit the random forest iff the usable results changed"""
+        import time
+
+        from sklearn.ensemble import RandomForestRegressor
+
+        from .forest import from_sklearn
+        key = (len(rows), ids[-1])
+        if key == self._fit_key:
+            return True
+        self._gather(rows, ids)
+        n = self._n
+        y = self._transform(self._ya[:n])
+        kw = dict(n_estimators=64, min_samples_leaf=3, random_state=self.seed)
+        kw.update(self.forest_kw)
+        t0 = time.perf_counter()
+        rf = RandomForestRegressor(**kw).fit(self._Xa[:n], y)
+        self.fit_seconds += time.perf_counter() - t0
+        self.engine.forest_set(from_sklearn(rf, leaf_var=True))
+        self.f_best = float(np.min(y))
+        self._fit_key = key
+        self.fits += 1
+        return True
+
+    def fit(self, driver) -> bool:
+        """(re)fit the surrogate iff the driver's results changed since the last
+        fit.  The GP: the new training rows are encoded on the device
+        (ut_encode_features) and the fit is enqueued without a host wait
+        (ut_gp_fit_async)"""
+        cons = self.constraints
+        rows, ids, bad = self._scan(driver)
+        if len(rows) < self.min_train:
+            return False
+        if self.surrogate == "forest":
+            return self._fit_forest(rows, ids)
+        if self._fit_unverified and self._fit_key is not None:
+            # the previous fit ran asynchronously (no host wait when it was
+            # enqueued): a kernel matrix that was not positive definite would
+            # leave every score NaN, so check it once, before reusing it
+            self._fit_unverified = False
+            if not self.engine.gp_fit_ok():
+                self.hyper["jitter"] = max(10.0 * self.hyper.get("jitter", 0.0), 1e-8)
+                log.warning("GP fit on %d results was not positive definite: refitting with jitter %g",
+                            self._fit_key[0], self.hyper["jitter"])
+                self._fit_key = None
+        key = (len(rows), ids[-1])
+        if key == self._fit_key:
+            self._load_failed(bad)      # failures alone do not refit, but they count
+            return True
+        self._gather(rows, ids)
         # Row order.  The GP posterior does not depend on it, but the EI bound of
         # pruned scoring (ut_gp_topk_pruned) comes from the first rows of L^-1:
         # with the best results first it sees the neighbourhood that GA / GGA
@@ -532,14 +602,7 @@ class SharedModel:
             if cons:
                 self._Cf[self._nf:n] = self._Ca[self._nf:n]
         self._nf = n
-        y = self._yf[:n]
-        if self.y_transform == "rank":
-            from scipy.special import ndtri
-            from scipy.stats import rankdata
-            # average ranks: tied (repeated) measurements get one normal score,
-            # whatever their row order
-            r = rankdata(y, method="average") - 1.0
-            y = ndtri((r + 0.5) / n)
+        y = self._transform(self._yf[:n])
         ell = self.lengthscale
         if isinstance(ell, str):   # "auto" / "ard"
             if npad != self._ell_npad:
@@ -763,8 +826,19 @@ class GpuBatchTechnique(SearchTechnique):
                  group=None, surrogate=None, shared: Optional[SharedModel] = None, engine_factory=None,
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
-                 *pargs, **kwargs):
+                 forest_kw: Optional[Dict[str, Any]] = None, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
+        # surrogate="forest" (SharedModel): a random forest refitted from the
+        # driver's results, scored by EI / UCB on its mean and variance over
+        # trees.  A shared model carries its own setting (and forest_kw)
+        refit = isinstance(surrogate, str) and surrogate == "forest"
+        if shared is not None:
+            if refit and shared.surrogate != "forest":
+                raise ValueError("surrogate='forest' with a shared model that fits a GP")
+            if surrogate is not None and not refit and shared.surrogate == "forest":
+                raise ValueError("a model object as surrogate with a shared model that refits a forest")
+            refit = shared.surrogate == "forest"
+        tree = refit or surrogate is not None
         # prune_weighted (SharedModel): pruned rounds under constraints / feasibility,
         # by the weighted bound of ut_gp_set_prune_weighted.  A shared model carries its own
         weighted = shared.prune_weighted if shared is not None else bool(prune_weighted)
@@ -778,7 +852,7 @@ class GpuBatchTechnique(SearchTechnique):
                 raise ValueError("constraints are not known to the per-pick acquisition: not with diversify")
             if acq == "ucb":
                 raise ValueError("constraints multiply a score that is >= 0: EI, not acq='ucb'")
-            if surrogate is not None:
+            if tree:
                 raise ValueError("constraints weight the GP's EI: not with a tree surrogate")
         # feasibility (SharedModel): EI times the estimated probability that the
         # candidate does not fail.  A shared model carries its own setting; the
@@ -790,7 +864,7 @@ class GpuBatchTechnique(SearchTechnique):
                 raise ValueError("feasibility is not known to the per-pick acquisition: not with diversify")
             if acq == "ucb":
                 raise ValueError("feasibility multiplies a score that is >= 0: EI, not acq='ucb'")
-            if surrogate is not None:
+            if tree:
                 raise ValueError("feasibility weights the GP's EI: not with a tree surrogate")
         # diversify = D > 0: a round with a GP takes the D best-scoring candidates
         # as a shortlist and picks its `batch` from them with ut_gp_select_batch,
@@ -802,18 +876,22 @@ class GpuBatchTechnique(SearchTechnique):
                 raise ValueError("diversify must be 0 or in [batch, 4096]")
             if int(prune_rows) > 0:
                 raise ValueError("diversify needs every candidate's score: not with prune_rows")
-            if surrogate is not None:
+            if tree:
                 raise ValueError("diversify conditions a GP posterior: not with a tree surrogate")
         # prune_rows > 0: score rounds with ut_gp_topk_pruned (selection-exact EI
         # bound from the first prune_rows rows of L^-1 k*; fp64 fits, EI / UCB):
         # the same selections as the dense variance at a fraction of its cost
         # when the bounds are tight (or the GP is flat: exact ties by index)
         self.prune_rows = int(prune_rows)
+        if refit and self.prune_rows > 0:
+            raise ValueError("prune_rows bounds a GP posterior: not with a tree surrogate")
         # surrogate: None = the GP fitted on the driver's results (EI / UCB); or a
         # tree ensemble over the same features (sklearn regressor, XGBoost JSON,
         # forest.Forest) ranking candidates by predicted objective (minimised),
-        # the multi-stage tuner's model scoring (multi_stage.py:8-22, :109-123)
-        self.surrogate = surrogate
+        # the multi-stage tuner's model scoring (multi_stage.py:8-22, :109-123);
+        # or "forest": the model's own refitted random forest (above)
+        self.surrogate = "forest" if refit else surrogate
+        self._static = tree and not refit    # a fixed model object: no fit, mean ranking
         # precision: the GP contractions of a private model (64 / 32 / 16 = f16x3);
         # a shared model (the bandit's) carries its own
         self.model = shared if shared is not None else SharedModel(device=device, seed=seed,
@@ -823,7 +901,9 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    y_transform=y_transform,
                                                                    feasibility=feasibility,
                                                                    constraints=constraints,
-                                                                   prune_weighted=prune_weighted)
+                                                                   prune_weighted=prune_weighted,
+                                                                   surrogate="forest" if refit else None,
+                                                                   forest_kw=forest_kw)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -900,7 +980,7 @@ class GpuBatchTechnique(SearchTechnique):
         # instead of starving beside the hash, and no host wait sits between the
         # hash and the fit (the proposals never read the GP).  Dense fp64 rounds
         # keep the fit beside their K* (only the variance GEMM waits for it).
-        have_model = self.surrogate is None and self.model.fit(self.driver)
+        have_model = not self._static and self.model.fit(self.driver)
         if have_model and self.prune_rows > 0 and self.model.precision == 64:
             eng.gp_join_fit()
         base = self.round_base()
@@ -909,10 +989,12 @@ class GpuBatchTechnique(SearchTechnique):
         dup = eng.dedup(dig)
         if invalid is not None:
             dup = torch.maximum(dup, invalid)
-        if self.surrogate is not None:
+        if self._static:
             if getattr(eng, "forest", None) is None:
                 eng.forest_set(self.surrogate)
             _, score = eng.forest_predict(eng.encode(vals), dup=dup)
+        elif have_model and self.model.surrogate == "forest":
+            _, _, score = eng.forest_score(eng.encode(vals), eng.acq(self.acq_kind), self.model.f_best, dup=dup)
         elif have_model:
             if self.prune_rows > 0 and self.model.precision == 64:
                 idx, top, _ = eng.gp_topk_pruned(eng.encode(vals), self.batch, acq=eng.acq(self.acq_kind), dup=dup,
@@ -976,7 +1058,7 @@ class GpuBatchTechnique(SearchTechnique):
         eng = self.engine
         # the selections (and, for the GP's next fit, their features) reach the
         # host in ONE copy: global indices, value rows, digests, features
-        feat = eng.encode(rows) if self.surrogate is None else None
+        feat = None if self._static else eng.encode(rows)
         parts = [idx.contiguous().view(torch.float64), rows.contiguous().reshape(-1),
                  dig.to(torch.int32).contiguous().view(torch.float64).reshape(-1)]
         if feat is not None:
@@ -1128,7 +1210,9 @@ def _shared_model(kw) -> SharedModel:
                        min_train=kw.get("min_train", 4), precision=kw.get("precision", 64),
                        engine_factory=kw.pop("engine_factory", None), y_transform=kw.get("y_transform"),
                        feasibility=kw.get("feasibility", False), constraints=kw.get("constraints"),
-                       prune_weighted=kw.get("prune_weighted", False))
+                       prune_weighted=kw.get("prune_weighted", False),
+                       surrogate="forest" if isinstance(kw.get("surrogate"), str) and kw["surrogate"] == "forest"
+                       else None, forest_kw=kw.get("forest_kw"))
 
 
 def pso_ga_de_bandit(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
