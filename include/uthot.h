@@ -467,6 +467,87 @@ int ut_gp_lml_grad(ut_ctx* ctx, int32_t d, double* dlog_ell_host, double* dlog_s
 int ut_gp_select_batch(ut_ctx* ctx, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
                        const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);
 
+/* ---- acquisition gradient and projected-ascent polish --------------------- */
+/* The reference's default bandit carries a local-search arm, RandomNelderMead
+ * (bandittechniques.py:273-278; the simplex walk itself is
+ * simplextechniques.py:180-320).  Here the shortlist of a GP round is refined
+ * by the acquisition's own gradient instead: the polish below stands in for
+ * that arm, it is not a Nelder-Mead.
+ *
+ * ut_gp_acq_grad: score, mean, variance and d score / d u of p candidates
+ * (values [ncols][ld], raw values as for ut_gp_score_values; 1 <= p <= 4096).
+ * With u the candidate's unit features, us = u / ell, xs_i the fit's scaled
+ * training rows (the dense RBF over every feature, as ut_gp_select_batch):
+ *   k_i = sigma_f2 exp(-1/2 |us - xs_i|^2),  v = L^-1 k,  w = L^-T v,
+ *   mu = v . beta,  var = max(sigma_f2 - |v|^2, 0),  sigma = sqrt(var),
+ *   dmu/du_j  = -(1/ell_j) (us_j sum_i alpha_i k_i - sum_i alpha_i k_i xs_ij)
+ *   dvar/du_j = +(2/ell_j) (us_j sum_i w_i k_i     - sum_i w_i k_i xs_ij)
+ *   dsigma/du_j = dvar/du_j / (2 sigma) where sigma > 0, else 0
+ *   EI:  ds = -Phi(z) dmu + phi(z) dsigma,  I = f_best - mu - xi, z = I / sigma;
+ *        where sigma is not > 0: ds = -[I > 0] dmu
+ *   UCB: ds = kappa dsigma - dmu
+ * f_best and xi as in ut_gp_score (the same ut_acq); score is that call's
+ * acquisition of (mu, var).  Device outputs: out_score [p] (may be NULL),
+ * out_mu [p], out_var [p] (may be NULL), out_grad [n_feat][ld_g]: the
+ * derivative in EVERY unit feature, one-hot and PERM columns included.
+ * Stream-ordered, no host wait: an in-flight fit is waited for on the device; a
+ * failed fit makes every score NaN (the return code is still 0).  Always fp64,
+ * whatever ut_gp_set_precision says.  Reads the fit, writes scratch of its
+ * own.  Sums in a fixed order: two calls on one fit return the same bits.
+ * UT_EINVAL: p < 1, p > 4096, ld < p, ld_g < p, a NULL values, acq, out_mu or
+ * out_grad, no fit, a fit whose feature count is not the space's, and while
+ * constraint values (ut_gp_cons_set) or failed rows (ut_gp_feas_set) are
+ * loaded: the gradient of the weighted score is not built.
+ * UT_ENOMEM: the scratch could not be allocated. */
+int ut_gp_acq_grad(ut_ctx* ctx, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
+                   double* out_score, double* out_mu, double* out_var, double* out_grad, int64_t ld_g);
+
+typedef struct ut_polish_params {
+  int32_t steps;   /* T >= 0 ascent steps */
+  int32_t pad;
+  double step0;    /* first step length, in lengthscale units; 0: 0.25 */
+  double step_max; /* its cap; 0: 1.0 */
+  double grow;     /* factor after an accepted step; 0: 2.0 */
+  double shrink;   /* factor after a rejected step; 0: 0.5 */
+} ut_polish_params;
+
+/* ut_gp_polish: T steps of projected gradient ascent on the acquisition for
+ * each of p candidates, all on the device.  Per candidate i:
+ *   1. u = the encoder's unit features of the input values, eta = step0,
+ *      s = s0 = score(u) (ut_gp_acq_grad's score).  A candidate with
+ *      dup[i] != 0 (dup may be NULL) never moves: its out_score and out_score0
+ *      are -inf and its out_values the input.  A failed fit makes every score
+ *      NaN, so nothing moves.
+ *   2. T times: g = ds/du; g_j = 0 on every feature that is not a FREE column
+ *      (the unit value of a FLOAT, INT, LOGINT or POW2 parameter with
+ *      u_lo < u_hi; BOOL, ENUM and PERM columns are never free) and where
+ *      (u_j <= 0 and g_j < 0) or (u_j >= 1 and g_j > 0);
+ *      N = sqrt(sum_j (ell_j g_j)^2), j ascending.  N == 0 or not finite: the
+ *      candidate stays and eta is unchanged.  Otherwise the trial is
+ *      u'_j = clip(u_j + eta ell_j^2 g_j / N, 0, 1) on the free columns, and
+ *      s' = score(u').  s' > s (strictly): u <- u', s <- s',
+ *      eta <- min(grow eta, step_max); otherwise eta <- shrink eta.
+ *   3. A candidate that accepted no step is returned as it came.  Otherwise
+ *      v' = set_unit_value(u) on the free parameters (manipulator.py:490-503;
+ *      integer kinds round there), every other column the input's bits; v' is
+ *      encoded again by the same encoder and scored: s_v.  If s_v > s0:
+ *      out_values = v', out_score = s_v, moved = 1; otherwise out_values are
+ *      the input's bits, out_score = s0, moved = 0.
+ * So out_score >= out_score0 for every candidate, out_score is bitwise what
+ * ut_gp_acq_grad returns as score on out_values (same p), and steps = 0
+ * returns the input bitwise.
+ * Device outputs: out_values [ncols][ld_o], out_score [p], out_score0 [p] (may
+ * be NULL), out_moved [p] (may be NULL).  Stream-ordered, no host wait; always
+ * fp64; fixed summation order (two calls return the same bits); 2 T + 1
+ * evaluations of K* and V = L^-1 K*^T (T = 0: 2), T of W = L^-T V.
+ * UT_EINVAL: as ut_gp_acq_grad (p, ld, NULL values / acq / out_values /
+ * out_score / prm, no fit, feature count, loaded constraint values or failed
+ * rows), ld_o < p, steps < 0, a negative or non-finite step0, step_max, grow
+ * or shrink.  UT_ENOMEM: the scratch could not be allocated. */
+int ut_gp_polish(ut_ctx* ctx, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
+                 const uint8_t* dup, const ut_polish_params* prm, double* out_values, int64_t ld_o,
+                 double* out_score, double* out_score0, uint8_t* out_moved);
+
 /* ---- failure-aware scoring ---------------------------------------------- */
 /* The surrogate is fitted on results that succeeded; a configuration that
  * failed (compile error, crash, timeout) only joins the dedup set.  These calls

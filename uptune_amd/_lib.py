@@ -93,6 +93,11 @@ class FeasParams(C.Structure):
     _fields_ = [("prior", C.c_double), ("strength", C.c_double), ("ell_scale", C.c_double), ("power", C.c_double)]
 
 
+class PolishParams(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("pad", C.c_int32), ("step0", C.c_double), ("step_max", C.c_double),
+                ("grow", C.c_double), ("shrink", C.c_double)]
+
+
 class RoundOut(C.Structure):
     _fields_ = [("topk_idx", C.c_void_p), ("topk_score", C.c_void_p), ("topk_digest", C.c_void_p),
                 ("topk_values", C.c_void_p)]
@@ -159,6 +164,8 @@ SIGNATURES = {
     "ut_gp_lml_grad": (C.c_int, [P, I32, P, C.POINTER(D), C.POINTER(D)]),
     "ut_gp_lml_grid": (C.c_int, [P, P, P, I32, I32, C.POINTER(GpHyper), I32, P, P, P, C.POINTER(I32)]),
     "ut_gp_select_batch": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, I32, P, P, P]),
+    "ut_gp_acq_grad": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, P, P, P, I64]),
+    "ut_gp_polish": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, C.POINTER(PolishParams), P, I64, P, P, P]),
     "ut_gp_feas_set": (C.c_int, [P, P, I32, I32, C.POINTER(FeasParams)]),
     "ut_gp_feas_prob": (C.c_int, [P, P, P, I64, I64, P, P, P]),
     "ut_gp_feas_info": (C.c_int, [P, C.POINTER(I32), C.POINTER(FeasParams)]),

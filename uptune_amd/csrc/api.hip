@@ -864,6 +864,30 @@ int ut_gp_select_batch(ut_ctx* c, const double* values, int64_t ld, int32_t p, c
   return rc;
 }
 
+int ut_gp_acq_grad(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, double* out_score,
+                   double* out_mu, double* out_var, double* out_grad, int64_t ld_g) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  // a stand-alone call is a timing round of its own (stages pl_kstar, pl_v, pl_tail, pl_w, pl_grad)
+  const bool own = c->timing.on && !c->timing.in_round;
+  if (own) timing_begin(c);
+  const int rc = gp_acq_grad_impl(c, values, ld, p, acq, out_score, out_mu, out_var, out_grad, ld_g);
+  if (own) timing_end(c);
+  return rc;
+}
+
+int ut_gp_polish(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, const uint8_t* dup,
+                 const ut_polish_params* prm, double* out_values, int64_t ld_o, double* out_score,
+                 double* out_score0, uint8_t* out_moved) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  const bool own = c->timing.on && !c->timing.in_round;
+  if (own) timing_begin(c);
+  const int rc = gp_polish_impl(c, values, ld, p, acq, dup, prm, out_values, ld_o, out_score, out_score0, out_moved);
+  if (own) timing_end(c);
+  return rc;
+}
+
 int ut_gp_feas_set(ut_ctx* c, const double* Xfail_host, int32_t nf, int32_t d, const ut_feas_params* p) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));

@@ -78,6 +78,12 @@ __global__ __launch_bounds__(256) void k_bs_v(const double* __restrict__ Linv, i
       for (int r = 0; r < 4; ++r) V[(row0 + tile_row(a, r)) * ldp + col0 + tile_col(b)] = acc[a][b][r];
 }
 
+int launch_bs_v(ut_ctx* c, int32_t CT, int32_t npad, const double* kst, int64_t ldp, double* V) {
+  hipLaunchKernelGGL(k_bs_v, dim3(CT, npad / 64), dim3(256), 0, c->stream, c->gp_Linv.p, npad, kst, ldp, V);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 __global__ __launch_bounds__(256) void k_bs_mu(const double* __restrict__ V, int64_t ldp, const double* __restrict__ beta,
                                                int32_t n, int32_t p, double* __restrict__ mu) {
   const int32_t i = blockIdx.x * 256 + threadIdx.x;

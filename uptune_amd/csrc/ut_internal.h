@@ -501,6 +501,12 @@ struct ut_ctx {
   ut::DevBuf<double> bs_vec;               // mu [ldp] | var [ldp] | the launches' partial scores [2][16]
   ut::DevBuf<int32_t> bs_pos;              // ... and partial positions [2][16]
   ut::DevBuf<uint8_t> bs_picked;           // [ldp]
+  // the acquisition gradient's and the polish's scratch (gp_polish.hip), beside bs_u, bs_cn, bs_kst, bs_v
+  ut::DevBuf<double> bs_w;                 // W = L^-T V [npad][ldp]
+  ut::DevBuf<double> bs_pu;                // unit features: current [d][ldp] | trial [d][ldp] | gradient [d][ldp]
+  ut::DevBuf<double> bs_pvec;              // per candidate [ldp] each: mu, var, score, cm, cs, s, s0, eta
+  ut::DevBuf<double> bs_pval;              // the decoded rows [ncols][ldp]
+  ut::DevBuf<uint8_t> bs_pflag;            // free [d to 256] | active [ldp] | accepted [ldp]
   // failure-aware scoring (gp_feas.hip): the loaded failed rows, and their K*
   // operands under the current fit's lengthscales -- a per-fit cache like pr_f2
   ut::DevBuf<double> fs_X;                 // [fs_n][fs_d] features as given to ut_gp_feas_set
@@ -731,6 +737,14 @@ int weights_refuse_ucb(ut_ctx* c, const ut_acq* acq, bool feas, bool cons);
 // gp_batch.hip: k picks from a shortlist of p, each conditioned on the picks before it
 int gp_select_batch_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
                          const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);
+// ... its V = L^-1 K*^T [npad][ldp] alone (k_bs_v), CT column tiles of 64
+int launch_bs_v(ut_ctx* c, int32_t CT, int32_t npad, const double* kst, int64_t ldp, double* V);
+// gp_polish.hip: the acquisition's gradient in the unit features, and the projected-ascent polish of a shortlist
+int gp_acq_grad_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, double* out_score,
+                     double* out_mu, double* out_var, double* out_grad, int64_t ld_g);
+int gp_polish_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, const uint8_t* dup,
+                   const ut_polish_params* prm, double* out_values, int64_t ld_o, double* out_score,
+                   double* out_score0, uint8_t* out_moved);
 
 // kernel launchers implemented in the .hip translation units
 int launch_population_init(ut_ctx* c, uint32_t round_);

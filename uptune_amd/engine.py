@@ -453,6 +453,47 @@ class BatchEngine:
                 "ut_gp_select_batch")
         return pos, score, var
 
+    def _shortlist(self, values: torch.Tensor, who: str) -> torch.Tensor:
+        if values.dim() != 2 or values.shape[0] != self.spec.ncols:
+            raise ValueError(f"{who}: values must be [{self.spec.ncols}][p]")
+        return values if values.stride(1) == 1 else values.contiguous()
+
+    def gp_acq_grad(self, values: torch.Tensor, acq: Optional[L.Acq] = None):
+        """ut_gp_acq_grad: -> (score [p], mu [p], var [p], grad [n_features][p]),
+        the acquisition of values[:, :p] under the current fit and its
+        derivative in every unit feature.  Always fp64; stream-ordered."""
+        values = self._shortlist(values, "gp_acq_grad")
+        p = values.shape[1]
+        acq = acq or self.acq()
+        score, mu, var = self._empty(p), self._empty(p), self._empty(p)
+        grad = torch.empty((self.spec.n_features, max(p, 1)), dtype=torch.float64, device=self.device)
+        L.check(self.ctx, self.lib.ut_gp_acq_grad(self.ctx, _ptr(values), values.stride(0), p, C.byref(acq),
+                                                  _ptr(score), _ptr(mu), _ptr(var), _ptr(grad), grad.stride(0)),
+                "ut_gp_acq_grad")
+        return score, mu, var, grad
+
+    def gp_polish(self, values: torch.Tensor, steps: int, acq: Optional[L.Acq] = None,
+                  dup: Optional[torch.Tensor] = None, step0: float = 0.0, step_max: float = 0.0,
+                  grow: float = 0.0, shrink: float = 0.0):
+        """ut_gp_polish: `steps` projected gradient-ascent steps on the
+        acquisition for each candidate of values[:, :p]; only FLOAT / INT /
+        LOGINT / POW2 values move.  -> (values [ncols][p], score [p], score0
+        [p], moved [p] uint8); score >= score0, and an unmoved row is the
+        input's bits.  A 0 parameter takes the library's default (step0 0.25,
+        step_max 1.0, grow 2.0, shrink 0.5)."""
+        values = self._shortlist(values, "gp_polish")
+        p = values.shape[1]
+        acq = acq or self.acq()
+        prm = L.PolishParams(steps=int(steps), pad=0, step0=float(step0), step_max=float(step_max),
+                             grow=float(grow), shrink=float(shrink))
+        out = torch.empty((self.spec.ncols, max(p, 1)), dtype=torch.float64, device=self.device)
+        score, score0 = self._empty(p), self._empty(p)
+        moved = self._empty(p, dtype=torch.uint8)
+        L.check(self.ctx, self.lib.ut_gp_polish(self.ctx, _ptr(values), values.stride(0), p, C.byref(acq), _ptr(dup),
+                                                C.byref(prm), _ptr(out), out.stride(0), _ptr(score), _ptr(score0),
+                                                _ptr(moved)), "ut_gp_polish")
+        return out, score, score0, moved
+
     # -- failure-aware scoring ----------------------------------------------
     def gp_feas_set(self, X_fail, prior: Optional[float] = None, strength: float = 1.0, ell_scale: float = 1.0,
                     power: float = 1.0):

@@ -826,7 +826,8 @@ class GpuBatchTechnique(SearchTechnique):
                  group=None, surrogate=None, shared: Optional[SharedModel] = None, engine_factory=None,
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
-                 forest_kw: Optional[Dict[str, Any]] = None, *pargs, **kwargs):
+                 forest_kw: Optional[Dict[str, Any]] = None, polish: int = 0, polish_pool: Optional[int] = None,
+                 *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
         # surrogate="forest" (SharedModel): a random forest refitted from the
         # driver's results, scored by EI / UCB on its mean and variance over
@@ -878,6 +879,26 @@ class GpuBatchTechnique(SearchTechnique):
                 raise ValueError("diversify needs every candidate's score: not with prune_rows")
             if tree:
                 raise ValueError("diversify conditions a GP posterior: not with a tree surrogate")
+        # polish = T > 0: a dense GP round refines its polish_pool best-scoring
+        # candidates with T steps of projected gradient ascent on the acquisition
+        # (ut_gp_polish) before it takes its batch from them -- the local search
+        # that the reference's default bandit has in its RandomNelderMead arm
+        # (bandittechniques.py:273-278); 0 = today's path, untouched
+        self.polish = int(polish)
+        self.polish_pool = max(4 * int(batch), 64) if polish_pool is None else int(polish_pool)
+        if self.polish < 0:
+            raise ValueError("polish must be >= 0")
+        if self.polish:
+            if not int(batch) <= self.polish_pool <= 4096:
+                raise ValueError("polish_pool must be in [batch, 4096]")
+            if int(prune_rows) > 0:
+                raise ValueError("polish needs every candidate's score: not with prune_rows")
+            if tree:
+                raise ValueError("polish climbs a GP's acquisition: not with a tree surrogate")
+            if shared.constraints if shared is not None else _cons_setting(constraints):
+                raise ValueError("the gradient of the constrained score is not built: no polish with constraints")
+            if (shared.feasibility if shared is not None else _feas_setting(feasibility)) is not None:
+                raise ValueError("the gradient of the weighted score is not built: no polish with feasibility")
         # prune_rows > 0: score rounds with ut_gp_topk_pruned (selection-exact EI
         # bound from the first prune_rows rows of L^-1 k*; fp64 fits, EI / UCB):
         # the same selections as the dense variance at a fraction of its cost
@@ -1003,6 +1024,8 @@ class GpuBatchTechnique(SearchTechnique):
                 return vals, idx, top, dig[loc], vals[:, loc]
             # encoding fused into the K* operand pass (no feature matrix)
             _, _, score = eng.gp_score_values(vals, acq=eng.acq(self.acq_kind), dup=dup)
+            if self.polish > 0:
+                return self._polished_picks(vals, score, dup, dig, base)
             if self.diversify > 0:
                 return self._diverse_picks(vals, score, dup, dig, base)
         else:  # no model yet: every non-duplicate candidate is equally good (lowest index first)
@@ -1027,9 +1050,42 @@ class GpuBatchTechnique(SearchTechnique):
         idx = torch.where(pos >= 0, loc + base, torch.full_like(pos, -1))
         return vals, idx, top, dig[loc], vals[:, loc]
 
+    def _polished_picks(self, vals, score, dup, dig, base):
+        """the round's selections from the polish_pool best-scoring candidates
+        after `polish` ascent steps on each (BatchEngine.gp_polish); what
+        _local_round returns.  A pick keeps the global index of the shortlist
+        entry it descends from; its row, digest and score are the final ones."""
+        import torch
+        eng = self.engine
+        acq = eng.acq(self.acq_kind)
+        D = min(self.polish_pool, vals.shape[1])
+        sidx, _ = eng.topk(score, D, dup=dup, cand_base=0)       # local positions, -1 = none
+        none = sidx < 0
+        sloc = torch.where(none, torch.zeros_like(sidx), sidx)
+        short, sdig = vals[:, sloc].contiguous(), dig[sloc]
+        rows, fscore, score0, moved = eng.gp_polish(short, self.polish, acq=acq, dup=none.to(torch.uint8))
+        pdig = eng.hash(rows)
+        # a moved entry that landed on a configuration already seen (or on an
+        # earlier entry's row) goes back to where it came from
+        back = (moved != 0) & (eng.dedup(pdig) != 0)
+        rows = torch.where(back[None, :], short, rows)
+        fscore = torch.where(back, score0, fscore)
+        fdig = torch.where(back[:, None], sdig, pdig)
+        out = torch.maximum(eng.dedup(fdig), none.to(torch.uint8))   # what is still a repeat is left out
+        k = min(self.batch, D)
+        if self.diversify > 0:   # polishing pulls neighbours onto one hill; conditioning spreads them again
+            pos, top, _ = eng.gp_select_batch(rows, k, acq=acq, dup=out)
+        else:
+            pos, top = eng.topk(fscore, k, dup=out, cand_base=0)
+        at = torch.where(pos >= 0, pos, torch.zeros_like(pos))
+        idx = torch.where(pos >= 0, sloc[at] + base, torch.full_like(pos, -1))
+        return vals, idx, top, fdig[at], rows[:, at]
+
     def _round(self):
         from .engine import digests_to_hex
         rank, world = self._dist()
+        if self.polish > 0 and world > 1 and self.sharded:
+            raise ValueError("polish is not built for sharded rounds over several ranks")
         if self.diversify > 0 and world > 1 and self.sharded:
             # (every rank holds the same setting: all raise together, before any collective)
             raise ValueError("diversify is not built for sharded rounds over several ranks")
@@ -1238,7 +1294,8 @@ def bandit_a(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
     0.1, evolutionarytechniques.py:13-24) and NormalGreedyMutation(mutation_rate
     =0.3) on one shared model.  The fourth child, RandomNelderMead, is a
     sequential simplex technique outside the scoring path (DESIGN.md "Out of
-    scope") and is not built."""
+    scope") and is not built; polish=T (GpuBatchTechnique) is the local search
+    that stands in for it."""
     kw = dict(kw)
     shared = kw.pop("shared", None) or _shared_model(kw)
     return AUCBanditMetaTechnique([
