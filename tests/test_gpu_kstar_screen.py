@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 import _ard_cases as A  # noqa: E402
+import _i8_plan_model as PM  # noqa: E402
 import _kstar_cases as KC  # noqa: E402
 import _kstar_mask_cases as MC  # noqa: E402
 import _kstar_screen_cases as SC  # noqa: E402
@@ -205,6 +206,48 @@ def test_the_library_choice(monkeypatch):
     ran = [r["screen"][0] for r in res[0]]
     print("screened calls:", ran)
     assert ran[0] is False and ran[2] is True
+
+
+# far: unscreened, every block zero -> the hint; far: screened; dense: screened, 7 units of 16 (under half) ->
+# held off; eight unscreened calls whose zero blocks (68 of 128 and more) alone would screen; dense: the hint
+# returns; four screened calls
+POLICY_SEQUENCE = ("far", "far", "dense", "dense", "half", "rows", "far", "dense", "half", "rows", "far", "dense",
+                   "far", "half", "rows", "dense")
+POLICY_SCREENED = "USSUUUUUUUUUSSSS"
+
+
+def test_the_hint_policy_across_calls(monkeypatch):
+    """all three variables unset, sixteen calls on one context: each call screens exactly when the policy model
+    (_i8_plan_model.py), stepped with the counts read from the call before it (its mask and statistics), says
+    so -- through a back-off episode: a screen that cleared under half, the eight held-off calls, the return"""
+    X, y, sets = _two_clusters()
+    e = _engine(A.float_space(8), monkeypatch, None, tol=0.999)
+    e.gp_fit(X, y, lengthscale=1.0, sigma_f2=1.0, sigma_n2=0.25, jitter=0.0)
+    hints, trace, held = PM.Hints(), "", []
+    for i, name in enumerate(POLICY_SEQUENCE):
+        plan = PM.plan(256, 1, PM.Env(), hints)
+        e.gp_score(dev(sets[name].T))
+        screened, ncert, units = e.gp_kstar_screen_stats()
+        mask = e.gp_kstar_mask_read().cpu().numpy()
+        assert mask.shape == (8, 16) and units == 16
+        assert screened is plan.screen, "call %d (%s): the library %s, the model %s after %s" % (
+            i, name, screened, plan.screen, hints)
+        trace += "S" if screened else "U"
+        # (a certified unit's 8 bytes are 0 and were not visited to be counted)
+        cert = ncert if screened else 0
+        n = PM.Counts(int((mask != 0x3f).sum()) - 8 * cert, cert, 0 if screened else int((mask == 0).sum()), mask.size)
+        # held off: the counts alone (no back-off pending) would turn the hint on, the model leaves it off
+        alone = PM.hints_next(hints._replace(backoff=0), plan, n).screen
+        hints = PM.hints_next(hints, plan, n)
+        held.append(alone and not hints.screen and not plan.screen)
+        print("call %2d %-5s %s cert %2d zero %3d -> %s" % (i, name, trace[-1], ncert, int((mask == 0).sum()), hints))
+    e.close()
+    print("screened calls:", trace)
+    # the episode, in the model's own trace: a screened call that set the back-off, held-off calls, the return
+    assert trace == POLICY_SCREENED
+    start = trace.index("SU")
+    assert POLICY_SEQUENCE[start] == "dense" and sum(held) == 8 and all(held[start + 1:start + 9])
+    assert "S" in trace[start + 9:]
 
 
 def test_paths_without_the_screen(monkeypatch):

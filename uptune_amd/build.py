@@ -8,7 +8,7 @@ travels with the repository snapshot to the GPU box.  hipcc cross-compiles
 for gfx950 without a GPU present.
 
 Also builds libuthot_hostcheck.so (g++) -- the host build of ut_core.h used
-only by tests/test_core_host.py.
+only by tests/test_core_host.py, and of gp_i8_plan.h (tests/test_i8_plan_cpu.py).
 """
 from __future__ import annotations
 
@@ -27,7 +27,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("UT_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["api.hip", "propose.hip", "hash.hip", "dedup.hip", "gp_fit.hip", "gp_score.hip", "gp_prune.hip", "gp_gemm.hip", "gp_i8.hip", "gp_kq.hip", "gp_lml.hip", "gp_lml_grad.hip", "gp_batch.hip", "gp_polish.hip", "gp_feas.hip", "gp_cons.hip", "gp_kstar_sums.hip", "topk.hip", "forest.hip", "forest_score.hip", "comm.hip"]
-HEADERS = ["ut_core.h", "ut_internal.h", "gp_tiles.h", "gp_post.h", "gp_kstar_tile.h", "ut_param.h", "ut_perm.h", "ryu_tables.h", "libm_log_data.h", os.path.join("..", "..", "include", "uthot.h")]
+HEADERS = ["ut_core.h", "ut_internal.h", "gp_i8_plan.h", "gp_tiles.h", "gp_post.h", "gp_kstar_tile.h", "ut_param.h", "ut_perm.h", "ryu_tables.h", "libm_log_data.h", os.path.join("..", "..", "include", "uthot.h")]
 
 # RCCL for the multi-GPU exchange (comm.hip); the soname (librccl.so.1) is the
 # one torch loads too, so a process that imported torch first shares its copy

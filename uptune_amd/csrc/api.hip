@@ -791,14 +791,22 @@ int ut_gp_set_i8_tol(ut_ctx* c, double tol) {
   return 0;
 }
 
-int ut_gp_i8_bounds(ut_ctx* c, double* E, double* Emu) {
-  if (!c) return UT_EINVAL;
+// the current fit's E and Emu (gp_i8rs behind its 2 npad row scales), once the staged fit is
+// enqueued and its stream has finished; zeros where the fit is not a precision-8 one
+static int i8_read_bounds(ut_ctx* c, double (&b)[2]) {
+  b[0] = b[1] = 0.0;
   if (int rc = gp_fit_flush(c)) return rc;
-  double b[2] = {0.0, 0.0};
   if (c->gp_fit_prec == 8 && c->gp_i8rs.p) {
     UT_HIP(c, hipStreamSynchronize(c->fit_stream));
     UT_HIP(c, hipMemcpy(b, c->gp_i8rs.p + 2 * (int64_t)c->gp_npad_fit, sizeof(b), hipMemcpyDeviceToHost));
   }
+  return 0;
+}
+
+int ut_gp_i8_bounds(ut_ctx* c, double* E, double* Emu) {
+  if (!c) return UT_EINVAL;
+  double b[2];
+  if (int rc = i8_read_bounds(c, b)) return rc;
   if (E) *E = b[0];
   if (Emu) *Emu = b[1];
   return 0;
@@ -806,15 +814,10 @@ int ut_gp_i8_bounds(ut_ctx* c, double* E, double* Emu) {
 
 int ut_gp_i8_stats(ut_ctx* c, int64_t* recomputed, double* bound) {
   if (!c) return UT_EINVAL;
-  if (int rc = gp_fit_flush(c)) return rc;
-  if (recomputed) *recomputed = c->i8_recomputed;
-  if (bound) {
-    *bound = 0.0;
-    if (c->gp_fit_prec == 8 && c->gp_i8rs.p) {
-      UT_HIP(c, hipStreamSynchronize(c->fit_stream));
-      UT_HIP(c, hipMemcpy(bound, c->gp_i8rs.p + 2 * (int64_t)c->gp_npad_fit, sizeof(double), hipMemcpyDeviceToHost));
-    }
-  }
+  double b[2];
+  if (int rc = bound ? i8_read_bounds(c, b) : gp_fit_flush(c)) return rc;
+  if (recomputed) *recomputed = c->i8_stats.recomputed;
+  if (bound) *bound = b[0];
   return 0;
 }
 
@@ -1274,36 +1277,39 @@ int ut_gp_prune_bounds(ut_ctx* c, double* ub_out, uint8_t* exact_out, int64_t m)
 int ut_gp_kstar_read(ut_ctx* c, double* k_out, int64_t c0, int64_t nc, int32_t* npad, int64_t* ldk,
                      int32_t* format) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->kst_fmt >= 0, UT_EUNSUPPORTED, "gp_kstar_read: the fp32 and f16x3 K* formats are not read out");
-  UT_CHECK(c, c->kst_fmt != 0 && c->kst.p, UT_EINVAL, "gp_kstar_read: no dense scoring call since the last fit");
-  UT_CHECK(c, c0 >= 0 && nc >= 0 && c0 + nc <= c->kst_ldk, UT_EINVAL, "gp_kstar_read: columns outside [0, ldk]");
-  if (npad) *npad = c->kst_npad;
-  if (ldk) *ldk = c->kst_ldk;
-  if (format) *format = c->kst_fmt;
+  const KstDesc& k = c->kst_desc;
+  UT_CHECK(c, !k.valid() || k.readable(), UT_EUNSUPPORTED,
+           "gp_kstar_read: the fp32 and f16x3 K* formats are not read out");
+  UT_CHECK(c, k.valid() && c->kst.p, UT_EINVAL, "gp_kstar_read: no dense scoring call since the last fit");
+  UT_CHECK(c, c0 >= 0 && nc >= 0 && c0 + nc <= k.ldk, UT_EINVAL, "gp_kstar_read: columns outside [0, ldk]");
+  if (npad) *npad = k.npad;
+  if (ldk) *ldk = k.ldk;
+  if (format) *format = k.fmt;
   if (!k_out || nc == 0) return 0;
-  if (c->kst_fmt == 8)
-    return launch_kstar_decode_i8(c, reinterpret_cast<const int8_t*>(c->kst.p), c->kst_npad, c->kst_ldk, c0, nc,
-                                  k_out, c->kst_masked ? c->kmask.p : nullptr);
-  UT_HIP(c, hipMemcpy2DAsync(k_out, sizeof(double) * nc, c->kst.p + c0, sizeof(double) * c->kst_ldk,
-                             sizeof(double) * nc, (size_t)c->kst_npad, hipMemcpyDeviceToDevice, c->stream));
+  if (k.planes())
+    return launch_kstar_decode_i8(c, reinterpret_cast<const int8_t*>(c->kst.p), k.npad, k.ldk, c0, nc, k_out,
+                                  k.mask_of(c->kmask.p));
+  UT_HIP(c, hipMemcpy2DAsync(k_out, sizeof(double) * nc, c->kst.p + c0, sizeof(double) * k.ldk, sizeof(double) * nc,
+                             (size_t)k.npad, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
 int ut_gp_kstar_screen_stats(ut_ctx* c, int32_t* screened, int64_t* certified, int64_t* units) {
   if (!c) return UT_EINVAL;
-  if (screened) *screened = c->ks_last_screened;
-  if (certified) *certified = c->ks_last_cert;
-  if (units) *units = c->ks_last_units;
+  if (screened) *screened = c->i8_stats.screened;
+  if (certified) *certified = c->i8_stats.cert;
+  if (units) *units = c->i8_stats.units;
   return 0;
 }
 
 int ut_gp_kstar_mask_read(ut_ctx* c, uint8_t* mask_out, int32_t* rows, int64_t* cols) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->kst_fmt == 8 || c->kst_fmt == 64, UT_EINVAL,
-           "gp_kstar_mask_read: no precision-8 dense scoring call since the last fit");
-  if (c->kst_fmt != 8 || !c->kst_masked) return UT_NOMASK;
-  const int32_t r = c->kst_npad / 32;
-  const int64_t cc = c->kst_ldk / 32;
+  const KstDesc& k = c->kst_desc;
+  // (format 64 here: the whole-round fp64 fallback of a precision-8 call, or a precision-64 call)
+  UT_CHECK(c, k.readable(), UT_EINVAL, "gp_kstar_mask_read: no precision-8 dense scoring call since the last fit");
+  if (!k.masked) return UT_NOMASK;
+  const int32_t r = k.npad / 32;
+  const int64_t cc = k.ldk / 32;
   if (rows) *rows = r;
   if (cols) *cols = cc;
   if (mask_out)
@@ -1313,12 +1319,13 @@ int ut_gp_kstar_mask_read(ut_ctx* c, uint8_t* mask_out, int32_t* rows, int64_t* 
 
 int ut_gp_i8_parts_read(ut_ctx* c, double* var_part_out, double* mu_part_out, int32_t* rows, int64_t* ldk) {
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, c->kst_fmt == 8 && c->var_part.p && c->mu_part.p, UT_EINVAL,
+  const KstDesc& k = c->kst_desc;
+  UT_CHECK(c, k.planes() && c->var_part.p && c->mu_part.p, UT_EINVAL,
            "gp_i8_parts_read: no precision-8 dense scoring call that kept its digit planes since the last fit");
-  const int32_t r = c->kst_npad / I8_BM;
+  const int32_t r = k.npad / I8_BM;
   if (rows) *rows = r;
-  if (ldk) *ldk = c->kst_ldk;
-  const size_t bytes = sizeof(double) * (size_t)r * (size_t)c->kst_ldk;
+  if (ldk) *ldk = k.ldk;
+  const size_t bytes = sizeof(double) * (size_t)r * (size_t)k.ldk;
   if (var_part_out) UT_HIP(c, hipMemcpyAsync(var_part_out, c->var_part.p, bytes, hipMemcpyDeviceToDevice, c->stream));
   if (mu_part_out) UT_HIP(c, hipMemcpyAsync(mu_part_out, c->mu_part.p, bytes, hipMemcpyDeviceToDevice, c->stream));
   return 0;

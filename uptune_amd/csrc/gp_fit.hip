@@ -968,7 +968,7 @@ int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32
   const int32_t npad = gp_npad(n);
   UT_CHECK(c, c->gp_prec != 8 || npad <= I8_MAX_K, UT_EINVAL,
            "gp_fit: precision 8 takes at most 16384 training points (exact int32 digit sums)");
-  c->kst_fmt = 0;   // (ut_gp_kstar_read: c->kst is an earlier fit's from here on)
+  c->kst_desc.invalidate();   // (ut_gp_kstar_read: c->kst is an earlier fit's from here on)
   // a fit staged and never used is enqueued first (its staging is about to be
   // reused; an append compares against it), then the previous fit's copies out
   // of the pinned staging (and its factor) are complete once ev_fit is

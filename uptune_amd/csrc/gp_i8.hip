@@ -46,15 +46,16 @@
 // k_gp_var_i8<true> neither loads them nor issues their MFMAs.  A product with
 // an all-zero operand adds exact zeros to an exact int32 sum: no output bit
 // changes, and the error contract above is the unmasked kernel's.  The masked
-// kernel's guarded MFMA groups cost a dense K* about 3 %, so gp_score.hip runs
-// it only while the last call's K* was sparse (ut_ctx::var_skip_hint).
+// kernel's guarded MFMA groups cost a dense K* about 3 %, so it runs only
+// while the last call's K* was sparse (I8Hints::var_skip, gp_i8_plan.h).
 // After a screened K* (k_q_screen, gp_kq.hip) the planes behind cleared mask
 // dwords were not written at all: the masked kernel always runs then.  Where
-// the launcher expects few live strips (ut_ctx::kst_list: 7 blocks in 8 of the
+// the plan expects few live strips (I8Hints::list: 7 blocks in 8 of the
 // last call all-zero, or UT_KSTAR_STRIPS=1) it is the instance <true, true>
 // over the screen's list of strips with a live unit (the other strips'
 // partials already hold their zeros); otherwise <true> over every strip, which
-// gives the same bits and is the faster instance per live strip.
+// gives the same bits and is the faster instance per live strip.  i8_plan
+// (gp_i8_plan.h) chooses among the three; launch_gemm_var_i8 runs the one named.
 #include "ut_internal.h"
 
 namespace ut {
@@ -456,9 +457,12 @@ __global__ __launch_bounds__(256, 2) void k_gp_var_i8(const int8_t* __restrict__
 }
 
 int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk, int64_t m, double* part,
-                       double* mpart, const uint8_t* kmask, bool strip_list) {
+                       double* mpart, I8Var var) {
   UT_CHECK(c, npad % 128 == 0 && npad <= I8_MAX_K && ldk % I8_WN == 0 && ldk >= m, UT_EINVAL,
            "gemm_var_i8: bad padding");
+  const uint8_t* kmask = c->kmask.p;
+  UT_CHECK(c, var == I8Var::Unmasked || (kmask && npad <= I8_MASK_MAX_K), UT_EINVAL,
+           "gemm_var_i8: a masked kernel needs K*'s mask and at most 2048 training rows");
   UT_CHECK(c, c->gp_i8a.p && c->gp_i8rs.p, UT_EINVAL, "gemm_var_i8: the fit has no int8 planes");
   const int32_t RT = npad / I8_BM, CT = (int32_t)((m + I8_WN - 1) / I8_WN);
   const int32_t P = (RT + 1) / 2;
@@ -467,11 +471,10 @@ int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk,
   if (items < nb) nb = (int32_t)(((items + 7) / 8) * 8);
   const int32_t W = nb / 8, Sg = W / P > 1 ? W / P : 1;
   UT_HIP(c, hipMemsetAsync(c->gp_ctr.p, 0, sizeof(int32_t) * 8, c->stream));
-  // (past I8_MASK_MAX_K rows a tile has more than 64 stages: the unmasked kernel)
-  if (kmask && npad <= I8_MASK_MAX_K && strip_list)
+  if (var == I8Var::MaskedList)
     hipLaunchKernelGGL((k_gp_var_i8<true, true>), dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT,
                        m, c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg, kmask);
-  else if (kmask && npad <= I8_MASK_MAX_K)
+  else if (var == I8Var::Masked)
     hipLaunchKernelGGL(k_gp_var_i8<true>, dim3(nb), dim3(256), 0, c->stream, c->gp_i8a.p, kst8, npad, ldk, RT, CT, m,
                        c->gp_ctr.p, c->gp_i8rs.p, c->gp_beta.p, part, mpart, Sg, kmask);
   else

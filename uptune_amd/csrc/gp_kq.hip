@@ -536,7 +536,6 @@ __global__ __launch_bounds__(Q_NT, 2) void k_gp_kstar_q(
 // the zeros in part / mpart that the variance kernel would have written.
 // One workgroup per 128-candidate strip: the strip's B planes 0 and 1 in LDS,
 // wave w takes the row tiles w, w + 4, ... with A fragments straight from Xd.
-constexpr int QS_MAX_K32 = 4;                  // 8 KiB of LDS per 32 k (48 KiB with 2048 rows' norms)
 constexpr double QS_LINE = -12288.5;           // rint(t) <= -49 * 256 + 255 below it
 constexpr double QS_REM = 0.76 * 256.0;        // the remainder bound per k, in units of U
 
@@ -700,11 +699,11 @@ int launch_split_x8(ut_ctx* c, const double* XsT, int32_t K, int32_t npad) {
   return 0;
 }
 
-int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m, void* kst, int64_t ldk,
-                        DevBuf<int8_t>& u8, DevBuf<double>& scol) {
+int launch_gemm_kstar_q(ut_ctx* c, const I8Plan& plan, const double* ucand, int32_t dpad, int64_t m, void* kst,
+                        int64_t ldk, DevBuf<int8_t>& u8, DevBuf<double>& scol) {
   const DevBuf<int8_t>& xd = c->gp_x8;
   const int32_t npad = gp_npad(c->gp_n);
-  const int32_t K32 = (dpad + 31) / 32;
+  const int32_t K32 = kstar_q_k32(dpad);
   const bool pair = K32 * 32 <= Q_PAIR_MAX_K;
   // exact int32 group sums: K 6 2^14 < 2^31
   UT_CHECK(c, npad % Q_BM == 0 && ldk % Q_BN == 0 && ldk >= m && (int64_t)K32 * 32 * 6 * 16384 < (1LL << 31),
@@ -724,23 +723,14 @@ int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m,
   UT_HIP(c, hipMemsetAsync(c->kmask.p, 0x3f, (size_t)(npad / 32) * (size_t)(ldk / 32), c->stream));
   const int32_t RT = npad / Q_BM;
   const int32_t CT = (int32_t)(ldk / Q_BN);
-  // The screen (k_q_screen) runs where the masked variance kernel can follow it
-  // (npad <= I8_MASK_MAX_K, UT_VAR_SKIP not 0: a screened call leaves unwritten
-  // planes behind cleared mask dwords) and its strip's planes fit in LDS;
-  // UT_KSTAR_SCREEN (read per call) 1 / 0 forces it on / off, unset it follows
-  // c->kstar_screen_hint (at least half of the last call's blocks all-zero).
-  const char* vs_env = getenv("UT_VAR_SKIP");
-  const char* ks_env = getenv("UT_KSTAR_SCREEN");
-  const bool can_screen = npad <= I8_MASK_MAX_K && K32 <= QS_MAX_K32 && !(vs_env && atoi(vs_env) == 0);
-  const bool screen = can_screen && (ks_env ? atoi(ks_env) == 1 : c->kstar_screen_hint);
+  UT_CHECK(c, plan.mask && !(plan.screen && plan.count), UT_EINVAL, "gemm_kstar_q: not a plan of i8_plan");
   const int32_t icap = ((CT + 7) / 8) * RT;
   int32_t* strips = reinterpret_cast<int32_t*>(c->kmask.p + mask_bytes);
-  c->kst_screened = false, c->kst_counted = false;
-  if (can_screen) {
+  if (plan.screen || plan.count) {
     if ((rc = ensure(c, c->ks_cnt, 24))) return rc;
     UT_HIP(c, hipMemsetAsync(c->ks_cnt.p, 0, sizeof(int32_t) * 24, c->stream));
   }
-  if (screen) {
+  if (plan.screen) {
     if ((rc = ensure(c, c->ks_items, (size_t)8 * icap))) return rc;
     UT_HIP(c, hipMemsetAsync(strips, 0, sizeof(int32_t) * 8, c->stream));
   }
@@ -754,10 +744,12 @@ int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m,
                      npad, u8.p, ldk, K32, scol.p, RT, CT, c->gp_xnorm.p, c->cnorm.p, c->gp_alpha.p, c->gp_sf2,         \
                      c->gp_n, m, (int8_t*)kst, nullptr, kscale, (int64_t)npad * ldk, RT, nullptr, nullptr, nullptr, 0, \
                      0.0, 0.0, c->kmask.p, c->kmask_cnt.p, LI, LC)
-  if (screen) {
+  if (plan.screen) {
     UT_CHECK(c, c->var_part.p && c->mu_part.p && c->var_part.n >= (size_t)RT * ldk && c->mu_part.n >= (size_t)RT * ldk,
              UT_EINVAL, "gemm_kstar_q: the screen needs the variance partials allocated");
     const size_t lds = (size_t)2 * K32 * 4096 + sizeof(double) * (npad + 4) + 16;
+    // (i8_plan's limits keep both; a plan made for another shape is refused, not run out of bounds)
+    UT_CHECK(c, RT <= 32 && lds <= c->max_lds, UT_EINVAL, "gemm_kstar_q: the screen's row set or LDS image is too large");
     hipLaunchKernelGGL(k_q_screen, dim3((unsigned)(ldk / 128)), dim3(256), lds, c->stream, xd.p, npad, u8.p, ldk, K32,
                        scol.p, pair ? 1.0 : 0x1p-8, c->gp_xnorm.p, c->cnorm.p, c->gp_n, m, c->kmask.p, c->ks_items.p,
                        icap, strips, scap, CTv, c->ks_cnt.p, c->var_part.p, c->mu_part.p);
@@ -770,17 +762,12 @@ int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m,
   }
 #undef UT_KQ_LAUNCH
   UT_LAUNCH_CHECK(c);
-  c->kst_screened = screen;
-  const char* st_env = getenv("UT_KSTAR_STRIPS");
-  c->kst_list = screen && (st_env ? atoi(st_env) == 1 : c->ks_list_hint);
-  if (can_screen && !screen && !ks_env) {
+  if (plan.count) {
     const int64_t ndw = (int64_t)(npad / 32) * (ldk / 32) / 4;
     hipLaunchKernelGGL(k_q_mask_zeros, dim3(64), dim3(256), 0, c->stream, c->kmask.p, ndw, c->kmask_cnt.p,
                        c->ks_cnt.p);
     UT_LAUNCH_CHECK(c);
-    c->kst_counted = true;
   }
-  c->kst_masked = true;   // c->kmask describes the planes now in kst (gp_score_dense clears it)
   return 0;
 }
 

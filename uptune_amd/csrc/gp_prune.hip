@@ -295,7 +295,7 @@ int gp_topk_pruned_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, co
   Acq pa = make_acq(c, acq);
   int rc;
   if (wv && (rc = ensure(c, c->pr_p, (size_t)ldk))) return rc;
-  c->kst_fmt = 0;   // (c->kst becomes this call's bound rows: nothing ut_gp_kstar_read reads)
+  c->kst_desc.invalidate();   // (c->kst becomes this call's bound rows: nothing ut_gp_kstar_read reads)
   if ((rc = ensure(c, c->kst, (size_t)npad * ldk))) return rc;
   if ((rc = ensure(c, c->mu_part, (size_t)RT * ldk))) return rc;
   if ((rc = ensure(c, c->var_part, (size_t)RT * ldk))) return rc;

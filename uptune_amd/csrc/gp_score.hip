@@ -177,14 +177,92 @@ int gp_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m) {
   return launch_encode_scaled(c, values, ld, m, c->ucand.p, s.dpad, s.ldk, c->cnorm.p);
 }
 
+// Precision 8's dense tail, from K* on: plan, K*, variance, the bound test, the
+// call's one host sync (the flagged count and the K* counts that make the next
+// call's hints), the fp64 recompute of the candidates the bound did not clear.
+// ka: gp_score_dense's K* of all m candidates into c->kst (its fp64-MFMA
+// kernels here and in the whole-round fallback).
+static int gp_score_dense_i8(ut_ctx* c, const ScoreShape& s, int64_t m, const KstarArgs& ka, const Acq& pa,
+                             const uint8_t* dup, double* mu, double* var, double* score, hipEvent_t dup_ready) {
+  const int32_t npad = s.npad, RT = s.RT;
+  const int64_t ldk = s.ldk;
+  int rc;
+  UT_CHECK(c, npad <= I8_MAX_K, UT_EINVAL, "gp_score: precision 8 takes at most 16384 training points");
+  if ((rc = ensure(c, c->pr_idx, (size_t)ldk))) return rc;
+  if ((rc = ensure(c, c->pr_count, 1))) return rc;
+  // the distance contraction on the int8 MFMA (gp_kq.hip): beside the round's
+  // hash its MFMAs issue under the hash's integer VALU work (C2 ~1 % per
+  // round).  Categorical fits keep the fp64-MFMA K* (C3 HPL-64: K* 43 against
+  // 28.5 ms, the round 288 against 270; C4 no better; scripts/r06_lines.sh),
+  // which leaves no mask: the default plan
+  const bool kq = c->kstar_q && !c->cat_on && c->gp_x8.p;
+  const I8Plan plan = kq ? i8_plan(npad, kstar_q_k32(s.dpad), i8_env_read(), c->i8_hints) : I8Plan{};
+  if (kq) rc = launch_gemm_kstar_q(c, plan, c->ucand.p, s.dpad, m, c->kst.p, ldk, c->u8, c->scol);
+  else rc = launch_gemm_kstar(c, 8, npad, ka);
+  if (rc) return rc;
+  mark(c, "kstar");
+  if (c->fit_pending) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));
+  // the variance GEMM starts when K* ends and the side stream's hash tail runs
+  // beside it (only the finalize needs the dup mask): C2 16.60 -> 16.40 ms at
+  // ell 0.2, 19.62 -> 19.36 at ell 2, C3 / C4 unchanged (their hash ends before
+  // K*; scripts/ab/r06_varjoin*.sh, r06_sched.sh)
+  mark(c, "var_wait");  // the wait for the fit is not variance time
+  if ((rc = launch_gemm_var_i8(c, npad, reinterpret_cast<const int8_t*>(c->kst.p), ldk, m, c->var_part.p,
+                               c->mu_part.p, plan.var)))
+    return rc;
+  mark(c, "var");
+  if (dup_ready) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));
+  UT_HIP(c, hipMemsetAsync(c->pr_count.p, 0, sizeof(int64_t), c->stream));
+  hipLaunchKernelGGL(k_gp_finalize_i8, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, 2 * RT, 2 * RT, c->mu_part.p,
+                     c->var_part.p, ldk, pa, dup, mu, var, score, c->gp_i8rs.p + 2 * npad, c->i8_tol, s.n,
+                     c->pr_idx.p, reinterpret_cast<unsigned long long*>(c->pr_count.p));
+  UT_LAUNCH_CHECK(c);
+  mark(c, "finalize");
+  int64_t nf = 0;
+  int32_t nsparse = 0, ksc[2] = {0, 0};   // ks_cnt[16], [17]: certified units, an unscreened mask's all-zero bytes
+  UT_HIP(c, hipMemcpyAsync(&nf, c->pr_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (plan.mask)
+    UT_HIP(c, hipMemcpyAsync(&nsparse, c->kmask_cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (plan.screen || plan.count)
+    UT_HIP(c, hipMemcpyAsync(ksc, c->ks_cnt.p + 16, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  UT_HIP(c, hipStreamSynchronize(c->stream));
+  I8Counts cnt;
+  cnt.nsparse = nsparse, cnt.cert = plan.screen ? ksc[0] : 0, cnt.zero_bytes = plan.count ? ksc[1] : 0;
+  cnt.blocks = (int64_t)(npad / 32) * (ldk / 32);
+  c->i8_hints = i8_hints_next(c->i8_hints, plan, cnt);
+  // most candidates need fp64: the whole K* (fp64, over the planes) and the
+  // fp64 contraction, with the mean from its epilogue
+  const bool whole = nf * 2 > m;
+  c->i8_stats = I8Stats{plan.screen ? 1 : 0, cnt.cert, plan.mask ? cnt.blocks / 8 : 0, whole ? -1 : nf};
+  if (nf > 0 && (rc = gp_ensure_linvt(c))) return rc;   // (the fp64 contraction reads (L^-1)^T)
+  if (whole) {
+    if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldk))) return rc;
+    if ((rc = launch_gemm_kstar(c, 64, npad, ka))) return rc;
+    if ((rc = launch_gemm_var64(c, npad, c->kst.p, ldk, npad, m, c->var_part.p))) return rc;
+    if ((rc = launch_gp_finalize(c, m, RT, RT, c->pr_mpart.p, c->var_part.p, ldk, pa, dup, mu, var, score))) return rc;
+  } else if (nf > 0) {
+    const int64_t ldf = gp_ldk(nf);
+    if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldf))) return rc;
+    if ((rc = gather_kstar_cols(c, s, c->pr_idx.p, 0, nf, ldf))) return rc;
+    if ((rc = launch_gemm_var64(c, npad, c->pr_kst.p, ldf, npad, nf, c->pr_vpart.p))) return rc;
+    if ((rc = launch_gp_finalize(c, nf, RT, RT, c->pr_mpart.p, c->pr_vpart.p, ldf, pa, dup, mu, var, score,
+                                 c->pr_idx.p)))
+      return rc;
+  }
+  mark(c, "recompute");
+  // the digit planes and their mask, or the fp64 rows the whole-round fallback wrote over them
+  if (whole) c->kst_desc.set(64, npad, ldk, false);
+  else c->kst_desc.set(8, npad, ldk, plan.mask);
+  return 0;
+}
+
 // the dense posterior and acquisition of every tier (gp_score_impl below adds the feasibility weight)
 static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
                           double* mu, double* var, double* score, hipEvent_t dup_ready) {
   UT_CHECK(c, c->gp_ready, UT_EINVAL, "gp_score: call ut_gp_fit first");
   UT_CHECK(c, acq != nullptr, UT_EINVAL, "gp_score: acq is NULL");
   if (m <= 0) return 0;
-  c->kst_fmt = 0;   // (ut_gp_kstar_read: set again where this call returns with K* in c->kst)
-  c->kst_masked = false;   // (set by launch_gemm_kstar_q alone: every other writer of kst leaves no mask)
+  c->kst_desc.invalidate();   // (set again where this call returns with K* in c->kst)
   if (int rc0 = gp_fit_flush(c)) return rc0;
   const int prec = c->gp_fit_prec;
   const bool fp32 = prec != 64;  // fp32, h3 (f16x3) and i8: K* stores a reduced-precision K*
@@ -210,11 +288,6 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
   // (i8: the variance and mean partials come per 64-row tile)
   if ((rc = ensure(c, c->mu_part, (size_t)(i8 ? 2 * RT : RT) * ldk))) return rc;
   if ((rc = ensure(c, c->var_part, (size_t)(i8 ? 2 * RT : RT) * ldk))) return rc;
-  if (i8) {
-    UT_CHECK(c, npad <= I8_MAX_K, UT_EINVAL, "gp_score: precision 8 takes at most 16384 training points");
-    if ((rc = ensure(c, c->pr_idx, (size_t)ldk))) return rc;
-    if ((rc = ensure(c, c->pr_count, 1))) return rc;
-  }
   if (feat) {
     if ((rc = prep_cand_features(c, s, feat, ld, m))) return rc;
     mark(c, "cnorm");
@@ -225,117 +298,25 @@ static int gp_score_dense(ut_ctx* c, const double* feat, int64_t ld, int64_t m, 
   ka.ucand = c->ucand.p, ka.dpad = s.dpad;
   ka.m = m, ka.kst = c->kst.p, ka.ldk = ldk;
   ka.part = kmu ? c->mu_part.p : nullptr;   // (i8's fp64 recompute: the mean from the variance epilogue)
-  if (i8 && c->kstar_q && !c->cat_on && c->gp_x8.p) {
-    // the distance contraction on the int8 MFMA (gp_kq.hip): beside the round's
-    // hash its MFMAs issue under the hash's integer VALU work (C2 ~1 % per
-    // round).  Categorical fits keep the fp64-MFMA K* (C3 HPL-64: K* 43 against
-    // 28.5 ms, the round 288 against 270; C4 no better; scripts/r06_lines.sh)
-    if ((rc = launch_gemm_kstar_q(c, c->ucand.p, s.dpad, m, c->kst.p, ldk, c->u8, c->scol))) return rc;
-  } else if ((rc = launch_gemm_kstar(c, prec, npad, ka))) {
-    return rc;
-  }
+  if (i8) return gp_score_dense_i8(c, s, m, ka, pa, dup, mu, var, score, dup_ready);
+  if ((rc = launch_gemm_kstar(c, prec, npad, ka))) return rc;
   mark(c, "kstar");
   if (c->fit_pending && !kmu) UT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_fit, 0));
-  // fp64 / fp32 / h3: the variance GEMM runs alone, the side stream's hash +
-  // dedup share the CUs with K* only (C2: 27.95 -> 28.2 ms per round when they
-  // spilled into it, the GEMM at 0.74 instead of 0.80 of peak; round 1).  i8:
-  // it starts when K* ends and the hash's tail runs beside it (only the
-  // finalize needs the dup mask): C2 16.60 -> 16.40 ms at ell 0.2, 19.62 ->
-  // 19.36 at ell 2, C3 / C4 unchanged (their hash ends before K*;
-  // scripts/ab/r06_varjoin*.sh, r06_sched.sh)
-  if (dup_ready && !i8) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));
-  mark(c, "var_wait");  // the wait for the fit (and the dup mask) is not variance time
-  if (i8) {
-    // K*'s all-zero digit-plane blocks are skipped where k_gp_kstar_q left their
-    // mask (exact: zero products add nothing to an int32 sum).  The masked
-    // kernel's guarded MFMA groups cost a dense K* about 3 % (C2 at ell = 2:
-    // 10.5 -> 10.9 ms), so it runs while the last call's K* had a zero plane in
-    // at least 1 block of 16 (c->var_skip_hint, from the count read back below).
-    // UT_VAR_SKIP (read per call): 0 keeps the unmasked kernel, 1 the masked one.
-    const char* vs_env = getenv("UT_VAR_SKIP");
-    // A screened K* (k_q_screen) left the planes of its certified units
-    // unwritten: always the masked kernel; over the screen's list of strips with
-    // a live unit (it wrote the other strips' zeros) where the launcher chose so
-    // (c->kst_list: few live strips expected; the kernel over every strip gives
-    // the same bits, and is the faster instance where most strips are live).
-    const bool screened = c->kst_masked && c->kst_screened;
-    const bool vskip = c->kst_masked && (screened || (vs_env ? atoi(vs_env) != 0 : c->var_skip_hint));
-    if ((rc = launch_gemm_var_i8(c, npad, reinterpret_cast<const int8_t*>(c->kst.p), ldk, m, c->var_part.p,
-                                 c->mu_part.p, vskip ? c->kmask.p : nullptr, screened && c->kst_list)))
-      return rc;
-  } else if ((rc = launch_gemm_var(c, prec, fp32 ? (const void*)c->gp_LinvT_f.p : (const void*)c->gp_LinvT.p, npad,
-                                   c->kst.p, ldk, npad, m, c->var_part.p, fp32 ? nullptr : c->gp_beta.p,
-                                   fp32 ? nullptr : c->mu_part.p))) {
-    return rc;
-  }
-  mark(c, "var");
+  // the variance GEMM runs alone, the side stream's hash + dedup share the CUs
+  // with K* only (C2: 27.95 -> 28.2 ms per round when they spilled into it, the
+  // GEMM at 0.74 instead of 0.80 of peak; round 1); precision 8 joins them later
   if (dup_ready) UT_HIP(c, hipStreamWaitEvent(c->stream, dup_ready, 0));
-  if (i8) {
-    // the bound test, then the fp64 recompute of the candidates it did not clear
-    UT_HIP(c, hipMemsetAsync(c->pr_count.p, 0, sizeof(int64_t), c->stream));
-    hipLaunchKernelGGL(k_gp_finalize_i8, dim3(grid1(m, 256)), dim3(256), 0, c->stream, m, 2 * RT, 2 * RT, c->mu_part.p,
-                       c->var_part.p, ldk, pa, dup, mu, var, score, c->gp_i8rs.p + 2 * npad, c->i8_tol, s.n,
-                       c->pr_idx.p, reinterpret_cast<unsigned long long*>(c->pr_count.p));
-    UT_LAUNCH_CHECK(c);
-    mark(c, "finalize");
-    int64_t nf = 0;
-    UT_HIP(c, hipMemcpyAsync(&nf, c->pr_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    int32_t nsparse = 0;
-    if (c->kst_masked)
-      UT_HIP(c, hipMemcpyAsync(&nsparse, c->kmask_cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    // the screen's certified units / the unscreened mask's all-zero bytes, in the same sync
-    int32_t ksc[2] = {0, 0};
-    const bool ks_read = c->kst_masked && (c->kst_screened || c->kst_counted);
-    if (ks_read)
-      UT_HIP(c, hipMemcpyAsync(ksc, c->ks_cnt.p + 16, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    UT_HIP(c, hipStreamSynchronize(c->stream));
-    const int64_t blocks = (int64_t)(npad / 32) * (ldk / 32);
-    c->ks_last_screened = c->kst_masked && c->kst_screened ? 1 : 0;
-    c->ks_last_units = c->kst_masked ? blocks / 8 : 0;
-    c->ks_last_cert = c->ks_last_screened ? ksc[0] : 0;
-    if (c->kst_masked) {
-      // (a certified unit is 8 blocks that k_gp_kstar_q never visited to count)
-      c->var_skip_hint = ((int64_t)nsparse + (c->kst_screened ? 8 * (int64_t)ksc[0] : 0)) * 16 >= blocks;
-      const int64_t zero_blocks = c->kst_screened ? 8 * (int64_t)ksc[0] : (c->kst_counted ? (int64_t)ksc[1] : 0);
-      c->kstar_screen_hint = 2 * zero_blocks >= blocks;
-      // (zero blocks the certificate cannot clear -- k* below 2^-49 of the scale by
-      // less than its remainder bound -- would turn the screen on after every
-      // unscreened call and off after every screened one: a screen that cleared
-      // less than half holds the hint off for the next 8 calls)
-      if (c->kst_screened && !c->kstar_screen_hint) c->ks_backoff = 8;
-      else if (!c->kst_screened && c->ks_backoff > 0) --c->ks_backoff, c->kstar_screen_hint = false;
-      c->ks_list_hint = 8 * zero_blocks >= 7 * blocks;
-    }
-    c->i8_recomputed = nf;
-    if (nf > 0 && (rc = gp_ensure_linvt(c))) return rc;   // (the fp64 contraction reads (L^-1)^T)
-    if (nf * 2 > m) {
-      // most candidates need fp64: the whole K* (fp64, over the planes) and the
-      // fp64 contraction, with the mean from its epilogue
-      c->i8_recomputed = -1;
-      c->kst_masked = false;   // (kst becomes fp64 rows)
-      if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldk))) return rc;
-      if ((rc = launch_gemm_kstar(c, 64, npad, ka))) return rc;
-      if ((rc = launch_gemm_var64(c, npad, c->kst.p, ldk, npad, m, c->var_part.p))) return rc;
-      if ((rc = launch_gp_finalize(c, m, RT, RT, c->pr_mpart.p, c->var_part.p, ldk, pa, dup, mu, var, score))) return rc;
-    } else if (nf > 0) {
-      const int64_t ldf = gp_ldk(nf);
-      if ((rc = ensure(c, c->pr_mpart, (size_t)RT * ldf))) return rc;
-      if ((rc = gather_kstar_cols(c, s, c->pr_idx.p, 0, nf, ldf))) return rc;
-      if ((rc = launch_gemm_var64(c, npad, c->pr_kst.p, ldf, npad, nf, c->pr_vpart.p))) return rc;
-      if ((rc = launch_gp_finalize(c, nf, RT, RT, c->pr_mpart.p, c->pr_vpart.p, ldf, pa, dup, mu, var, score,
-                                   c->pr_idx.p)))
-        return rc;
-    }
-    mark(c, "recompute");
-    // the digit planes, or the fp64 rows the whole-round fallback wrote over them
-    c->kst_fmt = c->i8_recomputed == -1 ? 64 : 8, c->kst_npad = npad, c->kst_ldk = ldk;
-    return 0;
-  }
+  mark(c, "var_wait");  // the wait for the fit (and the dup mask) is not variance time
+  if ((rc = launch_gemm_var(c, prec, fp32 ? (const void*)c->gp_LinvT_f.p : (const void*)c->gp_LinvT.p, npad, c->kst.p,
+                            ldk, npad, m, c->var_part.p, fp32 ? nullptr : c->gp_beta.p,
+                            fp32 ? nullptr : c->mu_part.p)))
+    return rc;
+  mark(c, "var");
   // h3's variance partials come per 256-row tile
   const int32_t RTv = prec == 16 ? (npad + 255) / 256 : RT;
   if ((rc = launch_gp_finalize(c, m, RT, RTv, c->mu_part.p, c->var_part.p, ldk, pa, dup, mu, var, score))) return rc;
   mark(c, "finalize");
-  c->kst_fmt = prec == 64 ? 64 : -1, c->kst_npad = npad, c->kst_ldk = ldk;
+  c->kst_desc.set(prec == 64 ? 64 : -1, npad, ldk, false);
   return 0;
 }
 

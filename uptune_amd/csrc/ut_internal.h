@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/uthot.h"
+#include "gp_i8_plan.h"
 #include "ut_core.h"
 
 namespace ut {
@@ -166,6 +167,28 @@ struct Timing {
   int64_t round = 0;
   std::vector<Mark> marks;  // a stage's time = its mark - the previous mark of the round on the same stream
   std::vector<std::pair<std::string, std::pair<double, int64_t>>> totals;  // name -> (sum ms, rounds)
+};
+
+// What the last dense scoring call left in ut_ctx::kst (ut_gp_kstar_read and
+// the other readers in api.hip).  fmt: 64 = fp64 rows [npad][ldk], 8 = six
+// digit planes, -1 = the fp32 / f16x3 formats, 0 = nothing of the current fit
+// (a fit, a pruned call or a failed dense call since).  masked: ut_ctx::kmask
+// describes those planes -- k_gp_kstar_q's alone; k_gp_kstar<int8_t>
+// (UT_KSTAR_Q=0, categorical fits) writes no mask.  After a screened call the
+// planes behind cleared mask dwords hold whatever an earlier call left: every
+// reader of masked planes goes through mask_of.
+struct KstDesc {
+  int32_t fmt = 0, npad = 0;
+  int64_t ldk = 0;
+  bool masked = false;
+  void invalidate() { fmt = 0, masked = false; }
+  void set(int32_t fmt_, int32_t npad_, int64_t ldk_, bool masked_) {
+    fmt = fmt_, npad = npad_, ldk = ldk_, masked = masked_ && fmt_ == 8;
+  }
+  bool valid() const { return fmt != 0; }
+  bool readable() const { return fmt > 0; }   // (not the fp32 / f16x3 formats)
+  bool planes() const { return fmt == 8; }
+  const uint8_t* mask_of(const uint8_t* kmask) const { return masked ? kmask : nullptr; }
 };
 
 }  // namespace ut
@@ -329,54 +352,24 @@ struct ut_ctx {
   // k_gp_kstar_q's plane-occupancy mask [npad / 32][ldk / 32]: bit p of a byte is
   // set iff plane p of that 32-row x 32-candidate block of K* holds a non-zero
   // digit (the four bytes of a 128-candidate variance strip at one k stage: one
-  // aligned dword).  kst_masked: it describes the planes now in kst -- set by
-  // launch_gemm_kstar_q, cleared at the start of every dense call and where the
-  // whole-round fp64 fallback rewrites kst; k_gp_kstar<int8_t> (UT_KSTAR_Q=0,
-  // categorical fits) writes none, and its planes take the dense variance path.
+  // aligned dword); kst_desc.masked says whether it describes the planes now in
+  // kst.  Behind the mask's bytes, the K* screen's variance strips with a live
+  // unit, [8] counts and [8][scap] strips (there, so that the variance kernel
+  // needs no further pointer).
   ut::DevBuf<uint8_t> kmask;
-  bool kst_masked = false;
   // kmask_cnt [1]: the blocks of the last k_gp_kstar_q whose mask is not 0x3f
   // (padding included), read back with each precision-8 call's recompute count.
-  // var_skip_hint: the last such call had enough of them (1 in 16) for the masked
-  // variance kernel to pay; a dense K* (long lengthscales) runs the unmasked
-  // kernel from the next call on.  Both kernels give the same bits, so a stale
-  // hint costs time only.  UT_VAR_SKIP=1 forces the masked kernel, 0 the unmasked.
   ut::DevBuf<int32_t> kmask_cnt;
-  bool var_skip_hint = true;
-  // The K* screen (k_q_screen, gp_kq.hip): before k_gp_kstar_q it certifies, from
-  // the products of the operands' two top digit planes, the 64-row x
-  // 128-candidate units whose every element the kernel would store as six zero
-  // digits, clears their mask dwords and lists the rest: ks_items [8][icap] the
-  // live 64 x 64 K* items per XCD (64 * column tile + row tile); behind the
-  // mask's bytes in kmask, [8] counts and [8][scap] the variance strips with a
-  // live unit (there, so that the variance kernel needs no further pointer);
-  // ks_cnt [24] = item counts [0, 8), certified units [16], all-zero mask bytes
-  // of an unscreened call [17] (k_q_mask_zeros).  A certified unit's planes are NOT
-  // written: they hold whatever an earlier call left, and every reader goes
-  // through the mask (the masked variance kernel, ut_gp_kstar_read).
-  // kst_screened: this call's K* was screened (the variance kernel must be a
-  // masked one: over the strip list if kst_list, else over every strip); kst_counted: it was not and [17] was counted.
-  // kstar_screen_hint: at least half of the last call's blocks were all-zero
-  // (the certified units of a screened call, [17] of an unscreened one), read
-  // back in the call's one sync; a stale hint costs time only.
-  // ks_list_hint: at least 7 blocks in 8 were; kst_list: this screened call's
-  // variance kernel walks the strip list (the hint, or UT_KSTAR_STRIPS=1).  The
-  // list instance of k_gp_var_i8 is about 18 % slower per live strip than the
-  // plain masked one (C2 at ell = 0.5, screen forced: 7.78 against 6.63 ms), which
-  // visits every strip and gives the same bits: the list pays where nearly all
-  // strips are dead.
-  // UT_KSTAR_SCREEN=1 / 0 (read per call) forces the screen on / off and leaves
-  // the list to its hint; UT_KSTAR_STRIPS=1 / 0 (read per call) forces the list
-  // on / off in a screened call.
+  // The K* screen (k_q_screen, gp_kq.hip): ks_items [8][icap] the live 64 x 64
+  // K* items per XCD (64 * column tile + row tile); ks_cnt [24] = item counts
+  // [0, 8), certified units [16], all-zero mask bytes of an unscreened call [17]
+  // (k_q_mask_zeros).
   ut::DevBuf<int32_t> ks_items, ks_cnt;
-  bool kst_screened = false, kst_counted = false, kst_list = false, kstar_screen_hint = false, ks_list_hint = false;
-  int32_t ks_backoff = 0;                 // unscreened calls left before the hint may turn on again
-  int32_t ks_last_screened = 0;           // (ut_gp_kstar_screen_stats) the last precision-8 dense call:
-  int64_t ks_last_cert = 0, ks_last_units = 0;   // screened?, certified units, units
+  ut::I8Hints i8_hints;   // (gp_i8_plan.h) all that precision-8 dense scoring carries from call to call
+  ut::I8Stats i8_stats;   // the last precision-8 dense call, for the API
   int32_t kstar_q = 1;  // UT_KSTAR_Q=0: precision-8 K* on k_gp_kstar<int8_t> (the fp64 MFMA)
   int32_t gp_i8_eb = 0;          // K* digit scale: y = k* 2^-eb <= 0.49
   double i8_tol = 0x1p-20;       // accepted relative variance error (ut_gp_set_i8_tol)
-  int64_t i8_recomputed = 0;     // candidates of the last score recomputed in fp64 (-1: all, dense)
   ut::DevBuf<int32_t> gp_ctr;   // [32] per-XCD work tickets: [0,8) variance, [8,16) K*; [16,18) max|L^-1| bits (h3)
   int32_t n_cu = 256;
   // LDS one workgroup may hold (hipDeviceAttributeMaxSharedMemoryPerBlock): the
@@ -386,11 +379,7 @@ struct ut_ctx {
 
   // scratch for GP scoring / round pipeline
   ut::DevBuf<double> kst;        // [n][ld]
-  // what the last dense scoring call left in kst (ut_gp_kstar_read): 64 = fp64
-  // rows [npad][ldk], 8 = six digit planes, -1 = the fp32 / f16x3 formats,
-  // 0 = nothing of the current fit (a fit, a pruned call or a failed dense call since)
-  int32_t kst_fmt = 0, kst_npad = 0;
-  int64_t kst_ldk = 0;
+  ut::KstDesc kst_desc;          // what is in kst
   ut::DevBuf<double> mu_part;    // [RT][ld]
   ut::DevBuf<double> var_part;   // [RT][ld]
   ut::DevBuf<double> cnorm;      // [ld]
@@ -908,11 +897,13 @@ int launch_gemm_kstar_f32c(ut_ctx* c, const float* XsT_f, const float* ucand_f, 
 // candidates' operand per call into u8 / scol), stored as the six digit planes
 // the int8 variance reads (no mean partial, no one-hot codes; norms in
 // c->gp_xnorm / c->cnorm).  launch_gemm_kstar_q also writes the planes'
-// occupancy mask into c->kmask and sets c->kst_masked.
+// occupancy mask into c->kmask, and runs the screen / the zero-block count
+// that plan (i8_plan of this npad and kstar_q_k32(dpad)) names: it decides nothing.
+inline int32_t kstar_q_k32(int32_t dpad) { return (dpad + 31) / 32; }
 int alloc_split_x8(ut_ctx* c, int32_t npad, int32_t K);
 int launch_split_x8(ut_ctx* c, const double* XsT, int32_t K, int32_t npad);
-int launch_gemm_kstar_q(ut_ctx* c, const double* ucand, int32_t dpad, int64_t m, void* kst, int64_t ldk,
-                        DevBuf<int8_t>& u8, DevBuf<double>& scol);
+int launch_gemm_kstar_q(ut_ctx* c, const I8Plan& plan, const double* ucand, int32_t dpad, int64_t m, void* kst,
+                        int64_t ldk, DevBuf<int8_t>& u8, DevBuf<double>& scol);
 // a caller's feature matrix feat [s.d][ld] becomes the K* operands of the m candidates of a call of shape s (dense
 // over every feature) in c->ucand / c->cnorm, grown as needed
 int prep_cand_features(ut_ctx* c, const ScoreShape& s, const double* feat, int64_t ld, int64_t m);
@@ -1005,13 +996,12 @@ int launch_split_i8(ut_ctx* c, int32_t n, int32_t npad);
 // the variance contraction from K*'s digit planes (kst8, [6][npad/32][ldk][32]):
 // part [npad / 64][ldk] column partials of |v|^2
 // part / mpart: per 64-row tile the column sums of v^2 and of v beta (the mean)
-// kmask: the planes' occupancy mask [npad / 32][ldk / 32] (k_gp_kstar_q's), whose
-// all-zero blocks are neither loaded nor multiplied; nullptr: no mask
-constexpr int32_t I8_MASK_MAX_K = 2048;   // the masked kernel keeps a tile's live stages in one 64-bit set
-// strip_list (with kmask): visit only the strips of k_q_screen's list, which sits behind the mask's bytes
-// ([8] counts, [8][ceil(CT / 8)] strips per XCD); every other strip's part / mpart already hold their zeros
+// var (I8Plan::var): Masked skips the all-zero blocks of the planes' occupancy mask c->kmask
+// [npad / 32][ldk / 32] (k_gp_kstar_q's), neither loaded nor multiplied; MaskedList also visits only the
+// strips of k_q_screen's list, which sits behind the mask's bytes ([8] counts, [8][ceil(CT / 8)] strips
+// per XCD): every other strip's part / mpart already hold their zeros
 int launch_gemm_var_i8(ut_ctx* c, int32_t npad, const int8_t* kst8, int64_t ldk, int64_t m, double* part,
-                       double* mpart, const uint8_t* kmask, bool strip_list = false);
+                       double* mpart, I8Var var);
 // (for tests) columns c0 .. c0 + nc - 1 of K*'s digit planes as doubles, out [npad][nc]
 // kmask (nullptr: none): a digit of a plane whose mask bit is clear reads as 0 -- true by the mask's
 // definition, and what a screened call's unwritten planes need
