@@ -211,6 +211,57 @@ int ut_propose_ga(ut_ctx* ctx, const ut_ga_params* p, const double* parent1, con
                   uint32_t round_, int64_t cand_base, int64_t m, double* out_values, int64_t ld,
                   uint8_t* out_invalid);
 
+/* Trust-region proposals: candidates inside a box around one centre row,
+ * each moving a random subset of the parameters (TuRBO's perturbation rule,
+ * Eriksson et al. 2019; uptune_amd/trust_region.py keeps the box's size).
+ *
+ * Inputs: centre c (device row of ncols SoA values, as ut_propose_ga's
+ * parent1), half_width_host h[P] (host, unit space, finite and >= 0; read by
+ * primitive kinds only), prob / cat_prob the perturbation probability of the
+ * primitive kinds (FLOAT, INT, LOGINT, POW2) / of BOOL, ENUM and PERM, and
+ * must: that many parameters are always perturbed.
+ *
+ * Candidate g = cand_base + i is a function of (seed, g, round_) alone, so
+ * any split of [cand_base, cand_base + m) over calls or ranks gives the same
+ * rows.  Draws use op code OP_TR = 6 (ut_core.h).  For p = 0 .. P - 1 in order,
+ * with sel = 0 at p = 0:
+ *   A = draw(seed, g, p, round_, OP_TR)
+ *   forced: (double)(P - p) * u01(A.x, A.y) < (double)must - sel; then sel += 1
+ *           (selection sampling, as ut_propose_ga's must_mutate_count)
+ *   rate:   (double)A.z * 2^-32 < prob        (cat_prob for BOOL / ENUM / PERM)
+ *   A.w is unused.  p is selected iff forced or rate; an unselected parameter
+ *   keeps the centre's value(s), bit for bit.
+ * For a selected p, B = draw(seed, g, p | 1 << 28, round_, OP_TR) and
+ *   FLOAT / INT / LOGINT / POW2:
+ *       uc = get_unit_value(c_p);  lo = max(uc - h_p, 0);  hi = min(uc + h_p, 1)
+ *       u  = lo + (hi - lo) * u01(B.x, B.y)     (each operation rounded, this order)
+ *       v  = set_unit_value(u) + 0.0, or c_p when the range is a single point
+ *            (+ 0.0: an integer kind whose value rounds to zero from below
+ *            stores +0.0 as the centre does, not -0.0, which int() does not have)
+ *     (lo and hi are computed once per call and parameter, not per candidate)
+ *   BOOL:  v = 1 - c_p
+ *   ENUM:  n_opt = 1 keeps c_p; else r = floor(u64(B.z, B.w) * (n_opt - 1) / 2^64),
+ *          r += (r >= c_p), v = r: uniform over the other options
+ *   PERM:  op1_small_random_change (manipulator.py:1066-1079, p = 0.25) on a copy
+ *          of the centre's permutation, from the perm draw site
+ *          (seed, g, p | 1 << 28, round_, OP_TR); B itself is not drawn.
+ * out_invalid[i] = 1 when row i equals the centre bit for bit in every column
+ * (integer rounding can bring a value back; there are no retries).
+ *
+ * UT_EINVAL: a NULL params, centre or half_width_host, prob or cat_prob outside
+ * [0, 1], a half-width that is negative or not finite, must outside [0, P],
+ * m < 0, cand_base < 0, ld < m, a NULL out_values or out_invalid with m > 0.
+ * UT_ENOSPACE before ut_space_define.  No kernel runs on a refused call. */
+typedef struct ut_tr_params {
+  double prob;
+  double cat_prob;
+  int32_t must;
+  int32_t pad;
+} ut_tr_params;
+int ut_propose_tr(ut_ctx* ctx, const ut_tr_params* p, const double* centre, const double* half_width_host,
+                  uint32_t round_, int64_t cand_base, int64_t m, double* out_values, int64_t ld,
+                  uint8_t* out_invalid);
+
 /* GP features of configurations: unit values (get_unit_value), BOOL 0/1,
  * ENUM one-hot, PERM position of each item / (size - 1).  out_features[f * ld_out + i]. */
 int ut_encode_features(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, double* out_features,

@@ -70,6 +70,10 @@ class GaParams(C.Structure):
                 ("max_retries", C.c_int32), ("op", C.c_int32), ("crossover", C.c_int32), ("pad", C.c_int32)]
 
 
+class TrParams(C.Structure):
+    _fields_ = [("prob", C.c_double), ("cat_prob", C.c_double), ("must", C.c_int32), ("pad", C.c_int32)]
+
+
 class GpHyper(C.Structure):
     _fields_ = [("sigma_f2", C.c_double), ("sigma_n2", C.c_double), ("jitter", C.c_double),
                 ("lengthscale_host", C.c_void_p)]
@@ -134,6 +138,7 @@ SIGNATURES = {
     "ut_pso_commit": (C.c_int, [P, P, P, I64, I64, I64]),
     "ut_pso_update_best": (C.c_int, [P, P, I64, P, I64]),
     "ut_propose_ga": (C.c_int, [P, C.POINTER(GaParams), P, P, U32, I64, I64, P, I64, P]),
+    "ut_propose_tr": (C.c_int, [P, C.POINTER(TrParams), P, P, U32, I64, I64, P, I64, P]),
     "ut_encode_features": (C.c_int, [P, P, I64, I64, P, I64]),
     "ut_hash": (C.c_int, [P, P, I64, I64, P]),
     "ut_history_reset": (C.c_int, [P, I64]),

@@ -37,6 +37,7 @@ long long uthc_sizeof(int which) {
     case 7: return (long long)sizeof(ut_tree_node);
     case 8: return (long long)sizeof(ut_prune_stats);
     case 9: return (long long)sizeof(ut_gp_fit_info);
+    case 10: return (long long)sizeof(ut_tr_params);
     default: return -1;
   }
 }

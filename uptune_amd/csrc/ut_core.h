@@ -90,7 +90,7 @@ UT_HD uint64_t below64(uint64_t x, uint64_t n) { return umulhi64(x, n); }
 //   c.z      = stream (param index p, or STREAM_* | sub)
 //   c.w      = (round << 8) | op
 enum : uint32_t {
-  OP_INIT = 1, OP_DE = 2, OP_PSO = 3, OP_GA = 4, OP_GGA = 5,
+  OP_INIT = 1, OP_DE = 2, OP_PSO = 3, OP_GA = 4, OP_GGA = 5, OP_TR = 6,
 };
 enum : uint32_t {
   STREAM_CAND = 0xFFFF0000u,   // per-candidate draws: STREAM_CAND | k

@@ -391,6 +391,7 @@ struct ut_ctx {
   ut::DevBuf<double> tk_score[2];
   ut::DevBuf<int64_t> tk_idx[2];
   ut::DevBuf<int64_t> r_topk_idx;
+  ut::DevBuf<double> tr_box;     // [3][P] trust-region call: half-widths h | box faces lo | hi (propose_tr.hip)
   ut::DevBuf<double> perm_ws;    // [2 * perm_cols + 3 * perm_smax][ld]: GA parents + crossover scratch
   ut::DevBuf<uint32_t> perm_dig; // [n_perm][m][8] inner digests of PERM values (hash pre-pass)
   ut::DevBuf<double> r_topk_score;

@@ -212,6 +212,23 @@ class BatchEngine:
                                                  int(cand_base), int(m), _ptr(out), m, _ptr(inv)), "ut_propose_ga")
         return out, inv
 
+    def propose_tr(self, m: int, centre, half_width, prob: float, cat_prob: Optional[float] = None, must: int = 1,
+                   round_: int = 0, cand_base: int = 0):
+        """Trust-region proposals (ut_propose_tr): candidates in the box centre +- half_width
+        (unit space, one entry per parameter) that move each primitive parameter with
+        probability `prob`, each BOOL / ENUM / PERM with `cat_prob` (default: prob), and
+        `must` parameters always.  Returns (values [ncols][m], invalid [m])."""
+        c = self._row(centre)
+        h = np.ascontiguousarray(half_width, dtype=np.float64).reshape(-1)
+        if h.size != self.spec.P:
+            raise ValueError(f"half_width has {h.size} entries for {self.spec.P} parameters")
+        out = self._empty(self.spec.ncols, m)
+        inv = self._empty(m, dtype=torch.uint8)
+        a = L.TrParams(prob=float(prob), cat_prob=float(prob if cat_prob is None else cat_prob), must=int(must))
+        L.check(self.ctx, self.lib.ut_propose_tr(self.ctx, C.byref(a), _ptr(c), C.c_void_p(h.ctypes.data), int(round_),
+                                                 int(cand_base), int(m), _ptr(out), m, _ptr(inv)), "ut_propose_tr")
+        return out, inv
+
     def encode(self, values: torch.Tensor, m: Optional[int] = None) -> torch.Tensor:
         m = values.shape[1] if m is None else m
         feat = self._empty(self.spec.n_features, m)

@@ -12,7 +12,8 @@ per-candidate CPU techniques sit:
 `desired_configuration()` returns a config dict, None (nothing to propose ->
 the bandit credits 0 and moves on) or False (waiting for results) exactly as
 in the reference.  The GPU techniques (GpuDifferentialEvolution, GpuPSO,
-GpuGA, GpuGGA) score a whole candidate pool per round on the device
+GpuGA, GpuGGA, and the opt-in GpuTrustRegion) score a whole candidate pool
+per round on the device
 (proposal -> hash_config -> dedup -> GP-EI -> top-k) and hand the top-k out one
 per call.  Device contexts are created lazily in set_driver and are never
 deep-copied (technique instances are deepcopied per driver, driver.py:75).
@@ -1261,6 +1262,110 @@ class GpuGGA(GpuGA):
         super().__init__(*pargs, crossover_rate=0.5, crossover_strength=0.2, normal=True, op=5, **kwargs)
 
 
+class GpuTrustRegion(GpuBatchTechnique):
+    """Trust-region proposals (TuRBO-1, Eriksson et al. 2019): every round draws
+    its pool inside a box around one centre (ut_propose_tr), sized by the outcome
+    of the rounds before it (trust_region.TrustRegion) and shaped by the GP's
+    per-feature lengthscales; the shared surrogate scores the pool as it does
+    any other.  Off by default everywhere: trust_region=True on the bandits adds
+    it as an arm.
+
+    centre="best": the box sits on the driver's best result; a round succeeds
+    when one of its own evaluated requests beat the best at proposal time.
+    centre="own": the centre is the best result of this technique's own
+    requests since its last restart; with none yet (the first round, the round
+    after a restart) the round is uniform random rows scored by the model, and
+    its best result becomes the centre.  Before any result exists both modes
+    take that uniform round.  A round is judged when the next one starts, from
+    the results that have arrived by then."""
+
+    def __init__(self, centre: str = "best", L_init: float = 0.8, L_min: float = 2.0 ** -7, L_max: float = 1.6,
+                 succ_tol: int = 3, fail_tol: Optional[int] = None, must: int = 1, *pargs, **kwargs):
+        super().__init__(*pargs, **kwargs)
+        if centre not in ("best", "own"):
+            raise ValueError("centre must be 'best' or 'own'")
+        self.centre_mode = centre
+        self.must = int(must)
+        self._tr_kw = dict(L_init=L_init, L_min=L_min, L_max=L_max, succ_tol=succ_tol, fail_tol=fail_tol)
+        self.tr = None                           # TrustRegion, once the space is known (init_population)
+        self._pending: Dict[str, int] = {}       # request digest -> the round that proposed it
+        self._open: Dict[int, Dict[str, Any]] = {}   # rounds not yet judged: ref, improved, uniform
+        self._own_best = None                    # centre="own": best Result of the own requests since the restart
+        self._since = 0                          # ... the first round after it
+        self._parent = None
+        self.last_centre = self.last_half = None   # the last box round's centre row and half-widths
+        self.last_uniform = False                # the last round was a uniform one
+
+    def init_population(self):
+        # no standing population: a uniform round draws its own rows
+        from .trust_region import TrustRegion
+        from . import _lib as L
+        n_move = 0
+        for p in self.engine.spec.params:
+            if p.kind <= L.UT_POW2:
+                n_move += p.lo < p.hi
+            elif p.kind == L.UT_BOOL:
+                n_move += 1
+            else:
+                n_move += (p.width if p.kind == L.UT_PERM else len(p.options)) > 1
+        if self.tr is None:
+            self.tr = TrustRegion(n_move, self.batch, **self._tr_kw)
+
+    def _judge_open_rounds(self):
+        for rnd in sorted(self._open):
+            st = self._open.pop(rnd)
+            if st["uniform"]:
+                continue
+            if self.tr.judge(st["improved"]) and self.centre_mode == "own":
+                self._own_best, self._since = None, self.round   # restart: the next round is uniform
+
+    def _centre_result(self):
+        return self._own_best if self.centre_mode == "own" else self.driver.best_result
+
+    def propose(self, m):
+        eng = self.engine
+        self._judge_open_rounds()
+        ref = self._centre_result()
+        self._open[self.round] = dict(ref=ref, improved=False, uniform=ref is None)
+        self.last_uniform = ref is None
+        if ref is None:
+            # rows [rank * m, (rank + 1) * m) of one population keyed by (seed, member, round)
+            rank, world = self._dist()
+            eng.population_init(max(world * m, 4), round_=self.round)
+            self._parent = None
+            return eng.population_get()[:, rank * m:(rank + 1) * m].contiguous(), None
+        centre = eng.spec.encode_configs([ref.configuration.data])[:, 0]
+        ell = self.model.lengthscale_
+        half = self.tr.half_widths(eng.spec, 1.0 if ell is None else ell)
+        prob, cat_prob = self.tr.probs()
+        self.last_centre, self.last_half = centre, half
+        self._parent = centre
+        return eng.propose_tr(m, centre, half, prob, cat_prob, must=min(self.must, eng.spec.P), round_=self.round,
+                              cand_base=self.round_base())
+
+    def hash_proposals(self, vals, base):
+        # most columns keep the centre's value: reuse its inner digests
+        hp = getattr(self.engine, "hash_parent", None)
+        if self._parent is None or hp is None:
+            return self.engine.hash(vals)
+        return hp(vals, self._parent)
+
+    def after_round(self, idx, hexes):
+        for hx in hexes:
+            self._pending[hx] = self.round
+
+    def handle_requested_result(self, result):
+        rnd = self._pending.pop(result.configuration.hash, None)
+        if rnd is None:
+            return
+        st = self._open.get(rnd)
+        if st is not None and (st["ref"] is None or self.objective.lt(result, st["ref"])):
+            st["improved"] = True
+        if self.centre_mode == "own" and rnd >= self._since and (
+                self._own_best is None or self.objective.lt(result, self._own_best)):
+            self._own_best = result
+
+
 def _shared_model(kw) -> SharedModel:
     return SharedModel(device=kw.get("device", 0), seed=kw.get("seed", 0), lengthscale=kw.get("lengthscale", 0.3),
                        min_train=kw.get("min_train", 4), precision=kw.get("precision", 64),
@@ -1271,20 +1376,27 @@ def _shared_model(kw) -> SharedModel:
                        else None, forest_kw=kw.get("forest_kw"))
 
 
+def _tr_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:
+    """the bandits' opt-in trust-region arm (trust_region=True)"""
+    return [GpuTrustRegion(name="gpu-trust-region", shared=shared, **kw)] if on else []
+
+
 def pso_ga_de_bandit(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
     """GPU counterpart of the reference's "PSO_GA_DE" bandit (bandittechniques.py:311-320):
     the four techniques share ONE SharedModel (one device context: one GP fit
     per generation, one dedup set) with a population slot each.  bandit_seed
     fixes the bandit's tie-break shuffles (required for SPMD runs: every rank
-    must order the techniques the same way)."""
+    must order the techniques the same way).  trust_region=True adds a
+    GpuTrustRegion arm on the same model."""
     kw = dict(kw)
+    tr = bool(kw.pop("trust_region", False))
     shared = kw.pop("shared", None) or _shared_model(kw)
     return AUCBanditMetaTechnique([
         GpuPSO(name="gpu-pso", shared=shared, **kw),
         GpuGA(name="gpu-ga", crossover_rate=0.5, shared=shared, **kw),
         GpuDifferentialEvolution(name="gpu-de", shared=shared, **kw),
         GpuGGA(name="gpu-gga", shared=shared, **kw),
-    ], name="GPU_PSO_GA_DE", seed=bandit_seed)
+    ] + _tr_arm(tr, shared, kw), name="GPU_PSO_GA_DE", seed=bandit_seed)
 
 
 def bandit_a(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
@@ -1295,25 +1407,29 @@ def bandit_a(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
     =0.3) on one shared model.  The fourth child, RandomNelderMead, is a
     sequential simplex technique outside the scoring path (DESIGN.md "Out of
     scope") and is not built; polish=T (GpuBatchTechnique) is the local search
-    that stands in for it."""
+    that stands in for it.  trust_region=True adds a GpuTrustRegion arm, a local
+    search that stays batch-parallel, in that fourth slot."""
     kw = dict(kw)
+    tr = bool(kw.pop("trust_region", False))
     shared = kw.pop("shared", None) or _shared_model(kw)
     return AUCBanditMetaTechnique([
         GpuDifferentialEvolution(name="gpu-de-alt", cr=0.2, shared=shared, **kw),
         GpuGA(name="gpu-uniform-greedy-mutation", mutation_rate=0.1, shared=shared, **kw),
         GpuGA(name="gpu-normal-greedy-mutation", mutation_rate=0.3, normal=True, shared=shared, **kw),
-    ], name="GpuAUCBanditMetaTechniqueA", seed=bandit_seed)
+    ] + _tr_arm(tr, shared, kw), name="GpuAUCBanditMetaTechniqueA", seed=bandit_seed)
 
 
 def bandit_b(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
     """"AUCBanditMetaTechniqueB" (bandittechniques.py:279-282): DifferentialEvolutionAlt
-    and UniformGreedyMutation on one shared model"""
+    and UniformGreedyMutation on one shared model (trust_region=True: and a
+    GpuTrustRegion arm)"""
     kw = dict(kw)
+    tr = bool(kw.pop("trust_region", False))
     shared = kw.pop("shared", None) or _shared_model(kw)
     return AUCBanditMetaTechnique([
         GpuDifferentialEvolution(name="gpu-de-alt", cr=0.2, shared=shared, **kw),
         GpuGA(name="gpu-uniform-greedy-mutation", mutation_rate=0.1, shared=shared, **kw),
-    ], name="GpuAUCBanditMetaTechniqueB", seed=bandit_seed)
+    ] + _tr_arm(tr, shared, kw), name="GpuAUCBanditMetaTechniqueB", seed=bandit_seed)
 
 
 _XO = ("op3_cross_OX3", "op3_cross_OX1", "op3_cross_PMX", "op3_cross_PX", "op3_cross_CX")
@@ -1341,9 +1457,11 @@ def reference_registry(wrap=None, bandit_cls=None, **kw) -> List[SearchTechnique
     and `bandit_cls` replaces this module's AUCBanditMetaTechnique for the
     bandit.  `kw` goes to every technique (pool, batch, device, seed, ...).  The
     DE population size is the device population (`population=`), not 30 / 100:
-    every member is scored each round."""
+    every member is scored each round.  trust_region=True appends a stand-alone
+    GpuTrustRegion (an addition of this library: the reference has none)."""
     W = wrap or (lambda c: c)
     kw = dict(kw)
+    tr = bool(kw.pop("trust_region", False))
     ef = kw.get("engine_factory")
     sm = _shared_model(kw)          # the bandit's children share one model (pops engine_factory; every
     #                                 technique, stand-alone or not, gets the requested precision)
@@ -1379,4 +1497,6 @@ def reference_registry(wrap=None, bandit_cls=None, **kw) -> List[SearchTechnique
                       [DE(name="gpu-de-alt", cr=0.2, shared=sb, **kw),
                        GA(name="gpu-uniform-greedy-mutation", mutation_rate=0.1, shared=sb, **kw)])):
         out.append((bandit_cls or AUCBanditMetaTechnique)(kids, name=nm))
+    if tr:
+        out.append(W(GpuTrustRegion)(name="GpuTrustRegion", **kw))
     return out
