@@ -518,6 +518,77 @@ int ut_gp_lml_grad(ut_ctx* ctx, int32_t d, double* dlog_ell_host, double* dlog_s
 int ut_gp_select_batch(ut_ctx* ctx, const double* values, int64_t ld, int32_t p, const ut_acq* acq,
                        const uint8_t* dup, int32_t k, int64_t* out_pos, double* out_score, double* out_var);
 
+/* ---- Thompson sampling: posterior sample paths over the pool --------------- */
+/* The reference has no GP.  Its model-based selection is randomised all the
+ * same: multi_stage.py:109-123 samples its picks from a rank window of the
+ * model's ordering, and bandittechniques.py breaks the ties of its arm
+ * ordering at random (bandittechniques.py:58).  Here the randomisation is the GP's own: one sample path of the
+ * posterior per batch slot over the whole pool, each slot taking its path's
+ * minimiser (TuRBO's acquisition inside the trust-region box).  The joint
+ * posterior is not sampled exactly (cubic in the pool); the paths are built by
+ * pathwise conditioning (Matheron's rule), linear in the pool.
+ *
+ * Inputs: the current fit's training features X (n x d), 1/ell per feature,
+ * sigma_f2, diag = sigma_n2 + jitter, the standardised targets ys, the factor
+ * L with its explicit L^-1; the call's q paths, D features, 24-bit round_.
+ *
+ * Draws (the counter generator of ut_core.h with OP_TS = 7; indices < 2^20;
+ * normal_draw's attempts take stream bits 24-27, the sub-blocks bits 28-29):
+ *   Z[j][k]     = normal_draw(seed, cand = j, stream = k, round_, OP_TS)       j < D, k < d
+ *   b[j]        = u01(x, y) of draw(seed, j, STREAM_CAND, round_, OP_TS)       a phase in turns, [0, 1)
+ *   Theta[s][j] = normal_draw(seed, j, s | (1 << STREAM_SUB_SHIFT), round_, OP_TS)   s < q
+ *   Eps[s][r]   = normal_draw(seed, r, s | (2 << STREAM_SUB_SHIFT), round_, OP_TS)   r < n
+ *
+ * Paths, with us = u * (1/ell) per feature and Zs[j][k] = Z[j][k] * INV_2PI,
+ * INV_2PI = 0.15915494309189535 the fp64 nearest of 1 / (2 pi), the product
+ * rounded once per entry of Z (that is where the 1 / (2 pi) rounding sits):
+ *   tau_j(u) = sum_k Zs[j][k] us_k + b_j                      (turns)
+ *   phi_j(u) = sqrt(2 sigma_f2 / D) cos2pi(tau_j - rint(tau_j))
+ *   g_s(u)   = sum_j Theta[s][j] phi_j(u)                     (the prior path)
+ *   r_s      = ys - g_s(X) - sqrt(diag) Eps[s]                (length n)
+ *   a_s      = L^-T (L^-1 r_s)
+ *   f_s(u)   = g_s(u) + sum_r k(x_r, u) a_s[r],   k = sigma_f2 exp(-1/2 |xs_r - us|^2) over every feature
+ * cos2pi is ut_core.h's (IEEE + - * only; its error bound COS_ERR is stated
+ * there).  At every training row r, whatever D:
+ *   f_s(x_r) + sqrt(diag) Eps[s][r] + diag a_s[r] = ys[r].
+ *
+ * Picks, for s = 0 .. k-1 (k <= q): pos_s = the position of the smallest
+ * f_s(u_i) over the candidates with dup[i] == 0 (dup may be NULL) that no
+ * earlier path picked; ties to the smallest position; if none is left or the
+ * minimum is NaN (any remaining value NaN), slot s and every later slot are
+ * empty: -1, +inf.
+ *
+ * ut_gp_ts_draw: Z, b, Theta, Eps and A = [a_s] ([q][npad], 0 on padding rows)
+ *   on the device for the current fit; g_s(X) by the path kernel itself on the
+ *   training rows, a_s for all q columns by two products with the explicit
+ *   inverse on the fp64 MFMA.
+ * ut_gp_ts_eval: device out_F [q][ldf] = f_s(u_i) for the m candidates values
+ *   [ncols][ld] (raw values as for ut_gp_score_values).
+ * ut_gp_ts_select: the pick rule; device out_pos [k], out_f [k] (may be NULL).
+ *   Paths are evaluated in groups of 32 (the F workspace is 32 x m doubles:
+ *   256 MiB at m = 2^20); a group's picks finish before the next group is
+ *   evaluated, a taken mask on the device carries across groups, a pick is two
+ *   small launches, and nothing is read by the host in between.
+ * ut_gp_ts_read: (for tests) what = 0 Z [D][d], 1 b [D], 2 Theta [q][D],
+ *   3 Eps [q][n], 4 A [q][n] into out_host; info (may be NULL) = {q, D, n, d}.
+ *   out_host NULL: info alone.  Waits for the stream.
+ * Always fp64 and over every feature, whatever ut_gp_set_precision says and
+ * whichever K* the fit scores with.  Stream-ordered, no host wait (ut_gp_ts_read
+ * apart): an in-flight fit is waited for on the device, and a failed fit makes
+ * every path NaN, so every slot is empty.  Reads the fit, writes scratch of its
+ * own.  Sums run in a fixed order with no atomics into results: two calls on
+ * one fit and one draw return the same bits.
+ * UT_EINVAL: no fit; draws made for an earlier fit (stale: draw again after
+ * every fit) or none; q < 1 or q > 256; D < 128, not a multiple of 128, or
+ * > 4096; round_ >= 2^24; k < 1 or k > q; a NULL values, out_F or out_pos;
+ * m < 1; ld or ldf < m; a fit whose feature count is not the space's.
+ * UT_ENOMEM: the scratch could not be allocated. */
+int ut_gp_ts_draw(ut_ctx* ctx, int32_t q, int32_t D, uint32_t round_);
+int ut_gp_ts_eval(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, double* out_F, int64_t ldf);
+int ut_gp_ts_select(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, const uint8_t* dup, int32_t k,
+                    int64_t* out_pos, double* out_f);
+int ut_gp_ts_read(ut_ctx* ctx, int32_t what, double* out_host, int32_t* info);
+
 /* ---- acquisition gradient and projected-ascent polish --------------------- */
 /* The reference's default bandit carries a local-search arm, RandomNelderMead
  * (bandittechniques.py:273-278; the simplex walk itself is

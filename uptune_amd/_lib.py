@@ -169,6 +169,10 @@ SIGNATURES = {
     "ut_gp_lml_grad": (C.c_int, [P, I32, P, C.POINTER(D), C.POINTER(D)]),
     "ut_gp_lml_grid": (C.c_int, [P, P, P, I32, I32, C.POINTER(GpHyper), I32, P, P, P, C.POINTER(I32)]),
     "ut_gp_select_batch": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, I32, P, P, P]),
+    "ut_gp_ts_draw": (C.c_int, [P, I32, I32, U32]),
+    "ut_gp_ts_eval": (C.c_int, [P, P, I64, I64, P, I64]),
+    "ut_gp_ts_select": (C.c_int, [P, P, I64, I64, P, I32, P, P]),
+    "ut_gp_ts_read": (C.c_int, [P, I32, P, C.POINTER(I32)]),
     "ut_gp_acq_grad": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, P, P, P, I64]),
     "ut_gp_polish": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, C.POINTER(PolishParams), P, I64, P, P, P]),
     "ut_gp_feas_set": (C.c_int, [P, P, I32, I32, C.POINTER(FeasParams)]),

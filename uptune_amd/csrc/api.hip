@@ -867,6 +867,31 @@ int ut_gp_select_batch(ut_ctx* c, const double* values, int64_t ld, int32_t p, c
   return rc;
 }
 
+int ut_gp_ts_draw(ut_ctx* c, int32_t q, int32_t D, uint32_t round_) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_ts_draw_impl(c, q, D, round_);
+}
+
+int ut_gp_ts_eval(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* out_F, int64_t ldf) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_ts_eval_impl(c, values, ld, m, out_F, ldf);
+}
+
+int ut_gp_ts_select(ut_ctx* c, const double* values, int64_t ld, int64_t m, const uint8_t* dup, int32_t k,
+                    int64_t* out_pos, double* out_f) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_ts_select_impl(c, values, ld, m, dup, k, out_pos, out_f);
+}
+
+int ut_gp_ts_read(ut_ctx* c, int32_t what, double* out_host, int32_t* info) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_ts_read_impl(c, what, out_host, info);
+}
+
 int ut_gp_acq_grad(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, double* out_score,
                    double* out_mu, double* out_var, double* out_grad, int64_t ld_g) {
   if (!c) return UT_EINVAL;

@@ -91,6 +91,9 @@ void uthc_exp2(const double* x, double* out, long long n) {
 void uthc_logint_unscale(const double* s, double mn, double* out, long long n) {
   for (long long i = 0; i < n; ++i) out[i] = rint((ut::exp2_cr(s[i]) - 1.0) + mn);
 }
+void uthc_cos2pi(const double* t, double* out, long long n) {
+  for (long long i = 0; i < n; ++i) out[i] = ut::cos2pi(t[i]);
+}
 void uthc_philox_raw(const unsigned* ctr4, const unsigned* key2, unsigned* out4) {
   ut::u32x4 c{ctr4[0], ctr4[1], ctr4[2], ctr4[3]};
   ut::u32x4 r = ut::philox4x32_10(c, key2[0], key2[1]);

@@ -91,6 +91,7 @@ UT_HD uint64_t below64(uint64_t x, uint64_t n) { return umulhi64(x, n); }
 //   c.w      = (round << 8) | op
 enum : uint32_t {
   OP_INIT = 1, OP_DE = 2, OP_PSO = 3, OP_GA = 4, OP_GGA = 5, OP_TR = 6,
+  OP_TS = 7,   // Thompson-sampling path draws (gp_ts.hip; uthot.h states the streams)
 };
 enum : uint32_t {
   STREAM_CAND = 0xFFFF0000u,   // per-candidate draws: STREAM_CAND | k
@@ -678,6 +679,38 @@ UT_HD double normal_draw(uint64_t seed, uint64_t cand, uint32_t stream, uint32_t
     if (s > 0.0 && s < 1.0) return u * dsqrt((-2.0 * ut_log(s)) / s);
   }
   return 0.0;
+}
+
+// cos(2 pi t) for t in [-1/2, 1/2] (a phase in turns after its exact reduction
+// t = tau - rint(tau)), from IEEE + - * alone, so the host build, the device
+// and tests/_ts_oracle.py's numpy restatement agree bit for bit:
+//   a = |t|;  a > 1/4: a <- 1/2 - a, negate          (exact: a in [0, 1/4])
+//   a <= 1/8:  the Taylor series of cos(2 pi z) in z^2, z = a
+//   a >  1/8:  z times that of sin(2 pi z) / z, z = 1/4 - a    (exact)
+// nine terms each with the coefficients (2 pi)^j / j! rounded once (the
+// remainder at z = 1/8 is below 2e-18), Horner from the highest.
+// COS_ERR = 1.6e-16: the largest |cos2pi(t) - cos(2 pi t)| against long double
+// over 10^6 arguments (tests/test_ts_oracle_cpu.py measures it and holds it).
+constexpr double UT_COS_ERR = 1.6e-16;
+constexpr double UT_INV_2PI = 0.15915494309189535;   // fp64 nearest of 1 / (2 pi)
+UT_HD double cos2pi(double t) {
+  double a = t < 0.0 ? -t : t;
+  const bool neg = a > 0.25;
+  a = neg ? 0.5 - a : a;
+  const bool sb = a > 0.125;
+  const double z = sb ? 0.25 - a : a;
+  const double z2 = z * z;
+  double p = sb ? 0.10422916220813984 : 0.28200596845579123;
+  p = p * z2 + (sb ? -0.7181223017785006 : -1.714390711088672);
+  p = p * z2 + (sb ? 3.819952584848282 : 7.903536371318469);
+  p = p * z2 + (sb ? -15.09464257682299 : -26.4262567833744);
+  p = p * z2 + (sb ? 42.058693944897655 : 60.24464137187666);
+  p = p * z2 + (sb ? -76.70585975306139 : -85.45681720669373);
+  p = p * z2 + (sb ? 81.60524927607506 : 64.9393940226683);
+  p = p * z2 + (sb ? -41.34170224039976 : -19.739208802178716);
+  p = p * z2 + (sb ? 6.283185307179586 : 1.0);
+  const double r = sb ? z * p : p;
+  return neg ? -r : r;
 }
 
 // ---------------------------------------------------------------------------

@@ -525,6 +525,21 @@ struct ut_ctx {
   ut::DevBuf<double> cs_stats;             // [UT_CONS_MAX][4] ystats of column j, [3] = tau_j; then f_best_c, n_feasible
   ut::DevBuf<double> cs_part;              // [RT][cs_nc][ldk] column partials of sum k alpha_j
   ut::DevBuf<double> cs_mu, cs_var;        // [ldk] the posterior of a call that asked for neither
+  // Thompson-sampling paths (gp_ts.hip): one draw of q paths for one fit
+  int32_t ts_q = 0, ts_D = 0;              // ts_q = 0: nothing drawn
+  uint64_t ts_fit = 0;                     // the fit (fit_gen) the draw was made for
+  ut::DevBuf<double> ts_Z, ts_b;           // Z [D][d] as drawn, b [D]
+  ut::DevBuf<double> ts_ZT;                // [dpad][D] Z / (2 pi), transposed: the frequency rows' A operand
+  ut::DevBuf<double> ts_theta;             // [q][D]
+  ut::DevBuf<double> ts_eps;               // [q][npad], 0 on padding rows
+  ut::DevBuf<double> ts_A;                 // [q][npad] a_s, 0 on padding rows
+  ut::DevBuf<double> ts_R;                 // [2][q][npad] the residuals r_s, then L^-1 r_s
+  ut::DevBuf<double> ts_xu;                // [dpad][npad] the training rows as candidates (g_s(X))
+  ut::DevBuf<double> ts_u, ts_cn;          // a call's candidates: scaled features [dpad][ldk], norms [ldk]
+  ut::DevBuf<double> ts_F;                 // select: one path group's values [TS_GROUP][ldk]
+  ut::DevBuf<double> ts_pv;                // select: the pick launches' partial minima [TS_PICK_WG]
+  ut::DevBuf<int64_t> ts_pp;               // ... their positions [TS_PICK_WG], then [1] the dead flag
+  ut::DevBuf<uint8_t> ts_taken;            // select: [m] picked by an earlier path
   int32_t dbg_fail_alloc = 0;             // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
@@ -735,6 +750,14 @@ int gp_acq_grad_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, con
 int gp_polish_impl(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, const uint8_t* dup,
                    const ut_polish_params* prm, double* out_values, int64_t ld_o, double* out_score,
                    double* out_score0, uint8_t* out_moved);
+// gp_ts.hip: Thompson-sampling posterior paths (uthot.h states the rule)
+constexpr int32_t TS_GROUP = 32;      // paths per work item of k_ts_paths, and per F workspace of ut_gp_ts_select
+constexpr int32_t TS_MAX_Q = 256, TS_MAX_D = 4096;
+int gp_ts_draw_impl(ut_ctx* c, int32_t q, int32_t D, uint32_t round_);
+int gp_ts_eval_impl(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* out_F, int64_t ldf);
+int gp_ts_select_impl(ut_ctx* c, const double* values, int64_t ld, int64_t m, const uint8_t* dup, int32_t k,
+                      int64_t* out_pos, double* out_f);
+int gp_ts_read_impl(ut_ctx* c, int32_t what, double* out_host, int32_t* info);
 
 // kernel launchers implemented in the .hip translation units
 int launch_population_init(ut_ctx* c, uint32_t round_);

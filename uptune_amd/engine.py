@@ -470,6 +470,59 @@ class BatchEngine:
                 "ut_gp_select_batch")
         return pos, score, var
 
+    # ---- Thompson sampling: posterior sample paths (csrc/gp_ts.hip) ----
+    def gp_ts_draw(self, q: int, features: int = 1024, round_: int = 0) -> None:
+        """ut_gp_ts_draw: q sample paths of the current fit's posterior with
+        `features` random Fourier features, keyed by (seed, round_).  The paths
+        belong to that fit: draw again after every fit."""
+        L.check(self.ctx, self.lib.ut_gp_ts_draw(self.ctx, int(q), int(features), int(round_)), "ut_gp_ts_draw")
+
+    def _pool(self, values: torch.Tensor, m: Optional[int], who: str):
+        if values.dim() != 2 or values.shape[0] != self.spec.ncols:
+            raise ValueError(f"{who}: values must be [{self.spec.ncols}][m]")
+        if values.stride(1) != 1:
+            values = values.contiguous()
+        return values, (values.shape[1] if m is None else int(m))
+
+    def gp_ts_eval(self, values: torch.Tensor, m: Optional[int] = None) -> torch.Tensor:
+        """ut_gp_ts_eval: -> F [q][m], every drawn path at every candidate of
+        values[:, :m].  Always fp64; stream-ordered."""
+        values, m = self._pool(values, m, "gp_ts_eval")
+        info = self.gp_ts_read(None)
+        F = torch.empty((info["q"], max(m, 1)), dtype=torch.float64, device=self.device)
+        L.check(self.ctx, self.lib.ut_gp_ts_eval(self.ctx, _ptr(values), values.stride(0), m, _ptr(F), F.stride(0)),
+                "ut_gp_ts_eval")
+        return F
+
+    def gp_ts_select(self, values: torch.Tensor, k: int, dup: Optional[torch.Tensor] = None,
+                     m: Optional[int] = None):
+        """ut_gp_ts_select: path s < k picks its minimiser over the candidates
+        of values[:, :m] that are no duplicates and that no earlier path
+        picked.  -> (pos [k], f [k]) in pick order; an empty slot holds -1,
+        +inf.  Always fp64; stream-ordered, no host wait."""
+        values, m = self._pool(values, m, "gp_ts_select")
+        k = int(k)
+        n = max(k, 1)
+        pos, f = self._empty(n, dtype=torch.int64), self._empty(n)
+        L.check(self.ctx, self.lib.ut_gp_ts_select(self.ctx, _ptr(values), values.stride(0), m, _ptr(dup), k,
+                                                   _ptr(pos), _ptr(f)), "ut_gp_ts_select")
+        return pos, f
+
+    def gp_ts_read(self, what: Optional[str]):
+        """ut_gp_ts_read (tests): what in "Z" [D][d], "b" [D], "Theta" [q][D],
+        "Eps" [q][n], "A" [q][n] -> a numpy array; None -> the sizes alone."""
+        info = (C.c_int32 * 4)()
+        L.check(self.ctx, self.lib.ut_gp_ts_read(self.ctx, 0, None, info), "ut_gp_ts_read")
+        q, D, n, d = (int(v) for v in info)
+        if what is None:
+            return dict(q=q, D=D, n=n, d=d)
+        code, shape = {"Z": (0, (D, d)), "b": (1, (D,)), "Theta": (2, (q, D)), "Eps": (3, (q, n)),
+                       "A": (4, (q, n))}[what]
+        out = np.empty(shape, dtype=np.float64)
+        L.check(self.ctx, self.lib.ut_gp_ts_read(self.ctx, code, out.ctypes.data_as(C.c_void_p), None),
+                "ut_gp_ts_read")
+        return out
+
     def _shortlist(self, values: torch.Tensor, who: str) -> torch.Tensor:
         if values.dim() != 2 or values.shape[0] != self.spec.ncols:
             raise ValueError(f"{who}: values must be [{self.spec.ncols}][p]")

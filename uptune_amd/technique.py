@@ -380,6 +380,7 @@ class SharedModel:
         self._fit_key = None
         self._fit_unverified = False
         self.fits = 0
+        self.ts_rounds = 0          # Thompson-sampling draws made on this model (next_ts_round)
         self.f_best = None          # surrogate="forest": min(y) of the last fit, in the units fitted
         self.fit_seconds = 0.0      # ... and the host time of its RandomForestRegressor.fit calls
         # list drivers (append-only results table): the usable rows found so
@@ -410,6 +411,13 @@ class SharedModel:
         new.__dict__.update({k: copy.deepcopy(v, memo) for k, v in self.__dict__.items() if k != "engine"})
         new._reset()
         return new
+
+    def next_ts_round(self) -> int:
+        """the 24-bit key of the next Thompson-sampling draw: a counter, so that
+        no two draws on one model (whichever technique makes them) share a key"""
+        r = self.ts_rounds & 0xFFFFFF
+        self.ts_rounds += 1
+        return r
 
     def slot(self, tech) -> int:
         return self.slots.setdefault(tech.name, len(self.slots))
@@ -828,7 +836,7 @@ class GpuBatchTechnique(SearchTechnique):
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  forest_kw: Optional[Dict[str, Any]] = None, polish: int = 0, polish_pool: Optional[int] = None,
-                 *pargs, **kwargs):
+                 ts_features: int = 1024, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
         # surrogate="forest" (SharedModel): a random forest refitted from the
         # driver's results, scored by EI / UCB on its mean and variance over
@@ -900,6 +908,31 @@ class GpuBatchTechnique(SearchTechnique):
                 raise ValueError("the gradient of the constrained score is not built: no polish with constraints")
             if (shared.feasibility if shared is not None else _feas_setting(feasibility)) is not None:
                 raise ValueError("the gradient of the weighted score is not built: no polish with feasibility")
+        # acq="ts": Thompson sampling.  A dense GP round draws `batch` sample paths
+        # of the posterior over the whole pool (ut_gp_ts_draw, ts_features random
+        # Fourier features, keyed by a counter on the shared model so that no two
+        # draws on one model share a key) and slot s takes path s's minimiser among
+        # the candidates no earlier slot took (ut_gp_ts_select): TuRBO's
+        # acquisition, whose batches are diverse without a second mechanism.  The
+        # reported score of a pick is -f_s there.  Off by default
+        self.ts_features = int(ts_features)
+        if acq == "ts":
+            if not (128 <= self.ts_features <= 4096 and self.ts_features % 128 == 0):
+                raise ValueError("ts_features must be a multiple of 128 in [128, 4096]")
+            if not 1 <= int(batch) <= 256:
+                raise ValueError("acq='ts' draws one path per batch slot: batch must be in [1, 256]")
+            if int(prune_rows) > 0:
+                raise ValueError("acq='ts' evaluates its paths at every candidate: not with prune_rows")
+            if self.diversify:
+                raise ValueError("acq='ts' spreads its batch by its own paths: not with diversify")
+            if self.polish:
+                raise ValueError("a sample path has no acquisition gradient built: no polish with acq='ts'")
+            if shared.constraints if shared is not None else _cons_setting(constraints):
+                raise ValueError("paths under constraints are not built: no constraints with acq='ts'")
+            if (shared.feasibility if shared is not None else _feas_setting(feasibility)) is not None:
+                raise ValueError("paths under the failure vote are not built: no feasibility with acq='ts'")
+            if tree:
+                raise ValueError("acq='ts' samples a GP posterior: not with a tree surrogate")
         # prune_rows > 0: score rounds with ut_gp_topk_pruned (selection-exact EI
         # bound from the first prune_rows rows of L^-1 k*; fp64 fits, EI / UCB):
         # the same selections as the dense variance at a fraction of its cost
@@ -1023,6 +1056,8 @@ class GpuBatchTechnique(SearchTechnique):
                                                  cand_base=base, bound_rows=self.prune_rows)
                 loc = torch.where(idx >= 0, idx - base, torch.zeros_like(idx))
                 return vals, idx, top, dig[loc], vals[:, loc]
+            if self.acq_kind == "ts":
+                return self._ts_picks(vals, dup, dig, base)
             # encoding fused into the K* operand pass (no feature matrix)
             _, _, score = eng.gp_score_values(vals, acq=eng.acq(self.acq_kind), dup=dup)
             if self.polish > 0:
@@ -1034,6 +1069,20 @@ class GpuBatchTechnique(SearchTechnique):
         idx, top = eng.topk(score, self.batch, dup=dup, cand_base=base)   # GLOBAL candidate indices
         loc = torch.where(idx >= 0, idx - base, torch.zeros_like(idx))
         return vals, idx, top, dig[loc], vals[:, loc]
+
+    def _ts_picks(self, vals, dup, dig, base):
+        """the round's selections by Thompson sampling: one posterior sample path
+        per batch slot, each slot its path's minimiser among the candidates that
+        are new and that no earlier slot took (BatchEngine.gp_ts_draw /
+        gp_ts_select); what _local_round returns, in pick order"""
+        import torch
+        eng = self.engine
+        k = min(self.batch, vals.shape[1])
+        eng.gp_ts_draw(k, self.ts_features, round_=self.model.next_ts_round())
+        pos, f = eng.gp_ts_select(vals, k, dup=dup)
+        loc = torch.where(pos >= 0, pos, torch.zeros_like(pos))
+        idx = torch.where(pos >= 0, loc + base, torch.full_like(pos, -1))
+        return vals, idx, -f, dig[loc], vals[:, loc]
 
     def _diverse_picks(self, vals, score, dup, dig, base):
         """the round's selections from the `diversify` best-scoring candidates,
@@ -1087,6 +1136,8 @@ class GpuBatchTechnique(SearchTechnique):
         rank, world = self._dist()
         if self.polish > 0 and world > 1 and self.sharded:
             raise ValueError("polish is not built for sharded rounds over several ranks")
+        if self.acq_kind == "ts" and world > 1 and self.sharded:
+            raise ValueError("acq='ts' is not built for sharded rounds over several ranks")
         if self.diversify > 0 and world > 1 and self.sharded:
             # (every rank holds the same setting: all raise together, before any collective)
             raise ValueError("diversify is not built for sharded rounds over several ranks")

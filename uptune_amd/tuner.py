@@ -40,7 +40,7 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                 precision: int = 64, prune_rows: int = 0, diversify: int = 0, feasibility=False,
                 constraints=None, prune_weighted: bool = False, surrogate=None,
                 forest_kw=None, polish: int = 0, polish_pool: Optional[int] = None,
-                trust_region: bool = False) -> SearchDriver:
+                trust_region: bool = False, acq: str = "ei", ts_features: int = 1024) -> SearchDriver:
     """Run the bandit for `generations` generations; returns the driver (results,
     best_result, bandit statistics).  With torch.distributed initialised and
     world > 1 the run is SPMD: call it on every rank with the same arguments.
@@ -53,14 +53,18 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
     polish=T > 0: every dense GP round refines its polish_pool best candidates
     with T gradient-ascent steps on the acquisition first (GpuBatchTechnique).
     trust_region=True: a fifth arm proposes inside a trust region around the best
-    result (GpuTrustRegion)."""
+    result (GpuTrustRegion).
+    acq="ucb" / "ts": the children's acquisition; "ts" = Thompson sampling, one
+    posterior sample path of ts_features random features per batch slot
+    (GpuBatchTechnique)."""
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     meta = pso_ga_de_bandit(bandit_seed=seed, pool=pool, batch=batch, population=population, seed=seed,
                             device=device, lengthscale=lengthscale, group=group, precision=precision,
                             prune_rows=prune_rows, diversify=diversify, feasibility=feasibility,
                             constraints=constraints, prune_weighted=prune_weighted, surrogate=surrogate,
-                            forest_kw=forest_kw, polish=polish, polish_pool=polish_pool,
+                            forest_kw=forest_kw, polish=polish, polish_pool=polish_pool, acq=acq,
+                            **({"ts_features": ts_features} if acq == "ts" else {}),
                             **({"trust_region": True} if trust_region else {}))
     if world > 1:
         import torch
