@@ -791,6 +791,89 @@ int ut_gp_cons_prob(ut_ctx* ctx, const double* values, const double* features, i
  * last two is asked for; UT_EINVAL then if the values belong to an earlier fit. */
 int ut_gp_cons_info(ut_ctx* ctx, int32_t* n, int32_t* nc, int32_t* n_feasible, double* f_best_c);
 
+/* ---- two objectives ------------------------------------------------------ */
+/* The reference orders results by a pair in MaximizeAccuracyMinimizeSize
+ * (objective.py:218-230), lexicographically: one point comes back.  Here a
+ * second measured quantity is a GP target like the objective -- same inputs,
+ * kernel and hyperparameters, so the fit's factor L and, in standardised
+ * units, its posterior variance are shared -- and the score of a candidate is
+ * the exact expected hypervolume improvement (EHVI) against the Pareto front
+ * of the fit's rows.
+ *
+ * Both objectives are minimised (a maximised one: negate it on the host).  For
+ * the current fit -- n rows, the standardised objective ys with its mean m_1
+ * and std s_1, sigma_f2, L -- values Y2 [n] row-aligned with the fit's rows and
+ * a reference point (R1, R2), R1 in the units of the y given to ut_gp_fit, R2
+ * in Y2's:
+ *   m_2, s_2   = mean, std (ddof 0; std 0 -> 1) of Y2      (the fit's own rule for y)
+ *   y2s        = (Y2 - m_2) / s_2        r_j = (R_j - m_j) / s_j
+ *   alpha_2    = L^-T (L^-1 y2s)
+ *   mu_1(u), var(u) = the objective's posterior as ut_gp_score gives it at the
+ *                     fit's precision tier
+ *   mu_2(u)    = sigma_f2 (k*(u) . alpha_2)   (fp64, row-tile partials summed tile 0 upward)
+ *   sigma      = sqrt(var(u))
+ * The front F of the rows (a, b) = (ys[r], y2s[r]): row r is in F iff
+ *   a_r < r_1 and b_r < r_2, and
+ *   no row s has a_s <= a_r, b_s <= b_r and one of a_s < a_r, b_s < b_r, s < r
+ * (of identical points the smallest row stays).  F is ordered by (a, r)
+ * ascending, so a_1 < ... < a_P and b_1 > ... > b_P; the sentinels are
+ * a_0 = -inf, a_{P+1} = r_1, b_0 = r_2.
+ *   psi(t; mu) = 0                                        t = -inf
+ *              = max(t - mu, 0)                           var == 0
+ *              = (t - mu) Phi(z) + sigma phi(z),  z = (t - mu) / sigma   otherwise
+ *   w_i        = max(psi(a_{i+1}; mu_1) - psi(a_i; mu_1), 0)             i = 0 .. P
+ *   EHVI(u)    = sum_{i = 0 .. P} w_i psi(b_i; mu_2)                     i ascending, fp64
+ * (Phi and phi as in the EI of ut_gp_score.)  This is the exact expectation of
+ * the hypervolume gain of (Y1, Y2) ~ N(mu_1, var) x N(mu_2, var): the region
+ * inside the reference box that F does not dominate is the union of the strips
+ * [a_i, a_{i+1}) x (-inf, b_i), and E[(a' - max(Y, a))+] = psi(a') - psi(a).
+ * EHVI >= 0; P = 0 gives psi(r_1; mu_1) psi(r_2; mu_2).  -inf (a duplicate)
+ * and NaN (a failed fit) scores pass through; mu and var are never changed;
+ * two calls return the same bits. */
+/* Load (replace) the second objective of the fit that is current at the call
+ * (objective.py:218-230): Y2_host [n], ref_host [2]; n = 0 clears (both
+ * pointers may then be NULL).  A fit staged by ut_gp_fit_async counts as
+ * current and is not waited for.  Synchronous on the host side.  The values
+ * belong to that fit: after any later fit every scoring call that would apply
+ * them returns UT_EINVAL, naming the stale fit, until ut_gp_mo_set is called
+ * again or the values are cleared.
+ * While a second objective is loaded ut_gp_score, ut_gp_score_values,
+ * ut_score_round_de and ut_score_round_ga with UT_ACQ_EI return score = EHVI
+ * at every precision, applied after the dense posterior (xi is ignored);
+ * UT_ACQ_UCB returns UT_EUNSUPPORTED, and so do ut_gp_topk_pruned and
+ * ut_score_round_de_pruned (whatever ut_gp_set_prune_weighted says),
+ * ut_gp_select_batch, ut_gp_acq_grad, ut_gp_polish and ut_gp_ts_select, and
+ * ut_gp_cons_set and ut_gp_feas_set with values or rows to load.  No kernel
+ * runs on a refused call.
+ * UT_EINVAL (what was loaded before stays loaded): no fit, n < 0 or not the
+ * fit's n, a NULL pointer with n > 0, a non-finite value or reference
+ * coordinate.  UT_EUNSUPPORTED (likewise): constraint values or failed rows
+ * are loaded. */
+int ut_gp_mo_set(ut_ctx* ctx, const double* Y2_host, int32_t n, const double* ref_host);
+/* EHVI (ehvi_out [m], required) and optionally mu_2 (mu2_out [m], may be NULL)
+ * of m candidates under the loaded second objective (objective.py:218-230).
+ * Exactly one of values ([ncols][ld], raw values: the K* the fit scores with)
+ * and features ([d][ld]: the dense contraction over every feature) is
+ * non-NULL.  Runs the objective's posterior first.  Device outputs;
+ * stream-ordered, no host wait.  UT_EINVAL: nothing loaded, values of an
+ * earlier fit, no fit, bad arguments. */
+int ut_gp_mo_score(ut_ctx* ctx, const double* values, const double* features, int64_t ld, int64_t m,
+                   double* ehvi_out, double* mu2_out);
+/* What is loaded (objective.py:218-230): the row count (0: nothing), the size
+ * P of F, the standardised reference point (r_1, r_2) and the hypervolume of F
+ * inside it, sum_i (a_{i+1} - a_i) (r_2 - b_i), in standardised units (NaN
+ * when nothing is loaded).  Any pointer may be NULL.  Waits for the fit when
+ * any of the last three is asked for; UT_EINVAL then if the values belong to
+ * an earlier fit. */
+int ut_gp_mo_info(ut_ctx* ctx, int32_t* n, int32_t* P, double* ref_std, double* hv);
+/* The ordered front (objective.py:218-230): *P its size, and its first
+ * min(P, cap) members' rows, a and b into the host arrays (each may be NULL).
+ * Waits for the fit.  UT_EINVAL: nothing loaded, values of an earlier fit,
+ * cap < 0, P NULL. */
+int ut_gp_mo_front(ut_ctx* ctx, int32_t* rows_host, double* a_host, double* b_host, int32_t cap, int32_t* P);
+/* (for tests) what = 0: y2s [n], 1: alpha_2 [n], 2: m_2, s_2 into out_host.  Waits for the fit. */
+int ut_gp_mo_read(ut_ctx* ctx, int32_t what, double* out_host);
+
 /* ---- selection ---------------------------------------------------------- */
 /* k largest scores, ties -> smallest global index; entries with dup[i]!=0 or
  * NaN score are never selected; missing slots get index -1. */

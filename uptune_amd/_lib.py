@@ -181,6 +181,11 @@ SIGNATURES = {
     "ut_gp_cons_set": (C.c_int, [P, P, I32, I32, P]),
     "ut_gp_cons_prob": (C.c_int, [P, P, P, I64, I64, P, P]),
     "ut_gp_cons_info": (C.c_int, [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(D)]),
+    "ut_gp_mo_set": (C.c_int, [P, P, I32, P]),
+    "ut_gp_mo_score": (C.c_int, [P, P, P, I64, I64, P, P]),
+    "ut_gp_mo_info": (C.c_int, [P, C.POINTER(I32), C.POINTER(I32), P, C.POINTER(D)]),
+    "ut_gp_mo_front": (C.c_int, [P, P, P, P, I32, C.POINTER(I32)]),
+    "ut_gp_mo_read": (C.c_int, [P, I32, P]),
     "ut_topk": (C.c_int, [P, P, P, I64, I64, I32, P, P]),
     "ut_score_round_ga": (C.c_int, [P, C.POINTER(GaParams), C.c_void_p, C.c_void_p, C.POINTER(Acq), U32, I64, I64,
                                     I32, C.POINTER(RoundOut)]),

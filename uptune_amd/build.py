@@ -26,7 +26,7 @@ HOSTLIB = os.path.join(HERE, "libuthot_hostcheck.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("UT_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["api.hip", "propose.hip", "propose_tr.hip", "hash.hip", "dedup.hip", "gp_fit.hip", "gp_score.hip", "gp_prune.hip", "gp_gemm.hip", "gp_i8.hip", "gp_kq.hip", "gp_lml.hip", "gp_lml_grad.hip", "gp_batch.hip", "gp_polish.hip", "gp_feas.hip", "gp_cons.hip", "gp_kstar_sums.hip", "gp_ts.hip", "topk.hip", "forest.hip", "forest_score.hip", "comm.hip"]
+SOURCES = ["api.hip", "propose.hip", "propose_tr.hip", "hash.hip", "dedup.hip", "gp_fit.hip", "gp_score.hip", "gp_prune.hip", "gp_gemm.hip", "gp_i8.hip", "gp_kq.hip", "gp_lml.hip", "gp_lml_grad.hip", "gp_batch.hip", "gp_polish.hip", "gp_feas.hip", "gp_cons.hip", "gp_mo.hip", "gp_kstar_sums.hip", "gp_ts.hip", "topk.hip", "forest.hip", "forest_score.hip", "comm.hip"]
 HEADERS = ["ut_core.h", "ut_internal.h", "gp_i8_plan.h", "gp_tiles.h", "gp_post.h", "gp_kstar_tile.h", "ut_param.h", "ut_perm.h", "ryu_tables.h", "libm_log_data.h", os.path.join("..", "..", "include", "uthot.h")]
 
 # RCCL for the multi-GPU exchange (comm.hip); the soname (librccl.so.1) is the

@@ -282,10 +282,11 @@ int ut_ctx_destroy(ut_ctx* c) {
   if (c->stream) ut::sync_all(c);
   ut::comm_release(c);
   for (auto& m : c->timing.marks) hipEventDestroy(m.ev);
-  for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_fit, c->ev_prefit, c->ev_fit_x, c->cs_ev})
+  for (hipEvent_t e : {c->ev_fork, c->ev_join, c->ev_fit, c->ev_prefit, c->ev_fit_x, c->cs_ev, c->mo_ev})
     if (e) hipEventDestroy(e);
   if (c->fit_host) hipHostFree(c->fit_host);
   if (c->cs_host) hipHostFree(c->cs_host);
+  if (c->mo_host) hipHostFree(c->mo_host);
   if (c->flag_host) hipHostFree(c->flag_host);
   if (c->lml_host) hipHostFree(c->lml_host);
   for (hipStream_t st : {c->own_stream, c->side, c->fit_stream})
@@ -733,6 +734,9 @@ int ut_gp_score_values(ut_ctx* c, const double* values, int64_t ld, int64_t m, c
   if (!c) return UT_EINVAL;
   UT_CHECK(c, m >= 0 && (values || m == 0) && ld >= m, UT_EINVAL, "gp_score_values: bad arguments");
   UT_CHECK(c, acq != nullptr, UT_EINVAL, "gp_score: acq is NULL");
+  // (a second objective that cannot be applied: refused before the encode)
+  if (score)
+    if (int rs = ut::mo_check(c, "gp_score_values", acq)) return rs;
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
   // encode + 1/ell scaling + |u'|^2 in one pass (k_encode_scaled): no feature matrix
@@ -755,6 +759,7 @@ int ut_gp_topk_pruned(ut_ctx* c, const double* feat, int64_t ld, int64_t m, cons
   UT_CHECK(c, c->cs_nc == 0 || c->prune_weighted, UT_EUNSUPPORTED,
            "gp_topk_pruned: constraint values are loaded (ut_gp_cons_set) and the pruning bound does not know the "
            "constraint weight");
+  if (int rs = ut::mo_refuse(c, "gp_topk_pruned", "the pruning bound does not know EHVI")) return rs;
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
   int rc = gp_topk_pruned_impl(c, feat, ld, m, acq, dup, cand_base, k, bound_rows, out_idx, out_score, stats);
@@ -859,6 +864,7 @@ int ut_gp_select_batch(ut_ctx* c, const double* values, int64_t ld, int32_t p, c
   UT_CHECK(c, c->cs_nc == 0, UT_EUNSUPPORTED,
            "gp_select_batch: constraint values are loaded (ut_gp_cons_set) and the per-pick acquisition does not know the "
            "constraint weight");
+  if (int rs = ut::mo_refuse(c, "gp_select_batch", "the per-pick acquisition does not know EHVI")) return rs;
   // a stand-alone call is a timing round of its own (stages bs_kstar, bs_v, bs_sigma, bs_loop)
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
@@ -883,6 +889,7 @@ int ut_gp_ts_select(ut_ctx* c, const double* values, int64_t ld, int64_t m, cons
                     int64_t* out_pos, double* out_f) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
+  if (int rs = ut::mo_refuse(c, "gp_ts_select", "paths of two objectives are not built")) return rs;
   return gp_ts_select_impl(c, values, ld, m, dup, k, out_pos, out_f);
 }
 
@@ -896,6 +903,7 @@ int ut_gp_acq_grad(ut_ctx* c, const double* values, int64_t ld, int32_t p, const
                    double* out_mu, double* out_var, double* out_grad, int64_t ld_g) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
+  if (int rs = ut::mo_refuse(c, "gp_acq_grad", "EHVI's gradient is not built")) return rs;
   // a stand-alone call is a timing round of its own (stages pl_kstar, pl_v, pl_tail, pl_w, pl_grad)
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
@@ -909,6 +917,7 @@ int ut_gp_polish(ut_ctx* c, const double* values, int64_t ld, int32_t p, const u
                  double* out_score0, uint8_t* out_moved) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
+  if (int rs = ut::mo_refuse(c, "gp_polish", "EHVI's gradient is not built")) return rs;
   const bool own = c->timing.on && !c->timing.in_round;
   if (own) timing_begin(c);
   const int rc = gp_polish_impl(c, values, ld, p, acq, dup, prm, out_values, ld_o, out_score, out_score0, out_moved);
@@ -919,6 +928,8 @@ int ut_gp_polish(ut_ctx* c, const double* values, int64_t ld, int32_t p, const u
 int ut_gp_feas_set(ut_ctx* c, const double* Xfail_host, int32_t nf, int32_t d, const ut_feas_params* p) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
+  if (nf > 0)
+    if (int rs = ut::mo_refuse(c, "gp_feas_set", "EHVI under the feasibility vote is not built")) return rs;
   return gp_feas_set_impl(c, Xfail_host, nf, d, p);
 }
 
@@ -944,6 +955,8 @@ int ut_gp_feas_info(ut_ctx* c, int32_t* nf, ut_feas_params* p) {
 int ut_gp_cons_set(ut_ctx* c, const double* C_host, int32_t n, int32_t nc, const double* threshold_host) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
+  if (nc > 0)
+    if (int rs = ut::mo_refuse(c, "gp_cons_set", "constrained EHVI is not built")) return rs;
   return gp_cons_set_impl(c, C_host, n, nc, threshold_host);
 }
 
@@ -963,6 +976,43 @@ int ut_gp_cons_info(ut_ctx* c, int32_t* n, int32_t* nc, int32_t* n_feasible, dou
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
   return gp_cons_info_impl(c, n, nc, n_feasible, f_best_c);
+}
+
+int ut_gp_mo_set(ut_ctx* c, const double* Y2_host, int32_t n, const double* ref_host) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  UT_CHECK(c, n >= 0, UT_EINVAL, "gp_mo_set: n < 0");
+  return gp_mo_set_impl(c, Y2_host, n, ref_host);
+}
+
+int ut_gp_mo_score(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* ehvi_out,
+                   double* mu2_out) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  // a stand-alone call is a timing round of its own (stages encode / cnorm, kstar, var, finalize, mo_means, mo_ehvi)
+  const bool own = c->timing.on && !c->timing.in_round;
+  if (own) timing_begin(c);
+  const int rc = gp_mo_score_impl(c, values, features, ld, m, ehvi_out, mu2_out);
+  if (own) timing_end(c);
+  return rc;
+}
+
+int ut_gp_mo_info(ut_ctx* c, int32_t* n, int32_t* P, double* ref_std, double* hv) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_mo_info_impl(c, n, P, ref_std, hv);
+}
+
+int ut_gp_mo_front(ut_ctx* c, int32_t* rows_host, double* a_host, double* b_host, int32_t cap, int32_t* P) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_mo_front_impl(c, rows_host, a_host, b_host, cap, P);
+}
+
+int ut_gp_mo_read(ut_ctx* c, int32_t what, double* out_host) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return gp_mo_read_impl(c, what, out_host);
 }
 
 int ut_gp_kstar_mode(ut_ctx* c, int32_t* categorical) {
@@ -1013,6 +1063,7 @@ int ut_score_round_de_pruned(ut_ctx* c, const ut_de_params* de, const ut_acq* ac
   UT_CHECK(c, c->cs_nc == 0 || c->prune_weighted, UT_EUNSUPPORTED,
            "score_round_de_pruned: constraint values are loaded (ut_gp_cons_set) and the pruning bound does not know the "
            "constraint weight");
+  if (int rs = ut::mo_refuse(c, "score_round_de_pruned", "the pruning bound does not know EHVI")) return rs;
   return score_round_de_impl(c, de, acq, round_, cand_base, m, k, out, bound_rows, stats);
 }
 
@@ -1027,6 +1078,7 @@ static int score_round_de_impl(ut_ctx* c, const ut_de_params* de, const ut_acq* 
   UT_CHECK(c, m >= 1 && de && acq, UT_EINVAL, "score_round: bad arguments");
   // (constraint values of an earlier fit: refused before the round enqueues anything)
   if (int rs = ut::cons_stale(c, "score_round")) return rs;
+  if (int rs = ut::mo_check(c, "score_round", acq)) return rs;
   const int64_t ld = ((m + 127) / 128) * 128;
   const int32_t NC = c->space.ncols;
   int rc;
@@ -1212,6 +1264,7 @@ int ut_score_round_ga(ut_ctx* c, const ut_ga_params* ga, const double* parent1, 
   UT_CHECK(c, c->gp_d == c->space.n_feat, UT_EINVAL, "score_round: GP feature width != space feature width");
   UT_CHECK(c, m >= 1 && ga && acq && cand_base >= 0 && k >= 1, UT_EINVAL, "score_round_ga: bad arguments");
   if (int rs = ut::cons_stale(c, "score_round_ga")) return rs;
+  if (int rs = ut::mo_check(c, "score_round_ga", acq)) return rs;
   UT_CHECK(c, ga->max_retries >= 1 && ga->max_retries <= 15, UT_EINVAL, "propose_ga: max_retries must be in [1, 15]");
   UT_CHECK(c, ga->must_mutate_count >= 0 && ga->must_mutate_count <= c->space.P, UT_EINVAL,
            "propose_ga: must_mutate_count out of range");

@@ -339,15 +339,20 @@ int weights_refuse_ucb(ut_ctx* c, const ut_acq* acq, bool feas, bool cons) {
 // exactly when its K* was.  While constraint values are loaded
 // (ut_gp_cons_set) the constrained-EI tail (gp_cons.hip) rewrites the scores
 // first, from the posterior the dense body wrote (into context scratch where
-// the caller asked for no mu or var): dense, constraint tail, vote.  With
-// nothing loaded: no launch, no wait.
+// the caller asked for no mu or var): dense, constraint tail, vote.  While a
+// second objective is loaded (ut_gp_mo_set; refused beside rows or values) the
+// EHVI tail (gp_mo.hip) rewrites the scores in the constraint tail's place.
+// With nothing loaded: no launch, no wait.
 int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
                   double* mu, double* var, double* score, hipEvent_t dup_ready) {
   const bool weigh = c->fs_n > 0 && score != nullptr;
   const bool cons = c->cs_nc > 0 && score != nullptr;
+  // a second objective (ut_gp_mo_set; never beside rows or values): the EHVI tail (gp_mo.hip) in the same place
+  const bool mo = c->mo_n > 0 && score != nullptr;
   int rc;
   if ((rc = weights_refuse_ucb(c, acq, weigh, cons))) return rc;
-  if (cons && m > 0) {
+  if (mo && (rc = mo_check(c, "gp_score", acq))) return rc;
+  if ((cons || mo) && m > 0) {
     if ((rc = cons_stale(c, "gp_score"))) return rc;
     const int64_t ldk = gp_ldk(m);
     if (!mu && (rc = ensure(c, c->cs_mu, (size_t)ldk))) return rc;
@@ -356,8 +361,9 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
     if (!var) var = c->cs_var.p;
   }
   rc = gp_score_dense(c, feat, ld, m, acq, dup, mu, var, score, dup_ready);
-  if (rc || !(weigh || cons) || m <= 0) return rc;
+  if (rc || !(weigh || cons || mo) || m <= 0) return rc;
   const ScoreShape s = score_shape(c, m, !feat && c->cat_on && c->ucand_cat);
+  if (mo) return mo_weight(c, s, m, mu, var, score);
   if (cons && (rc = cons_weight(c, s, m, acq->xi, mu, var, score))) return rc;
   return weigh ? feas_weight(c, s, m, score) : 0;
 }

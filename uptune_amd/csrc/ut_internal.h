@@ -525,6 +525,23 @@ struct ut_ctx {
   ut::DevBuf<double> cs_stats;             // [UT_CONS_MAX][4] ystats of column j, [3] = tau_j; then f_best_c, n_feasible
   ut::DevBuf<double> cs_part;              // [RT][cs_nc][ldk] column partials of sum k alpha_j
   ut::DevBuf<double> cs_mu, cs_var;        // [ldk] the posterior of a call that asked for neither
+  // two objectives (gp_mo.hip): the second objective's values of the fit's rows
+  // and their per-fit operands on the shared factor, kept as the constraint
+  // values' are; the Pareto front of the rows in standardised units
+  double* mo_host = nullptr;               // pinned: Y2 [npad], then the reference point [2]
+  size_t mo_host_n = 0;
+  hipEvent_t mo_ev = nullptr;              // the last copy out of mo_host
+  int32_t mo_n = 0;                        // 0: nothing loaded, every score is the plain acquisition
+  uint64_t mo_fit = 0;                     // the fit (fit_gen) the values were loaded for
+  uint64_t mo_gen = 0;                     // the fit the operands below were built from; 0 = stale
+  ut::DevBuf<double> mo_Y;                 // [npad] raw values, then the raw reference point [2]
+  ut::DevBuf<double> mo_y2s;               // [npad] standardised, zero on padding rows
+  ut::DevBuf<double> mo_beta, mo_alpha;    // [npad] L^-1 y2s, K^-1 y2s
+  ut::DevBuf<double> mo_stats;             // [4] ystats of Y2: [1] = m_2, [2] = s_2
+  ut::DevBuf<uint8_t> mo_keep;             // [npad] the row is on the front
+  ut::DevBuf<double> mo_fr;                // [MO_A] r_1, r_2, hv, P | a [0 .. P + 1] | b [0 .. P] (mo_b_off)
+  ut::DevBuf<int32_t> mo_rows;             // [npad] the front's rows, in its order
+  ut::DevBuf<double> mo_part;              // [RT][ldk] column partials of sum k alpha_2
   // Thompson-sampling paths (gp_ts.hip): one draw of q paths for one fit
   int32_t ts_q = 0, ts_D = 0;              // ts_q = 0: nothing drawn
   uint64_t ts_fit = 0;                     // the fit (fit_gen) the draw was made for
@@ -737,6 +754,24 @@ int cons_weight(ut_ctx* c, const ScoreShape& s, int64_t m, double xi, const doub
 // candidates in c->ucand / c->cnorm / c->bcat (or in ops) into c->cs_part [RT][cs_nc][ld] (k_kstar_sums)
 int cons_means(ut_ctx* c, const ScoreShape& s, int64_t m, const CandOps* ops = nullptr);
 constexpr int CS_INFO = 4 * UT_CONS_MAX;   // cs_stats[CS_INFO] = f_best_c, [CS_INFO + 1] = n_feasible
+// gp_mo.hip: two objectives (uthot.h "two objectives").  mo_fr's layout: the header, then a with both
+// sentinels, then b with its one
+constexpr int MO_A = 4;
+inline int64_t mo_b_off(int32_t npad) { return MO_A + (int64_t)npad + 2; }
+int gp_mo_set_impl(ut_ctx* c, const double* Y2, int32_t n, const double* ref);
+int gp_mo_score_impl(ut_ctx* c, const double* values, const double* features, int64_t ld, int64_t m, double* ehvi_out,
+                     double* mu2_out);
+int gp_mo_info_impl(ut_ctx* c, int32_t* n, int32_t* P, double* ref_std, double* hv);
+int gp_mo_front_impl(ut_ctx* c, int32_t* rows_host, double* a_host, double* b_host, int32_t cap, int32_t* P);
+int gp_mo_read_impl(ut_ctx* c, int32_t what, double* out_host);
+// UT_EUNSUPPORTED while a second objective is loaded: `who` does not know EHVI (why: the reason's words)
+int mo_refuse(ut_ctx* c, const char* who, const char* why);
+// what a dense scoring call checks before it enqueues anything: UT_EINVAL when the loaded values belong to an
+// earlier fit, UT_EUNSUPPORTED for a UCB score (EHVI stands in for EI only)
+int mo_check(ut_ctx* c, const char* who, const ut_acq* acq);
+// score[i] = EHVI_i (finite scores only) for the m candidates whose K* operands (of shape s) are in c->ucand /
+// c->cnorm / c->bcat and whose posterior the dense body left in mu / var
+int mo_weight(ut_ctx* c, const ScoreShape& s, int64_t m, const double* mu, const double* var, double* score);
 // gp_score.hip: UT_EUNSUPPORTED for a UCB score while rows (feas) or values (cons) would weight it
 int weights_refuse_ucb(ut_ctx* c, const ut_acq* acq, bool feas, bool cons);
 // gp_batch.hip: k picks from a shortlist of p, each conditioned on the picks before it

@@ -134,6 +134,64 @@ class ThresholdAccuracyMinimizeTime(MinimizeTime):
         return result.accuracy is not None and result.accuracy >= self.accuracy_target
 
 
+class ParetoMinimize(MinimizeTime):
+    """Two objectives, no trade-off fixed beforehand: time and a second
+    measurement (`second`: accuracy, energy, size or confidence; maximize=True
+    negates it).  The reference's only pair objective,
+    MaximizeAccuracyMinimizeSize (objective.py:218-230), orders the pair
+    lexicographically and so returns one point; this one keeps the Pareto
+    front.  lt(a, b): a dominates b; lte(a, b): b does not dominate a.  A result
+    without a finite time and second measurement dominates nothing and is
+    never admitted.  The surrogate's side of it is
+    SharedModel(objectives=[("time", "min"), (second, "min" or "max")])."""
+
+    SECOND = ("accuracy", "energy", "size", "confidence")
+
+    def __init__(self, second: str = "size", maximize: bool = False):
+        if second not in self.SECOND:
+            raise ValueError("ParetoMinimize: second is one of " + ", ".join(self.SECOND))
+        self.second, self.maximize = second, bool(maximize)
+        self.front: List[Result] = []
+
+    def set_driver(self, driver):
+        self.driver = driver
+        self.front = []
+
+    def point(self, r: Result):
+        """(time, second as minimised), or None when either is missing or not finite"""
+        v = getattr(r, self.second, None)
+        if v is None or r.time is None or not np.isfinite(r.time) or not np.isfinite(v):
+            return None
+        return (float(r.time), -float(v) if self.maximize else float(v))
+
+    @staticmethod
+    def _dominates(p, q) -> bool:
+        return p[0] <= q[0] and p[1] <= q[1] and (p[0] < q[0] or p[1] < q[1])
+
+    def lt(self, a: Result, b: Result) -> bool:
+        p, q = self.point(a), self.point(b)
+        return p is not None and (q is None or self._dominates(p, q))
+
+    def lte(self, a: Result, b: Result) -> bool:
+        return not self.lt(b, a)
+
+    def admit(self, result: Result) -> bool:
+        """True iff `result` is not dominated by, and not equal to, a member of
+        the front; it then joins it and the members it dominates leave"""
+        p = self.point(result)
+        if p is None:
+            return False
+        pts = [self.point(m) for m in self.front]
+        if any(q == p or self._dominates(q, p) for q in pts):
+            return False
+        self.front = [m for m, q in zip(self.front, pts) if not self._dominates(p, q)] + [result]
+        return True
+
+    def pareto_front(self) -> List[Result]:
+        """the members ordered by time (ties: the earlier result first)"""
+        return sorted(self.front, key=lambda r: (r.time, r.id))
+
+
 def _measured(value):
     """what an evaluator returned -> (time, {further named measurements}): a
     float, or a mapping with "time" and e.g. "accuracy" """
@@ -339,15 +397,31 @@ class SearchDriver:
     def process_new_results(self) -> None:
         """driver.py:209-225"""
         self.new_results = []
+        admit = getattr(self.objective, "admit", None)
         for r in self._unprocessed:
             self.new_results.append(r)
-            if self.best_result is None or self.objective.lt(r, self.best_result):
+            if admit is not None:
+                # a front-keeping objective (ParetoMinimize) decides the credit; the
+                # best result is the front's fastest member, so techniques that
+                # centre on it keep working
+                r.was_new_best = bool(admit(r))
+                if r.was_new_best:
+                    self.best_result = self.objective.pareto_front()[0]
+            elif self.best_result is None or self.objective.lt(r, self.best_result):
                 self.best_result = r
                 r.was_new_best = True
             else:
                 r.was_new_best = False
         self._unprocessed = []
         self.result_callbacks()
+
+    def pareto_front(self) -> List[Result]:
+        """the objective's Pareto front ordered by time (ParetoMinimize); under
+        any other objective the best result alone"""
+        front = getattr(self.objective, "pareto_front", None)
+        if front is not None:
+            return front()
+        return [] if self.best_result is None else [self.best_result]
 
     def convergence_criteria(self, test_limit: int) -> bool:
         return self.test_count > test_limit
@@ -433,6 +507,9 @@ class TuningRunManager:
 
     def get_best_result(self) -> Optional[Result]:
         return self.search_driver.best_result
+
+    def get_pareto_front(self) -> List[Result]:
+        return self.search_driver.pareto_front()
 
     def finish(self) -> None:
         self.search_driver.process_new_results()

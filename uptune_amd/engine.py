@@ -672,6 +672,76 @@ class BatchEngine:
                 "ut_gp_cons_info")
         return {"n": int(n.value), "nc": int(nc.value), "n_feasible": int(nf.value), "f_best_c": float(fb.value)}
 
+    # -- two objectives ---------------------------------------------------------
+    def gp_mo_set(self, Y2, ref):
+        """ut_gp_mo_set: load (replace) the second objective's values Y2 [n] of
+        the current fit's rows, in the fit's row order, and the reference point
+        (R1 in the units of gp_fit's y, R2 in Y2's); both objectives are
+        minimised (a maximised one: negate it).  While loaded every dense EI
+        score becomes the expected hypervolume improvement against the rows'
+        Pareto front inside the reference box.  The values belong to that fit:
+        call again after every gp_fit (scoring raises UT_EINVAL until then).
+        Does not wait for a fit in flight."""
+        y2 = np.ascontiguousarray(Y2, dtype=np.float64).ravel()
+        r = np.ascontiguousarray(ref, dtype=np.float64).ravel()
+        if r.shape != (2,):
+            raise ValueError("gp_mo_set: the reference point has two coordinates")
+        n = y2.shape[0]
+        L.check(self.ctx, self.lib.ut_gp_mo_set(self.ctx, y2.ctypes.data if n else None, n, r.ctypes.data),
+                "ut_gp_mo_set")
+
+    def gp_mo_clear(self):
+        """no second objective: every call scores as it did before one was loaded"""
+        L.check(self.ctx, self.lib.ut_gp_mo_set(self.ctx, None, 0, None), "ut_gp_mo_set")
+
+    def gp_mo_score(self, values: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None,
+                    m: Optional[int] = None):
+        """ut_gp_mo_score: (EHVI [m], mu_2 [m]) of candidates given as raw values
+        [ncols][m] (the K* the fit scores with) or as features [F][m] (the dense
+        contraction); stream-ordered, no host wait"""
+        if (values is None) == (features is None):
+            raise ValueError("gp_mo_score: exactly one of values and features")
+        x = values if values is not None else features
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        m = x.shape[1] if m is None else int(m)
+        ehvi, mu2 = self._empty(m), self._empty(m)
+        L.check(self.ctx, self.lib.ut_gp_mo_score(self.ctx, _ptr(x) if values is not None else None,
+                                                  _ptr(x) if values is None else None, x.stride(0), m, _ptr(ehvi),
+                                                  _ptr(mu2)), "ut_gp_mo_score")
+        return ehvi, mu2
+
+    def gp_mo_info(self) -> Dict[str, Any]:
+        """what is loaded: {"n": rows (0: nothing), "P": the front's size, "ref_std":
+        the standardised reference point, "hv": the front's hypervolume inside
+        it, standardised units}; waits for the fit"""
+        n, P, hv = C.c_int32(), C.c_int32(), C.c_double()
+        ref = (C.c_double * 2)()
+        L.check(self.ctx, self.lib.ut_gp_mo_info(self.ctx, C.byref(n), C.byref(P), ref, C.byref(hv)), "ut_gp_mo_info")
+        return {"n": int(n.value), "P": int(P.value), "ref_std": (float(ref[0]), float(ref[1])), "hv": float(hv.value)}
+
+    def gp_mo_front(self):
+        """ut_gp_mo_front: (rows int32 [P], a [P], b [P]) of the front, ordered by
+        the standardised first objective ascending; waits for the fit"""
+        n = C.c_int32()
+        L.check(self.ctx, self.lib.ut_gp_mo_info(self.ctx, C.byref(n), None, None, None), "ut_gp_mo_info")
+        cap = int(n.value)
+        rows = np.zeros(max(cap, 1), dtype=np.int32)
+        a, b = np.zeros(max(cap, 1)), np.zeros(max(cap, 1))
+        P = C.c_int32()
+        L.check(self.ctx, self.lib.ut_gp_mo_front(self.ctx, rows.ctypes.data, a.ctypes.data, b.ctypes.data, cap,
+                                                  C.byref(P)), "ut_gp_mo_front")
+        k = int(P.value)
+        return rows[:k].copy(), a[:k].copy(), b[:k].copy()
+
+    def gp_mo_read(self, what: int) -> np.ndarray:
+        """(for tests) ut_gp_mo_read: 0 = y2s [n], 1 = alpha_2 [n], 2 = (m_2, s_2)"""
+        n = C.c_int32()
+        L.check(self.ctx, self.lib.ut_gp_mo_info(self.ctx, C.byref(n), None, None, None), "ut_gp_mo_info")
+        out = np.zeros(2 if what == 2 else max(int(n.value), 1))
+        L.check(self.ctx, self.lib.ut_gp_mo_read(self.ctx, int(what), out.ctypes.data), "ut_gp_mo_read")
+        return out if what == 2 else out[:int(n.value)]
+
     def gp_topk_pruned(self, feat: torch.Tensor, k: int, m: Optional[int] = None, acq: Optional[L.Acq] = None,
                        dup: Optional[torch.Tensor] = None, cand_base: int = 0, bound_rows: int = 256):
         """ut_gp_topk_pruned: the top-k of the GP score, selection-exact, with the

@@ -276,7 +276,8 @@ class SharedModel:
                  precision: int = 64, sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 1e-8,
                  engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
-                 surrogate: Optional[str] = None, forest_kw: Optional[Dict[str, Any]] = None):
+                 surrogate: Optional[str] = None, forest_kw: Optional[Dict[str, Any]] = None,
+                 objectives=None, ref_point=None):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -352,6 +353,34 @@ class SharedModel:
             raise ValueError("feasibility and constraints weight the GP's EI: not with a tree surrogate")
         self.surrogate = surrogate
         self.forest_kw = dict(forest_kw or {})
+        # objectives: [("time", "min"), (attr, "min" or "max")] -- a second
+        # measurement every result carries (accuracy, energy, size, confidence)
+        # is minimised (or maximised) beside the time, with no trade-off fixed
+        # beforehand.  time stays the GP's y (with its y_transform); the second
+        # one's values of the training rows ride beside it as constraint values
+        # do, are loaded after every gp_fit (engine.gp_mo_set; "max" negated),
+        # and every EI score becomes the expected hypervolume improvement against
+        # the rows' Pareto front.  ref_point: the reference point in raw units
+        # (time, second), its first coordinate passed through y_transform; None =
+        # pareto.default_ref of the usable rows at the first fit, held from then
+        # on so that hypervolumes within a run compare.  ref_point_ is the point
+        # in use, in the units fitted (time, signed second).
+        self.objectives = _mo_setting(objectives)
+        if self.objectives:
+            if self.constraints:
+                raise ValueError("objectives: constrained EHVI is not built: no constraints with two objectives")
+            if self.feasibility is not None:
+                raise ValueError("objectives: EHVI under the failure vote is not built: no feasibility with two "
+                                 "objectives")
+            if surrogate is not None:
+                raise ValueError("objectives: EHVI needs the GP's joint posterior: not with a tree surrogate")
+        if ref_point is not None:
+            if not self.objectives:
+                raise ValueError("ref_point belongs to objectives=")
+            ref_point = tuple(float(v) for v in ref_point)
+            if len(ref_point) != 2 or not all(math.isfinite(v) for v in ref_point):
+                raise ValueError("ref_point: two finite coordinates (time, second), raw units")
+        self.ref_point = ref_point
         self._reset()
         self.slots: Dict[str, int] = {}
 
@@ -402,6 +431,15 @@ class SharedModel:
         self._Ca = np.zeros((0, 0))
         self._Cf = np.zeros((0, 0))
         self.n_feasible_ = None
+        self.ref_point_ = None      # objectives: the reference point in use, units fitted
+
+    def _side_columns(self) -> List[Any]:
+        """what rides beside y as (attr, op, _): the constraints, or the second
+        objective as one column ("max" = ">=": negated)"""
+        if self.objectives:
+            attr, sense = self.objectives[1]
+            return [(attr, ">=" if sense == "max" else "<=", None)]
+        return self.constraints
 
     def __deepcopy__(self, memo):
         # techniques (and so their shared model) are deep-copied per driver
@@ -457,7 +495,7 @@ class SharedModel:
     def _scan(self, driver):
         """the driver's results as (usable rows, their ids, failed results), in
         arrival order: what either surrogate trains on"""
-        cons = self.constraints
+        cons = self._side_columns()
 
         def measured(r):   # (constraints) every constrained measurement is there and finite
             for attr, _, _ in cons:
@@ -503,7 +541,7 @@ class SharedModel:
         """_Xa / _ya (and _Ca) := the features, objectives (and signed constraint
         values) of `rows`, arrival order; only the rows appended since the last
         call are encoded"""
-        cons = self.constraints
+        cons = self._side_columns()
         k = self._n
         if k == 0 or ids[:k] != self._res_ids:      # not an append: re-encode everything
             k = self._n = self._nf = 0
@@ -534,6 +572,17 @@ class SharedModel:
             y = ndtri((r + 0.5) / len(y))
         return y
 
+    def _transform_point(self, t: float, y) -> float:
+        """one raw objective value in the units _transform(y) is in: under
+        "rank" the normal score of its rank among y (average rank on ties),
+        which moves with the data, so it is taken again at every fit"""
+        if self.y_transform == "rank":
+            from scipy.special import ndtri
+            y = np.asarray(y)
+            r = float(np.sum(y < t)) + 0.5 * float(np.sum(y == t))
+            return float(ndtri((r + 0.5) / (len(y) + 1)))
+        return float(t)
+
     def _fit_forest(self, rows, ids) -> bool:
         """surrogate="forest": refit the random forest iff the usable results changed"""
         import time
@@ -563,7 +612,7 @@ class SharedModel:
         fit.  The GP: the new training rows are encoded on the device
         (ut_encode_features) and the fit is enqueued without a host wait
         (ut_gp_fit_async)"""
-        cons = self.constraints
+        cons = self._side_columns()
         rows, ids, bad = self._scan(driver)
         if len(rows) < self.min_train:
             return False
@@ -622,7 +671,17 @@ class SharedModel:
                 self._ell_npad = npad
             ell = self.lengthscale_
         self.engine.gp_fit(self._Xf[:n], y, lengthscale=ell, wait=False, **self.hyper)
-        if cons:
+        if self.objectives:
+            # the second objective's values belong to this fit, as constraint
+            # values do; the reference point is chosen once
+            if self.ref_point is not None:
+                sign = -1.0 if self.objectives[1][1] == "max" else 1.0
+                self.ref_point_ = (self._transform_point(self.ref_point[0], self._yf[:n]), sign * self.ref_point[1])
+            elif self.ref_point_ is None:
+                from .pareto import default_ref
+                self.ref_point_ = tuple(float(v) for v in default_ref(np.column_stack([y, self._Cf[:n, 0]])))
+            self.engine.gp_mo_set(self._Cf[:n, 0], self.ref_point_)
+        elif cons:
             # the values belong to this fit (the last one, after any of the
             # lengthscale selection's own); no host wait in between
             thr = [(-1.0 if op == ">=" else 1.0) * float(t) for _, op, t in cons]
@@ -794,6 +853,20 @@ def _cons_setting(constraints) -> List[Any]:
     return out
 
 
+def _mo_setting(objectives) -> List[Any]:
+    """objectives= as [("time", sense), (attr, sense)]; [] = off (one objective)"""
+    if not objectives:
+        return []
+    out = [tuple(o) if isinstance(o, (tuple, list)) else o for o in objectives]
+    if len(out) != 2 or any(not isinstance(o, tuple) or len(o) != 2 or o[1] not in ("min", "max") for o in out):
+        raise ValueError("objectives: exactly two of (attribute, 'min' or 'max'); more than two are not built")
+    if out[0] != ("time", "min"):
+        raise ValueError("objectives: the first is ('time', 'min'), the GP's own target")
+    if out[1][0] not in ("accuracy", "energy", "size", "confidence"):
+        raise ValueError("objectives: the second is one of accuracy, energy, size, confidence")
+    return out
+
+
 def _cols_room(Cm, used, n, nc):
     """Cm with room for n rows of nc constraint values, the first `used` rows kept"""
     if Cm.shape[0] >= n and Cm.shape[1] == nc:
@@ -836,7 +909,7 @@ class GpuBatchTechnique(SearchTechnique):
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  forest_kw: Optional[Dict[str, Any]] = None, polish: int = 0, polish_pool: Optional[int] = None,
-                 ts_features: int = 1024, *pargs, **kwargs):
+                 ts_features: int = 1024, objectives=None, ref_point=None, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
         # surrogate="forest" (SharedModel): a random forest refitted from the
         # driver's results, scored by EI / UCB on its mean and variance over
@@ -876,6 +949,27 @@ class GpuBatchTechnique(SearchTechnique):
                 raise ValueError("feasibility multiplies a score that is >= 0: EI, not acq='ucb'")
             if tree:
                 raise ValueError("feasibility weights the GP's EI: not with a tree surrogate")
+        # objectives (SharedModel): every EI score becomes the expected hypervolume
+        # improvement over time and a second measurement.  A shared model carries
+        # its own setting; EHVI is built for the dense EI score alone
+        if shared.objectives if shared is not None else _mo_setting(objectives):
+            if int(prune_rows) > 0:
+                raise ValueError("objectives: the pruning bound does not know EHVI: not with prune_rows")
+            if int(diversify) > 0:
+                raise ValueError("objectives: EHVI is not known to the per-pick acquisition: not with diversify")
+            if acq == "ucb":
+                raise ValueError("objectives: EHVI stands in for EI, there is no two-objective UCB: not acq='ucb'")
+            if acq == "ts":
+                raise ValueError("objectives: paths of two objectives are not built: not acq='ts'")
+            if int(polish) > 0:
+                raise ValueError("objectives: EHVI's gradient is not built: no polish with two objectives")
+            if tree:
+                raise ValueError("objectives: EHVI needs the GP's joint posterior: not with a tree surrogate")
+            if shared is None and _cons_setting(constraints):
+                raise ValueError("objectives: constrained EHVI is not built: no constraints with two objectives")
+            if shared is None and _feas_setting(feasibility) is not None:
+                raise ValueError("objectives: EHVI under the failure vote is not built: no feasibility with two "
+                                 "objectives")
         # diversify = D > 0: a round with a GP takes the D best-scoring candidates
         # as a shortlist and picks its `batch` from them with ut_gp_select_batch,
         # each pick conditioned on the picks before it, so that a batch drawn
@@ -958,7 +1052,8 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    constraints=constraints,
                                                                    prune_weighted=prune_weighted,
                                                                    surrogate="forest" if refit else None,
-                                                                   forest_kw=forest_kw)
+                                                                   forest_kw=forest_kw, objectives=objectives,
+                                                                   ref_point=ref_point)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -1424,7 +1519,8 @@ def _shared_model(kw) -> SharedModel:
                        feasibility=kw.get("feasibility", False), constraints=kw.get("constraints"),
                        prune_weighted=kw.get("prune_weighted", False),
                        surrogate="forest" if isinstance(kw.get("surrogate"), str) and kw["surrogate"] == "forest"
-                       else None, forest_kw=kw.get("forest_kw"))
+                       else None, forest_kw=kw.get("forest_kw"), objectives=kw.get("objectives"),
+                       ref_point=kw.get("ref_point"))
 
 
 def _tr_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:

@@ -40,7 +40,8 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                 precision: int = 64, prune_rows: int = 0, diversify: int = 0, feasibility=False,
                 constraints=None, prune_weighted: bool = False, surrogate=None,
                 forest_kw=None, polish: int = 0, polish_pool: Optional[int] = None,
-                trust_region: bool = False, acq: str = "ei", ts_features: int = 1024) -> SearchDriver:
+                trust_region: bool = False, acq: str = "ei", ts_features: int = 1024, objectives=None,
+                ref_point=None, driver_objective=None) -> SearchDriver:
     """Run the bandit for `generations` generations; returns the driver (results,
     best_result, bandit statistics).  With torch.distributed initialised and
     world > 1 the run is SPMD: call it on every rank with the same arguments.
@@ -56,7 +57,20 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
     result (GpuTrustRegion).
     acq="ucb" / "ts": the children's acquisition; "ts" = Thompson sampling, one
     posterior sample path of ts_features random features per batch slot
-    (GpuBatchTechnique)."""
+    (GpuBatchTechnique).
+    objectives=[("time", "min"), (attr, "min" or "max")]: two objectives; the
+    objective function then returns a mapping with "time" and attr, the rounds
+    score by expected hypervolume improvement (SharedModel; ref_point: its
+    reference point in raw units) and the driver keeps the Pareto front
+    (driver.ParetoMinimize, drv.pareto_front()).
+    driver_objective: the driver's objective object when not the default
+    (MinimizeTime, or ParetoMinimize under objectives=)."""
+    if objectives and driver_objective is None:
+        from .driver import ParetoMinimize
+        from .technique import _mo_setting
+        second, sense = _mo_setting(objectives)[1]
+        driver_objective = ParetoMinimize(second, maximize=sense == "max")
+    mo_kw = {"objectives": objectives, "ref_point": ref_point} if objectives else {}
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     meta = pso_ga_de_bandit(bandit_seed=seed, pool=pool, batch=batch, population=population, seed=seed,
@@ -65,14 +79,17 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                             constraints=constraints, prune_weighted=prune_weighted, surrogate=surrogate,
                             forest_kw=forest_kw, polish=polish, polish_pool=polish_pool, acq=acq,
                             **({"ts_features": ts_features} if acq == "ts" else {}),
-                            **({"trust_region": True} if trust_region else {}))
+                            **({"trust_region": True} if trust_region else {}), **mo_kw)
+    if world > 1 and objectives:
+        raise ValueError("objectives: the ranks exchange one measurement per result: two objectives run on one rank")
     if world > 1:
         import torch
-        drv = DistributedSearchDriver(manipulator, meta, parallelism=parallelism, group=group,
+        drv = DistributedSearchDriver(manipulator, meta, objective=driver_objective, parallelism=parallelism,
+                                      group=group,
                                       device=torch.device("cuda", device) if dist.get_backend(group) != "gloo"
                                       else None)
     else:
-        drv = SearchDriver(manipulator, meta, parallelism=parallelism)
+        drv = SearchDriver(manipulator, meta, objective=driver_objective, parallelism=parallelism)
     import time
     t0 = time.perf_counter()
     if n_init:
