@@ -1,6 +1,10 @@
 """The shared device arithmetic (uptune_amd/csrc/ut_core.h), compiled for the
 host with g++, against CPython's repr / hashlib and the oracle's Philox.
-This exercises the exact source the gfx950 kernels compile (CPU, no GPU)."""
+This tests the shared source as compiled for the host (CPU, no GPU).  The
+device build of that source takes its own branches (__umul64hi,
+__double_as_longlong, the power-of-5 tables in device memory, hipcc's
+lowering of the 64-bit divisions) and writes through the LDS byte emitter of
+csrc/hash.hip; tests/test_gpu_repr.py holds it to CPython."""
 import ctypes
 import hashlib
 import math

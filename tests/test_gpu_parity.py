@@ -742,9 +742,11 @@ def hpl_space():
 def _non_cr_log_ints(golden_dir):
     """integers x in [2^22, 2^31) where CPython's math.log(x) is NOT the
     correctly rounded log -- the arguments a correctly rounded device log got
-    wrong in round 1 (tests/golden/make_libm_log_cases.py)"""
-    with open(os.path.join(golden_dir, "libm_log_non_cr.json")) as f:
-        return json.load(f)["ints"]
+    wrong in round 1 (tests/golden/make_libm_log_cases.py); the one reader of the
+    fixture is tests/_repr_cases.py, which tests/test_gpu_repr.py shares"""
+    from _repr_cases import GOLDEN, non_cr_log_ints
+    assert os.path.samefile(golden_dir, GOLDEN)
+    return non_cr_log_ints()
 
 
 def test_hpl_population_de_encode_hash():
