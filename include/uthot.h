@@ -876,7 +876,10 @@ int ut_gp_mo_read(ut_ctx* ctx, int32_t what, double* out_host);
 
 /* ---- selection ---------------------------------------------------------- */
 /* k largest scores, ties -> smallest global index; entries with dup[i]!=0 or
- * NaN score are never selected; missing slots get index -1. */
+ * NaN score are never selected; missing slots get index -1.  out_score of a
+ * missing slot is unspecified (it depends on the route the call takes: the
+ * score of some unselectable entry, or 0.0); read out_score only where
+ * out_idx >= 0.  The same holds for the padded slots of a round's topk_score. */
 int ut_topk(ut_ctx* ctx, const double* score, const uint8_t* dup, int64_t m, int64_t cand_base, int32_t k,
             int64_t* out_idx, double* out_score);
 

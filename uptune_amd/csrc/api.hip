@@ -268,6 +268,8 @@ int ut_ctx_create(int device, uint64_t seed, ut_ctx** out) {
   if (const char* e = getenv("UT_VAR_SPLIT")) c->var_split = atoi(e) != 0;
   if (const char* e = getenv("UT_DE_AOS")) c->de_aos = atoi(e) != 0;
   if (const char* e = getenv("UT_HASH_WG_PER_CU")) c->hash_wg_per_cu = atoi(e);
+  if (const char* e = getenv("UT_TOPK_SELECT")) c->topk_select = atoi(e);
+  if (const char* e = getenv("UT_HASH_WIDE")) c->hash_wide = atoi(e);
   if (const char* e = getenv("UT_CAT_KSTAR")) c->cat_enable = atoi(e) != 0;
   if (const char* e = getenv("UT_FIT_DEFER")) c->fit_defer = atoi(e) != 0;
   if (const char* e = getenv("UT_KSTAR_Q")) c->kstar_q = atoi(e) != 0;

@@ -482,12 +482,195 @@ static int launch_hash_impl(ut_ctx* c, const double* values, int64_t ld, int64_t
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Small-m outer hash, one wave per candidate.  With one lane per candidate a
+// few hundred rows are a handful of waves, each running its row's outer blocks
+// back to back with the word assembly and the message schedule on the chain
+// (~1.5k dependent VALU ops per block): the time is one row's serial chain
+// whatever m is.  Here a wave owns a row and works in slabs of up to 64 blocks:
+//   holes    lane = hole: the hex digests of the holes the slab touches, from
+//            where k_hash<true> reads them (LUT / perm_dig / hs_fresh), to LDS;
+//   phase A  lane = block: the 16 message words from the word table and those
+//            hex words, the 64-word schedule, W[t] + K[t] to LDS;
+//   phase B  the blocks in order, only the round function on the chain (the
+//            lanes all compute the same state), the next block's W + K read
+//            ahead of the rounds.
+// A block touches at most two holes (block_last[b] and the one before it: a
+// hole is 64 bytes and its neighbours are at least 3 bytes away), so the hex
+// register number of a word (slot = hole % 2) names the hole.
+// ---------------------------------------------------------------------------
+constexpr int HW_SLAB = 64;    // outer blocks per slab (one per lane)
+constexpr int HW_WKS = 68;     // LDS words per block: 16-byte writes of 64 lanes at this stride do not conflict
+constexpr int HW_HOLES = 80;   // hex slots per slab (hole starts are >= 67 bytes apart: at most 64 touch 64 blocks)
+constexpr int HW_HXS = 17;     // LDS words per hex slot
+
+// 64 rounds over W[t] + K[t]
+__device__ __forceinline__ void sha256_rounds_wk(uint32_t H[8], const uint4 (&wk)[16]) {
+  uint32_t a = H[0], b = H[1], c = H[2], d = H[3], e = H[4], f = H[5], g = H[6], h = H[7];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const uint32_t w4[4] = {wk[q].x, wk[q].y, wk[q].z, wk[q].w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t S1 = xor3(rotr32(e, 6), rotr32(e, 11), rotr32(e, 25));
+      const uint32_t t1 = (h + w4[r]) + S1 + sha_ch(e, f, g);
+      const uint32_t S0 = xor3(rotr32(a, 2), rotr32(a, 13), rotr32(a, 22));
+      const uint32_t mj = sha_maj(a, b, c);
+      h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
+    }
+  }
+  H[0] += a; H[1] += b; H[2] += c; H[3] += d; H[4] += e; H[5] += f; H[6] += g; H[7] += h;
+}
+
+__global__ __launch_bounds__(HW_SLAB) void k_hash_wide(const DevParam* __restrict__ params,
+                                                       const int32_t* __restrict__ order,
+                                                       const int32_t* __restrict__ order_col,
+                                                       const uint2* __restrict__ words,
+                                                       const int32_t* __restrict__ block_last, int32_t nblocks,
+                                                       int32_t P, const uint4* __restrict__ lut,
+                                                       const double* __restrict__ values, int64_t ld, int64_t m,
+                                                       const uint4* __restrict__ perm_dig,
+                                                       const uint4* __restrict__ fresh, uint32_t* __restrict__ out) {
+  __shared__ uint4 wk4[HW_SLAB * HW_WKS / 4];
+  __shared__ uint32_t hx[HW_HOLES * HW_HXS];
+  const int lane = threadIdx.x;
+  const int64_t i = blockIdx.x;
+  if (i >= m) return;
+  uint32_t H[8];
+  sha256_init(H);
+  for (int32_t b0 = 0; b0 < nblocks; b0 += HW_SLAB) {
+    const int32_t nb = nblocks - b0 < HW_SLAB ? nblocks - b0 : HW_SLAB;
+    // the holes blocks b0 .. b0 + nb - 1 touch lie in [jlo, jhi]
+    int32_t jlo = block_last[b0] - 1;
+    jlo = jlo < 0 ? 0 : jlo;
+    int32_t jhi = block_last[b0 + nb - 1];
+    jhi = jhi >= P ? P - 1 : jhi;
+    __syncthreads();   // the slab before has been read
+    for (int32_t j = jlo + lane; j <= jhi && j - jlo < HW_HOLES; j += HW_SLAB) {
+      const DevParam& pr = params[order[j]];
+      uint32_t X[16];
+      if (pr.hash_mode == HM_PERM) {
+        const uint4* src = perm_dig + 2 * ((int64_t)pr.pslot * m + i);
+        const uint4 a = src[0], c = src[1];
+        const uint32_t D[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+        digest_hex(D, X);
+      } else {
+        const uint4* src = pr.hash_mode == HM_LUT
+                               ? lut + 4 * lut_row(pr, values[(int64_t)order_col[j] * ld + i])
+                               : fresh + 4 * ((int64_t)pr.cslot * m + i);
+        const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+        X[0] = q0.x; X[1] = q0.y; X[2] = q0.z; X[3] = q0.w;
+        X[4] = q1.x; X[5] = q1.y; X[6] = q1.z; X[7] = q1.w;
+        X[8] = q2.x; X[9] = q2.y; X[10] = q2.z; X[11] = q2.w;
+        X[12] = q3.x; X[13] = q3.y; X[14] = q3.z; X[15] = q3.w;
+      }
+#pragma unroll
+      for (int w = 0; w < 16; ++w) hx[(j - jlo) * HW_HXS + w] = X[w];
+    }
+    __syncthreads();
+    // phase A: this lane's block
+    if (lane < nb) {
+      const int32_t blk = b0 + lane;
+      const int32_t last = block_last[blk];
+      const uint2* hw = words + (int64_t)blk * 16;
+      // hex register r (slot r / 16 = hole % 2, word r % 16) of this block
+      auto hexreg = [&](uint32_t r) -> uint32_t {
+        int32_t slot = last - ((last - (int32_t)(r >> 4)) & 1) - jlo;
+        slot = slot < 0 ? 0 : (slot >= HW_HOLES ? HW_HOLES - 1 : slot);   // never fault on a bad table
+        return hx[slot * HW_HXS + (int32_t)(r & 15u)];
+      };
+      uint32_t W[16];
+#pragma unroll
+      for (int w = 0; w < 16; ++w) {
+        const uint2 e = hw[w];
+        uint32_t x = e.x;
+        if (e.y) {
+          const uint32_t lo = (e.y & HW_LO_VALID) ? hexreg(e.y & 31u) : 0u;
+          const uint32_t hi = (e.y & HW_HI_VALID) ? hexreg((e.y >> HW_HI_POS) & 31u) : 0u;
+          const uint64_t cat = ((uint64_t)lo << 32) | hi;
+          x |= (uint32_t)((cat << ((e.y >> HW_SHIFT_POS) & 31u)) >> 32);
+        }
+        W[w] = x;
+      }
+      uint4* row = wk4 + lane * (HW_WKS / 4);
+#pragma unroll
+      for (int t = 0; t < 64; t += 4) {
+        uint32_t o[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int tt = t + r;
+          uint32_t w;
+          if (tt < 16) {
+            w = W[tt];
+          } else {
+            const uint32_t w15 = W[(tt - 15) & 15], w2 = W[(tt - 2) & 15];
+            const uint32_t s0 = xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
+            const uint32_t s1 = xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+            w = W[tt & 15] + s0 + W[(tt - 7) & 15] + s1;
+            W[tt & 15] = w;
+          }
+          o[r] = w + SHA256_K[tt];
+        }
+        row[t / 4] = make_uint4(o[0], o[1], o[2], o[3]);
+      }
+    }
+    __syncthreads();
+    // phase B: the slab's blocks in order; every lane reads the same words
+    uint4 cur[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) cur[q] = wk4[q];
+    for (int32_t bb = 0; bb < nb; ++bb) {
+      const int32_t nx = bb + 1 < nb ? bb + 1 : bb;
+      uint4 nxt[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) nxt[q] = wk4[nx * (HW_WKS / 4) + q];
+      sha256_rounds_wk(H, cur);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) cur[q] = nxt[q];
+    }
+  }
+  if (lane == 0) {
+    uint4* dst = reinterpret_cast<uint4*>(out + i * 8);
+    dst[0] = make_uint4(H[0], H[1], H[2], H[3]);
+    dst[1] = make_uint4(H[4], H[5], H[6], H[7]);
+  }
+}
+
 // up to this many candidates ut_hash computes the inner digests first, all
 // (param, candidate) pairs in parallel, then the outer messages from them
 constexpr int64_t HASH_SMALL_M = 16384;   // R64 0.66 -> 0.34-0.44 ms at 2^12-2^14; HPL-64 at 2^15 was 2% slower
+// up to this many of them the outer messages go one wave per row (k_hash_wide:
+// 64 lanes on one chain win on latency and lose on throughput;
+// profiles/tail_select.json has the table)
+constexpr int64_t HASH_WIDE_M = 1024;   // R64 0.31 -> 0.18 ms up to 512, 0.29 at 1024; 0.47 against 0.31 at 2048
 
 int launch_hash(ut_ctx* c, const double* values, int64_t ld, int64_t m, uint32_t* out) {
   const Space& s = c->space;
+  const int64_t wide_m = c->hash_wide > 1 ? c->hash_wide : HASH_WIDE_M;   // (UT_HASH_WIDE > 1: the limit, to measure it)
+  if (s.n_comp > 0 && m > 0 && m <= HASH_SMALL_M && m <= wide_m && c->hash_wide != 0 && !c->round_gate) {
+    int rc;
+    if ((rc = ensure(c, c->hs_fresh, (size_t)s.n_comp * m * 16))) return rc;
+    const uint32_t* pd = nullptr;
+    if (s.n_perm > 0) {
+      if ((rc = ensure(c, c->perm_dig, (size_t)s.n_perm * (size_t)m * 8))) return rc;
+      hipLaunchKernelGGL(k_perm_digest, dim3(grid1(m, PD_NT)), dim3(PD_NT), 0, c->stream, s.d_params.p,
+                         s.d_perm_params.p, s.n_perm, s.d_perm_bytes.p, s.d_perm_off.p, s.d_perm_offbase.p,
+                         s.d_perm_len.p, values, ld, m, c->perm_dig.p, (const int32_t*)nullptr);
+      UT_LAUNCH_CHECK(c);
+      pd = c->perm_dig.p;
+    }
+    const int64_t want = ((int64_t)s.n_comp * m + HASH_NT - 1) / HASH_NT;
+    const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)c->n_cu * 8);
+    hipLaunchKernelGGL(k_inner_all, dim3(grid), dim3(HASH_NT), 0, c->stream, s.d_params.p, s.d_comp.p, s.n_comp, values,
+                       ld, m, reinterpret_cast<uint4*>(c->hs_fresh.p));
+    UT_LAUNCH_CHECK(c);
+    hipLaunchKernelGGL(k_hash_wide, dim3((unsigned)m), dim3(HW_SLAB), 0, c->stream, s.d_params.p, s.d_order.p,
+                       s.d_order_col.p, reinterpret_cast<const uint2*>(s.d_words.p), s.d_block_last.p,
+                       (int32_t)s.outer_blocks, s.P, reinterpret_cast<const uint4*>(s.d_lut.p), values, ld, m,
+                       reinterpret_cast<const uint4*>(pd), reinterpret_cast<const uint4*>(c->hs_fresh.p), out);
+    UT_LAUNCH_CHECK(c);
+    return 0;
+  }
   if (s.n_comp > 0 && m > 0 && m <= HASH_SMALL_M) {
     const int32_t nw = (s.n_comp + 31) / 32;
     int rc;

@@ -272,6 +272,13 @@ struct ut_ctx {
   // uncapped, -1 capped while a large refit is in flight (hash.hip hash_cap);
   // UT_HASH_WG_PER_CU
   int32_t hash_wg_per_cu = -1;
+  // top-k of raw scores (topk.hip): 1 threshold selection at every size, 0 the
+  // tournament of sorts everywhere, -1 the selection where the tournament needs
+  // more than two launches; UT_TOPK_SELECT
+  int32_t topk_select = -1;
+  // small-m outer hash (hash.hip): 1 one wave per row up to HASH_WIDE_M, 0 the
+  // lane-per-row k_hash, -1 = 1; UT_HASH_WIDE
+  int32_t hash_wide = -1;
   // refit: the next diagonal block factored inside the trailing update
   // (k_chol_update_diag). -1 = from 2048 padded rows on: the fit alone 6.5 ->
   // 5.7 ms at n = 4096, C3 pruned 60.1 -> 59.2 ms; at C2 (n = 1024, the fit
@@ -390,6 +397,8 @@ struct ut_ctx {
   ut::DevBuf<uint8_t> r_inval;      // GA rounds: children whose retries all reproduced a parent
   ut::DevBuf<double> tk_score[2];
   ut::DevBuf<int64_t> tk_idx[2];
+  ut::DevBuf<uint32_t> tk_sel;      // top-k selection: global digit histogram + SelState (topk.hip), zero between kernels
+  ut::DevBuf<uint32_t> tk_wcnt;     // top-k selection: ties of the threshold key per workgroup
   ut::DevBuf<int64_t> r_topk_idx;
   ut::DevBuf<double> tr_box;     // [3][P] trust-region call: half-widths h | box faces lo | hi (propose_tr.hip)
   ut::DevBuf<double> perm_ws;    // [2 * perm_cols + 3 * perm_smax][ld]: GA parents + crossover scratch
