@@ -40,6 +40,13 @@ int set_fit_prio(int32_t on) {
   return set_fit_prio_gemm(on);
 }
 
+// The chain of a fit of up to FIT_CHAIN_MAX_NPAD padded rows: k_gp_prep_rows,
+// the lower-triangle k_gp_kmat, k_trinv_small.  Larger fits keep the kernels
+// they had (C3, n = 4096: with the new head the round measured 0.4 ms of 269
+// longer, with the old one inside the parent's range), as does UT_FIT_LEGACY.
+constexpr int FIT_CHAIN_MAX_NPAD = 2048;
+static bool new_chain(const ut_ctx* c, int32_t npad) { return !c->fit_legacy && npad <= FIT_CHAIN_MAX_NPAD; }
+
 __global__ void k_gp_prep_train(const double* __restrict__ X, int32_t n, int32_t npad, int32_t d,
                                 const double* __restrict__ inv_ell, double* __restrict__ Xs,
                                 double* __restrict__ xnorm) {
@@ -53,6 +60,56 @@ __global__ void k_gp_prep_train(const double* __restrict__ X, int32_t n, int32_t
     s += v * v;
   }
   xnorm[j] = s;
+}
+
+// The same outputs with coalesced traffic: a workgroup takes PREP_ROWS rows in
+// chunks of PREP_KC features, lanes along the features on the way in and out
+// (k_gp_prep_train's thread walks its row alone: 64 strided loads and stores
+// per thread, npad / 256 workgroups, 27 us alone and 139 us beside k_de at
+// n = 1024).  The scaled values pass through LDS, where one thread per row
+// adds their squares in feature order: the norm is the same sequential sum
+// (multiply and add, uncontracted), so the same bits.
+constexpr int PREP_ROWS = 16, PREP_KC = 64;
+
+__global__ __launch_bounds__(256) void k_gp_prep_rows(const double* __restrict__ X, int32_t n, int32_t npad,
+                                                      int32_t d, const double* __restrict__ inv_ell,
+                                                      double* __restrict__ Xs, double* __restrict__ xnorm) {
+  fit_prio();
+  __shared__ double tile[PREP_ROWS][PREP_KC + 1];
+  const int t = threadIdx.x, kk = t & (PREP_KC - 1);
+  const int64_t r0 = (int64_t)blockIdx.x * PREP_ROWS;
+  double s = 0.0;
+  for (int32_t k0 = 0; k0 < d; k0 += PREP_KC) {
+    const int32_t k = k0 + kk;
+#pragma unroll
+    for (int u = 0; u < PREP_ROWS / 4; ++u) {
+      const int rr = 4 * u + (t >> 6);
+      const int64_t j = r0 + rr;
+      if (k < d && j < npad) {
+        const double v = (j < n) ? X[j * d + k] * inv_ell[k] : 0.0;
+        Xs[j * d + k] = v;
+        tile[rr][kk] = v;
+      }
+    }
+    __syncthreads();
+    if (t < PREP_ROWS) {
+      const int32_t kn = min(PREP_KC, d - k0);
+      if (kn == PREP_KC) {  // (unrolled: the LDS reads go out together, the sum stays in order)
+#pragma unroll
+        for (int32_t q = 0; q < PREP_KC; ++q) {
+          const double v = tile[t][q];
+          s += v * v;
+        }
+      } else {
+        for (int32_t q = 0; q < kn; ++q) {
+          const double v = tile[t][q];
+          s += v * v;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (t < PREP_ROWS && r0 + t < npad) xnorm[r0 + t] = s;
 }
 
 // categorical K* operands of the training rows (gp_kstar_tile.h "Categorical K*"):
@@ -151,8 +208,12 @@ __global__ __launch_bounds__(256) void k_gp_ystats(const double* __restrict__ y,
 // the two staging kernels above on buffers other than the fit's (gp_lml.hip)
 int launch_gp_prep_train(ut_ctx* c, const double* X, int32_t n, int32_t npad, int32_t d, const double* inv_ell,
                          double* Xs, double* xnorm) {
-  hipLaunchKernelGGL(k_gp_prep_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, X, n, npad, d, inv_ell, Xs,
-                     xnorm);
+  if (!new_chain(c, npad))
+    hipLaunchKernelGGL(k_gp_prep_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, X, n, npad, d, inv_ell, Xs,
+                       xnorm);
+  else
+    hipLaunchKernelGGL(k_gp_prep_rows, dim3(grid1(npad, PREP_ROWS)), dim3(256), 0, c->stream, X, n, npad, d, inv_ell,
+                       Xs, xnorm);
   UT_LAUNCH_CHECK(c);
   return 0;
 }
@@ -259,7 +320,10 @@ __global__ __launch_bounds__(256) void k_chol_update(double* __restrict__ K, int
 // k_chol_update with the next panel's diagonal block factored in the same
 // launch: the workgroup that updates block (kb + 1, kb + 1) keeps it in LDS
 // and runs k_chol_diag's steps on it while the others update the rest, so the
-// fit's serial chain loses one launch per level (ut_ctx::chol_fuse)
+// fit's serial chain loses one launch per level (ut_ctx::chol_fuse); by default
+// from CHOL_FUSE_MIN padded rows on
+constexpr int CHOL_FUSE_MIN = 1024;
+
 template <bool MERGED>
 __global__ __launch_bounds__(256) void k_chol_update_diag(double* __restrict__ K, double* __restrict__ Li,
                                                           int32_t npad, int32_t kb, int32_t* flag) {
@@ -312,14 +376,23 @@ __global__ __launch_bounds__(256) void k_chol_update_diag(double* __restrict__ K
 }
 
 // K = sf2 exp(-0.5 |xs_i - xs_j|^2) + diag I, 64 x 64 tiles on fp64 MFMA;
-// padded rows/columns (>= n) form an identity block; block rows from rb0 on
+// padded rows/columns (>= n) form an identity block; block rows from rb0 on.
+// lower: blockIdx.x numbers the tiles on and below the diagonal (lower_tile),
+// the diagonal tiles whole (k_chol_diag loads full rows).  A refit reads
+// nothing above them: k_chol_rows / k_chol_update(_diag) take blocks (i, kb),
+// (j, kb) and write (i, j) with kb < j <= i, k_trinv_* take L[o + s .., o ..],
+// k_lml_fit the diagonal, k_fit_read_lower masks the rest, and an append
+// computes the block rows it reads itself.  The blocks above keep whatever
+// the buffer held.
 __global__ __launch_bounds__(256) void k_gp_kmat(const double* __restrict__ Xs, const double* __restrict__ xnorm,
                                                  int32_t n, int32_t npad, int32_t d, double sf2, double diag,
-                                                 double* __restrict__ K, int32_t rb0) {
+                                                 double* __restrict__ K, int32_t rb0, int32_t lower) {
   fit_prio();
   __shared__ double As[16 * 80];
   __shared__ double Bs[16 * 80];
-  const int64_t ib = (int64_t)(blockIdx.y + rb0) * 64, jb = (int64_t)blockIdx.x * 64;
+  int32_t ti = blockIdx.y + rb0, tj = blockIdx.x;
+  if (lower) lower_tile(blockIdx.x, ti, tj);
+  const int64_t ib = (int64_t)ti * 64, jb = (int64_t)tj * 64;
   fd4 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
@@ -527,6 +600,107 @@ __global__ __launch_bounds__(256, 2) void k_trinv_big(const double* __restrict__
       for (int r = 0; r < 4; ++r) {
         const int row = tr + wm * 64 + i * 16 + (lane >> 4) + 4 * r;
         const int col = tc + wn * 64 + j * 16 + (lane & 15);
+        C[(int64_t)row * ldc + col] = sign * acc[i][j][r];
+      }
+}
+
+// The same two products where the launch would be a handful of workgroups
+// (n = 1024: level 512 is 16 workgroups of k_trinv_big, level 256 eight, on
+// 256 CUs; each walks a k range of up to 512 alone): one wave per 32 x 32
+// output tile (2 x 2 v_mfma_f64_16x16x4), a one-wave workgroup, so a level of
+// s rows is (s / 32)^2 workgroups per pair.  Stages of TRS_BK = 32 k through
+// LDS, the next stage's 16 global loads per lane in flight under the current
+// stage's MFMAs.  k runs upward in MFMA groups of 4 from a multiple of 64 and
+// is not split, as in k_trinv_level; the products a tile takes on beyond its
+// own triangle are exact zeros of the triangular operand: the same bits.
+// Every level of a fit of up to FIT_CHAIN_MAX_NPAD padded rows goes here: the
+// stand-alone refit by the workgroup count below which a level does (DESIGN.md,
+// "The refit chain for small training sets") is, at n = 1024, 1.42 ms at 0,
+// 1.37 at 9, 1.26 from 17 on; at n = 2048, 2.48 at 0 and 9, 2.43 at 17, 2.32 at
+// 33, 2.19 from 65 on, which is every level (the largest launch it replaces is
+// 64 workgroups).  ut_ctx::trinv_small_wg sets such a count for the sweep and
+// the tests.
+constexpr int TRS_BM = 32, TRS_BK = 32, TRS_LD = 40;
+
+__global__ __launch_bounds__(64) void k_trinv_small(const double* __restrict__ L, double* __restrict__ Li,
+                                                    double* __restrict__ T, int32_t npad, int32_t s, int32_t phase) {
+  fit_prio();
+  __shared__ double As[TRS_BK * TRS_LD];
+  __shared__ double Bs[TRS_BK * TRS_LD];
+  const int32_t z = blockIdx.z;
+  const int64_t o = (int64_t)z * 2 * s;
+  const int32_t s2 = (int32_t)min((int64_t)s, (int64_t)npad - o - s);  // ragged last pair (multiple of 64)
+  const int32_t tr = blockIdx.y * TRS_BM, tc = blockIdx.x * TRS_BM;
+  if (s2 <= 0 || tr >= s2) return;
+  const double* A;
+  const double* B;
+  int64_t lda, ldb, ldc;
+  int32_t k_lo, k_hi;
+  double* C;
+  double sign;
+  if (phase == 0) {
+    A = L + (o + s) * npad + o; lda = npad;
+    B = Li + o * npad + o; ldb = npad;
+    k_lo = tc & ~63; k_hi = s;
+    C = T + (int64_t)z * s * s; ldc = s; sign = 1.0;
+  } else {
+    A = Li + (o + s) * npad + (o + s); lda = npad;
+    B = T + (int64_t)z * s * s; ldb = s;
+    k_lo = 0; k_hi = min((tr & ~63) + 64, s2);
+    C = Li + (o + s) * npad + o; ldc = npad; sign = -1.0;
+  }
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  const int lane = threadIdx.x;
+  // lane's share of a stage: A rows (lane >> 5) + 2 u at k = lane & 31, B rows k = (lane >> 5) + 2 u at column lane & 31
+  const int h = lane >> 5, q = lane & 31;
+  const double* ap = A + (int64_t)(tr + h) * lda + q;
+  const double* bp = B + (int64_t)h * ldb + tc + q;
+  double ar[16], br[16];
+  auto fetch = [&](int32_t k0) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      ar[u] = ap[(int64_t)(2 * u) * lda + k0];
+      br[u] = bp[(int64_t)(k0 + 2 * u) * ldb];
+    }
+  };
+  d4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+  fetch(k_lo);
+  for (int32_t k0 = k_lo; k0 < k_hi; k0 += TRS_BK) {
+    // As[k][row], Bs[k][col]
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      As[q * TRS_LD + h + 2 * u] = ar[u];
+      Bs[(h + 2 * u) * TRS_LD + q] = br[u];
+    }
+    __syncthreads();
+    if (k0 + TRS_BK < k_hi) fetch(k0 + TRS_BK);
+#pragma unroll
+    for (int ks = 0; ks < TRS_BK / 4; ++ks) {
+      const int kr = ks * 4 + (lane >> 4);
+      double af[2], bf[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) af[i] = As[kr * TRS_LD + i * 16 + (lane & 15)];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bf[j] = Bs[kr * TRS_LD + j * 16 + (lane & 15)];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = tr + i * 16 + (lane >> 4) + 4 * r;
+        const int col = tc + j * 16 + (lane & 15);
         C[(int64_t)row * ldc + col] = sign * acc[i][j][r];
       }
 }
@@ -761,8 +935,7 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
                              hipMemcpyHostToDevice, c->stream));
     UT_HIP(c, hipMemcpyAsync(dy, hy, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     if (!app) UT_HIP(c, hipMemsetAsync(c->gp_flag.p, 0, sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(k_gp_prep_train, dim3(grid1(npad, 256)), dim3(256), 0, c->stream, dX, n, npad, d,
-                       c->gp_inv_ell.p, c->gp_Xs.p, c->gp_xnorm.p);
+    if ((rc = launch_gp_prep_train(c, dX, n, npad, d, c->gp_inv_ell.p, c->gp_Xs.p, c->gp_xnorm.p))) return rc;
     // the candidate side of K* needs only the scaled inputs: fp64 scoring starts
     // its K* here while the factorisation below is still running
     if ((rc = launch_xs_t(c, c->gp_Xs.p, npad, d, kstar_dpad(d), c->gp_XsT.p))) return rc;
@@ -783,7 +956,7 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
     // recomputed whole)
     const int32_t b0 = n0 / NB, b1 = (n - 1) / NB;
     hipLaunchKernelGGL(k_gp_kmat, dim3(b1 + 1, b1 - b0 + 1), dim3(256), 0, c->stream, c->gp_Xs.p, c->gp_xnorm.p, n,
-                       npad, d, sf2, diag, c->gp_K.p, b0);
+                       npad, d, sf2, diag, c->gp_K.p, b0, 0);
     hipLaunchKernelGGL(k_gp_ystats, dim3(1), dim3(256), 0, c->stream, dy, n, npad, c->gp_y.p, c->gp_stats.p);
     double* Et = c->gp_T.p + (int64_t)NB * npad;
     for (int32_t b = b0; b <= b1; ++b) {
@@ -811,13 +984,18 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
     }
     UT_LAUNCH_CHECK(c);
   } else {
-    hipLaunchKernelGGL(k_gp_kmat, dim3(npad / 64, npad / 64), dim3(256), 0, c->stream, c->gp_Xs.p,
-                       c->gp_xnorm.p, n, npad, d, sf2, diag, c->gp_K.p, 0);
+    const int32_t nbk = npad / 64;
+    if (!new_chain(c, npad))
+      hipLaunchKernelGGL(k_gp_kmat, dim3(nbk, nbk), dim3(256), 0, c->stream, c->gp_Xs.p, c->gp_xnorm.p, n, npad, d,
+                         sf2, diag, c->gp_K.p, 0, 0);
+    else
+      hipLaunchKernelGGL(k_gp_kmat, dim3(nbk * (nbk + 1) / 2), dim3(256), 0, c->stream, c->gp_Xs.p, c->gp_xnorm.p, n,
+                         npad, d, sf2, diag, c->gp_K.p, 0, 1);
     hipLaunchKernelGGL(k_gp_ystats, dim3(1), dim3(256), 0, c->stream, dy, n, npad, c->gp_y.p, c->gp_stats.p);
     UT_LAUNCH_CHECK(c);
     const int32_t nb = npad / NB;
     UT_HIP(c, hipMemsetAsync(c->gp_Linv.p, 0, sizeof(double) * npad * npad, c->stream));
-    const bool fuse = c->chol_fuse > 0 || (c->chol_fuse < 0 && npad >= 2048);
+    const bool fuse = c->chol_fuse > 0 || (c->chol_fuse < 0 && npad >= (c->fit_legacy ? 2048 : CHOL_FUSE_MIN));
     for (int32_t kb = 0; kb < nb; ++kb) {
       // (fused: diagonal blocks after the first come from the previous update)
       if (!fuse || kb == 0)
@@ -836,7 +1014,16 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
     // off-diagonal blocks of L^-1 by recursive doubling (diagonal blocks came from k_chol_diag)
     for (int32_t lv = NB; lv < npad; lv *= 2) {
       const int32_t pairs = (int32_t)((npad - lv + 2 * lv - 1) / (2 * lv));
-      if (c->trinv_big && lv >= TRB_MIN) {
+      const bool big = c->trinv_big && lv >= TRB_MIN;
+      // the one-wave tiles (with trinv_small_wg set: where the launch has fewer workgroups than that)
+      const int64_t wgs = (int64_t)(big ? lv / TRB_BM : lv / 64) * (big ? lv / TRB_BM : lv / 64) * pairs;
+      if (new_chain(c, npad) && (c->trinv_small_wg < 0 || wgs < c->trinv_small_wg)) {
+        const dim3 gs(lv / TRS_BM, lv / TRS_BM, pairs);
+        hipLaunchKernelGGL(k_trinv_small, gs, dim3(64), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 0);
+        hipLaunchKernelGGL(k_trinv_small, gs, dim3(64), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 1);
+        continue;
+      }
+      if (big) {
         // k_trinv_big's tiles: every pair's sizes are multiples of 128
         UT_CHECK(c, npad % TRB_BM == 0 && lv % TRB_BM == 0, UT_EINVAL, "gp_fit: npad not a multiple of 128");
         const dim3 gb(lv / TRB_BM, lv / TRB_BM, pairs);

@@ -280,9 +280,11 @@ struct ut_ctx {
   // lane-per-row k_hash, -1 = 1; UT_HASH_WIDE
   int32_t hash_wide = -1;
   // refit: the next diagonal block factored inside the trailing update
-  // (k_chol_update_diag). -1 = from 2048 padded rows on: the fit alone 6.5 ->
-  // 5.7 ms at n = 4096, C3 pruned 60.1 -> 59.2 ms; at C2 (n = 1024, the fit
-  // beside K*) the heavier update workgroups cost the round 0.25 ms. UT_CHOL_FUSE
+  // (k_chol_update_diag). -1 = from 1024 padded rows on: the fit alone 6.5 ->
+  // 5.7 ms at n = 4096, 1.26 -> 1.11 ms at n = 1024, where the C2 round now
+  // waits for the refit and not for K* (2.87 -> 2.73 ms fused; when the round
+  // was 26 ms and the fit ran beside a full K*, fusing cost it 0.25 ms).
+  // Smaller fits are not measured and stay unfused. UT_CHOL_FUSE
   int32_t chol_fuse = -1;
   // L^-1 levels of 256 rows and more on k_trinv_big (128 x 128 tiles, glds
   // ring) instead of k_trinv_level (64 x 64 tiles, plain loads); UT_TRINV_BIG
@@ -290,6 +292,16 @@ struct ut_ctx {
   // the diagonal blocks' inverse solved inside the Cholesky column loop
   // (gp_tiles.h chol_diag_core<true>); UT_CHOL_MERGED
   int32_t chol_merged = 1;
+  // L^-1 levels on k_trinv_small (one wave per 32 x 32 tile) instead of the two
+  // kernels above, in fits of up to 2048 padded rows (gp_fit.hip new_chain):
+  // -1 every level, otherwise the levels whose launch would have fewer
+  // workgroups than this (0 none); UT_TRINV_SMALL_WG
+  int32_t trinv_small_wg = -1;
+  // 1: the refit chain as it was before the coalesced k_gp_prep_rows, the
+  // lower-triangle k_gp_kmat, k_trinv_small and the fused Cholesky from 1024
+  // rows (-1 above = from 2048): the bitwise reference of
+  // tests/test_gpu_fit_chain.py; UT_FIT_LEGACY
+  int32_t fit_legacy = 0;
 
   // history set
   ut::DevBuf<uint32_t> hist_keys;   // [cap][8]
