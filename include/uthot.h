@@ -1089,6 +1089,59 @@ int ut_forest_leaf_var(ut_ctx* ctx, const double* var_host, int64_t n_nodes);
  * per call, for measurements). */
 int ut_forest_score(ut_ctx* ctx, const double* features, int64_t ld, int64_t m, int32_t n_features,
                     const uint8_t* dup, const ut_acq* acq, double f_best, double* mu, double* var, double* score);
+/* ut_forest_fit: grow the averaged ensemble on the device and load it, in place
+ * of a host fit followed by ut_forest_set + ut_forest_leaf_var (the reference
+ * trains its models on the host: src/multi_stage.py:8-22,
+ * plugins/xgbregressor.py:50-63).  A histogram random forest for regression in
+ * which every sum is an integer, so the trees depend on the data, the
+ * parameters and the context's seed alone, not on the order of any atomic:
+ *   X [n][d] row-major, the features ut_encode_features writes; y [n] finite.
+ *   code = clamp(floor((float)x * 256), 0, 255), NaN -> 0: the resolution is
+ *     1/256 of a parameter's range.  A split "code <= b" is stored as
+ *     threshold (b + 1) / 256 under UT_SPLIT_LT with default_left = 1, which
+ *     sends every x, in [0, 1] or not, where its code went.
+ *   q = (int32) nearbyint(clamp((y - y_shift) / y_scale, -32, 32) * 65536);
+ *     per node W = sum w, Q1 = sum w q, Q2 = sum w q^2, min q, max q.
+ *   bootstrap: tree t draws n rows with replacement; draws 4b .. 4b + 3 are the
+ *     words of draw(seed, b, stream t, round_, OP_RF = 8), row = umulhi32(word, n);
+ *     bootstrap = 0: every weight is 1.
+ *   feature j is eligible at node k (index within the tree) iff feature_frac >= 1
+ *     or (double)word * 2^-32 < feature_frac, word (j & 3) of
+ *     draw(seed, (k << 32) | (j >> 2), stream 0x10000 | t, round_, OP_RF).
+ *   nodes are numbered breadth first, a level's nodes visited in index order,
+ *     each split taking the next two indices (left, right).  A node is a leaf
+ *     iff W < 2 min_leaf, its depth is max_depth, all its q are equal, or no
+ *     eligible (j, b <= 254) leaves W_L >= min_leaf and W_R >= min_leaf; else
+ *     it takes the largest s = S_L S_L / W_L + S_R S_R / W_R (fp64: two
+ *     products, two quotients, one sum, nothing fused), ties to the smaller j,
+ *     then the smaller b.
+ *   every record's value = y_shift + y_scale * ((Q1 / W) / 65536); a leaf has
+ *     feature = left = right = -1, default_left = 0 and, in its threshold
+ *     field, the variance y_scale^2 * (max(Q2 / W - (Q1 / W)^2, 0) / 2^32).
+ * Trees are contiguous and in order, child indices global; base 0, scale 1,
+ * div = n_trees, rule LT.  UT_EINVAL for n outside [1, 16384], d outside
+ * [1, 4096], a parameter outside its range below, a non-finite y or a NULL
+ * pointer; that, and a failed allocation (UT_ENOMEM), leave the loaded ensemble
+ * as it was.  Enqueued on the context's stream; the host reads one word back
+ * per level of the trees and two at the end.  The levels are bounded by
+ * min(max_depth or n, n / min_leaf + 1) on the host. */
+typedef struct ut_forest_fit_params {
+  int32_t n_trees;        /* 1..256 */
+  int32_t min_leaf;       /* >= 1 */
+  int32_t max_depth;      /* 0 = unlimited, else 1..n */
+  int32_t bootstrap;      /* 0 | 1 */
+  double  feature_frac;   /* (0, 1] */
+  double  y_shift, y_scale;   /* y_scale > 0 */
+  uint32_t round_;        /* < 2^24 */
+} ut_forest_fit_params;
+int ut_forest_fit(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
+                  const ut_forest_fit_params* params);
+/* The loaded ensemble, however it was loaded, as the device holds it (a leaf's
+ * threshold field is its variance): *n_trees and *n_nodes always; with
+ * roots_host [n_trees] and nodes_host [cap_nodes] both given, the records too
+ * (cap_nodes < *n_nodes is UT_EINVAL).  Waits for the stream. */
+int ut_forest_get(ut_ctx* ctx, int32_t* roots_host, ut_tree_node* nodes_host, int64_t cap_nodes,
+                  int32_t* n_trees, int64_t* n_nodes);
 
 /* ---- multi-GPU exchange over RCCL -------------
  * One process per GPU, one communicator per context.  Rank r scores the

@@ -49,6 +49,12 @@ class TreeNode(C.Structure):
 UT_SPLIT_LE, UT_SPLIT_LT = 0, 1
 
 
+class ForestFitParams(C.Structure):
+    _fields_ = [("n_trees", C.c_int32), ("min_leaf", C.c_int32), ("max_depth", C.c_int32), ("bootstrap", C.c_int32),
+                ("feature_frac", C.c_double), ("y_shift", C.c_double), ("y_scale", C.c_double),
+                ("round_", C.c_uint32)]
+
+
 class DeParams(C.Structure):
     _fields_ = [("cr", C.c_double), ("n_cross", C.c_int32), ("information_sharing", C.c_int32),
                 ("best", C.c_void_p)]
@@ -153,6 +159,8 @@ SIGNATURES = {
     "ut_forest_predict": (C.c_int, [P, P, I64, I64, I32, P, D, P, P]),
     "ut_forest_leaf_var": (C.c_int, [P, P, I64]),
     "ut_forest_score": (C.c_int, [P, P, I64, I64, I32, P, P, D, P, P, P]),
+    "ut_forest_fit": (C.c_int, [P, P, P, I32, I32, C.POINTER(ForestFitParams)]),
+    "ut_forest_get": (C.c_int, [P, P, P, I64, C.POINTER(I32), C.POINTER(I64)]),
     "ut_gp_score": (C.c_int, [P, P, I64, I64, C.POINTER(Acq), P, P, P, P]),
     "ut_gp_score_values": (C.c_int, [P, P, I64, I64, C.POINTER(Acq), P, P, P, P]),
     "ut_gp_set_precision": (C.c_int, [P, I32]),

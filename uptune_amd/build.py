@@ -26,7 +26,7 @@ HOSTLIB = os.path.join(HERE, "libuthot_hostcheck.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("UT_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["api.hip", "propose.hip", "propose_tr.hip", "hash.hip", "dedup.hip", "gp_fit.hip", "gp_score.hip", "gp_prune.hip", "gp_gemm.hip", "gp_i8.hip", "gp_kq.hip", "gp_lml.hip", "gp_lml_grad.hip", "gp_batch.hip", "gp_polish.hip", "gp_feas.hip", "gp_cons.hip", "gp_mo.hip", "gp_kstar_sums.hip", "gp_ts.hip", "topk.hip", "forest.hip", "forest_score.hip", "comm.hip"]
+SOURCES = ["api.hip", "propose.hip", "propose_tr.hip", "hash.hip", "dedup.hip", "gp_fit.hip", "gp_score.hip", "gp_prune.hip", "gp_gemm.hip", "gp_i8.hip", "gp_kq.hip", "gp_lml.hip", "gp_lml_grad.hip", "gp_batch.hip", "gp_polish.hip", "gp_feas.hip", "gp_cons.hip", "gp_mo.hip", "gp_kstar_sums.hip", "gp_ts.hip", "topk.hip", "forest.hip", "forest_score.hip", "forest_fit.hip", "comm.hip"]
 HEADERS = ["ut_core.h", "ut_internal.h", "gp_i8_plan.h", "gp_tiles.h", "gp_post.h", "gp_kstar_tile.h", "ut_param.h", "ut_perm.h", "ryu_tables.h", "libm_log_data.h", os.path.join("..", "..", "include", "uthot.h")]
 
 # RCCL for the multi-GPU exchange (comm.hip); the soname (librccl.so.1) is the
@@ -39,6 +39,10 @@ HIP_FLAGS = [
     "-ffp-contract=off",
     "-Wno-unused-result",
 ]
+
+# per-source additions: forest_fit.hip is compiled with fp32 pairs kept out of
+# the packed-math instructions
+EXTRA_FLAGS = {"forest_fit.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _mtime(p: str) -> float:
@@ -61,7 +65,7 @@ def _compile(src: str, force: bool) -> str:
     newest_dep = max([_mtime(srcp)] + [_mtime(os.path.join(CSRC, h)) for h in HEADERS])
     if not force and _mtime(obj) > newest_dep:
         return obj
-    cmd = [HIPCC, *HIP_FLAGS, "-c", srcp, "-o", obj]
+    cmd = [HIPCC, *HIP_FLAGS, *EXTRA_FLAGS.get(src, []), "-c", srcp, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")

@@ -294,6 +294,7 @@ int ut_ctx_destroy(ut_ctx* c) {
   if (c->cs_host) hipHostFree(c->cs_host);
   if (c->mo_host) hipHostFree(c->mo_host);
   if (c->flag_host) hipHostFree(c->flag_host);
+  if (c->rf_host) hipHostFree(c->rf_host);
   if (c->lml_host) hipHostFree(c->lml_host);
   for (hipStream_t st : {c->own_stream, c->side, c->fit_stream})
     if (st) hipStreamDestroy(st);

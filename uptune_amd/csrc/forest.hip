@@ -51,6 +51,18 @@ __global__ __launch_bounds__(256) void k_forest(const ut_tree_node* __restrict__
   if (score) score[i] = (dup && dup[i]) ? -1.0 / 0.0 : sign * p;
 }
 
+// the records of an ensemble that ut_forest_fit grew live on the device alone
+int forest_host_fetch(ut_ctx* c) {
+  if (c->forest_host_valid) return 0;
+  std::vector<ut_tree_node> recs((size_t)c->forest_n_nodes);
+  UT_HIP(c, hipSetDevice(c->device));
+  UT_HIP(c, ut::sync_all(c));
+  UT_HIP(c, hipMemcpy(recs.data(), c->forest_nodes.p, sizeof(ut_tree_node) * recs.size(), hipMemcpyDeviceToHost));
+  c->forest_host.swap(recs);
+  c->forest_host_valid = true;
+  return 0;
+}
+
 }  // namespace ut
 
 extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_host, int64_t n_nodes,
@@ -83,6 +95,8 @@ extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_ho
   UT_HIP(c, c->forest_roots.alloc((size_t)n_trees));
   UT_HIP(c, hipMemcpy(c->forest_nodes.p, recs.data(), sizeof(ut_tree_node) * n_nodes, hipMemcpyHostToDevice));
   c->forest_host.swap(recs);
+  c->forest_host_valid = true;
+  c->forest_n_nodes = n_nodes;
   UT_HIP(c, hipMemcpy(c->forest_roots.p, roots_host, sizeof(int32_t) * n_trees, hipMemcpyHostToDevice));
   c->forest_trees = n_trees;
   c->forest_rule = rule;
@@ -97,6 +111,7 @@ extern "C" int ut_forest_leaf_var(ut_ctx* c, const double* var_host, int64_t n_n
   if (!c) return UT_EINVAL;
   UT_CHECK(c, c->forest_trees > 0, UT_EINVAL, "forest_leaf_var: call ut_forest_set first");
   UT_CHECK(c, var_host != nullptr, UT_EINVAL, "forest_leaf_var: var is NULL");
+  if (int e = ut::forest_host_fetch(c)) return e;
   UT_CHECK(c, n_nodes == (int64_t)c->forest_host.size(), UT_EINVAL,
            "forest_leaf_var: " + std::to_string(n_nodes) + " values for the " +
                std::to_string(c->forest_host.size()) + " nodes loaded");
@@ -110,6 +125,23 @@ extern "C" int ut_forest_leaf_var(ut_ctx* c, const double* var_host, int64_t n_n
   UT_HIP(c, ut::sync_all(c));   // a scoring kernel still queued reads the old records
   UT_HIP(c, hipMemcpy(c->forest_nodes.p, c->forest_host.data(), sizeof(ut_tree_node) * n_nodes,
                       hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int ut_forest_get(ut_ctx* c, int32_t* roots_host, ut_tree_node* nodes_host, int64_t cap_nodes,
+                             int32_t* n_trees, int64_t* n_nodes) {
+  if (!c) return UT_EINVAL;
+  UT_CHECK(c, c->forest_trees > 0, UT_EINVAL, "forest_get: no ensemble is loaded");
+  if (n_trees) *n_trees = c->forest_trees;
+  if (n_nodes) *n_nodes = c->forest_n_nodes;
+  if (!roots_host && !nodes_host) return 0;
+  UT_CHECK(c, roots_host && nodes_host, UT_EINVAL, "forest_get: roots and nodes go together");
+  UT_CHECK(c, cap_nodes >= c->forest_n_nodes, UT_EINVAL,
+           "forest_get: room for " + std::to_string(cap_nodes) + " of the " + std::to_string(c->forest_n_nodes) +
+               " nodes loaded");
+  if (int e = ut::forest_host_fetch(c)) return e;
+  std::copy(c->forest_host.begin(), c->forest_host.end(), nodes_host);
+  UT_HIP(c, hipMemcpy(roots_host, c->forest_roots.p, sizeof(int32_t) * c->forest_trees, hipMemcpyDeviceToHost));
   return 0;
 }
 

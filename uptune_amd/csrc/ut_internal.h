@@ -191,6 +191,24 @@ struct KstDesc {
   const uint8_t* mask_of(const uint8_t* kmask) const { return masked ? kmask : nullptr; }
 };
 
+// forest_fit.hip: what a growing tree keeps per node beside its record -- its
+// slice of the tree's row list and the integer sums over it
+struct RfState {
+  int32_t start, count;   // rows [start, start + count) of the level's row list
+  uint32_t W;             // sum w
+  int32_t depth;
+  int64_t Q1;             // sum w q
+  uint64_t Q2;            // sum w q^2
+  int32_t qmin, qmax;
+  int32_t closed;         // a leaf by W, depth or constant q: its record is written
+  int32_t bin;            // the split's bin once k_rf_split has chosen one
+};
+// ... and the best split of one (node, feature block): s < 0 = none
+struct RfCand {
+  double s;
+  int32_t j, b;
+};
+
 }  // namespace ut
 
 // Every device array of a context is a DevBuf: a member here, of its Space or
@@ -478,6 +496,21 @@ struct ut_ctx {
   // the loaded records as the device holds them: every leaf's threshold field
   // is its variance (0 until ut_forest_leaf_var; forest_score.hip reads it)
   std::vector<ut_tree_node> forest_host;
+  // ut_forest_fit leaves the records on the device only: the host copy is
+  // fetched by whoever needs it (forest_host_fetch)
+  bool forest_host_valid = false;
+  int64_t forest_n_nodes = 0;
+  // the fit's scratch (forest_fit.hip), T trees, n rows, d features
+  ut::DevBuf<double> rf_X, rf_y;         // staged X [n][d], y [n]
+  ut::DevBuf<uint8_t> rf_rm, rf_fm;      // bin codes, row-major [n][d_pad] and feature-major [d][n_pad]
+  ut::DevBuf<int32_t> rf_q;              // [n] fixed-point targets
+  ut::DevBuf<uint32_t> rf_w;             // [T][n] bootstrap weights
+  ut::DevBuf<int32_t> rf_rows;           // [2][T][n] every tree's row list, one copy per level parity
+  ut::DevBuf<ut::RfState> rf_state;      // [T][cap] the growing trees' per-node sums
+  ut::DevBuf<ut_tree_node> rf_tnodes;    // [T][cap] their records, child indices within the tree
+  ut::DevBuf<ut::RfCand> rf_cand;        // [T][width][blocks] the level's best split per feature block
+  ut::DevBuf<int32_t> rf_ctl;            // total, max feature | level widths | per tree: level ranges, size
+  int32_t* rf_host = nullptr;            // pinned [2]: the one word read back per level
 
   // multi-GPU exchange (comm.hip): the RCCL communicator of this context's
   // rank and the packed top-k records of the all-gather / merge
@@ -708,6 +741,8 @@ int dalloc(ut_ctx* c, DevBuf<T>& b, size_t n) {
 }
 
 void mark(ut_ctx* c, const char* name);
+// forest.hip: c->forest_host holds the loaded records (copied from the device after ut_forest_fit)
+int forest_host_fetch(ut_ctx* c);
 int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h);
 int gp_wait_fit(ut_ctx* c);
 int gp_fit_flush(ut_ctx* c);

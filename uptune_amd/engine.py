@@ -773,6 +773,39 @@ class BatchEngine:
             lv = np.ascontiguousarray(f.leaf_var, dtype=np.float64)
             L.check(self.ctx, self.lib.ut_forest_leaf_var(self.ctx, lv.ctypes.data, lv.size), "ut_forest_leaf_var")
 
+    def forest_fit(self, X, y, n_trees: int = 64, min_leaf: int = 3, max_depth: int = 0, bootstrap: bool = True,
+                   feature_frac: float = 1.0, seed_round: int = 0):
+        """ut_forest_fit: grow the random forest of rows X [n][d] (features as
+        encode() writes them) and targets y [n] on the device and load it, as
+        forest_set of a host fit with its leaf variances would.  The targets are
+        quantised about mean(y) in units of std(y) / 65536 (1 for a constant
+        y); seed_round separates the draws of successive fits of one context."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if X.ndim != 2 or y.shape != (X.shape[0],):
+            raise ValueError("forest_fit: X [n][d] and y [n]")
+        finite = y.size > 0 and bool(np.all(np.isfinite(y)))
+        std = float(np.std(y)) if finite else 1.0
+        par = L.ForestFitParams(int(n_trees), int(min_leaf), int(max_depth), int(bool(bootstrap)),
+                                float(feature_frac), float(np.mean(y)) if finite else 0.0,
+                                std if std > 0.0 and np.isfinite(std) else 1.0, int(seed_round))
+        L.check(self.ctx, self.lib.ut_forest_fit(self.ctx, X.ctypes.data, y.ctypes.data, X.shape[0], X.shape[1],
+                                                 C.byref(par)), "ut_forest_fit")
+        self.forest = "device"
+
+    def forest_get(self):
+        """ut_forest_get: the loaded ensemble as the device holds it -> (roots
+        [T] int32, nodes [N] records of forest.NODE_DTYPE; a leaf's threshold
+        is its variance)"""
+        from .forest import NODE_DTYPE
+        nt, nn = C.c_int32(0), C.c_int64(0)
+        L.check(self.ctx, self.lib.ut_forest_get(self.ctx, None, None, 0, C.byref(nt), C.byref(nn)), "ut_forest_get")
+        roots = np.zeros(nt.value, dtype=np.int32)
+        nodes = np.zeros(nn.value, dtype=NODE_DTYPE)
+        L.check(self.ctx, self.lib.ut_forest_get(self.ctx, roots.ctypes.data, nodes.ctypes.data, nodes.size,
+                                                 C.byref(nt), C.byref(nn)), "ut_forest_get")
+        return roots, nodes
+
     def forest_predict(self, feat: torch.Tensor, m: Optional[int] = None, dup: Optional[torch.Tensor] = None,
                        sign: float = -1.0):
         """-> (pred [m], score [m] = sign * pred, -inf on duplicates)"""

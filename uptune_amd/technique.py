@@ -277,7 +277,7 @@ class SharedModel:
                  engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  surrogate: Optional[str] = None, forest_kw: Optional[Dict[str, Any]] = None,
-                 objectives=None, ref_point=None):
+                 objectives=None, ref_point=None, forest_fit: str = "host"):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -353,6 +353,21 @@ class SharedModel:
             raise ValueError("feasibility and constraints weight the GP's EI: not with a tree surrogate")
         self.surrogate = surrogate
         self.forest_kw = dict(forest_kw or {})
+        # forest_fit: "host" = the sklearn fit above; "device" = the forest is
+        # grown by the engine (engine.forest_fit, csrc/forest_fit.hip: 256-bin
+        # histogram trees, bootstrap and feature draws from the context's seed
+        # and the fit counter, so SPMD replicas agree) and sklearn is never
+        # imported.  forest_kw then takes sklearn's names for what the device
+        # fit has: n_estimators, min_samples_leaf, max_depth (None = unlimited),
+        # bootstrap, max_features (a fraction in (0, 1]).  fit_seconds is the
+        # host time of the engine call.
+        if forest_fit not in ("host", "device"):
+            raise ValueError("forest_fit: 'host' or 'device'")
+        self.forest_fit = forest_fit
+        if forest_fit == "device":
+            if surrogate != "forest":
+                raise ValueError("forest_fit='device' belongs to surrogate='forest'")
+            self._device_forest_kw()
         # objectives: [("time", "min"), (attr, "min" or "max")] -- a second
         # measurement every result carries (accuracy, energy, size, confidence)
         # is minimised (or maximised) beside the time, with no trade-off fixed
@@ -583,19 +598,42 @@ class SharedModel:
             return float(ndtri((r + 0.5) / (len(y) + 1)))
         return float(t)
 
+    def _device_forest_kw(self) -> Dict[str, Any]:
+        """forest_kw as engine.forest_fit's arguments (forest_fit="device")"""
+        names = {"n_estimators": "n_trees", "min_samples_leaf": "min_leaf", "max_depth": "max_depth",
+                 "bootstrap": "bootstrap", "max_features": "feature_frac"}
+        unknown = sorted(set(self.forest_kw) - set(names))
+        if unknown:
+            raise ValueError("forest_kw with forest_fit='device': %s not among %s" % (unknown, sorted(names)))
+        kw = {names[k]: v for k, v in self.forest_kw.items()}
+        if kw.get("max_depth", 0) is None:
+            kw["max_depth"] = 0
+        frac = kw.get("feature_frac", 1.0)
+        if isinstance(frac, bool) or not isinstance(frac, (int, float)) or not 0.0 < frac <= 1.0:
+            raise ValueError("forest_kw max_features with forest_fit='device': a fraction in (0, 1]")
+        return kw
+
     def _fit_forest(self, rows, ids) -> bool:
         """surrogate="forest": refit the random forest iff the usable results changed"""
         import time
 
-        from sklearn.ensemble import RandomForestRegressor
-
-        from .forest import from_sklearn
         key = (len(rows), ids[-1])
         if key == self._fit_key:
             return True
         self._gather(rows, ids)
         n = self._n
         y = self._transform(self._ya[:n])
+        if self.forest_fit == "device":
+            t0 = time.perf_counter()
+            self.engine.forest_fit(self._Xa[:n], y, seed_round=self.fits % (1 << 24), **self._device_forest_kw())
+            self.fit_seconds += time.perf_counter() - t0
+            self.f_best = float(np.min(y))
+            self._fit_key = key
+            self.fits += 1
+            return True
+        from sklearn.ensemble import RandomForestRegressor
+
+        from .forest import from_sklearn
         kw = dict(n_estimators=64, min_samples_leaf=3, random_state=self.seed)
         kw.update(self.forest_kw)
         t0 = time.perf_counter()
@@ -909,7 +947,8 @@ class GpuBatchTechnique(SearchTechnique):
                  prune_rows: int = 0, precision: int = 64, y_transform: Optional[str] = None, diversify: int = 0,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  forest_kw: Optional[Dict[str, Any]] = None, polish: int = 0, polish_pool: Optional[int] = None,
-                 ts_features: int = 1024, objectives=None, ref_point=None, *pargs, **kwargs):
+                 ts_features: int = 1024, objectives=None, ref_point=None, forest_fit: str = "host",
+                 *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
         # surrogate="forest" (SharedModel): a random forest refitted from the
         # driver's results, scored by EI / UCB on its mean and variance over
@@ -1053,7 +1092,7 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    prune_weighted=prune_weighted,
                                                                    surrogate="forest" if refit else None,
                                                                    forest_kw=forest_kw, objectives=objectives,
-                                                                   ref_point=ref_point)
+                                                                   ref_point=ref_point, forest_fit=forest_fit)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -1520,7 +1559,7 @@ def _shared_model(kw) -> SharedModel:
                        prune_weighted=kw.get("prune_weighted", False),
                        surrogate="forest" if isinstance(kw.get("surrogate"), str) and kw["surrogate"] == "forest"
                        else None, forest_kw=kw.get("forest_kw"), objectives=kw.get("objectives"),
-                       ref_point=kw.get("ref_point"))
+                       ref_point=kw.get("ref_point"), forest_fit=kw.get("forest_fit", "host"))
 
 
 def _tr_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:
