@@ -1143,6 +1143,71 @@ int ut_forest_fit(ut_ctx* ctx, const double* X_host, const double* y_host, int32
 int ut_forest_get(ut_ctx* ctx, int32_t* roots_host, ut_tree_node* nodes_host, int64_t cap_nodes,
                   int32_t* n_trees, int64_t* n_nodes);
 
+/* ---- TPE surrogate (tpe.hip) ---------------------------------------------
+ * The Tree-structured Parzen Estimator of Bergstra et al. 2011 (Hyperopt,
+ * Optuna): the results are split into a good and a bad set, each feature gets
+ * one density per set, and a candidate's score is sum_j log l_j(x_j) - log g_j(x_j).
+ * No factorisation; the fit is a sort per feature, linear in n otherwise.
+ *
+ * ut_tpe_fit: X [n][d] row-major, the features ut_encode_features writes; y [n]
+ * finite, lower is better; kinds [d] or NULL (every feature numeric):
+ *   0 a numeric feature in [0, 1]; 1 a BOOL column (two categories, values 0 / 1);
+ *   q >= 2 the first column of a one-hot block of q columns, whose other q - 1
+ *   entries are -1.
+ * Split: n_l = max(1, min(ceil(gamma n), n_good_max, n - 1)); the good set l is the n_l
+ *   rows of smallest y, ties to the earlier row; the bad set g the other
+ *   n_g = n - n_l rows.
+ * Numeric feature, set S of s rows: s + 1 centres, the column's s values and a
+ *   prior centre at 0.5, sorted; among equal centres the prior comes first.  A
+ *   centre's sigma is the larger of its gaps to its sorted neighbours (an end
+ *   centre has one), clipped to [1 / min(100, s + 2), 1]; the prior's is 1.
+ *   Weights w = 1 / (s + prior_weight), the prior's prior_weight / (s + prior_weight).
+ *   A component is N(x; mu, sigma) / Z, Z = Phi((1 - mu) / sigma) - Phi(-mu / sigma)
+ *   = (erf((1 - mu) / (sigma sqrt 2)) - erf(-mu / (sigma sqrt 2))) / 2 in fp64.
+ *   The scoring kernel's form: a term is exp2(A (x - mu)^2 + B),
+ *   A = -log2(e) / (2 sigma^2), B = log2(w / (sigma sqrt(2 pi) Z)), in fp64 and
+ *   rounded once to f32 for the f32 tier.
+ * Categorical block of q categories (BOOL: q = 2, category = the value):
+ *   p_S(c) = (count_S(c) + prior_weight / q) / (s + prior_weight), counts integer.
+ * UT_EINVAL, the previous fit staying loaded: n < 2, a set of more than
+ * 8191 rows (one workgroup sorts a set's 8192 centres in LDS), d outside
+ * [1, 4096], a non-finite y, a numeric value outside [0, 1], a BOOL value that is
+ * not 0 or 1, a block row that is not one-hot, kinds that do not parse, gamma
+ * outside (0, 1), n_good_max < 1, prior_weight not finite and positive,
+ * precision not 32 or 64.  The split runs on the host; everything per feature
+ * is enqueued on the context's stream with no host wait. */
+typedef struct ut_tpe_params {
+  double  gamma;          /* 0.10 */
+  int32_t n_good_max;     /* 25 */
+  int32_t precision;      /* 32 | 64: the scoring tier */
+  double  prior_weight;   /* 1.0 */
+} ut_tpe_params;
+int ut_tpe_fit(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
+               const int32_t* kinds_host, const ut_tpe_params* params);
+/* features [d][ld] device fp64 (the layout ut_encode_features writes), m <= ld.
+ * Per numeric feature and set, every candidate sums its terms in the tier's
+ * type -- fp64 x - mu, rounded to the tier, squared, one fma with A and B, exp2
+ * (f32: the hardware's; fp64: the device library's), added -- and takes the
+ * fp64 log of the sum: logl and logg are the sums of those logs over the
+ * features, score the sum of their differences, all in fp64.  A BOOL column
+ * adds log p(x != 0), a one-hot column x log p(column).  score [m] is -inf
+ * where dup[i] != 0 (dup may be NULL); logl and logg [m] may be NULL.  Nothing
+ * checks that a candidate's features lie in [0, 1].  UT_EINVAL without a fit or
+ * with d different from the fit's.  m == 0 returns 0 and launches nothing.
+ * Enqueued on the context's stream with no host wait. */
+int ut_tpe_score(ut_ctx* ctx, const double* features, int64_t ld, int64_t m, int32_t d, const uint8_t* dup,
+                 double* score, double* logl, double* logg);
+/* The fitted components of one feature and set (0 = l, 1 = g), in sorted order,
+ * prior included: mu, sigma and logw = ln(w / Z), *count = s + 1 of them.  For
+ * a BOOL column or a block's first column: *count = q, logw the q
+ * log-probabilities, mu the category, sigma 0.  A column inside a block is
+ * UT_EINVAL.  *count always; the arrays (each may be NULL) only when cap >=
+ * *count, else UT_EINVAL.  Waits for the stream. */
+int ut_tpe_get(ut_ctx* ctx, int32_t feature, int32_t set, double* mu_host, double* sigma_host, double* logw_host,
+               int32_t cap, int32_t* count);
+/* n_l, n_g, d and the parameters of the loaded fit (each may be NULL); UT_EINVAL without one */
+int ut_tpe_info(ut_ctx* ctx, int32_t* n_l, int32_t* n_g, int32_t* d, ut_tpe_params* params);
+
 /* ---- multi-GPU exchange over RCCL -------------
  * One process per GPU, one communicator per context.  Rank r scores the
  * global candidate indices [r*m, (r+1)*m) of a round; population, training

@@ -55,6 +55,11 @@ class ForestFitParams(C.Structure):
                 ("round_", C.c_uint32)]
 
 
+class TpeParams(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("n_good_max", C.c_int32), ("precision", C.c_int32),
+                ("prior_weight", C.c_double)]
+
+
 class DeParams(C.Structure):
     _fields_ = [("cr", C.c_double), ("n_cross", C.c_int32), ("information_sharing", C.c_int32),
                 ("best", C.c_void_p)]
@@ -161,6 +166,10 @@ SIGNATURES = {
     "ut_forest_score": (C.c_int, [P, P, I64, I64, I32, P, P, D, P, P, P]),
     "ut_forest_fit": (C.c_int, [P, P, P, I32, I32, C.POINTER(ForestFitParams)]),
     "ut_forest_get": (C.c_int, [P, P, P, I64, C.POINTER(I32), C.POINTER(I64)]),
+    "ut_tpe_fit": (C.c_int, [P, P, P, I32, I32, P, C.POINTER(TpeParams)]),
+    "ut_tpe_score": (C.c_int, [P, P, I64, I64, I32, P, P, P, P]),
+    "ut_tpe_get": (C.c_int, [P, I32, I32, P, P, P, I32, C.POINTER(I32)]),
+    "ut_tpe_info": (C.c_int, [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32), C.POINTER(TpeParams)]),
     "ut_gp_score": (C.c_int, [P, P, I64, I64, C.POINTER(Acq), P, P, P, P]),
     "ut_gp_score_values": (C.c_int, [P, P, I64, I64, C.POINTER(Acq), P, P, P, P]),
     "ut_gp_set_precision": (C.c_int, [P, I32]),

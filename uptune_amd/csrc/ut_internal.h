@@ -209,6 +209,23 @@ struct RfCand {
   int32_t j, b;
 };
 
+// tpe.hip: one mixture component as the scoring kernel stages it -- a term is
+// exp2(A (x - mu)^2 + B); the f32 tier keeps the centre in fp64 (x - mu is
+// taken there and the difference rounded)
+struct TpeRec32 {
+  double mu;
+  float A, B;
+};
+struct TpeRec64 {
+  double mu, A, B;
+};
+// ... and one categorical column: log p of the good (l) and bad (g) sets when
+// the column reads 0 (BOOL only; 0 for a one-hot column) and when it reads 1
+struct TpeCat {
+  int32_t col, q;
+  double l0, l1, g0, g1;
+};
+
 }  // namespace ut
 
 // Every device array of a context is a DevBuf: a member here, of its Space or
@@ -511,6 +528,20 @@ struct ut_ctx {
   ut::DevBuf<ut::RfCand> rf_cand;        // [T][width][blocks] the level's best split per feature block
   ut::DevBuf<int32_t> rf_ctl;            // total, max feature | level widths | per tree: level ranges, size
   int32_t* rf_host = nullptr;            // pinned [2]: the one word read back per level
+  // TPE surrogate (tpe.hip): the fitted mixtures of n_l good and n_g bad rows
+  bool tpe_valid = false;
+  int32_t tpe_d = 0, tpe_dnum = 0, tpe_ncat = 0, tpe_nl = 0, tpe_ng = 0;
+  int32_t tpe_cpad = 0;                  // components per numeric feature (n + 2: l's, then g's), rounded up to even
+  ut_tpe_params tpe_par{};
+  std::vector<int32_t> tpe_kinds;        // [d] as ut_tpe_fit received them (all 0 for NULL)
+  std::vector<int32_t> tpe_slot;         // [d] column -> numeric index, or its record in tpe_cat
+  ut::DevBuf<double> tpe_X;              // staged X [n][d]
+  ut::DevBuf<int32_t> tpe_rows;          // [n] the good rows, then the bad rows, each in row order
+  ut::DevBuf<int32_t> tpe_numcol;        // numeric index -> feature column
+  ut::DevBuf<double> tpe_mu, tpe_sig, tpe_lw;   // [dnum][cpad] centre, sigma, ln(w / Z): what ut_tpe_get reads
+  ut::DevBuf<ut::TpeRec32> tpe_t32;      // [dnum][cpad] the scoring kernel's tables, one per tier
+  ut::DevBuf<ut::TpeRec64> tpe_t64;
+  ut::DevBuf<ut::TpeCat> tpe_cat;        // [ncat]
 
   // multi-GPU exchange (comm.hip): the RCCL communicator of this context's
   // rank and the packed top-k records of the all-gather / merge

@@ -829,6 +829,73 @@ class BatchEngine:
                                                    _ptr(score)), "ut_forest_score")
         return mu, var, score
 
+    # -- TPE surrogate -------------------------------------------------------
+    def tpe_kinds(self) -> np.ndarray:
+        """ut_tpe_fit's `kinds` [n_features] of the compiled space: 0 a numeric
+        feature (PERM positions too), 1 a BOOL column, q the first column of an
+        ENUM's one-hot block of q columns, -1 its other columns"""
+        kinds = np.zeros(self.spec.n_features, dtype=np.int32)
+        for ps in self.spec.params:
+            if ps.kind == L.UT_BOOL:
+                kinds[ps.feat_col] = 1
+            elif ps.kind == L.UT_ENUM and ps.n_feat >= 2:
+                kinds[ps.feat_col] = ps.n_feat
+                kinds[ps.feat_col + 1:ps.feat_col + ps.n_feat] = -1
+        return kinds
+
+    def tpe_fit(self, X, y, kinds="space", gamma: float = 0.10, n_good_max: int = 25, prior_weight: float = 1.0,
+                precision: int = 32):
+        """ut_tpe_fit: the Parzen mixtures of rows X [n][d] (features as encode()
+        writes them) and targets y [n], lower is better.  kinds: "space" =
+        tpe_kinds(), None = every feature numeric, or the array itself."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if X.ndim != 2 or y.shape != (X.shape[0],):
+            raise ValueError("tpe_fit: X [n][d] and y [n]")
+        if isinstance(kinds, str):
+            if kinds != "space":
+                raise ValueError("tpe_fit kinds: 'space', None or an int32 array [d]")
+            kinds = self.tpe_kinds()
+        if kinds is not None:
+            kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+            if kinds.shape != (X.shape[1],):
+                raise ValueError("tpe_fit: kinds [d]")
+        par = L.TpeParams(float(gamma), int(n_good_max), int(precision), float(prior_weight))
+        L.check(self.ctx, self.lib.ut_tpe_fit(self.ctx, X.ctypes.data, y.ctypes.data, X.shape[0], X.shape[1],
+                                              None if kinds is None else kinds.ctypes.data, C.byref(par)),
+                "ut_tpe_fit")
+
+    def tpe_score(self, feat: torch.Tensor, dup: Optional[torch.Tensor] = None, m: Optional[int] = None,
+                  parts: bool = False):
+        """ut_tpe_score of the loaded fit: -> score [m] = sum over features of
+        log l - log g, -inf on duplicates; parts=True: (score, logl, logg)"""
+        m = feat.shape[1] if m is None else m
+        score = self._empty(m)
+        logl, logg = (self._empty(m), self._empty(m)) if parts else (None, None)
+        L.check(self.ctx, self.lib.ut_tpe_score(self.ctx, _ptr(feat), feat.stride(0), m, feat.shape[0], _ptr(dup),
+                                                _ptr(score), _ptr(logl), _ptr(logg)), "ut_tpe_score")
+        return (score, logl, logg) if parts else score
+
+    def tpe_get(self, feature: int, set_: int):
+        """ut_tpe_get: the fitted components of one feature and set (0 = good,
+        1 = bad) -> (mu, sigma, ln(w / Z)), sorted by mu, the prior included; for
+        a BOOL column or a block's first column the q log-probabilities"""
+        cnt = C.c_int32(0)
+        L.check(self.ctx, self.lib.ut_tpe_get(self.ctx, int(feature), int(set_), None, None, None, 0, C.byref(cnt)),
+                "ut_tpe_get")
+        mu, sg, lw = (np.zeros(cnt.value) for _ in range(3))
+        L.check(self.ctx, self.lib.ut_tpe_get(self.ctx, int(feature), int(set_), mu.ctypes.data, sg.ctypes.data,
+                                              lw.ctypes.data, cnt.value, C.byref(cnt)), "ut_tpe_get")
+        return mu, sg, lw
+
+    def tpe_info(self):
+        """-> dict(n_l, n_g, d, gamma, n_good_max, prior_weight, precision) of the loaded fit"""
+        nl, ng, d, par = C.c_int32(0), C.c_int32(0), C.c_int32(0), L.TpeParams()
+        L.check(self.ctx, self.lib.ut_tpe_info(self.ctx, C.byref(nl), C.byref(ng), C.byref(d), C.byref(par)),
+                "ut_tpe_info")
+        return dict(n_l=nl.value, n_g=ng.value, d=d.value, gamma=par.gamma, n_good_max=par.n_good_max,
+                    prior_weight=par.prior_weight, precision=par.precision)
+
     # -- selection ---------------------------------------------------------
     def topk(self, score: torch.Tensor, k: int, dup: Optional[torch.Tensor] = None, cand_base: int = 0):
         idx = self._empty(k, dtype=torch.int64)

@@ -259,6 +259,17 @@ class AUCBanditMetaTechnique(MetaSearchTechnique):
 # ---------------------------------------------------------------------------
 # GPU batch techniques
 # ---------------------------------------------------------------------------
+# SharedModel's tpe_kw: engine.tpe_fit's parameters
+_TPE_KW = ("gamma", "n_good_max", "prior_weight", "precision")
+# ... and the rows a refit passes on: one more than ut_tpe_fit's cap on a set (the bad set is at most all but one)
+_TPE_ROWS = 8192
+
+
+def _surrogate_word(surrogate) -> str:
+    """how the refusals name a surrogate that is not the GP"""
+    return "TPE" if surrogate == "tpe" else "tree"
+
+
 class SharedModel:
     """Device state the GPU techniques of one bandit share: ONE context, hence
     one history digest set and one GP fit per change of the training set (the
@@ -277,7 +288,8 @@ class SharedModel:
                  engine_factory=None, y_transform: Optional[str] = None, ell_grid=None, ard_maxiter: int = 40,
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  surrogate: Optional[str] = None, forest_kw: Optional[Dict[str, Any]] = None,
-                 objectives=None, ref_point=None, forest_fit: str = "host"):
+                 objectives=None, ref_point=None, forest_fit: str = "host",
+                 tpe_kw: Optional[Dict[str, Any]] = None):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -347,12 +359,28 @@ class SharedModel:
         # model).  f_best is min(y) in the units fitted, fit_seconds the host
         # time spent in RandomForestRegressor.fit.  The GP's weights
         # (feasibility, constraints) and its pruned rounds do not apply.
-        if surrogate not in (None, "forest"):
-            raise ValueError("SharedModel surrogate: None (the GP) or 'forest'")
+        # "tpe" = the Tree-structured Parzen Estimator (engine.tpe_fit,
+        # csrc/tpe.hip), refitted from the same usable rows, features and
+        # y_transform at the same moments: the rows split into a good and a bad
+        # set, one density per feature and set, ENUM / BOOL parameters as
+        # categorical distributions; the score is log l - log g, which has no
+        # variance and takes no acquisition.  tpe_kw: gamma, n_good_max,
+        # prior_weight, precision (32 | 64).  fit_seconds is the host time of
+        # the engine call.
+        if surrogate not in (None, "forest", "tpe"):
+            raise ValueError("SharedModel surrogate: None (the GP), 'forest' or 'tpe'")
         if surrogate is not None and (self.feasibility is not None or self.constraints):
-            raise ValueError("feasibility and constraints weight the GP's EI: not with a tree surrogate")
+            raise ValueError("feasibility and constraints weight the GP's EI: not with a %s surrogate"
+                             % _surrogate_word(surrogate))
         self.surrogate = surrogate
         self.forest_kw = dict(forest_kw or {})
+        self.tpe_kw = dict(tpe_kw or {})
+        if self.tpe_kw:
+            if surrogate != "tpe":
+                raise ValueError("tpe_kw belongs to surrogate='tpe'")
+            unknown = sorted(set(self.tpe_kw) - set(_TPE_KW))
+            if unknown:
+                raise ValueError("tpe_kw: %s not among %s" % (unknown, sorted(_TPE_KW)))
         # forest_fit: "host" = the sklearn fit above; "device" = the forest is
         # grown by the engine (engine.forest_fit, csrc/forest_fit.hip: 256-bin
         # histogram trees, bootstrap and feature draws from the context's seed
@@ -388,7 +416,8 @@ class SharedModel:
                 raise ValueError("objectives: EHVI under the failure vote is not built: no feasibility with two "
                                  "objectives")
             if surrogate is not None:
-                raise ValueError("objectives: EHVI needs the GP's joint posterior: not with a tree surrogate")
+                raise ValueError("objectives: EHVI needs the GP's joint posterior: not with a %s surrogate"
+                                 % _surrogate_word(surrogate))
         if ref_point is not None:
             if not self.objectives:
                 raise ValueError("ref_point belongs to objectives=")
@@ -613,6 +642,32 @@ class SharedModel:
             raise ValueError("forest_kw max_features with forest_fit='device': a fraction in (0, 1]")
         return kw
 
+    def _fit_tpe(self, rows, ids) -> bool:
+        """surrogate="tpe": refit the Parzen mixtures iff the usable results changed"""
+        import time
+
+        key = (len(rows), ids[-1])
+        if key == self._fit_key:
+            return True
+        self._gather(rows, ids)
+        n = self._n
+        y = self._transform(self._ya[:n])
+        X = self._Xa[:n]
+        if n > _TPE_ROWS:
+            # ut_tpe_fit sorts a set of at most 8,191 rows: a longer run keeps its
+            # best half-limit of results and the most recent of the others
+            best = np.argsort(y, kind="stable")[:_TPE_ROWS // 2]
+            rest = np.setdiff1d(np.arange(n), best)[-(_TPE_ROWS - len(best)):]
+            keep = np.sort(np.concatenate([best, rest]))
+            X, y = X[keep], y[keep]
+        t0 = time.perf_counter()
+        self.engine.tpe_fit(X, y, **self.tpe_kw)
+        self.fit_seconds += time.perf_counter() - t0
+        self.f_best = float(np.min(y))
+        self._fit_key = key
+        self.fits += 1
+        return True
+
     def _fit_forest(self, rows, ids) -> bool:
         """surrogate="forest": refit the random forest iff the usable results changed"""
         import time
@@ -656,6 +711,8 @@ class SharedModel:
             return False
         if self.surrogate == "forest":
             return self._fit_forest(rows, ids)
+        if self.surrogate == "tpe":
+            return len(rows) >= 2 and self._fit_tpe(rows, ids)
         if self._fit_unverified and self._fit_key is not None:
             # the previous fit ran asynchronously (no host wait when it was
             # enqueued): a kernel matrix that was not positive definite would
@@ -948,19 +1005,26 @@ class GpuBatchTechnique(SearchTechnique):
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  forest_kw: Optional[Dict[str, Any]] = None, polish: int = 0, polish_pool: Optional[int] = None,
                  ts_features: int = 1024, objectives=None, ref_point=None, forest_fit: str = "host",
-                 *pargs, **kwargs):
+                 tpe_kw: Optional[Dict[str, Any]] = None, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
         # surrogate="forest" (SharedModel): a random forest refitted from the
         # driver's results, scored by EI / UCB on its mean and variance over
         # trees.  A shared model carries its own setting (and forest_kw)
-        refit = isinstance(surrogate, str) and surrogate == "forest"
+        # surrogate="tpe" (SharedModel): the Parzen estimator, refitted the same
+        # way and ranked by log l - log g; word names the model in the refusals
+        refit = surrogate if isinstance(surrogate, str) and surrogate in ("forest", "tpe") else None
         if shared is not None:
-            if refit and shared.surrogate != "forest":
-                raise ValueError("surrogate='forest' with a shared model that fits a GP")
-            if surrogate is not None and not refit and shared.surrogate == "forest":
-                raise ValueError("a model object as surrogate with a shared model that refits a forest")
-            refit = shared.surrogate == "forest"
-        tree = refit or surrogate is not None
+            if refit and shared.surrogate != refit:
+                raise ValueError("surrogate='%s' with a shared model that fits %s" % (
+                    refit, "a GP" if shared.surrogate is None else "surrogate='%s'" % shared.surrogate))
+            if surrogate is not None and not refit and shared.surrogate is not None:
+                raise ValueError("a model object as surrogate with a shared model that refits a %s"
+                                 % ("forest" if shared.surrogate == "forest" else "TPE"))
+            refit = shared.surrogate
+        tree = refit is not None or surrogate is not None
+        word = _surrogate_word(refit)
+        if refit == "tpe" and acq == "ucb":
+            raise ValueError("acq='ucb' needs a posterior variance, TPE has none: not with a TPE surrogate")
         # prune_weighted (SharedModel): pruned rounds under constraints / feasibility,
         # by the weighted bound of ut_gp_set_prune_weighted.  A shared model carries its own
         weighted = shared.prune_weighted if shared is not None else bool(prune_weighted)
@@ -975,7 +1039,7 @@ class GpuBatchTechnique(SearchTechnique):
             if acq == "ucb":
                 raise ValueError("constraints multiply a score that is >= 0: EI, not acq='ucb'")
             if tree:
-                raise ValueError("constraints weight the GP's EI: not with a tree surrogate")
+                raise ValueError("constraints weight the GP's EI: not with a %s surrogate" % word)
         # feasibility (SharedModel): EI times the estimated probability that the
         # candidate does not fail.  A shared model carries its own setting; the
         # weight is defined for the dense EI score only
@@ -987,7 +1051,7 @@ class GpuBatchTechnique(SearchTechnique):
             if acq == "ucb":
                 raise ValueError("feasibility multiplies a score that is >= 0: EI, not acq='ucb'")
             if tree:
-                raise ValueError("feasibility weights the GP's EI: not with a tree surrogate")
+                raise ValueError("feasibility weights the GP's EI: not with a %s surrogate" % word)
         # objectives (SharedModel): every EI score becomes the expected hypervolume
         # improvement over time and a second measurement.  A shared model carries
         # its own setting; EHVI is built for the dense EI score alone
@@ -1003,7 +1067,7 @@ class GpuBatchTechnique(SearchTechnique):
             if int(polish) > 0:
                 raise ValueError("objectives: EHVI's gradient is not built: no polish with two objectives")
             if tree:
-                raise ValueError("objectives: EHVI needs the GP's joint posterior: not with a tree surrogate")
+                raise ValueError("objectives: EHVI needs the GP's joint posterior: not with a %s surrogate" % word)
             if shared is None and _cons_setting(constraints):
                 raise ValueError("objectives: constrained EHVI is not built: no constraints with two objectives")
             if shared is None and _feas_setting(feasibility) is not None:
@@ -1020,7 +1084,7 @@ class GpuBatchTechnique(SearchTechnique):
             if int(prune_rows) > 0:
                 raise ValueError("diversify needs every candidate's score: not with prune_rows")
             if tree:
-                raise ValueError("diversify conditions a GP posterior: not with a tree surrogate")
+                raise ValueError("diversify conditions a GP posterior: not with a %s surrogate" % word)
         # polish = T > 0: a dense GP round refines its polish_pool best-scoring
         # candidates with T steps of projected gradient ascent on the acquisition
         # (ut_gp_polish) before it takes its batch from them -- the local search
@@ -1036,7 +1100,7 @@ class GpuBatchTechnique(SearchTechnique):
             if int(prune_rows) > 0:
                 raise ValueError("polish needs every candidate's score: not with prune_rows")
             if tree:
-                raise ValueError("polish climbs a GP's acquisition: not with a tree surrogate")
+                raise ValueError("polish climbs a GP's acquisition: not with a %s surrogate" % word)
             if shared.constraints if shared is not None else _cons_setting(constraints):
                 raise ValueError("the gradient of the constrained score is not built: no polish with constraints")
             if (shared.feasibility if shared is not None else _feas_setting(feasibility)) is not None:
@@ -1065,20 +1129,20 @@ class GpuBatchTechnique(SearchTechnique):
             if (shared.feasibility if shared is not None else _feas_setting(feasibility)) is not None:
                 raise ValueError("paths under the failure vote are not built: no feasibility with acq='ts'")
             if tree:
-                raise ValueError("acq='ts' samples a GP posterior: not with a tree surrogate")
+                raise ValueError("acq='ts' samples a GP posterior: not with a %s surrogate" % word)
         # prune_rows > 0: score rounds with ut_gp_topk_pruned (selection-exact EI
         # bound from the first prune_rows rows of L^-1 k*; fp64 fits, EI / UCB):
         # the same selections as the dense variance at a fraction of its cost
         # when the bounds are tight (or the GP is flat: exact ties by index)
         self.prune_rows = int(prune_rows)
         if refit and self.prune_rows > 0:
-            raise ValueError("prune_rows bounds a GP posterior: not with a tree surrogate")
+            raise ValueError("prune_rows bounds a GP posterior: not with a %s surrogate" % word)
         # surrogate: None = the GP fitted on the driver's results (EI / UCB); or a
         # tree ensemble over the same features (sklearn regressor, XGBoost JSON,
         # forest.Forest) ranking candidates by predicted objective (minimised),
         # the multi-stage tuner's model scoring (multi_stage.py:8-22, :109-123);
         # or "forest": the model's own refitted random forest (above)
-        self.surrogate = "forest" if refit else surrogate
+        self.surrogate = refit if refit else surrogate
         self._static = tree and not refit    # a fixed model object: no fit, mean ranking
         # precision: the GP contractions of a private model (64 / 32 / 16 = f16x3);
         # a shared model (the bandit's) carries its own
@@ -1090,9 +1154,10 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    feasibility=feasibility,
                                                                    constraints=constraints,
                                                                    prune_weighted=prune_weighted,
-                                                                   surrogate="forest" if refit else None,
+                                                                   surrogate=refit,
                                                                    forest_kw=forest_kw, objectives=objectives,
-                                                                   ref_point=ref_point, forest_fit=forest_fit)
+                                                                   ref_point=ref_point, forest_fit=forest_fit,
+                                                                   tpe_kw=tpe_kw)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -1184,6 +1249,8 @@ class GpuBatchTechnique(SearchTechnique):
             _, score = eng.forest_predict(eng.encode(vals), dup=dup)
         elif have_model and self.model.surrogate == "forest":
             _, _, score = eng.forest_score(eng.encode(vals), eng.acq(self.acq_kind), self.model.f_best, dup=dup)
+        elif have_model and self.model.surrogate == "tpe":
+            score = eng.tpe_score(eng.encode(vals), dup=dup)
         elif have_model:
             if self.prune_rows > 0 and self.model.precision == 64:
                 idx, top, _ = eng.gp_topk_pruned(eng.encode(vals), self.batch, acq=eng.acq(self.acq_kind), dup=dup,
@@ -1557,9 +1624,10 @@ def _shared_model(kw) -> SharedModel:
                        engine_factory=kw.pop("engine_factory", None), y_transform=kw.get("y_transform"),
                        feasibility=kw.get("feasibility", False), constraints=kw.get("constraints"),
                        prune_weighted=kw.get("prune_weighted", False),
-                       surrogate="forest" if isinstance(kw.get("surrogate"), str) and kw["surrogate"] == "forest"
-                       else None, forest_kw=kw.get("forest_kw"), objectives=kw.get("objectives"),
-                       ref_point=kw.get("ref_point"), forest_fit=kw.get("forest_fit", "host"))
+                       surrogate=kw["surrogate"] if isinstance(kw.get("surrogate"), str)
+                       and kw["surrogate"] in ("forest", "tpe") else None, forest_kw=kw.get("forest_kw"),
+                       objectives=kw.get("objectives"), ref_point=kw.get("ref_point"),
+                       forest_fit=kw.get("forest_fit", "host"), tpe_kw=kw.get("tpe_kw"))
 
 
 def _tr_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:

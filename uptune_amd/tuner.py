@@ -41,7 +41,7 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                 constraints=None, prune_weighted: bool = False, surrogate=None,
                 forest_kw=None, polish: int = 0, polish_pool: Optional[int] = None,
                 trust_region: bool = False, acq: str = "ei", ts_features: int = 1024, objectives=None,
-                ref_point=None, driver_objective=None, forest_fit: str = "host") -> SearchDriver:
+                ref_point=None, driver_objective=None, forest_fit: str = "host", tpe_kw=None) -> SearchDriver:
     """Run the bandit for `generations` generations; returns the driver (results,
     best_result, bandit statistics).  With torch.distributed initialised and
     world > 1 the run is SPMD: call it on every rank with the same arguments.
@@ -52,6 +52,10 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
     surrogate="forest": the children share one refitted random forest scored by
     EI on its mean and variance over trees instead of the GP (SharedModel);
     forest_fit="device" grows it on the device instead of with sklearn on the host.
+    surrogate="tpe": the children share one Tree-structured Parzen Estimator,
+    refitted with the results, and rank by log l - log g (SharedModel; tpe_kw:
+    gamma, n_good_max, prior_weight, precision).  A fit takes at most 8,192
+    results: beyond that, the best 4,096 and the most recent of the others.
     polish=T > 0: every dense GP round refines its polish_pool best candidates
     with T gradient-ascent steps on the acquisition first (GpuBatchTechnique).
     trust_region=True: a fifth arm proposes inside a trust region around the best
@@ -79,6 +83,7 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                             prune_rows=prune_rows, diversify=diversify, feasibility=feasibility,
                             constraints=constraints, prune_weighted=prune_weighted, surrogate=surrogate,
                             forest_kw=forest_kw, **({"forest_fit": forest_fit} if forest_fit != "host" else {}),
+                            **({"tpe_kw": tpe_kw} if tpe_kw is not None else {}),
                             polish=polish, polish_pool=polish_pool, acq=acq,
                             **({"ts_features": ts_features} if acq == "ts" else {}),
                             **({"trust_region": True} if trust_region else {}), **mo_kw)
