@@ -2,7 +2,11 @@
 definition): 256-bin codes, 16.16 fixed-point targets, Philox bootstrap and
 feature draws, breadth-first growth, the split of largest
 s = S_L^2 / W_L + S_R^2 / W_R with ties to the smaller feature, then bin.  Every
-histogram entry is an integer below 2^53, so np.bincount's float64 sums are exact."""
+histogram entry is an integer below 2^53, so np.bincount's float64 sums are exact.
+
+level_widths, route and predict read a fitted forest's records alone: where a
+row of codes goes by integer comparison (no float is compared with a
+threshold), and the mean uthot.h states for ut_forest_predict's pred."""
 import numpy as np
 
 from oracle.philox import draw, umulhi32
@@ -52,8 +56,9 @@ def best_split(codes, w, q, rows, elig, min_leaf):
     return divmod(int(np.argmax(s)), 255)   # the first maximum: smaller j, then smaller b
 
 
-def grow(codes, q, w, t, seed, round_, min_leaf, max_depth, frac, shift, scale):
-    """one tree's records, child indices within the tree"""
+def grow(codes, q, w, t, seed, round_, min_leaf, max_depth, frac, shift, scale, node_rows=None):
+    """one tree's records, child indices within the tree; node_rows, a list,
+    receives every node's rows (those of weight > 0 that reached it)"""
     d = codes.shape[1]
     out, todo = [], [(np.flatnonzero(w > 0), 0)]   # node k is todo[k]: breadth first
     k = 0
@@ -75,22 +80,70 @@ def grow(codes, q, w, t, seed, round_, min_leaf, max_depth, frac, shift, scale):
             out.append((j, len(todo), len(todo) + 1, 1, (b + 1) / 256.0, value))
             todo += [(rows[left], depth + 1), (rows[~left], depth + 1)]
         k += 1
+    if node_rows is not None:
+        node_rows.extend(rows for rows, _ in todo)
     return np.array(out, dtype=NODE_DTYPE)
 
 
 def fit(X, y, seed, n_trees=64, min_leaf=3, max_depth=0, bootstrap=True, feature_frac=1.0, seed_round=0,
-        y_shift=None, y_scale=None):
+        y_shift=None, y_scale=None, node_rows=None):
     """-> (roots [T] int32, nodes [N] NODE_DTYPE) as ut_forest_get returns them;
-    y_shift / y_scale default to engine.forest_fit's: mean and std, 1 for a constant y"""
+    y_shift / y_scale default to engine.forest_fit's: mean and std, 1 for a constant y;
+    node_rows, a list, receives the rows of node k of the returned array at [k]"""
     y = np.asarray(y, np.float64)
     shift = float(np.mean(y)) if y_shift is None else y_shift
     scale = (float(np.std(y)) or 1.0) if y_scale is None else y_scale
     codes, q = codes_of(X), quantise(y, shift, scale)
     trees = [grow(codes, q, weights(seed, t, len(y), seed_round, bootstrap), t, seed, seed_round, min_leaf, max_depth,
-                  feature_frac, shift, scale) for t in range(n_trees)]
+                  feature_frac, shift, scale, node_rows) for t in range(n_trees)]
     roots = np.cumsum([0] + [len(a) for a in trees[:-1]]).astype(np.int32)
     for a, r in zip(trees, roots):
         inner = a["feature"] >= 0
         a["left"][inner] += r
         a["right"][inner] += r
     return roots, np.concatenate(trees)
+
+
+def level_widths(nodes, roots):
+    """-> per tree, the number of nodes at depth 0, 1, ..: from the records alone"""
+    out = []
+    for r in roots:
+        level, widths = np.array([int(r)]), []
+        while level.size:
+            widths.append(int(level.size))
+            inner = level[nodes["feature"][level] >= 0]
+            level = np.concatenate([nodes["left"][inner], nodes["right"][inner]])
+        out.append(widths)
+    return out
+
+
+def route(nodes, roots, codes):
+    """-> leaf node index [m][T] of integer codes [m][d]: at a split record go
+    left iff codes[i, feature] <= round(threshold * 256) - 1.  Where its code
+    went: integers only, no x is compared with a threshold"""
+    codes = np.asarray(codes, np.int64)
+    inner = nodes["feature"] >= 0
+    b = np.where(inner, np.rint(np.where(inner, nodes["threshold"], 0.0) * 256.0).astype(np.int64) - 1, -1)
+    m = codes.shape[0]
+    rows = np.arange(m)
+    out = np.empty((m, len(roots)), np.int64)
+    for t, r in enumerate(roots):
+        nd = np.full(m, int(r), np.int64)
+        while True:
+            live = inner[nd]
+            if not live.any():
+                break
+            left = codes[rows, np.where(live, nodes["feature"][nd], 0)] <= b[nd]
+            nd = np.where(live, np.where(left, nodes["left"][nd], nodes["right"][nd]), nd)
+        out[:, t] = nd
+    return out
+
+
+def predict(nodes, roots, codes):
+    """-> mu [m] = (0 + sum over trees, in tree order, of leaf value) / T in fp64,
+    nothing fused: uthot.h's pred for base 0, scale 1, div T"""
+    leaf = route(nodes, roots, codes)
+    acc = np.zeros(leaf.shape[0])
+    for t in range(len(roots)):
+        acc = acc + nodes["value"][leaf[:, t]]
+    return acc / float(len(roots))
