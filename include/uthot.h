@@ -1136,6 +1136,62 @@ typedef struct ut_forest_fit_params {
 } ut_forest_fit_params;
 int ut_forest_fit(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
                   const ut_forest_fit_params* params);
+/* ut_gbt_fit: fit a gradient-boosted ensemble on the device and load it: the
+ * model the reference retrains on the host (plugins/xgbregressor.py:35-41,
+ * :72-78; its parameters are n_rounds 300, eta 0.015, max_depth 10, subsample
+ * 0.4, colsample_bylevel 0.5, lambda 1).  Squared-error boosting with the
+ * formulae of XGBoost's hist method, on uniform bins and integer sums: it is a
+ * function of the data, the parameters and the context's seed alone and can be
+ * held bit for bit, but it is NOT XGBoost's bits (its bins are quantiles, its
+ * sums floats, its random numbers its own).
+ *   X, y, code and the stored split (threshold (b + 1) / 256, UT_SPLIT_LT,
+ *     default_left = 1) as ut_forest_fit.
+ *   z_i = clamp((y_i - y_shift) / y_scale, -32, 32) in fp64; pred_i = 0.
+ *   Round r = 0 .. n_rounds - 1 grows one tree:
+ *     g_i = (int32) nearbyint(clamp(pred_i - z_i, -64, 64) * 65536); the hessian is 1.
+ *     row i is in the round's sample iff subsample >= 1 or (double)word <
+ *       subsample * 2^32, word (i & 3) of draw(seed, i >> 2, stream r, round_, OP_GBT = 9).
+ *     feature j is eligible at level L (the root is level 0), the same for
+ *       every node of the level, iff colsample_bylevel >= 1 or (double)word <
+ *       colsample_bylevel * 2^32, word (j & 3) of
+ *       draw(seed, (L << 32) | (j >> 2), stream 0x10000 | r, round_, OP_GBT).
+ *     A node holds every row that reached it; G = sum g and H = the count over
+ *       its sampled rows.  A split (j, b), b <= 254, j eligible, sends code <= b
+ *       left and needs H_L >= min_child and H_R >= min_child; its score is
+ *       s = G_L G_L / (H_L + lambda) + G_R G_R / (H_R + lambda) (fp64: G and H
+ *       converted, two products, two sums, two quotients, one sum, nothing
+ *       fused); the largest s wins, ties to the smaller j, then the smaller b.
+ *     The node splits iff it has such a split, its level is below max_depth and
+ *       s - (G G) / (H + lambda) > gamma; otherwise it is a leaf.
+ *     step = (eta * ((double)(-G) / ((double)H + lambda))) / 65536, each
+ *       operation rounded once; 0 where H = 0.  A leaf adds it to pred of every
+ *       row it holds, sampled or not: pred_i = pred_i + step.
+ *     Every record's value = y_scale * step; a leaf has feature = left = right
+ *       = -1, default_left = 0, threshold 0.
+ *   A tree's records are in heap (breadth-first) order with absent nodes
+ *   skipped, trees in round order, child indices global; base = y_shift,
+ *   scale 1, div 1, rule LT: ut_forest_predict and ut_forest_get read it as any
+ *   loaded ensemble, ut_forest_score answers UT_EUNSUPPORTED (the stages of a
+ *   boosted ensemble are not samples of one function).
+ * UT_EINVAL for n outside [1, 16384], d outside [1, 4096], a parameter outside
+ * its range below, a non-finite y or a NULL pointer; that, and a failed
+ * allocation (UT_ENOMEM), leave the loaded ensemble as it was.  Enqueued on the
+ * context's stream: n_rounds * (max_depth + 2) + 2 launches, then the host
+ * reads two words; nothing is read back or waited for between the launches. */
+typedef struct ut_gbt_fit_params {
+  int32_t n_rounds;      /* 1..1024 */
+  int32_t max_depth;     /* 1..12  */
+  int32_t min_child;     /* >= 1   */
+  double  eta;           /* (0, 1] */
+  double  lambda;        /* >= 0   */
+  double  gamma;         /* >= 0   */
+  double  subsample;     /* (0, 1] */
+  double  colsample_bylevel; /* (0, 1] */
+  double  y_shift, y_scale;  /* finite, y_scale > 0 */
+  uint32_t round_;       /* < 2^24, joins the Philox key as in ut_forest_fit */
+} ut_gbt_fit_params;
+int ut_gbt_fit(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
+               const ut_gbt_fit_params* params);
 /* The loaded ensemble, however it was loaded, as the device holds it (a leaf's
  * threshold field is its variance): *n_trees and *n_nodes always; with
  * roots_host [n_trees] and nodes_host [cap_nodes] both given, the records too

@@ -55,6 +55,13 @@ class ForestFitParams(C.Structure):
                 ("round_", C.c_uint32)]
 
 
+class GbtFitParams(C.Structure):
+    _fields_ = [("n_rounds", C.c_int32), ("max_depth", C.c_int32), ("min_child", C.c_int32), ("eta", C.c_double),
+                ("lambda_", C.c_double), ("gamma", C.c_double), ("subsample", C.c_double),
+                ("colsample_bylevel", C.c_double), ("y_shift", C.c_double), ("y_scale", C.c_double),
+                ("round_", C.c_uint32)]
+
+
 class TpeParams(C.Structure):
     _fields_ = [("gamma", C.c_double), ("n_good_max", C.c_int32), ("precision", C.c_int32),
                 ("prior_weight", C.c_double)]
@@ -165,6 +172,7 @@ SIGNATURES = {
     "ut_forest_leaf_var": (C.c_int, [P, P, I64]),
     "ut_forest_score": (C.c_int, [P, P, I64, I64, I32, P, P, D, P, P, P]),
     "ut_forest_fit": (C.c_int, [P, P, P, I32, I32, C.POINTER(ForestFitParams)]),
+    "ut_gbt_fit": (C.c_int, [P, P, P, I32, I32, C.POINTER(GbtFitParams)]),
     "ut_forest_get": (C.c_int, [P, P, P, I64, C.POINTER(I32), C.POINTER(I64)]),
     "ut_tpe_fit": (C.c_int, [P, P, P, I32, I32, P, C.POINTER(TpeParams)]),
     "ut_tpe_score": (C.c_int, [P, P, I64, I64, I32, P, P, P, P]),

@@ -33,6 +33,7 @@
 // The host reads one word per level (the widest next level: the next grid, 0 =
 // done).  k_rf_offsets / k_rf_compact then lay the trees out contiguously.
 #include "ut_internal.h"
+#include "rf_codes.h"   // rf_code, rf_better: shared with gbt_fit.hip
 
 namespace ut {
 
@@ -56,11 +57,6 @@ struct RfParams {
 // then per tree the level ranges (lb, le) by level parity and the tree's size
 constexpr int32_t RF_CTL_W = 2;
 __host__ __device__ inline int32_t rf_ctl_tree(int32_t max_level, int32_t t) { return RF_CTL_W + max_level + 2 + 5 * t; }
-
-__device__ __forceinline__ uint8_t rf_code(double x) {
-  const float v = floorf((float)x * 256.0f);
-  return !(v > 0.0f) ? 0 : (v > 255.0f ? 255 : (uint8_t)(int32_t)v);   // NaN -> 0
-}
 
 __device__ __forceinline__ int32_t rf_quant(double y, double shift, double scale) {
   double z = (y - shift) / scale;
@@ -94,11 +90,6 @@ __device__ __forceinline__ bool rf_eligible(const RfParams& p, int32_t t, int32_
   const uint32_t k = (uint32_t)j & 3u;
   const uint32_t word = k == 0 ? r.x : (k == 1 ? r.y : (k == 2 ? r.z : r.w));
   return (double)word * (1.0 / 4294967296.0) < p.feature_frac;
-}
-
-// (s, j, b) order of the split choice: larger s, then smaller j, then smaller b
-__device__ __forceinline__ bool rf_better(double s, int32_t j, int32_t b, double s2, int32_t j2, int32_t b2) {
-  return s > s2 || (s == s2 && (j < j2 || (j == j2 && b < b2)));
 }
 
 // ---- prepare ---------------------------------------------------------------

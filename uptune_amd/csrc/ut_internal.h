@@ -209,6 +209,17 @@ struct RfCand {
   int32_t j, b;
 };
 
+// gbt_fit.hip: a node of the growing boosted tree, addressed by heap index
+// (children of k are 2k + 1 and 2k + 2); all zero = absent
+struct GbtNode {
+  int32_t start, count;    // rows [start, start + count) of the level's row list: every row, sampled or not
+  uint32_t H;              // sampled rows
+  int32_t open;            // 0 absent, 1 to be decided by its level's launch, 2 a leaf, 3 split
+  unsigned long long G;    // sum of g over the sampled rows, an int64 added in two's complement
+  int32_t ticket;          // slice workgroups of the level's launch that have written their candidate
+  int32_t pad_;
+};
+
 // tpe.hip: one mixture component as the scoring kernel stages it -- a term is
 // exp2(A (x - mu)^2 + B); the f32 tier keeps the centre in fp64 (x - mu is
 // taken there and the difference rounded)
@@ -528,6 +539,13 @@ struct ut_ctx {
   ut::DevBuf<ut::RfCand> rf_cand;        // [T][width][blocks] the level's best split per feature block
   ut::DevBuf<int32_t> rf_ctl;            // total, max feature | level widths | per tree: level ranges, size
   int32_t* rf_host = nullptr;            // pinned [2]: the one word read back per level
+  // the boosted fit's scratch (gbt_fit.hip) beside rf_X, rf_y, rf_rm, rf_fm, rf_rows, rf_cand, rf_host
+  ut::DevBuf<double> gbt_z, gbt_pred;    // [n] normalised targets, the ensemble's prediction of the training rows
+  ut::DevBuf<int32_t> gbt_g;             // [n] the round's fixed-point gradients
+  ut::DevBuf<uint8_t> gbt_samp;          // [n] the row is in the round's sample
+  ut::DevBuf<ut::GbtNode> gbt_state;     // [2][heap] the growing tree's nodes, one copy per round parity
+  ut::DevBuf<ut_tree_node> gbt_tn;       // [2][heap] ... and their records
+  ut::DevBuf<int32_t> gbt_ctl;           // [2] total nodes, largest split feature
   // TPE surrogate (tpe.hip): the fitted mixtures of n_l good and n_g bad rows
   bool tpe_valid = false;
   int32_t tpe_d = 0, tpe_dnum = 0, tpe_ncat = 0, tpe_nl = 0, tpe_ng = 0;

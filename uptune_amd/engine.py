@@ -793,6 +793,32 @@ class BatchEngine:
                                                  C.byref(par)), "ut_forest_fit")
         self.forest = "device"
 
+    def gbt_fit(self, X, y, n_rounds: int = 300, max_depth: int = 10, min_child: int = 1, eta: float = 0.015,
+                reg_lambda: float = 1.0, gamma: float = 0.0, subsample: float = 0.4, colsample_bylevel: float = 0.5,
+                y_shift: Optional[float] = None, y_scale: Optional[float] = None, seed_round: int = 0):
+        """ut_gbt_fit: fit a gradient-boosted tree ensemble (squared error,
+        256-bin histogram trees) of rows X [n][d] and targets y [n] on the
+        device and load it; forest_predict and forest_get read it.  The defaults
+        are the reference's XGBRegressor settings (plugins/xgbregressor.py:35-41).
+        y_shift / y_scale default to mean(y) and std(y) (1 for a constant y);
+        seed_round separates the draws of successive fits of one context."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if X.ndim != 2 or y.shape != (X.shape[0],):
+            raise ValueError("gbt_fit: X [n][d] and y [n]")
+        finite = y.size > 0 and bool(np.all(np.isfinite(y)))
+        if y_shift is None:
+            y_shift = float(np.mean(y)) if finite else 0.0
+        if y_scale is None:
+            std = float(np.std(y)) if finite else 1.0
+            y_scale = std if std > 0.0 and np.isfinite(std) else 1.0
+        par = L.GbtFitParams(int(n_rounds), int(max_depth), int(min_child), float(eta), float(reg_lambda),
+                             float(gamma), float(subsample), float(colsample_bylevel), float(y_shift), float(y_scale),
+                             int(seed_round))
+        L.check(self.ctx, self.lib.ut_gbt_fit(self.ctx, X.ctypes.data, y.ctypes.data, X.shape[0], X.shape[1],
+                                              C.byref(par)), "ut_gbt_fit")
+        self.forest = "device"
+
     def forest_get(self):
         """ut_forest_get: the loaded ensemble as the device holds it -> (roots
         [T] int32, nodes [N] records of forest.NODE_DTYPE; a leaf's threshold

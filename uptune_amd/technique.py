@@ -263,11 +263,15 @@ class AUCBanditMetaTechnique(MetaSearchTechnique):
 _TPE_KW = ("gamma", "n_good_max", "prior_weight", "precision")
 # ... and the rows a refit passes on: one more than ut_tpe_fit's cap on a set (the bad set is at most all but one)
 _TPE_ROWS = 8192
+# SharedModel's gbt_kw: engine.gbt_fit's parameters
+_GBT_KW = ("n_rounds", "max_depth", "min_child", "eta", "reg_lambda", "gamma", "subsample", "colsample_bylevel")
+# the surrogates a SharedModel refits itself
+_REFIT = ("forest", "tpe", "gbt")
 
 
 def _surrogate_word(surrogate) -> str:
     """how the refusals name a surrogate that is not the GP"""
-    return "TPE" if surrogate == "tpe" else "tree"
+    return {"tpe": "TPE", "gbt": "gbt"}.get(surrogate, "tree")
 
 
 class SharedModel:
@@ -289,7 +293,7 @@ class SharedModel:
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  surrogate: Optional[str] = None, forest_kw: Optional[Dict[str, Any]] = None,
                  objectives=None, ref_point=None, forest_fit: str = "host",
-                 tpe_kw: Optional[Dict[str, Any]] = None):
+                 tpe_kw: Optional[Dict[str, Any]] = None, gbt_kw: Optional[Dict[str, Any]] = None):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -367,8 +371,16 @@ class SharedModel:
         # variance and takes no acquisition.  tpe_kw: gamma, n_good_max,
         # prior_weight, precision (32 | 64).  fit_seconds is the host time of
         # the engine call.
-        if surrogate not in (None, "forest", "tpe"):
-            raise ValueError("SharedModel surrogate: None (the GP), 'forest' or 'tpe'")
+        # "gbt" = a gradient-boosted tree ensemble fitted on the device
+        # (engine.gbt_fit, csrc/gbt_fit.hip: the reference's own model,
+        # plugins/xgbregressor.py), refitted from the same usable rows, features
+        # and y_transform at the same moments, its draws keyed by the fit
+        # counter; candidates are ranked by the predicted objective
+        # (engine.forest_predict), which has no variance and takes no
+        # acquisition.  gbt_kw: engine.gbt_fit's parameters, the reference's by
+        # default.
+        if surrogate not in (None,) + _REFIT:
+            raise ValueError("SharedModel surrogate: None (the GP), 'forest', 'tpe' or 'gbt'")
         if surrogate is not None and (self.feasibility is not None or self.constraints):
             raise ValueError("feasibility and constraints weight the GP's EI: not with a %s surrogate"
                              % _surrogate_word(surrogate))
@@ -381,6 +393,13 @@ class SharedModel:
             unknown = sorted(set(self.tpe_kw) - set(_TPE_KW))
             if unknown:
                 raise ValueError("tpe_kw: %s not among %s" % (unknown, sorted(_TPE_KW)))
+        self.gbt_kw = dict(gbt_kw or {})
+        if self.gbt_kw:
+            if surrogate != "gbt":
+                raise ValueError("gbt_kw belongs to surrogate='gbt'")
+            unknown = sorted(set(self.gbt_kw) - set(_GBT_KW))
+            if unknown:
+                raise ValueError("gbt_kw: %s not among %s" % (unknown, sorted(_GBT_KW)))
         # forest_fit: "host" = the sklearn fit above; "device" = the forest is
         # grown by the engine (engine.forest_fit, csrc/forest_fit.hip: 256-bin
         # histogram trees, bootstrap and feature draws from the context's seed
@@ -668,6 +687,24 @@ class SharedModel:
         self.fits += 1
         return True
 
+    def _fit_gbt(self, rows, ids) -> bool:
+        """surrogate="gbt": refit the boosted ensemble iff the usable results changed"""
+        import time
+
+        key = (len(rows), ids[-1])
+        if key == self._fit_key:
+            return True
+        self._gather(rows, ids)
+        n = self._n
+        y = self._transform(self._ya[:n])
+        t0 = time.perf_counter()
+        self.engine.gbt_fit(self._Xa[:n], y, seed_round=self.fits % (1 << 24), **self.gbt_kw)
+        self.fit_seconds += time.perf_counter() - t0
+        self.f_best = float(np.min(y))
+        self._fit_key = key
+        self.fits += 1
+        return True
+
     def _fit_forest(self, rows, ids) -> bool:
         """surrogate="forest": refit the random forest iff the usable results changed"""
         import time
@@ -713,6 +750,8 @@ class SharedModel:
             return self._fit_forest(rows, ids)
         if self.surrogate == "tpe":
             return len(rows) >= 2 and self._fit_tpe(rows, ids)
+        if self.surrogate == "gbt":
+            return self._fit_gbt(rows, ids)
         if self._fit_unverified and self._fit_key is not None:
             # the previous fit ran asynchronously (no host wait when it was
             # enqueued): a kernel matrix that was not positive definite would
@@ -1005,26 +1044,32 @@ class GpuBatchTechnique(SearchTechnique):
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  forest_kw: Optional[Dict[str, Any]] = None, polish: int = 0, polish_pool: Optional[int] = None,
                  ts_features: int = 1024, objectives=None, ref_point=None, forest_fit: str = "host",
-                 tpe_kw: Optional[Dict[str, Any]] = None, *pargs, **kwargs):
+                 tpe_kw: Optional[Dict[str, Any]] = None, gbt_kw: Optional[Dict[str, Any]] = None,
+                 *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
         # surrogate="forest" (SharedModel): a random forest refitted from the
         # driver's results, scored by EI / UCB on its mean and variance over
         # trees.  A shared model carries its own setting (and forest_kw)
         # surrogate="tpe" (SharedModel): the Parzen estimator, refitted the same
-        # way and ranked by log l - log g; word names the model in the refusals
-        refit = surrogate if isinstance(surrogate, str) and surrogate in ("forest", "tpe") else None
+        # way and ranked by log l - log g; surrogate="gbt" (SharedModel): the
+        # boosted ensemble fitted on the device, ranked by its prediction; word
+        # names the model in the refusals
+        refit = surrogate if isinstance(surrogate, str) and surrogate in _REFIT else None
         if shared is not None:
             if refit and shared.surrogate != refit:
                 raise ValueError("surrogate='%s' with a shared model that fits %s" % (
                     refit, "a GP" if shared.surrogate is None else "surrogate='%s'" % shared.surrogate))
             if surrogate is not None and not refit and shared.surrogate is not None:
                 raise ValueError("a model object as surrogate with a shared model that refits a %s"
-                                 % ("forest" if shared.surrogate == "forest" else "TPE"))
+                                 % {"forest": "forest", "tpe": "TPE"}.get(shared.surrogate, shared.surrogate))
             refit = shared.surrogate
         tree = refit is not None or surrogate is not None
         word = _surrogate_word(refit)
         if refit == "tpe" and acq == "ucb":
             raise ValueError("acq='ucb' needs a posterior variance, TPE has none: not with a TPE surrogate")
+        if refit == "gbt" and acq == "ucb":
+            raise ValueError("acq='ucb' needs a posterior variance, a boosted ensemble has none: not with a gbt "
+                             "surrogate")
         # prune_weighted (SharedModel): pruned rounds under constraints / feasibility,
         # by the weighted bound of ut_gp_set_prune_weighted.  A shared model carries its own
         weighted = shared.prune_weighted if shared is not None else bool(prune_weighted)
@@ -1157,7 +1202,7 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    surrogate=refit,
                                                                    forest_kw=forest_kw, objectives=objectives,
                                                                    ref_point=ref_point, forest_fit=forest_fit,
-                                                                   tpe_kw=tpe_kw)
+                                                                   tpe_kw=tpe_kw, gbt_kw=gbt_kw)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -1251,6 +1296,8 @@ class GpuBatchTechnique(SearchTechnique):
             _, _, score = eng.forest_score(eng.encode(vals), eng.acq(self.acq_kind), self.model.f_best, dup=dup)
         elif have_model and self.model.surrogate == "tpe":
             score = eng.tpe_score(eng.encode(vals), dup=dup)
+        elif have_model and self.model.surrogate == "gbt":
+            _, score = eng.forest_predict(eng.encode(vals), dup=dup)
         elif have_model:
             if self.prune_rows > 0 and self.model.precision == 64:
                 idx, top, _ = eng.gp_topk_pruned(eng.encode(vals), self.batch, acq=eng.acq(self.acq_kind), dup=dup,
@@ -1625,9 +1672,10 @@ def _shared_model(kw) -> SharedModel:
                        feasibility=kw.get("feasibility", False), constraints=kw.get("constraints"),
                        prune_weighted=kw.get("prune_weighted", False),
                        surrogate=kw["surrogate"] if isinstance(kw.get("surrogate"), str)
-                       and kw["surrogate"] in ("forest", "tpe") else None, forest_kw=kw.get("forest_kw"),
+                       and kw["surrogate"] in _REFIT else None, forest_kw=kw.get("forest_kw"),
                        objectives=kw.get("objectives"), ref_point=kw.get("ref_point"),
-                       forest_fit=kw.get("forest_fit", "host"), tpe_kw=kw.get("tpe_kw"))
+                       forest_fit=kw.get("forest_fit", "host"), tpe_kw=kw.get("tpe_kw"),
+                       gbt_kw=kw.get("gbt_kw"))
 
 
 def _tr_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:

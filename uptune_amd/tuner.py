@@ -41,7 +41,8 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                 constraints=None, prune_weighted: bool = False, surrogate=None,
                 forest_kw=None, polish: int = 0, polish_pool: Optional[int] = None,
                 trust_region: bool = False, acq: str = "ei", ts_features: int = 1024, objectives=None,
-                ref_point=None, driver_objective=None, forest_fit: str = "host", tpe_kw=None) -> SearchDriver:
+                ref_point=None, driver_objective=None, forest_fit: str = "host", tpe_kw=None,
+                gbt_kw=None) -> SearchDriver:
     """Run the bandit for `generations` generations; returns the driver (results,
     best_result, bandit statistics).  With torch.distributed initialised and
     world > 1 the run is SPMD: call it on every rank with the same arguments.
@@ -56,6 +57,9 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
     refitted with the results, and rank by log l - log g (SharedModel; tpe_kw:
     gamma, n_good_max, prior_weight, precision).  A fit takes at most 8,192
     results: beyond that, the best 4,096 and the most recent of the others.
+    surrogate="gbt": the children share one gradient-boosted tree ensemble fitted
+    on the device with the results and rank by its prediction (SharedModel;
+    gbt_kw: engine.gbt_fit's parameters, the reference's XGBRegressor settings by default).
     polish=T > 0: every dense GP round refines its polish_pool best candidates
     with T gradient-ascent steps on the acquisition first (GpuBatchTechnique).
     trust_region=True: a fifth arm proposes inside a trust region around the best
@@ -84,6 +88,7 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                             constraints=constraints, prune_weighted=prune_weighted, surrogate=surrogate,
                             forest_kw=forest_kw, **({"forest_fit": forest_fit} if forest_fit != "host" else {}),
                             **({"tpe_kw": tpe_kw} if tpe_kw is not None else {}),
+                            **({"gbt_kw": gbt_kw} if gbt_kw is not None else {}),
                             polish=polish, polish_pool=polish_pool, acq=acq,
                             **({"ts_features": ts_features} if acq == "ts" else {}),
                             **({"trust_region": True} if trust_region else {}), **mo_kw)
