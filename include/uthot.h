@@ -262,6 +262,54 @@ int ut_propose_tr(ut_ctx* ctx, const ut_tr_params* p, const double* centre, cons
                   uint32_t round_, int64_t cand_base, int64_t m, double* out_values, int64_t ld,
                   uint8_t* out_invalid);
 
+/* Correlated-Gaussian proposals (the sampling step of CMA-ES, Hansen; the mean,
+ * step size and covariance are kept on the host by uptune_amd/cma.py): every
+ * candidate is one draw of N(mean, sigma^2 A A^T) over the unit values of the
+ * moving primitive parameters, folded into [0, 1] by mirroring.
+ *
+ * dn counts the moving primitive parameters: FLOAT, INT, LOGINT and POW2 with
+ * lo < hi, in parameter order; feature j is the j-th of them.  Inputs: centre c
+ * (device row of ncols SoA values, as ut_propose_tr's), mean_host [dn] and
+ * factor_host [dn][dn] (host, row-major A, unit space, any dense matrix),
+ * sigma > 0, and cat_prob, the perturbation probability of BOOL / ENUM / PERM.
+ *
+ * Candidate g = cand_base + i is a function of (seed, g, round_) and the
+ * arguments alone, so any split of [cand_base, cand_base + m) over calls or
+ * ranks gives the same rows, bit for bit.  Draws use op code OP_CMA = 10.
+ *   z_k = normal_draw(seed, g, k | 1 << 28, round_, OP_CMA),  k = 0 .. dn - 1
+ *         (ut_core.h: the polar method over counter draws, bit-reproducible)
+ *   x_j = mean_j + sigma * sum_k A[j][k] * z_k
+ *         (the sum runs on the fp64 matrix unit in an order of its own; the
+ *         scale and the add are rounded once each: |x_j - exact| <=
+ *         (dn + 4) 2^-53 (|mean_j| + sigma sum_k |A[j][k]| |z_k|))
+ *   u_j = fold(x_j):  t = x - 2 floor(x / 2);  u = t > 1 ? 2 - t : t
+ *         (mirroring at 0 and 1: continuous, 1-Lipschitz, even; it is evaluated
+ *         on |x_j|, where every step is exact in floating point)
+ *   v_j = set_unit_value(u_j) + 0.0 in the column of feature j's parameter
+ *         (+ 0.0 as in ut_propose_tr)
+ * A primitive parameter with lo == hi keeps the centre's value.  For p a BOOL,
+ * ENUM or PERM parameter: A = draw(seed, g, p, round_, OP_CMA); p is selected
+ * iff (double)A.z * 2^-32 < cat_prob (there is no `must`); a selected p moves
+ * by ut_propose_tr's rule for its kind from the draw site
+ * (seed, g, p | 1 << 28, round_, OP_CMA); an unselected p keeps the centre's
+ * value(s), bit for bit.
+ * out_invalid[i] = 1 when row i equals the centre bit for bit in every column.
+ * out_unit (optional, device [dn][ld]): out_unit[j * ld + i] = u_j.
+ *
+ * UT_EINVAL: a NULL argument other than out_unit; sigma not finite or <= 0;
+ * cat_prob outside [0, 1]; dn outside [1, 128] or not the space's count; a
+ * non-finite entry of mean_host or factor_host; m < 0, cand_base < 0, ld < m.
+ * UT_ENOSPACE before ut_space_define.  No kernel runs on a refused call. */
+typedef struct ut_cma_params {
+  double sigma;
+  double cat_prob;
+  int32_t dn;
+  int32_t pad;
+} ut_cma_params;
+int ut_propose_cma(ut_ctx* ctx, const ut_cma_params* p, const double* centre, const double* mean_host,
+                   const double* factor_host, uint32_t round_, int64_t cand_base, int64_t m, double* out_values,
+                   int64_t ld, uint8_t* out_invalid, double* out_unit);
+
 /* GP features of configurations: unit values (get_unit_value), BOOL 0/1,
  * ENUM one-hot, PERM position of each item / (size - 1).  out_features[f * ld_out + i]. */
 int ut_encode_features(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, double* out_features,

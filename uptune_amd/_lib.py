@@ -92,6 +92,10 @@ class TrParams(C.Structure):
     _fields_ = [("prob", C.c_double), ("cat_prob", C.c_double), ("must", C.c_int32), ("pad", C.c_int32)]
 
 
+class CmaParams(C.Structure):
+    _fields_ = [("sigma", C.c_double), ("cat_prob", C.c_double), ("dn", C.c_int32), ("pad", C.c_int32)]
+
+
 class GpHyper(C.Structure):
     _fields_ = [("sigma_f2", C.c_double), ("sigma_n2", C.c_double), ("jitter", C.c_double),
                 ("lengthscale_host", C.c_void_p)]
@@ -157,6 +161,7 @@ SIGNATURES = {
     "ut_pso_update_best": (C.c_int, [P, P, I64, P, I64]),
     "ut_propose_ga": (C.c_int, [P, C.POINTER(GaParams), P, P, U32, I64, I64, P, I64, P]),
     "ut_propose_tr": (C.c_int, [P, C.POINTER(TrParams), P, P, U32, I64, I64, P, I64, P]),
+    "ut_propose_cma": (C.c_int, [P, C.POINTER(CmaParams), P, P, P, U32, I64, I64, P, I64, P, P]),
     "ut_encode_features": (C.c_int, [P, P, I64, I64, P, I64]),
     "ut_hash": (C.c_int, [P, P, I64, I64, P]),
     "ut_history_reset": (C.c_int, [P, I64]),

@@ -94,6 +94,7 @@ enum : uint32_t {
   OP_TS = 7,   // Thompson-sampling path draws (gp_ts.hip; uthot.h states the streams)
   OP_RF = 8,   // the forest fit's bootstrap and feature draws (forest_fit.hip; uthot.h states the streams)
   OP_GBT = 9,  // the boosted fit's row-sample and per-level feature draws (gbt_fit.hip; uthot.h states the streams)
+  OP_CMA = 10, // the correlated-Gaussian proposals' normals and categorical moves (propose_cma.hip; uthot.h)
 };
 enum : uint32_t {
   STREAM_CAND = 0xFFFF0000u,   // per-candidate draws: STREAM_CAND | k

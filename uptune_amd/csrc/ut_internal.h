@@ -459,6 +459,9 @@ struct ut_ctx {
   ut::DevBuf<uint32_t> tk_wcnt;     // top-k selection: ties of the threshold key per workgroup
   ut::DevBuf<int64_t> r_topk_idx;
   ut::DevBuf<double> tr_box;     // [3][P] trust-region call: half-widths h | box faces lo | hi (propose_tr.hip)
+  ut::DevBuf<double> cma_in;     // [dn][dn] factor | [dn] mean of a ut_propose_cma call (propose_cma.hip)
+  ut::DevBuf<int32_t> cma_lists; // [P] the moving primitive parameters in order, then every other parameter
+  std::vector<int32_t> cma_lists_host;   // ... its host copy (the same content on every call over one space)
   ut::DevBuf<double> perm_ws;    // [2 * perm_cols + 3 * perm_smax][ld]: GA parents + crossover scratch
   ut::DevBuf<uint32_t> perm_dig; // [n_perm][m][8] inner digests of PERM values (hash pre-pass)
   ut::DevBuf<double> r_topk_score;

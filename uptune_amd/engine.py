@@ -229,6 +229,27 @@ class BatchEngine:
                                                  int(cand_base), int(m), _ptr(out), m, _ptr(inv)), "ut_propose_tr")
         return out, inv
 
+    def propose_cma(self, m: int, centre, mean, factor, sigma: float, cat_prob: float = 0.0, round_: int = 0,
+                    cand_base: int = 0, with_unit: bool = True):
+        """Correlated-Gaussian proposals (ut_propose_cma): candidates mean + sigma * factor @ z,
+        z ~ N(0, I), over the unit values of the moving primitive parameters (cma.moving_params),
+        mirrored into [0, 1]; BOOL / ENUM / PERM move with `cat_prob`, everything else keeps
+        `centre`'s value.  Returns (values [ncols][m], invalid [m], unit points [dn][m] or None)."""
+        c = self._row(centre)
+        mu = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        A = np.ascontiguousarray(factor, dtype=np.float64)
+        dn = mu.size
+        if A.shape != (dn, dn):
+            raise ValueError(f"factor has shape {A.shape} for a mean of {dn} entries")
+        out = self._empty(self.spec.ncols, m)
+        inv = self._empty(m, dtype=torch.uint8)
+        unit = self._empty(dn, m) if with_unit else None
+        a = L.CmaParams(sigma=float(sigma), cat_prob=float(cat_prob), dn=int(dn))
+        L.check(self.ctx, self.lib.ut_propose_cma(self.ctx, C.byref(a), _ptr(c), C.c_void_p(mu.ctypes.data),
+                                                  C.c_void_p(A.ctypes.data), int(round_), int(cand_base), int(m),
+                                                  _ptr(out), m, _ptr(inv), _ptr(unit)), "ut_propose_cma")
+        return out, inv, unit
+
     def encode(self, values: torch.Tensor, m: Optional[int] = None) -> torch.Tensor:
         m = values.shape[1] if m is None else m
         feat = self._empty(self.spec.n_features, m)

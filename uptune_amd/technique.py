@@ -1665,6 +1665,106 @@ class GpuTrustRegion(GpuBatchTechnique):
             self._own_best = result
 
 
+class GpuCMAES(GpuBatchTechnique):
+    """CMA-ES proposals (Hansen; cma.CMAState keeps the mean, the step size and the
+    covariance): every round draws its pool from N(mean, sigma^2 C) over the unit
+    values of the moving primitive parameters (ut_propose_cma) around the driver's
+    best result, whose values every other column keeps unless cat_prob moves it.
+    preselect=True (default): the shared surrogate ranks the pool and its top
+    `batch` rows are evaluated (model-assisted pre-selection, Ulmer et al. 2003);
+    preselect=False draws exactly `batch` rows, which is plain CMA-ES.  The
+    evaluated results of a round are told to the state when the next one starts,
+    ranked among themselves.  Before any result exists the round is the uniform
+    one GpuTrustRegion takes.  Off by default everywhere: cma=True on the bandits
+    adds it as an arm.  Spaces with no moving primitive parameter, or with more
+    than 128 (a diagonal covariance is not built), are refused."""
+
+    sharded = False   # every rank draws the same pool and tells the same results: one state, replicated
+
+    def __init__(self, sigma0: float = 0.3, sigma_min: float = 2.0 ** -20, cat_prob: Optional[float] = None,
+                 preselect: bool = True, *pargs, **kwargs):
+        super().__init__(*pargs, **kwargs)
+        self.preselect = bool(preselect)
+        if not self.preselect:
+            self.pool = self.batch
+        self.sigma0, self.sigma_min, self.cat_prob = float(sigma0), float(sigma_min), cat_prob
+        self.cma = None                          # cma.CMAState, from the first round with a result on
+        self._moving: List[int] = []             # the parameters the state samples (init_population)
+        self._pending: Dict[str, Any] = {}       # request digest -> its unit point [dn]
+        self._arrived: List[Any] = []            # (Result, unit point) not yet told
+        self._parent = self._unit = None
+        self._base = 0
+        self.last_uniform = False
+
+    def init_population(self):
+        # no standing population: a uniform round draws its own rows
+        from .cma import MAX_DN, moving_params
+        self._moving = moving_params(self.engine.spec)
+        dn = len(self._moving)
+        if dn == 0:
+            raise ValueError("GpuCMAES: the space has no primitive parameter with lo < hi to sample")
+        if dn > MAX_DN:
+            raise ValueError("GpuCMAES: %d moving primitive parameters, the full covariance is built for at most %d"
+                             % (dn, MAX_DN))
+
+    def _tell_arrived(self):
+        import functools
+        if self.cma is None or len(self._arrived) < 2:
+            return
+        lt = self.objective.lt
+        key = functools.cmp_to_key(lambda a, b: -1 if lt(a[0], b[0]) else (1 if lt(b[0], a[0]) else 0))
+        ranked = sorted(self._arrived, key=key)
+        self._arrived = []
+        self.cma.tell(np.stack([u for _, u in ranked], axis=1), np.arange(len(ranked)))
+
+    def propose(self, m):
+        from .cma import CMAState
+        eng = self.engine
+        self._tell_arrived()
+        ref = self.driver.best_result
+        self.last_uniform = ref is None
+        self._base = self.round_base()
+        if ref is None:
+            eng.population_init(max(m, 4), round_=self.round)
+            self._parent = self._unit = None
+            return eng.population_get()[:, :m].contiguous(), None
+        centre = eng.spec.encode_configs([ref.configuration.data])[:, 0]
+        if self.cma is None:
+            self.cma = CMAState(len(self._moving), self.batch, sigma0=self.sigma0, sigma_min=self.sigma_min)
+            feat = eng.features_host([ref.configuration.data])[0]
+            self.cma.mean = np.array([feat[eng.spec.params[p].feat_col] for p in self._moving], dtype=np.float64)
+        mean, sigma, A = self.cma.ask()
+        cat = self.cat_prob
+        if cat is None:   # about one BOOL / ENUM / PERM move per candidate, fewer as the step shrinks
+            cat = min(1.0, sigma / self.sigma0) / max(1, eng.spec.P - len(self._moving))
+        self._parent = centre
+        vals, inv, self._unit = eng.propose_cma(m, centre, mean, A, sigma, cat, round_=self.round,
+                                                cand_base=self._base)
+        return vals, inv
+
+    def hash_proposals(self, vals, base):
+        # the columns outside the sample keep the centre's value: reuse its inner digests
+        hp = getattr(self.engine, "hash_parent", None)
+        if self._parent is None or hp is None:
+            return self.engine.hash(vals)
+        return hp(vals, self._parent)
+
+    def after_round(self, idx, hexes):
+        if self._unit is None or not len(hexes):
+            return
+        import torch
+        loc = torch.as_tensor(np.asarray(idx, dtype=np.int64) - self._base, device=self._unit.device)
+        U = self._unit[:, loc].cpu().numpy()
+        for j, hx in enumerate(hexes):
+            self._pending[hx] = U[:, j].copy()
+        self._unit = None
+
+    def handle_requested_result(self, result):
+        u = self._pending.pop(result.configuration.hash, None)
+        if u is not None:
+            self._arrived.append((result, u))
+
+
 def _shared_model(kw) -> SharedModel:
     return SharedModel(device=kw.get("device", 0), seed=kw.get("seed", 0), lengthscale=kw.get("lengthscale", 0.3),
                        min_train=kw.get("min_train", 4), precision=kw.get("precision", 64),
@@ -1683,22 +1783,28 @@ def _tr_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:
     return [GpuTrustRegion(name="gpu-trust-region", shared=shared, **kw)] if on else []
 
 
+def _cma_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:
+    """the bandits' opt-in CMA-ES arm (cma=True)"""
+    return [GpuCMAES(name="gpu-cma-es", shared=shared, **kw)] if on else []
+
+
 def pso_ga_de_bandit(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
     """GPU counterpart of the reference's "PSO_GA_DE" bandit (bandittechniques.py:311-320):
     the four techniques share ONE SharedModel (one device context: one GP fit
     per generation, one dedup set) with a population slot each.  bandit_seed
     fixes the bandit's tie-break shuffles (required for SPMD runs: every rank
     must order the techniques the same way).  trust_region=True adds a
-    GpuTrustRegion arm on the same model."""
+    GpuTrustRegion arm on the same model, cma=True a GpuCMAES arm."""
     kw = dict(kw)
     tr = bool(kw.pop("trust_region", False))
+    cma = bool(kw.pop("cma", False))
     shared = kw.pop("shared", None) or _shared_model(kw)
     return AUCBanditMetaTechnique([
         GpuPSO(name="gpu-pso", shared=shared, **kw),
         GpuGA(name="gpu-ga", crossover_rate=0.5, shared=shared, **kw),
         GpuDifferentialEvolution(name="gpu-de", shared=shared, **kw),
         GpuGGA(name="gpu-gga", shared=shared, **kw),
-    ] + _tr_arm(tr, shared, kw), name="GPU_PSO_GA_DE", seed=bandit_seed)
+    ] + _tr_arm(tr, shared, kw) + _cma_arm(cma, shared, kw), name="GPU_PSO_GA_DE", seed=bandit_seed)
 
 
 def bandit_a(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
@@ -1710,28 +1816,31 @@ def bandit_a(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
     sequential simplex technique outside the scoring path (DESIGN.md "Out of
     scope") and is not built; polish=T (GpuBatchTechnique) is the local search
     that stands in for it.  trust_region=True adds a GpuTrustRegion arm, a local
-    search that stays batch-parallel, in that fourth slot."""
+    search that stays batch-parallel, in that fourth slot; cma=True adds a
+    GpuCMAES arm."""
     kw = dict(kw)
     tr = bool(kw.pop("trust_region", False))
+    cma = bool(kw.pop("cma", False))
     shared = kw.pop("shared", None) or _shared_model(kw)
     return AUCBanditMetaTechnique([
         GpuDifferentialEvolution(name="gpu-de-alt", cr=0.2, shared=shared, **kw),
         GpuGA(name="gpu-uniform-greedy-mutation", mutation_rate=0.1, shared=shared, **kw),
         GpuGA(name="gpu-normal-greedy-mutation", mutation_rate=0.3, normal=True, shared=shared, **kw),
-    ] + _tr_arm(tr, shared, kw), name="GpuAUCBanditMetaTechniqueA", seed=bandit_seed)
+    ] + _tr_arm(tr, shared, kw) + _cma_arm(cma, shared, kw), name="GpuAUCBanditMetaTechniqueA", seed=bandit_seed)
 
 
 def bandit_b(bandit_seed: Optional[int] = None, **kw) -> AUCBanditMetaTechnique:
     """"AUCBanditMetaTechniqueB" (bandittechniques.py:279-282): DifferentialEvolutionAlt
     and UniformGreedyMutation on one shared model (trust_region=True: and a
-    GpuTrustRegion arm)"""
+    GpuTrustRegion arm; cma=True: and a GpuCMAES arm)"""
     kw = dict(kw)
     tr = bool(kw.pop("trust_region", False))
+    cma = bool(kw.pop("cma", False))
     shared = kw.pop("shared", None) or _shared_model(kw)
     return AUCBanditMetaTechnique([
         GpuDifferentialEvolution(name="gpu-de-alt", cr=0.2, shared=shared, **kw),
         GpuGA(name="gpu-uniform-greedy-mutation", mutation_rate=0.1, shared=shared, **kw),
-    ] + _tr_arm(tr, shared, kw), name="GpuAUCBanditMetaTechniqueB", seed=bandit_seed)
+    ] + _tr_arm(tr, shared, kw) + _cma_arm(cma, shared, kw), name="GpuAUCBanditMetaTechniqueB", seed=bandit_seed)
 
 
 _XO = ("op3_cross_OX3", "op3_cross_OX1", "op3_cross_PMX", "op3_cross_PX", "op3_cross_CX")
@@ -1760,10 +1869,12 @@ def reference_registry(wrap=None, bandit_cls=None, **kw) -> List[SearchTechnique
     bandit.  `kw` goes to every technique (pool, batch, device, seed, ...).  The
     DE population size is the device population (`population=`), not 30 / 100:
     every member is scored each round.  trust_region=True appends a stand-alone
-    GpuTrustRegion (an addition of this library: the reference has none)."""
+    GpuTrustRegion, cma=True a stand-alone GpuCMAES (additions of this
+    library: the reference has neither)."""
     W = wrap or (lambda c: c)
     kw = dict(kw)
     tr = bool(kw.pop("trust_region", False))
+    cma = bool(kw.pop("cma", False))
     ef = kw.get("engine_factory")
     sm = _shared_model(kw)          # the bandit's children share one model (pops engine_factory; every
     #                                 technique, stand-alone or not, gets the requested precision)
@@ -1801,4 +1912,6 @@ def reference_registry(wrap=None, bandit_cls=None, **kw) -> List[SearchTechnique
         out.append((bandit_cls or AUCBanditMetaTechnique)(kids, name=nm))
     if tr:
         out.append(W(GpuTrustRegion)(name="GpuTrustRegion", **kw))
+    if cma:
+        out.append(W(GpuCMAES)(name="GpuCMAES", **kw))
     return out

@@ -40,7 +40,7 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                 precision: int = 64, prune_rows: int = 0, diversify: int = 0, feasibility=False,
                 constraints=None, prune_weighted: bool = False, surrogate=None,
                 forest_kw=None, polish: int = 0, polish_pool: Optional[int] = None,
-                trust_region: bool = False, acq: str = "ei", ts_features: int = 1024, objectives=None,
+                trust_region: bool = False, cma: bool = False, acq: str = "ei", ts_features: int = 1024, objectives=None,
                 ref_point=None, driver_objective=None, forest_fit: str = "host", tpe_kw=None,
                 gbt_kw=None) -> SearchDriver:
     """Run the bandit for `generations` generations; returns the driver (results,
@@ -64,6 +64,8 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
     with T gradient-ascent steps on the acquisition first (GpuBatchTechnique).
     trust_region=True: a fifth arm proposes inside a trust region around the best
     result (GpuTrustRegion).
+    cma=True: a further arm draws its pools from a Gaussian whose mean, step size
+    and covariance follow its own evaluated results (GpuCMAES).
     acq="ucb" / "ts": the children's acquisition; "ts" = Thompson sampling, one
     posterior sample path of ts_features random features per batch slot
     (GpuBatchTechnique).
@@ -91,7 +93,8 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                             **({"gbt_kw": gbt_kw} if gbt_kw is not None else {}),
                             polish=polish, polish_pool=polish_pool, acq=acq,
                             **({"ts_features": ts_features} if acq == "ts" else {}),
-                            **({"trust_region": True} if trust_region else {}), **mo_kw)
+                            **({"trust_region": True} if trust_region else {}),
+                            **({"cma": True} if cma else {}), **mo_kw)
     if world > 1 and objectives:
         raise ValueError("objectives: the ranks exchange one measurement per result: two objectives run on one rank")
     if world > 1:
