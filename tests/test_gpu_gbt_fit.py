@@ -105,6 +105,30 @@ def test_fit_equals_the_restatement(name):
     np.testing.assert_array_equal(pred.cpu().numpy().view(np.int64), acc.view(np.int64))
 
 
+def test_forest_and_boosted_fits_share_scratch_in_any_order():
+    """The two fits stage through one function (csrc/tree_fit.h) into the same scratch: forest 120 x 5, boosted
+    64 x 40, boosted 50 x 3, forest 120 x 5 again on one engine, d_pad and n shrinking and growing, so codes,
+    candidates or row lists left by the fit before would show.  Every result equals its restatement."""
+    e = _engine()
+    Xf, yf = _data("uniform", 120, 5)
+    want_forest = RF.fit(Xf, yf, SEED, n_trees=3)
+    got_forest = []
+    for name in (None, "three_blocks", "smallest", None):
+        if name is None:
+            e.forest_fit(Xf, yf, n_trees=3)
+            want_roots, want = want_forest
+        else:
+            kind, n, d, kw = CASES[name]
+            X, y = _data(kind, n, d)
+            e.gbt_fit(X, y, seed_round=3, **kw)
+            want_roots, want, _ = GB.fit(X, y, SEED, seed_round=3, **kw)
+        roots, nodes = e.forest_get()
+        _assert_records_equal(roots, nodes, want_roots, want)
+        if name is None:
+            got_forest.append((roots.tobytes(), nodes.tobytes()))
+    assert got_forest[0] == got_forest[1]
+
+
 def test_refusals_keep_the_loaded_ensemble_and_fits_repeat():
     from uptune_amd import _lib as L
     X, y = _data("uniform", 120, 5)

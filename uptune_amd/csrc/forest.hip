@@ -63,6 +63,23 @@ int forest_host_fetch(ut_ctx* c) {
   return 0;
 }
 
+// an ensemble grown on the device (records with children by global index, LT
+// splits) becomes the loaded one; the buffers leave with the old one's memory
+int forest_install(ut_ctx* c, DevBuf<ut_tree_node>& nodes, int32_t n_nodes, DevBuf<int32_t>& roots, int32_t n_trees,
+                   int32_t max_feat, double base, double scale, double div) {
+  UT_HIP(c, sync_all(c));   // a scoring kernel still queued reads the old records
+  c->forest_nodes.swap(nodes);
+  c->forest_roots.swap(roots);
+  c->forest_trees = n_trees;
+  c->forest_rule = UT_SPLIT_LT;
+  c->forest_max_feat = max_feat;
+  c->forest_base = base, c->forest_scale = scale, c->forest_div = div;
+  c->forest_n_nodes = n_nodes;
+  c->forest_host.clear();
+  c->forest_host_valid = false;
+  return 0;
+}
+
 }  // namespace ut
 
 extern "C" int ut_forest_set(ut_ctx* c, int32_t n_trees, const int32_t* roots_host, int64_t n_nodes,

@@ -11,17 +11,9 @@
 //
 // Trees grow level by level, all trees at once; a level's nodes are a
 // contiguous index range per tree (breadth first), one launch each of
-//   k_rf_hist       (tree, node of the level, feature block): 4 waves.  The
-//                   block's (W: u32, Q1: i64) histograms live in LDS (RF_F = 16
-//                   features x 256 bins x 12 B = 48 KiB, three workgroups per
-//                   CU).  A wave takes 4 rows x 16 features per step: a lane
-//                   reads one code byte of its row (16 contiguous bytes per
-//                   row, row-major codes) and issues two return-less LDS
-//                   atomics.  Then wave w scans features w, w + 4, ..: 4 bins
-//                   per lane, a shuffle scan across the lanes, the gain at the
-//                   occupied bins only (an empty bin repeats its left
-//                   neighbour's gain and loses the tie), a butterfly reduction
-//                   of (s, b).  One candidate per (node, block) leaves the CU.
+//   k_rf_hist       (tree, node of the level, feature block): the histogram
+//                   block of tree_fit.h over the node's rows, each adding
+//                   (w, w q).  One candidate per (node, block) leaves the CU.
 //   k_rf_split      one workgroup per tree: reduces the level's candidates,
 //                   numbers the children by a scan of the split flags in node
 //                   order, writes the records of the nodes that split or end.
@@ -33,13 +25,12 @@
 // The host reads one word per level (the widest next level: the next grid, 0 =
 // done).  k_rf_offsets / k_rf_compact then lay the trees out contiguously.
 #include "ut_internal.h"
-#include "rf_codes.h"   // rf_code, rf_better: shared with gbt_fit.hip
+#include "tree_fit.h"   // what gbt_fit.hip shares: the codes, the histogram block, the host half
 
 namespace ut {
 
-constexpr int32_t RF_F = 16;         // features per histogram block
 constexpr int32_t RF_MAX_FB = 64;    // workgroups per node; more feature blocks are strided over them
-constexpr int32_t RF_NT = 256;
+constexpr int32_t RF_NT = TREE_NT;
 
 struct RfParams {
   int32_t n, d, d_pad, n_pad, T, min_leaf;
@@ -59,9 +50,7 @@ constexpr int32_t RF_CTL_W = 2;
 __host__ __device__ inline int32_t rf_ctl_tree(int32_t max_level, int32_t t) { return RF_CTL_W + max_level + 2 + 5 * t; }
 
 __device__ __forceinline__ int32_t rf_quant(double y, double shift, double scale) {
-  double z = (y - shift) / scale;
-  z = z < -32.0 ? -32.0 : (z > 32.0 ? 32.0 : z);
-  return (int32_t)nearbyint(z * 65536.0);
+  return (int32_t)nearbyint(tree_norm(y, shift, scale) * 65536.0);
 }
 
 // a node's mean and variance in the caller's units; a leaf's threshold field is its variance
@@ -85,11 +74,9 @@ __device__ __forceinline__ bool rf_closed(const RfParams& p, uint32_t W, int32_t
 
 __device__ __forceinline__ bool rf_eligible(const RfParams& p, int32_t t, int32_t node, int32_t j) {
   if (p.feature_frac >= 1.0) return true;
-  const u32x4 r = draw(p.seed, ((uint64_t)(uint32_t)node << 32) | (uint32_t)(j >> 2), 0x10000u | (uint32_t)t, p.round_,
-                       OP_RF);
-  const uint32_t k = (uint32_t)j & 3u;
-  const uint32_t word = k == 0 ? r.x : (k == 1 ? r.y : (k == 2 ? r.z : r.w));
-  return (double)word * (1.0 / 4294967296.0) < p.feature_frac;
+  return tree_draw_below(draw(p.seed, ((uint64_t)(uint32_t)node << 32) | (uint32_t)(j >> 2), 0x10000u | (uint32_t)t,
+                              p.round_, OP_RF),
+                         (uint32_t)j, p.feature_frac);
 }
 
 // ---- prepare ---------------------------------------------------------------
@@ -99,13 +86,7 @@ __global__ __launch_bounds__(RF_NT) void k_rf_prepare(RfParams p, const double* 
                                                       uint8_t* __restrict__ fm, int32_t* __restrict__ q,
                                                       uint32_t* __restrict__ w) {
   const int64_t idx = (int64_t)blockIdx.x * RF_NT + threadIdx.x;
-  const int64_t total = (int64_t)p.n * p.d_pad;
-  if (idx < total) {
-    const int32_t row = (int32_t)(idx / p.d_pad), j = (int32_t)(idx % p.d_pad);
-    const uint8_t code = j < p.d ? rf_code(X[(int64_t)row * p.d + j]) : (uint8_t)0;
-    rm[idx] = code;
-    if (j < p.d) fm[(int64_t)j * p.n_pad + row] = code;
-  }
+  tree_codes(idx, p.n, p.d, p.d_pad, p.n_pad, X, rm, fm);
   if (idx < p.n) q[idx] = rf_quant(y[idx], p.y_shift, p.y_scale);
   const int64_t stride = (int64_t)gridDim.x * RF_NT, nw = (int64_t)p.T * p.n;
   const uint32_t w0 = p.bootstrap ? 0u : 1u;
@@ -197,88 +178,21 @@ __global__ __launch_bounds__(RF_NT) void k_rf_hist(RfParams p, int32_t level, co
                                                    const int32_t* __restrict__ rows, const uint8_t* __restrict__ rm,
                                                    const int32_t* __restrict__ q, const uint32_t* __restrict__ w,
                                                    RfCand* __restrict__ cand) {
-  __shared__ uint32_t hW[RF_F * 256];
-  __shared__ unsigned long long hQ[RF_F * 256];
-  __shared__ RfCand wbest[4];
+  __shared__ TreeHistLds lds;
   const int32_t t = blockIdx.z, pos = blockIdx.y;
   const int32_t* tc = ctl + rf_ctl_tree(p.max_level, t) + 2 * (level & 1);
   const int32_t node = tc[0] + pos;
   if (node >= tc[1]) return;
   const RfState st = state[(int64_t)t * p.cap + node];
   if (st.closed) return;
-  const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int32_t* list = rows + (int64_t)t * p.n + st.start;
   const uint32_t* wt = w + (int64_t)t * p.n;
-  const uint32_t ml = (uint32_t)p.min_leaf;
-  double bs = -1.0;
-  int32_t bj = p.d, bb = 256;
-  for (int32_t fb = blockIdx.x; fb < p.nfb; fb += gridDim.x) {
-    for (int32_t i = threadIdx.x; i < RF_F * 256; i += RF_NT) hW[i] = 0, hQ[i] = 0;
-    __syncthreads();
-    {
-      const int32_t f = lane & (RF_F - 1), j = fb * RF_F + f;
-      if (j < p.d) {
-        for (int32_t i = wave * 4 + (lane >> 4); i < st.count; i += 16) {
-          const int32_t row = list[i];
-          const uint32_t code = rm[(int64_t)row * p.d_pad + j];
-          const uint32_t wv = wt[row];
-          atomicAdd(&hW[f * 256 + code], wv);
-          atomicAdd(&hQ[f * 256 + code], (unsigned long long)((int64_t)wv * q[row]));
-        }
-      }
-    }
-    __syncthreads();
-    for (int32_t f = wave; f < RF_F; f += 4) {
-      const int32_t j = fb * RF_F + f;
-      if (j >= p.d || !rf_eligible(p, t, node, j)) continue;   // uniform over the wave
-      uint32_t hw[4], pw[4];
-      int64_t pq[4];
-#pragma unroll
-      for (int32_t k = 0; k < 4; ++k) {
-        hw[k] = hW[f * 256 + 4 * lane + k];
-        const int64_t hq = (int64_t)hQ[f * 256 + 4 * lane + k];
-        pw[k] = k ? pw[k - 1] + hw[k] : hw[k];
-        pq[k] = k ? pq[k - 1] + hq : hq;
-      }
-      uint32_t sw = pw[3];
-      long long sq = pq[3];
-#pragma unroll
-      for (int32_t o = 1; o < 64; o <<= 1) {
-        const uint32_t a = __shfl_up(sw, o);
-        const long long b = __shfl_up(sq, o);
-        if (lane >= o) sw += a, sq += b;
-      }
-      const uint32_t ew = sw - pw[3];
-      const int64_t eq = sq - pq[3];
-      double s = -1.0;
-      int32_t b = 256;
-#pragma unroll
-      for (int32_t k = 0; k < 4; ++k) {
-        const uint32_t WL = ew + pw[k], WR = st.W - WL;
-        if (hw[k] == 0 || 4 * lane + k > 254 || WL < ml || WR < ml) continue;
-        const double SL = (double)(eq + pq[k]), SR = (double)(st.Q1 - (eq + pq[k]));
-        const double a = SL * SL, c = SR * SR;
-        const double v = a / (double)WL + c / (double)WR;
-        if (v > s) s = v, b = 4 * lane + k;
-      }
-#pragma unroll
-      for (int32_t o = 32; o >= 1; o >>= 1) {
-        const double s2 = __shfl_xor(s, o);
-        const int32_t b2 = __shfl_xor(b, o);
-        if (s2 > s || (s2 == s && b2 < b)) s = s2, b = b2;
-      }
-      if (s >= 0.0 && rf_better(s, j, b, bs, bj, bb)) bs = s, bj = j, bb = b;
-    }
-    __syncthreads();   // the next block's clear
-  }
-  if (lane == 0) wbest[wave] = RfCand{bs, bj, bb};
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    RfCand r = wbest[0];
-    for (int32_t k = 1; k < 4; ++k)
-      if (rf_better(wbest[k].s, wbest[k].j, wbest[k].b, r.s, r.j, r.b)) r = wbest[k];
-    cand[((int64_t)t * p.width_cap + pos) * p.nfb_grid + blockIdx.x] = r;
-  }
+  // the gain is the boosted fit's at lambda = 0; no row of the list has w = 0
+  const RfCand r = tree_hist_best<false, false>(
+      lds, rows + (int64_t)t * p.n + st.start, st.count, rm, p.d, p.d_pad, p.nfb, (int32_t)blockIdx.x,
+      (int32_t)gridDim.x, st.W, st.Q1, (uint32_t)p.min_leaf, 0.0,
+      [&](int32_t row) { return TreeAdd{wt[row], (int64_t)wt[row] * q[row]}; },
+      [&](int32_t j) { return rf_eligible(p, t, node, j); });
+  if (threadIdx.x == 0) cand[((int64_t)t * p.width_cap + pos) * p.nfb_grid + blockIdx.x] = r;
 }
 
 // ---- the level's decisions, one workgroup per tree ---------------------------
@@ -421,42 +335,32 @@ extern "C" int ut_forest_fit(ut_ctx* c, const double* X_host, const double* y_ho
                              const ut_forest_fit_params* fp) {
   using namespace ut;
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, X_host && y_host && fp, UT_EINVAL, "forest_fit: X, y or the parameters are NULL");
-  UT_CHECK(c, n >= 1 && n <= 16384 && d >= 1 && d <= 4096, UT_EINVAL,
-           "forest_fit: n must be in [1, 16384] and d in [1, 4096]");
-  UT_CHECK(c, fp->n_trees >= 1 && fp->n_trees <= 256, UT_EINVAL, "forest_fit: n_trees must be in [1, 256]");
-  UT_CHECK(c, fp->min_leaf >= 1, UT_EINVAL, "forest_fit: min_leaf must be at least 1");
-  UT_CHECK(c, fp->max_depth >= 0 && fp->max_depth <= n, UT_EINVAL, "forest_fit: max_depth must be 0 or in [1, n]");
-  UT_CHECK(c, fp->bootstrap == 0 || fp->bootstrap == 1, UT_EINVAL, "forest_fit: bootstrap must be 0 or 1");
-  UT_CHECK(c, fp->feature_frac > 0.0 && fp->feature_frac <= 1.0, UT_EINVAL,
-           "forest_fit: feature_frac must be in (0, 1]");
-  UT_CHECK(c, __builtin_isfinite(fp->y_shift) && __builtin_isfinite(fp->y_scale) && fp->y_scale > 0.0, UT_EINVAL,
-           "forest_fit: y_shift must be finite and y_scale finite and positive");
-  UT_CHECK(c, fp->round_ < (1u << 24), UT_EINVAL, "forest_fit: round_ must be below 2^24");
-  for (int32_t i = 0; i < n; ++i)
-    UT_CHECK(c, __builtin_isfinite(y_host[i]), UT_EINVAL, "forest_fit: y[" + std::to_string(i) + "] is not finite");
+  if (int e = tree_fit_check(c, "forest_fit", X_host, y_host, n, d, fp, [&]() -> int {
+        UT_CHECK(c, fp->n_trees >= 1 && fp->n_trees <= 256, UT_EINVAL, "forest_fit: n_trees must be in [1, 256]");
+        UT_CHECK(c, fp->min_leaf >= 1, UT_EINVAL, "forest_fit: min_leaf must be at least 1");
+        UT_CHECK(c, fp->max_depth >= 0 && fp->max_depth <= n, UT_EINVAL,
+                 "forest_fit: max_depth must be 0 or in [1, n]");
+        UT_CHECK(c, fp->bootstrap == 0 || fp->bootstrap == 1, UT_EINVAL, "forest_fit: bootstrap must be 0 or 1");
+        UT_CHECK(c, fp->feature_frac > 0.0 && fp->feature_frac <= 1.0, UT_EINVAL,
+                 "forest_fit: feature_frac must be in (0, 1]");
+        return 0;
+      }))
+    return e;
 
   RfParams p;
   p.n = n, p.d = d, p.T = fp->n_trees, p.min_leaf = fp->min_leaf, p.bootstrap = fp->bootstrap;
-  p.d_pad = (d + RF_F - 1) / RF_F * RF_F;
-  p.n_pad = (n + 63) / 64 * 64;
   const int32_t leaves = std::max(1, n / p.min_leaf);
   p.max_level = std::min(fp->max_depth ? fp->max_depth : n, n / p.min_leaf + 1);
   p.cap = 2 * leaves + 1;
   p.width_cap = leaves + 1;
-  p.nfb = p.d_pad / RF_F;
-  p.nfb_grid = std::min(p.nfb, RF_MAX_FB);
   p.feature_frac = fp->feature_frac, p.y_shift = fp->y_shift, p.y_scale = fp->y_scale;
   p.seed = c->seed, p.round_ = fp->round_;
   const int32_t T = p.T;
   const int32_t n_ctl = rf_ctl_tree(p.max_level, T);
 
   // every allocation before anything of the loaded ensemble is touched
-  UT_HIP(c, hipSetDevice(c->device));
-  if (int e = ensure(c, c->rf_X, (size_t)n * d)) return e;
-  if (int e = ensure(c, c->rf_y, (size_t)n)) return e;
-  if (int e = ensure(c, c->rf_rm, (size_t)n * p.d_pad)) return e;
-  if (int e = ensure(c, c->rf_fm, (size_t)d * p.n_pad)) return e;
+  if (int e = tree_fit_stage(c, X_host, y_host, n, d, &p.d_pad, &p.n_pad, &p.nfb)) return e;
+  p.nfb_grid = std::min(p.nfb, RF_MAX_FB);
   if (int e = ensure(c, c->rf_q, (size_t)n)) return e;
   if (int e = ensure(c, c->rf_w, (size_t)T * n)) return e;
   if (int e = ensure(c, c->rf_rows, (size_t)2 * T * n)) return e;
@@ -466,11 +370,8 @@ extern "C" int ut_forest_fit(ut_ctx* c, const double* X_host, const double* y_ho
   if (int e = ensure(c, c->rf_ctl, (size_t)n_ctl)) return e;
   DevBuf<int32_t> roots;
   if (int e = dalloc(c, roots, (size_t)T)) return e;
-  if (!c->rf_host) UT_HIP(c, hipHostMalloc((void**)&c->rf_host, 2 * sizeof(int32_t), hipHostMallocDefault));
 
   hipStream_t s = c->stream;
-  UT_HIP(c, hipMemcpyAsync(c->rf_X.p, X_host, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, s));
-  UT_HIP(c, hipMemcpyAsync(c->rf_y.p, y_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_rf_ctl_clear, dim3(grid1(n_ctl, 256)), dim3(256), 0, s, c->rf_ctl.p, n_ctl);
   hipLaunchKernelGGL(k_rf_prepare, dim3(grid1((int64_t)n * p.d_pad, RF_NT)), dim3(RF_NT), 0, s, p, c->rf_X.p,
                      c->rf_y.p, c->rf_rm.p, c->rf_fm.p, c->rf_q.p, c->rf_w.p);
@@ -514,15 +415,5 @@ extern "C" int ut_forest_fit(ut_ctx* c, const double* X_host, const double* y_ho
   hipLaunchKernelGGL(k_rf_compact, dim3(grid1(p.cap, RF_NT), T), dim3(RF_NT), 0, s, p, c->rf_ctl.p, roots.p,
                      c->rf_tnodes.p, nodes.p);
   UT_LAUNCH_CHECK(c);
-  UT_HIP(c, sync_all(c));   // a scoring kernel still queued reads the old records
-  c->forest_nodes.swap(nodes);
-  c->forest_roots.swap(roots);
-  c->forest_trees = T;
-  c->forest_rule = UT_SPLIT_LT;
-  c->forest_max_feat = max_feat;
-  c->forest_base = 0.0, c->forest_scale = 1.0, c->forest_div = (double)T;
-  c->forest_n_nodes = total;
-  c->forest_host.clear();
-  c->forest_host_valid = false;
-  return 0;
+  return forest_install(c, nodes, total, roots, T, max_feat, 0.0, 1.0, (double)T);
 }

@@ -29,12 +29,11 @@
 //                 The host picks slices = clamp(ceil(256 / 2^L), 1, feature
 //                 blocks): nodes x slices is about the CU count at every level.
 //                 A slice takes feature blocks slice, slice + slices, ..: the
-//                 block's (H: u32, G: i64) histograms in LDS (GBT_F = 16
-//                 features x 256 bins x 12 B = 48 KiB: three workgroups, twelve
-//                 waves per CU of 160 KiB), filled by return-less LDS atomics
-//                 from the sampled rows only, scanned as k_rf_hist scans.  It
-//                 writes its best candidate and takes a ticket on the node
-//                 (agent-scope acq_rel).  The workgroup that draws the last
+//                 histogram block of tree_fit.h, the one k_rf_hist runs, over
+//                 the sampled rows only, each adding (1, g), with lambda in
+//                 the gain's denominators.  It writes its best candidate and
+//                 takes a ticket on the node (agent-scope acq_rel).  The
+//                 workgroup that draws the last
 //                 ticket reads the slices' candidates and decides the node:
 //                 a leaf adds its step to pred of every row it holds, sampled
 //                 or not (which is why no round needs a predict pass); a split
@@ -44,12 +43,11 @@
 //                 anybody: a workgroup that is not last has already left.
 // Levels past a tree's last open node run as empty grids.
 #include "ut_internal.h"
-#include "rf_codes.h"
+#include "tree_fit.h"
 
 namespace ut {
 
-constexpr int32_t GBT_F = 16;          // features per histogram block
-constexpr int32_t GBT_NT = 256;
+constexpr int32_t GBT_NT = TREE_NT;
 constexpr int32_t GBT_WG = 256;        // workgroups a level aims at: the CUs of gfx950; also the most slices of a node
 constexpr int32_t GBT_HEAP_MAX = 8191; // 2^(12 + 1) - 1
 
@@ -65,16 +63,16 @@ struct GbtParams {
 
 __device__ __forceinline__ bool gbt_sampled(const GbtParams& p, int32_t r, int32_t row) {
   if (p.subsample >= 1.0) return true;
-  const u32x4 v = draw(p.seed, (uint64_t)(uint32_t)(row >> 2), (uint32_t)r, p.round_, OP_GBT);
-  return (double)rf_word(v, (uint32_t)row) < p.subsample * 4294967296.0;
+  return tree_draw_below(draw(p.seed, (uint64_t)(uint32_t)(row >> 2), (uint32_t)r, p.round_, OP_GBT), (uint32_t)row,
+                         p.subsample);
 }
 
 // every node of a level sees the same features
 __device__ __forceinline__ bool gbt_eligible(const GbtParams& p, int32_t r, int32_t level, int32_t j) {
   if (p.colsample >= 1.0) return true;
-  const u32x4 v = draw(p.seed, ((uint64_t)(uint32_t)level << 32) | (uint32_t)(j >> 2), 0x10000u | (uint32_t)r, p.round_,
-                       OP_GBT);
-  return (double)rf_word(v, (uint32_t)j) < p.colsample * 4294967296.0;
+  return tree_draw_below(draw(p.seed, ((uint64_t)(uint32_t)level << 32) | (uint32_t)(j >> 2), 0x10000u | (uint32_t)r,
+                              p.round_, OP_GBT),
+                         (uint32_t)j, p.colsample);
 }
 
 // a node's step in normalised units: eta * (-G / (H + lambda)) / 65536, each operation rounded once
@@ -93,18 +91,8 @@ __global__ __launch_bounds__(GBT_NT) void k_gbt_prepare(GbtParams p, const doubl
                                                         double* __restrict__ pred, GbtNode* __restrict__ state,
                                                         int32_t* __restrict__ ctl) {
   const int64_t idx = (int64_t)blockIdx.x * GBT_NT + threadIdx.x;
-  const int64_t total = (int64_t)p.n * p.d_pad;
-  if (idx < total) {
-    const int32_t row = (int32_t)(idx / p.d_pad), j = (int32_t)(idx % p.d_pad);
-    const uint8_t code = j < p.d ? rf_code(X[(int64_t)row * p.d + j]) : (uint8_t)0;
-    rm[idx] = code;
-    if (j < p.d) fm[(int64_t)j * p.n_pad + row] = code;
-  }
-  if (idx < p.n) {
-    const double v = (y[idx] - p.y_shift) / p.y_scale;
-    z[idx] = v < -32.0 ? -32.0 : (v > 32.0 ? 32.0 : v);
-    pred[idx] = 0.0;
-  }
+  tree_codes(idx, p.n, p.d, p.d_pad, p.n_pad, X, rm, fm);
+  if (idx < p.n) z[idx] = tree_norm(y[idx], p.y_shift, p.y_scale), pred[idx] = 0.0;
   const int64_t stride = (int64_t)gridDim.x * GBT_NT;
   for (int64_t k = idx; k < 2 * (int64_t)p.heap; k += stride) state[k] = GbtNode{};
   if (idx == 0) ctl[0] = 0, ctl[1] = -1;
@@ -151,22 +139,12 @@ __global__ __launch_bounds__(GBT_NT) void k_gbt_round(GbtParams p, int32_t r, co
   // tree r - 1: the live nodes in heap order behind the trees before it
   GbtNode* st = state + (int64_t)((r - 1) & 1) * p.heap;
   const ut_tree_node* rec = tn + (int64_t)((r - 1) & 1) * p.heap;
-  const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int32_t per = (p.heap + GBT_NT - 1) / GBT_NT;
   const int32_t k0 = min((int32_t)threadIdx.x * per, p.heap), k1 = min(k0 + per, p.heap);
   int32_t cnt = 0;
   for (int32_t k = k0; k < k1; ++k) cnt += st[k].open != 0;
-  int32_t incl = cnt;
-#pragma unroll
-  for (int32_t o = 1; o < 64; o <<= 1) {
-    const int32_t a = __shfl_up(incl, o);
-    if (lane >= o) incl += a;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int32_t pos = incl - cnt;
-  for (int32_t w = 0; w < wave; ++w) pos += wsum[w];
-  const int32_t total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  int32_t total;
+  int32_t pos = tree_prefix(cnt, wsum, &total);
   for (int32_t k = k0; k < k1; ++k)
     if (st[k].open != 0) rank[k] = (uint16_t)pos++;
   const int32_t base = ctl[0];
@@ -195,9 +173,7 @@ __global__ __launch_bounds__(GBT_NT) void k_gbt_level(GbtParams p, int32_t r, in
                                                       const int32_t* __restrict__ g, const uint8_t* __restrict__ samp,
                                                       double* __restrict__ pred, RfCand* __restrict__ cand,
                                                       int32_t* __restrict__ ctl) {
-  __shared__ uint32_t hH[GBT_F * 256];
-  __shared__ unsigned long long hG[GBT_F * 256];
-  __shared__ RfCand wbest[4];
+  __shared__ TreeHistLds lds;
   __shared__ int32_t s_last;
   __shared__ GbtSide side[2];
   const int32_t k = (1 << level) - 1 + (int32_t)blockIdx.y;
@@ -217,76 +193,13 @@ __global__ __launch_bounds__(GBT_NT) void k_gbt_level(GbtParams p, int32_t r, in
   const bool search = level < p.max_depth && H >= 2u * mc;
   if (!search && blockIdx.x != 0) return;
   if (search) {
-    double bs = -1.0;
-    int32_t bj = p.d, bb = 256;
-    for (int32_t fb = blockIdx.x; fb < p.nfb; fb += gridDim.x) {
-      for (int32_t i = threadIdx.x; i < GBT_F * 256; i += GBT_NT) hH[i] = 0, hG[i] = 0;
-      __syncthreads();
-      {
-        const int32_t f = lane & (GBT_F - 1), j = fb * GBT_F + f;
-        if (j < p.d) {
-          for (int32_t i = wave * 4 + (lane >> 4); i < count; i += 16) {
-            const int32_t row = list[i];
-            if (!samp[row]) continue;
-            const uint32_t code = rm[(int64_t)row * p.d_pad + j];
-            atomicAdd(&hH[f * 256 + code], 1u);
-            atomicAdd(&hG[f * 256 + code], (unsigned long long)(int64_t)g[row]);
-          }
-        }
-      }
-      __syncthreads();
-      for (int32_t f = wave; f < GBT_F; f += 4) {
-        const int32_t j = fb * GBT_F + f;
-        if (j >= p.d || !gbt_eligible(p, r, level, j)) continue;   // uniform over the wave
-        uint32_t hw[4], pw[4];
-        int64_t pq[4];
-#pragma unroll
-        for (int32_t q = 0; q < 4; ++q) {
-          hw[q] = hH[f * 256 + 4 * lane + q];
-          const int64_t hq = (int64_t)hG[f * 256 + 4 * lane + q];
-          pw[q] = q ? pw[q - 1] + hw[q] : hw[q];
-          pq[q] = q ? pq[q - 1] + hq : hq;
-        }
-        uint32_t sw = pw[3];
-        long long sq = pq[3];
-#pragma unroll
-        for (int32_t o = 1; o < 64; o <<= 1) {
-          const uint32_t a = __shfl_up(sw, o);
-          const long long b = __shfl_up(sq, o);
-          if (lane >= o) sw += a, sq += b;
-        }
-        const uint32_t ew = sw - pw[3];
-        const int64_t eq = sq - pq[3];
-        double s = -1.0;
-        int32_t b = 256;
-#pragma unroll
-        for (int32_t q = 0; q < 4; ++q) {
-          // an empty bin repeats its left neighbour's score and loses the tie
-          const uint32_t HL = ew + pw[q], HR = H - HL;
-          if (hw[q] == 0 || 4 * lane + q > 254 || HL < mc || HR < mc) continue;
-          const double GL = (double)(eq + pq[q]), GR = (double)(G - (eq + pq[q]));
-          const double a = GL * GL, c = GR * GR;
-          const double v = a / ((double)HL + p.lambda) + c / ((double)HR + p.lambda);
-          if (v > s) s = v, b = 4 * lane + q;
-        }
-#pragma unroll
-        for (int32_t o = 32; o >= 1; o >>= 1) {
-          const double s2 = __shfl_xor(s, o);
-          const int32_t b2 = __shfl_xor(b, o);
-          if (s2 > s || (s2 == s && b2 < b)) s = s2, b = b2;
-        }
-        if (s >= 0.0 && rf_better(s, j, b, bs, bj, bb)) bs = s, bj = j, bb = b;
-      }
-      __syncthreads();   // the next block's clear
-    }
-    if (lane == 0) wbest[wave] = RfCand{bs, bj, bb};
-    __syncthreads();
+    const RfCand mine = tree_hist_best<true, true>(
+        lds, list, count, rm, p.d, p.d_pad, p.nfb, (int32_t)blockIdx.x, (int32_t)gridDim.x, H, G, mc, p.lambda,
+        [&](int32_t row) { return samp[row] ? TreeAdd{1u, (int64_t)g[row]} : TreeAdd{0u, 0}; },
+        [&](int32_t j) { return gbt_eligible(p, r, level, j); });
     RfCand* cs = cand + (int64_t)blockIdx.y * gridDim.x;
     if (threadIdx.x == 0) {
-      RfCand v = wbest[0];
-      for (int32_t q = 1; q < 4; ++q)
-        if (rf_better(wbest[q].s, wbest[q].j, wbest[q].b, v.s, v.j, v.b)) v = wbest[q];
-      cs[blockIdx.x] = v;
+      cs[blockIdx.x] = mine;
       // the release makes the candidate visible to whoever reads the count after
       // it, the acquire makes the others' visible here: the L2s are per XCD
       const int32_t t = __hip_atomic_fetch_add(&nd->ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
@@ -304,12 +217,10 @@ __global__ __launch_bounds__(GBT_NT) void k_gbt_level(GbtParams p, int32_t r, in
       const int32_t j2 = __shfl_xor(v.j, o), b2 = __shfl_xor(v.b, o);
       if (rf_better(s2, j2, b2, v.s, v.j, v.b)) v.s = s2, v.j = j2, v.b = b2;
     }
-    __syncthreads();   // wbest was read by thread 0 above
-    if (lane == 0) wbest[wave] = v;
+    // (wbest is free: its last read came before s_last's barrier)
+    if (lane == 0) lds.wbest[wave] = v;
     __syncthreads();
-    best = wbest[0];
-    for (int32_t q = 1; q < 4; ++q)
-      if (rf_better(wbest[q].s, wbest[q].j, wbest[q].b, best.s, best.j, best.b)) best = wbest[q];
+    best = tree_wave_best(lds.wbest);
   }
 
   // the decision, the same in every thread
@@ -380,30 +291,24 @@ extern "C" int ut_gbt_fit(ut_ctx* c, const double* X_host, const double* y_host,
                           const ut_gbt_fit_params* fp) {
   using namespace ut;
   if (!c) return UT_EINVAL;
-  UT_CHECK(c, X_host && y_host && fp, UT_EINVAL, "gbt_fit: X, y or the parameters are NULL");
-  UT_CHECK(c, n >= 1 && n <= 16384 && d >= 1 && d <= 4096, UT_EINVAL,
-           "gbt_fit: n must be in [1, 16384] and d in [1, 4096]");
-  UT_CHECK(c, fp->n_rounds >= 1 && fp->n_rounds <= 1024, UT_EINVAL, "gbt_fit: n_rounds must be in [1, 1024]");
-  UT_CHECK(c, fp->max_depth >= 1 && fp->max_depth <= 12, UT_EINVAL, "gbt_fit: max_depth must be in [1, 12]");
-  UT_CHECK(c, fp->min_child >= 1, UT_EINVAL, "gbt_fit: min_child must be at least 1");
-  UT_CHECK(c, fp->eta > 0.0 && fp->eta <= 1.0, UT_EINVAL, "gbt_fit: eta must be in (0, 1]");
-  UT_CHECK(c, fp->lambda >= 0.0 && __builtin_isfinite(fp->lambda), UT_EINVAL,
-           "gbt_fit: lambda must be finite and >= 0");
-  UT_CHECK(c, fp->gamma >= 0.0 && __builtin_isfinite(fp->gamma), UT_EINVAL, "gbt_fit: gamma must be finite and >= 0");
-  UT_CHECK(c, fp->subsample > 0.0 && fp->subsample <= 1.0, UT_EINVAL, "gbt_fit: subsample must be in (0, 1]");
-  UT_CHECK(c, fp->colsample_bylevel > 0.0 && fp->colsample_bylevel <= 1.0, UT_EINVAL,
-           "gbt_fit: colsample_bylevel must be in (0, 1]");
-  UT_CHECK(c, __builtin_isfinite(fp->y_shift) && __builtin_isfinite(fp->y_scale) && fp->y_scale > 0.0, UT_EINVAL,
-           "gbt_fit: y_shift must be finite and y_scale finite and positive");
-  UT_CHECK(c, fp->round_ < (1u << 24), UT_EINVAL, "gbt_fit: round_ must be below 2^24");
-  for (int32_t i = 0; i < n; ++i)
-    UT_CHECK(c, __builtin_isfinite(y_host[i]), UT_EINVAL, "gbt_fit: y[" + std::to_string(i) + "] is not finite");
+  if (int e = tree_fit_check(c, "gbt_fit", X_host, y_host, n, d, fp, [&]() -> int {
+        UT_CHECK(c, fp->n_rounds >= 1 && fp->n_rounds <= 1024, UT_EINVAL, "gbt_fit: n_rounds must be in [1, 1024]");
+        UT_CHECK(c, fp->max_depth >= 1 && fp->max_depth <= 12, UT_EINVAL, "gbt_fit: max_depth must be in [1, 12]");
+        UT_CHECK(c, fp->min_child >= 1, UT_EINVAL, "gbt_fit: min_child must be at least 1");
+        UT_CHECK(c, fp->eta > 0.0 && fp->eta <= 1.0, UT_EINVAL, "gbt_fit: eta must be in (0, 1]");
+        UT_CHECK(c, fp->lambda >= 0.0 && __builtin_isfinite(fp->lambda), UT_EINVAL,
+                 "gbt_fit: lambda must be finite and >= 0");
+        UT_CHECK(c, fp->gamma >= 0.0 && __builtin_isfinite(fp->gamma), UT_EINVAL,
+                 "gbt_fit: gamma must be finite and >= 0");
+        UT_CHECK(c, fp->subsample > 0.0 && fp->subsample <= 1.0, UT_EINVAL, "gbt_fit: subsample must be in (0, 1]");
+        UT_CHECK(c, fp->colsample_bylevel > 0.0 && fp->colsample_bylevel <= 1.0, UT_EINVAL,
+                 "gbt_fit: colsample_bylevel must be in (0, 1]");
+        return 0;
+      }))
+    return e;
 
   GbtParams p;
   p.n = n, p.d = d, p.n_rounds = fp->n_rounds, p.max_depth = fp->max_depth, p.min_child = fp->min_child;
-  p.d_pad = (d + GBT_F - 1) / GBT_F * GBT_F;
-  p.n_pad = (n + 63) / 64 * 64;
-  p.nfb = p.d_pad / GBT_F;
   p.heap = (2 << p.max_depth) - 1;
   // a tree of k leaves has 2k - 1 nodes; a leaf below the root holds min_child sampled rows
   const int32_t leaves = std::min(1 << p.max_depth, std::max(1, n / p.min_child));
@@ -414,11 +319,7 @@ extern "C" int ut_gbt_fit(ut_ctx* c, const double* X_host, const double* y_host,
   const int32_t R = p.n_rounds, D = p.max_depth;
 
   // every allocation before anything of the loaded ensemble is touched
-  UT_HIP(c, hipSetDevice(c->device));
-  if (int e = ensure(c, c->rf_X, (size_t)n * d)) return e;
-  if (int e = ensure(c, c->rf_y, (size_t)n)) return e;
-  if (int e = ensure(c, c->rf_rm, (size_t)n * p.d_pad)) return e;
-  if (int e = ensure(c, c->rf_fm, (size_t)d * p.n_pad)) return e;
+  if (int e = tree_fit_stage(c, X_host, y_host, n, d, &p.d_pad, &p.n_pad, &p.nfb)) return e;
   if (int e = ensure(c, c->rf_rows, (size_t)2 * n)) return e;
   if (int e = ensure(c, c->rf_cand, (size_t)GBT_WG + ((size_t)1 << D))) return e;   // 2^L x slices(L) <= max(256, 2^L)
   if (int e = ensure(c, c->gbt_z, (size_t)n)) return e;
@@ -432,11 +333,8 @@ extern "C" int ut_gbt_fit(ut_ctx* c, const double* X_host, const double* y_host,
   if (int e = dalloc(c, roots, (size_t)R)) return e;
   DevBuf<ut_tree_node> grown;
   if (int e = dalloc(c, grown, (size_t)p.out_cap)) return e;
-  if (!c->rf_host) UT_HIP(c, hipHostMalloc((void**)&c->rf_host, 2 * sizeof(int32_t), hipHostMallocDefault));
 
   hipStream_t s = c->stream;
-  UT_HIP(c, hipMemcpyAsync(c->rf_X.p, X_host, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, s));
-  UT_HIP(c, hipMemcpyAsync(c->rf_y.p, y_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_gbt_prepare, dim3(grid1((int64_t)n * p.d_pad, GBT_NT)), dim3(GBT_NT), 0, s, p, c->rf_X.p,
                      c->rf_y.p, c->rf_rm.p, c->rf_fm.p, c->gbt_z.p, c->gbt_pred.p, c->gbt_state.p, c->gbt_ctl.p);
   UT_LAUNCH_CHECK(c);
@@ -468,15 +366,5 @@ extern "C" int ut_gbt_fit(ut_ctx* c, const double* X_host, const double* y_host,
   DevBuf<ut_tree_node> nodes;
   if (int e = dalloc(c, nodes, (size_t)total)) return e;
   UT_HIP(c, hipMemcpyAsync(nodes.p, grown.p, sizeof(ut_tree_node) * (size_t)total, hipMemcpyDeviceToDevice, s));
-  UT_HIP(c, sync_all(c));   // a scoring kernel still queued reads the old records
-  c->forest_nodes.swap(nodes);
-  c->forest_roots.swap(roots);
-  c->forest_trees = R;
-  c->forest_rule = UT_SPLIT_LT;
-  c->forest_max_feat = max_feat;
-  c->forest_base = p.y_shift, c->forest_scale = 1.0, c->forest_div = 1.0;
-  c->forest_n_nodes = total;
-  c->forest_host.clear();
-  c->forest_host_valid = false;
-  return 0;
+  return forest_install(c, nodes, total, roots, R, max_feat, p.y_shift, 1.0, 1.0);
 }

@@ -795,6 +795,9 @@ int dalloc(ut_ctx* c, DevBuf<T>& b, size_t n) {
 void mark(ut_ctx* c, const char* name);
 // forest.hip: c->forest_host holds the loaded records (copied from the device after ut_forest_fit)
 int forest_host_fetch(ut_ctx* c);
+// ... and the tail of ut_forest_fit and ut_gbt_fit: the ensemble they grew becomes the loaded one
+int forest_install(ut_ctx* c, DevBuf<ut_tree_node>& nodes, int32_t n_nodes, DevBuf<int32_t>& roots, int32_t n_trees,
+                   int32_t max_feat, double base, double scale, double div);
 int gp_fit_enqueue(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h);
 int gp_wait_fit(ut_ctx* c);
 int gp_fit_flush(ut_ctx* c);
