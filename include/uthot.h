@@ -637,6 +637,64 @@ int ut_gp_ts_select(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, co
                     int64_t* out_pos, double* out_f);
 int ut_gp_ts_read(ut_ctx* ctx, int32_t what, double* out_host, int32_t* info);
 
+/* ---- sparse-spectrum GP: a surrogate with a variance for long histories ---- */
+/* The reference has no GP.  The exact GP above costs O(n^3) to fit, O(m n^2) to
+ * score and two n^2 matrices; Bayesian linear regression on D random Fourier
+ * features of the RBF kernel (Lazaro-Gredilla et al., sparse spectrum GP) is a
+ * GP with the kernel phi(u)^T phi(u') ~ k(u, u'): O(n D^2) to fit, O(m D^2) to
+ * score whatever n is, D x D of state.
+ *
+ * Inputs: training features X (n x d, the space's encoding), y, 1/ell per
+ * feature, sigma_f2, diag = sigma_n2 + jitter, D features.  All fp64.  ys is y
+ * standardised as ut_gp_fit standardises it (mean, std with ddof = 0, std 1
+ * where it is not positive); f_best = min ys.
+ *
+ * Draws (the counter generator of ut_core.h with OP_SSGP = 11, round 0, keyed
+ * by the context's seed alone):
+ *   Z[j][k] = normal_draw(seed, cand = j, stream = k, 0, OP_SSGP)        j < D, k < d
+ *   b[j]    = u01(x, y) of draw(seed, j, STREAM_CAND, 0, OP_SSGP)        a phase in turns, [0, 1)
+ * Features, with us = u * (1/ell) per feature and Zs[j][k] = Z[j][k] * INV_2PI
+ * (INV_2PI = 0.15915494309189535, the product rounded once per entry), over
+ * every feature column of the encoding, whatever ut_gp_kstar_mode says:
+ *   tau_j(u) = sum_k Zs[j][k] us_k + b_j                      (turns)
+ *   phi_j(u) = sqrt(2 sigma_f2 / D) cos2pi(tau_j - rint(tau_j))
+ * cos2pi is ut_core.h's (its error bound COS_ERR is stated there).
+ * Fit, Phi the n x D matrix of the training rows' features:
+ *   A = Phi^T Phi + diag I (D x D),  c = Phi^T ys,  L = chol(A) with its
+ *   explicit L^-1,  w = A^-1 c = L^-T (L^-1 c).
+ * Posterior at u:  mu = phi(u) . w,  var = diag |L^-1 phi(u)|^2 (a sum of
+ * squares: no cancellation), and the score is ut_gp_score's EI / UCB of
+ * (mu, var, f_best, acq); dup[i] != 0 forces -inf.  After a failed fit (A not
+ * positive definite) mu, var and every score are NaN.
+ *
+ * ut_ssgp_fit: stages X, y; A's lower 128 x 128 tiles and c in one pass over
+ *   the rows with Phi formed on the fly (never stored), the rows split into
+ *   units whose length is a function of (n, D) alone (ssgp.hip states it), the
+ *   units' partial tiles summed in unit order with no atomics; then ut_gp_fit's
+ *   own factorisation chain on A.  Independent of any ut_gp_fit state.
+ * ut_ssgp_score: device mu, var, score [m] (each may be NULL) for the m
+ *   candidates values [ncols][ld] (raw values as for ut_gp_score_values).  The
+ *   pool is walked in chunks whose Phi* workspace [D][chunk] stays at or under
+ *   256 MiB; V = L^-1 Phi* runs on ut_gp_score's fp64 variance contraction.
+ * ut_ssgp_read: (for tests) what = 0 Z [D][d], 1 b [D], 2 A [D][D] (full,
+ *   symmetric), 3 c [D], 4 L [D][D] (zeros above the diagonal), 5 L^-1 [D][D],
+ *   6 w [D] into out_host; info (may be NULL) = {n, d, D, ok}, ok = 1 iff A was
+ *   positive definite.  out_host NULL: info alone.  Waits for the stream.
+ * Stream-ordered, no host wait (ut_ssgp_read apart).  Every sum runs in a
+ * fixed order: two fits of the same data and two scoring calls return the same
+ * bits, and a candidate's results do not depend on how the pool is cut into
+ * calls or chunks (the variance contraction runs with its k loops unsplit).
+ * UT_EINVAL: n < 1 or n > 65536; D < 128, > 2048 or not a multiple of 128; d
+ * not the space's feature count (or no space); ut_gp_set_precision other than
+ * 64 (fp64 only); a NULL X_host, y_host, hyper, values or acq; m < 1; ld < m;
+ * what outside [0, 6]; scoring or reading without a fit.  UT_ENOMEM: a buffer
+ * could not be allocated (no fit is left). */
+int ut_ssgp_fit(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
+                const ut_gp_hyper* hyper, int32_t D);
+int ut_ssgp_score(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
+                  double* mu, double* var, double* score);
+int ut_ssgp_read(ut_ctx* ctx, int32_t what, double* out_host, int32_t* info);
+
 /* ---- acquisition gradient and projected-ascent polish --------------------- */
 /* The reference's default bandit carries a local-search arm, RandomNelderMead
  * (bandittechniques.py:273-278; the simplex walk itself is

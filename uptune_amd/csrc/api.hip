@@ -278,6 +278,8 @@ int ut_ctx_create(int device, uint64_t seed, ut_ctx** out) {
   if (const char* e = getenv("UT_FIT_DEFER")) c->fit_defer = atoi(e) != 0;
   if (const char* e = getenv("UT_KSTAR_Q")) c->kstar_q = atoi(e) != 0;
   if (const char* e = getenv("UT_LML_BATCH")) c->lml_batch = atoi(e);
+  if (const char* e = getenv("UT_SSGP_UNITS_PER_WG")) c->ssgp_units_per_wg = atoi(e);
+  if (const char* e = getenv("UT_SSGP_PHI_MIB")) c->ssgp_phi_mib = atoi(e);
   *out = c;
   return 0;
 }
@@ -904,6 +906,26 @@ int ut_gp_ts_read(ut_ctx* c, int32_t what, double* out_host, int32_t* info) {
   if (!c) return UT_EINVAL;
   UT_HIP(c, hipSetDevice(c->device));
   return gp_ts_read_impl(c, what, out_host, info);
+}
+
+int ut_ssgp_fit(ut_ctx* c, const double* X_host, const double* y_host, int32_t n, int32_t d, const ut_gp_hyper* hyper,
+                int32_t D) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return ssgp_fit_impl(c, X_host, y_host, n, d, hyper, D);
+}
+
+int ut_ssgp_score(ut_ctx* c, const double* values, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
+                  double* mu, double* var, double* score) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return ssgp_score_impl(c, values, ld, m, acq, dup, mu, var, score);
+}
+
+int ut_ssgp_read(ut_ctx* c, int32_t what, double* out_host, int32_t* info) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return ssgp_read_impl(c, what, out_host, info);
 }
 
 int ut_gp_acq_grad(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, double* out_score,

@@ -854,9 +854,74 @@ __global__ __launch_bounds__(256) void k_app_c(double* __restrict__ Li, double* 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static void launch_chol_diag(ut_ctx* c, int32_t npad, int32_t kb) {
-  hipLaunchKernelGGL(c->chol_merged ? k_chol_diag<true> : k_chol_diag<false>, dim3(1), dim3(256), 0, c->stream,
-                     c->gp_K.p, c->gp_Linv.p, npad, kb, c->gp_flag.p);
+static void launch_chol_diag(ut_ctx* c, double* K, double* Linv, int32_t* flag, int32_t npad, int32_t kb) {
+  hipLaunchKernelGGL(c->chol_merged ? k_chol_diag<true> : k_chol_diag<false>, dim3(1), dim3(256), 0, c->stream, K,
+                     Linv, npad, kb, flag);
+}
+
+// The refit chain on a symmetric positive-definite matrix already formed on the
+// device (its lower 64 x 64 tiles, the diagonal ones whole): K becomes L in
+// place, Linv (npad^2, zeroed here) L^-1, T (npad^2) is the inverse's scratch,
+// *flag is or-ed with 1 where a pivot is not positive.  npad is a multiple of
+// 128.  The GP's fit (K = the kernel matrix) and the sparse-spectrum fit
+// (ssgp.hip: K = Phi^T Phi + diag I) both factor here.
+int launch_factor_chain(ut_ctx* c, double* K, double* Linv, double* T, int32_t* flag, int32_t npad) {
+  const int32_t nb = npad / NB;
+  UT_HIP(c, hipMemsetAsync(Linv, 0, sizeof(double) * npad * npad, c->stream));
+  const bool fuse = c->chol_fuse > 0 || (c->chol_fuse < 0 && npad >= (c->fit_legacy ? 2048 : CHOL_FUSE_MIN));
+  for (int32_t kb = 0; kb < nb; ++kb) {
+    // (fused: diagonal blocks after the first come from the previous update)
+    if (!fuse || kb == 0)
+      launch_chol_diag(c, K, Linv, flag, npad, kb);
+    const int32_t Tn = nb - kb - 1;
+    if (Tn > 0) {
+      hipLaunchKernelGGL(k_chol_rows, dim3(Tn), dim3(256), 0, c->stream, K, Linv, npad, kb);
+      if (fuse)
+        hipLaunchKernelGGL(c->chol_merged ? k_chol_update_diag<true> : k_chol_update_diag<false>,
+                           dim3(Tn * (Tn + 1) / 2), dim3(256), 0, c->stream, K, Linv, npad, kb, flag);
+      else
+        hipLaunchKernelGGL(k_chol_update, dim3(Tn * (Tn + 1) / 2), dim3(256), 0, c->stream, K, npad, kb);
+    }
+  }
+  UT_LAUNCH_CHECK(c);
+  // off-diagonal blocks of L^-1 by recursive doubling (diagonal blocks came from k_chol_diag)
+  for (int32_t lv = NB; lv < npad; lv *= 2) {
+    const int32_t pairs = (int32_t)((npad - lv + 2 * lv - 1) / (2 * lv));
+    const bool big = c->trinv_big && lv >= TRB_MIN;
+    // the one-wave tiles (with trinv_small_wg set: where the launch has fewer workgroups than that)
+    const int64_t wgs = (int64_t)(big ? lv / TRB_BM : lv / 64) * (big ? lv / TRB_BM : lv / 64) * pairs;
+    if (new_chain(c, npad) && (c->trinv_small_wg < 0 || wgs < c->trinv_small_wg)) {
+      const dim3 gs(lv / TRS_BM, lv / TRS_BM, pairs);
+      hipLaunchKernelGGL(k_trinv_small, gs, dim3(64), 0, c->stream, K, Linv, T, npad, lv, 0);
+      hipLaunchKernelGGL(k_trinv_small, gs, dim3(64), 0, c->stream, K, Linv, T, npad, lv, 1);
+      continue;
+    }
+    if (big) {
+      // k_trinv_big's tiles: every pair's sizes are multiples of 128
+      UT_CHECK(c, npad % TRB_BM == 0 && lv % TRB_BM == 0, UT_EINVAL, "gp_fit: npad not a multiple of 128");
+      const dim3 gb(lv / TRB_BM, lv / TRB_BM, pairs);
+      hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, K, Linv, T, npad, lv, 0);
+      hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, K, Linv, T, npad, lv, 1);
+      continue;
+    }
+    const dim3 grid(lv / 64, lv / 64, pairs);
+    hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, K, Linv, T, npad, lv, 0);
+    hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, K, Linv, T, npad, lv, 1);
+  }
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
+// out = M v over npad rows: M = L^-1 (lower), or M = L^-T read through LinvT = (L^-1)^T
+int launch_lower_mv(ut_ctx* c, const double* Linv, int32_t npad, const double* v, double* out) {
+  hipLaunchKernelGGL(k_lower_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, Linv, npad, v, out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+int launch_upper_mv(ut_ctx* c, const double* LinvT, int32_t npad, const double* v, double* out) {
+  hipLaunchKernelGGL(k_upper_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, LinvT, npad, v, out);
+  UT_LAUNCH_CHECK(c);
+  return 0;
 }
 
 static int gp_alloc(ut_ctx* c, int32_t npad_need, int32_t d) {
@@ -972,7 +1037,7 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
         hipLaunchKernelGGL(k_app_red<1>, dim3(1), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p, c->gp_K.p,
                            c->gp_T.p, npad, b, maxq, W, Et);
       }
-      launch_chol_diag(c, npad, b);
+      launch_chol_diag(c, c->gp_K.p, c->gp_Linv.p, c->gp_flag.p, npad, b);
       if (b > 0) {
         double* W = c->app_ws.p;
         hipLaunchKernelGGL(k_app_part<2>, dim3(maxq, b), dim3(256), 0, c->stream, c->gp_Linv.p, c->gp_LinvT.p,
@@ -993,49 +1058,7 @@ static int fit_device(ut_ctx* c, int part, int32_t n, int32_t n0, int32_t d, int
                          npad, d, sf2, diag, c->gp_K.p, 0, 1);
     hipLaunchKernelGGL(k_gp_ystats, dim3(1), dim3(256), 0, c->stream, dy, n, npad, c->gp_y.p, c->gp_stats.p);
     UT_LAUNCH_CHECK(c);
-    const int32_t nb = npad / NB;
-    UT_HIP(c, hipMemsetAsync(c->gp_Linv.p, 0, sizeof(double) * npad * npad, c->stream));
-    const bool fuse = c->chol_fuse > 0 || (c->chol_fuse < 0 && npad >= (c->fit_legacy ? 2048 : CHOL_FUSE_MIN));
-    for (int32_t kb = 0; kb < nb; ++kb) {
-      // (fused: diagonal blocks after the first come from the previous update)
-      if (!fuse || kb == 0)
-        launch_chol_diag(c, npad, kb);
-      const int32_t T = nb - kb - 1;
-      if (T > 0) {
-        hipLaunchKernelGGL(k_chol_rows, dim3(T), dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, npad, kb);
-        if (fuse)
-          hipLaunchKernelGGL(c->chol_merged ? k_chol_update_diag<true> : k_chol_update_diag<false>,
-                             dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, npad, kb, c->gp_flag.p);
-        else
-          hipLaunchKernelGGL(k_chol_update, dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->gp_K.p, npad, kb);
-      }
-    }
-    UT_LAUNCH_CHECK(c);
-    // off-diagonal blocks of L^-1 by recursive doubling (diagonal blocks came from k_chol_diag)
-    for (int32_t lv = NB; lv < npad; lv *= 2) {
-      const int32_t pairs = (int32_t)((npad - lv + 2 * lv - 1) / (2 * lv));
-      const bool big = c->trinv_big && lv >= TRB_MIN;
-      // the one-wave tiles (with trinv_small_wg set: where the launch has fewer workgroups than that)
-      const int64_t wgs = (int64_t)(big ? lv / TRB_BM : lv / 64) * (big ? lv / TRB_BM : lv / 64) * pairs;
-      if (new_chain(c, npad) && (c->trinv_small_wg < 0 || wgs < c->trinv_small_wg)) {
-        const dim3 gs(lv / TRS_BM, lv / TRS_BM, pairs);
-        hipLaunchKernelGGL(k_trinv_small, gs, dim3(64), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 0);
-        hipLaunchKernelGGL(k_trinv_small, gs, dim3(64), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 1);
-        continue;
-      }
-      if (big) {
-        // k_trinv_big's tiles: every pair's sizes are multiples of 128
-        UT_CHECK(c, npad % TRB_BM == 0 && lv % TRB_BM == 0, UT_EINVAL, "gp_fit: npad not a multiple of 128");
-        const dim3 gb(lv / TRB_BM, lv / TRB_BM, pairs);
-        hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 0);
-        hipLaunchKernelGGL(k_trinv_big, gb, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 1);
-        continue;
-      }
-      const dim3 grid(lv / 64, lv / 64, pairs);
-      hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 0);
-      hipLaunchKernelGGL(k_trinv_level, grid, dim3(256), 0, c->stream, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, npad, lv, 1);
-    }
-    UT_LAUNCH_CHECK(c);
+    if ((rc = launch_factor_chain(c, c->gp_K.p, c->gp_Linv.p, c->gp_T.p, c->gp_flag.p, npad))) return rc;
   }
   hipLaunchKernelGGL(k_lower_mv, dim3(grid1(npad, 4)), dim3(256), 0, c->stream, c->gp_Linv.p, npad, c->gp_y.p,
                      c->gp_beta.p);

@@ -1196,7 +1196,7 @@ int launch_split_h3(ut_ctx* c, const double* Linv, int32_t n, _Float16* dst) {
 }
 
 int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const void* kst, int64_t ldk, int32_t npad,
-                    int64_t m, double* part, const double* beta, double* mpart) {
+                    int64_t m, double* part, const double* beta, double* mpart, bool may_split) {
   const bool fp32 = prec != 64;
   UT_CHECK(c, prec == 64 || prec == 32 || prec == 16, UT_EINVAL, "gemm_var: bad precision");
   UT_CHECK(c, (beta != nullptr) == !fp32 && (mpart != nullptr) == !fp32, UT_EINVAL,
@@ -1237,7 +1237,7 @@ int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const v
     // few strips (pruned scoring's survivor / threshold passes): split the k loops
     int64_t steps = 0;   // k-steps per strip
     for (int32_t r = 0; r < RT; ++r) steps += min(npad, (r + 1) * VAR_BM) / VP_BK;
-    if (c->var_split && items_p < slots && steps >= 64) {
+    if (may_split && c->var_split && items_p < slots && steps >= 64) {
       int32_t kcs = (int32_t)((steps * CTp + 2 * slots - 1) / (2 * slots));   // ~2 items per workgroup slot
       kcs = kcs < 8 ? 8 : kcs;
       int32_t per_strip = 0;

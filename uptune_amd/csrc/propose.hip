@@ -952,9 +952,10 @@ int launch_encode(ut_ctx* c, const double* values, int64_t ld, int64_t m, double
 }
 
 int launch_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* u, int32_t dpad, int64_t ldu,
-                         double* cn) {
+                         double* cn, const double* inv_ell) {
   hipLaunchKernelGGL(k_encode_scaled, dim3(grid1(ldu, 256)), dim3(256), 0, c->stream, c->space.d_params.p, c->space.P,
-                     c->space.d_vtab.p, values, ld, m, c->space.n_feat, c->gp_inv_ell.p, dpad, u, ldu, cn);
+                     c->space.d_vtab.p, values, ld, m, c->space.n_feat, inv_ell ? inv_ell : c->gp_inv_ell.p, dpad, u,
+                     ldu, cn);
   UT_LAUNCH_CHECK(c);
   return 0;
 }

@@ -95,6 +95,7 @@ enum : uint32_t {
   OP_RF = 8,   // the forest fit's bootstrap and feature draws (forest_fit.hip; uthot.h states the streams)
   OP_GBT = 9,  // the boosted fit's row-sample and per-level feature draws (gbt_fit.hip; uthot.h states the streams)
   OP_CMA = 10, // the correlated-Gaussian proposals' normals and categorical moves (propose_cma.hip; uthot.h)
+  OP_SSGP = 11, // the sparse-spectrum GP's frequencies and phases (ssgp.hip; uthot.h states the streams)
 };
 enum : uint32_t {
   STREAM_CAND = 0xFFFF0000u,   // per-candidate draws: STREAM_CAND | k

@@ -663,6 +663,27 @@ struct ut_ctx {
   ut::DevBuf<double> ts_pv;                // select: the pick launches' partial minima [TS_PICK_WG]
   ut::DevBuf<int64_t> ts_pp;               // ... their positions [TS_PICK_WG], then [1] the dead flag
   ut::DevBuf<uint8_t> ts_taken;            // select: [m] picked by an earlier path
+  // sparse-spectrum GP (ssgp.hip): Bayesian linear regression on ss_D random Fourier features
+  bool ss_ready = false;
+  int32_t ss_n = 0, ss_d = 0, ss_D = 0;
+  double ss_sf2 = 1.0, ss_diag = 0.0;
+  ut::DevBuf<double> ss_Z, ss_b, ss_ZT;    // Z [D][d] as drawn, b [D], ZT [dpad][D] = Z / (2 pi) transposed
+  ut::DevBuf<double> ss_inv_ell;           // [d]
+  ut::DevBuf<double> ss_in;                // staged X [n][d] | y [n]
+  ut::DevBuf<double> ss_Xs, ss_xn;         // scaled rows [npad][d] and their norms [npad] (unused)
+  ut::DevBuf<double> ss_xuT;               // [dpad][npad] the scaled rows transposed: the Gram's training operand
+  ut::DevBuf<double> ss_ys, ss_stats;      // standardised y [npad] (0 on padding rows), [f_best, mean, std]
+  ut::DevBuf<int32_t> ss_flag;             // [1] != 0: A was not positive definite
+  ut::DevBuf<double> ss_ws;                // the Gram's partial tiles [pairs][units][128][128], c's [D / 128][units][128]
+  ut::DevBuf<double> ss_A, ss_c;           // A [D][D] symmetric, c [D]
+  ut::DevBuf<double> ss_L, ss_Linv, ss_LinvT, ss_T;   // [D][D] each: chol(A), its inverse, the transpose, scratch
+  ut::DevBuf<double> ss_beta, ss_w;        // L^-1 c, A^-1 c
+  ut::DevBuf<double> ss_u, ss_cn;          // a call's candidates: scaled features [dpad][ld], norms [ld] (unused)
+  ut::DevBuf<double> ss_phi;               // Phi* of one chunk [D][ldc]
+  ut::DevBuf<double> ss_mu, ss_vpart, ss_mscr;   // [D / 128][ldc] each: mean partials, |v|^2 partials, scratch
+  // debug: the units of the Gram's row split one workgroup walks (results do not depend on it), and the
+  // cap on the Phi* workspace in MiB; UT_SSGP_UNITS_PER_WG, UT_SSGP_PHI_MIB
+  int32_t ssgp_units_per_wg = 1, ssgp_phi_mib = 256;
   int32_t dbg_fail_alloc = 0;             // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
@@ -904,6 +925,17 @@ int gp_ts_eval_impl(ut_ctx* c, const double* values, int64_t ld, int64_t m, doub
 int gp_ts_select_impl(ut_ctx* c, const double* values, int64_t ld, int64_t m, const uint8_t* dup, int32_t k,
                       int64_t* out_pos, double* out_f);
 int gp_ts_read_impl(ut_ctx* c, int32_t what, double* out_host, int32_t* info);
+// ssgp.hip: the sparse-spectrum GP (uthot.h states the rule)
+constexpr int32_t SSGP_MAX_N = 65536, SSGP_MAX_D = 2048;
+int ssgp_fit_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h, int32_t D);
+int ssgp_score_impl(ut_ctx* c, const double* values, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
+                    double* mu, double* var, double* score);
+int ssgp_read_impl(ut_ctx* c, int32_t what, double* out_host, int32_t* info);
+// gp_fit.hip: the refit chain (Cholesky, then the explicit inverse) on a formed device matrix of npad rows, and
+// the two triangular mat-vecs on a given factor
+int launch_factor_chain(ut_ctx* c, double* K, double* Linv, double* T, int32_t* flag, int32_t npad);
+int launch_lower_mv(ut_ctx* c, const double* Linv, int32_t npad, const double* v, double* out);
+int launch_upper_mv(ut_ctx* c, const double* LinvT, int32_t npad, const double* v, double* out);
 
 // kernel launchers implemented in the .hip translation units
 int launch_population_init(ut_ctx* c, uint32_t round_);
@@ -970,8 +1002,9 @@ int gp_score_impl(ut_ctx* c, const double* feat, int64_t ld, int64_t m, const ut
                   double* mu, double* var, double* score, hipEvent_t dup_ready = nullptr);
 // encode + scale in one pass into c->ucand / c->cnorm (sized for m), for gp_score_impl(feat = nullptr)
 int gp_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m);
+// (inv_ell: the scales to use; nullptr = the GP fit's)
 int launch_encode_scaled(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* u, int32_t dpad, int64_t ldu,
-                         double* cn);
+                         double* cn, const double* inv_ell = nullptr);
 // gp_score.hip: fp64 K* columns of the candidates idx[0..nc) of a call of shape s
 int gather_kstar_cols(ut_ctx* c, const ScoreShape& s, const int64_t* idx, int64_t base, int64_t nc, int64_t ldc,
                       double* mu_part = nullptr);
@@ -1111,8 +1144,9 @@ inline size_t code_rows_lds(int32_t cat_k) { return sizeof(uint32_t) * 256 * ((c
 int launch_encode_scaled_cat(ut_ctx* c, const double* values, int64_t ld, int64_t m, double* u, int32_t dpad,
                              int64_t ldu, double* cn, int8_t* bcat);
 int launch_xs_t(ut_ctx* c, const double* Xs, int32_t npad, int32_t d, int32_t dpad, double* XsT);
+// (may_split = false: the fp64 contraction never splits its k loops, whatever ut_ctx::var_split says)
 int launch_gemm_var(ut_ctx* c, int prec, const void* LinvT, int64_t lda, const void* kst, int64_t ldk, int32_t npad,
-                    int64_t m, double* part, const double* beta, double* mpart);
+                    int64_t m, double* part, const double* beta, double* mpart, bool may_split = true);
 // the fp64 contraction of cnt columns against the first `rows` rows of L^-1, the mean partials into c->pr_mpart
 inline int launch_gemm_var64(ut_ctx* c, int32_t npad, const double* kst, int64_t ldk, int32_t rows, int64_t cnt,
                              double* vpart) {

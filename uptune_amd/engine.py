@@ -544,6 +544,48 @@ class BatchEngine:
                 "ut_gp_ts_read")
         return out
 
+    # ---- sparse-spectrum GP: a surrogate with a variance for long histories (csrc/ssgp.hip) ----
+    def ssgp_fit(self, X: np.ndarray, y: np.ndarray, lengthscale, sigma_f2: float = 1.0, sigma_n2: float = 1e-6,
+                 jitter: float = 0.0, features: int = 1024) -> None:
+        """ut_ssgp_fit: Bayesian linear regression on `features` random Fourier
+        features of the RBF kernel, keyed by the engine's seed.  O(n D^2),
+        D x D of state whatever n is; independent of gp_fit's state."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        n, d = X.shape
+        ell = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscale, dtype=np.float64), (d,)))
+        h = L.GpHyper(sigma_f2=float(sigma_f2), sigma_n2=float(sigma_n2), jitter=float(jitter),
+                      lengthscale_host=ell.ctypes.data)
+        L.check(self.ctx, self.lib.ut_ssgp_fit(self.ctx, X.ctypes.data, y.ctypes.data, n, d, C.byref(h),
+                                               int(features)), "ut_ssgp_fit")
+
+    def ssgp_score(self, values: torch.Tensor, m: Optional[int] = None, acq: Optional[L.Acq] = None,
+                   dup: Optional[torch.Tensor] = None):
+        """ut_ssgp_score: -> (mu, var, score) [m] of values[:, :m] under the
+        current ssgp_fit; EI / UCB as gp_score_values.  Stream-ordered."""
+        values, m = self._pool(values, m, "ssgp_score")
+        acq = acq or self.acq()
+        n = max(m, 1)
+        mu, var, score = self._empty(n), self._empty(n), self._empty(n)
+        L.check(self.ctx, self.lib.ut_ssgp_score(self.ctx, _ptr(values), values.stride(0), m, C.byref(acq), _ptr(dup),
+                                                 _ptr(mu), _ptr(var), _ptr(score)), "ut_ssgp_score")
+        return mu, var, score
+
+    def ssgp_read(self, what: Optional[str]):
+        """ut_ssgp_read (tests): what in "Z" [D][d], "b" [D], "A" [D][D], "c" [D],
+        "L" [D][D], "Linv" [D][D], "w" [D] -> a numpy array; None -> dict(n, d, D, ok)."""
+        info = (C.c_int32 * 4)()
+        L.check(self.ctx, self.lib.ut_ssgp_read(self.ctx, 0, None, info), "ut_ssgp_read")
+        n, d, D, ok = (int(v) for v in info)
+        if what is None:
+            return dict(n=n, d=d, D=D, ok=bool(ok))
+        code, shape = {"Z": (0, (D, d)), "b": (1, (D,)), "A": (2, (D, D)), "c": (3, (D,)), "L": (4, (D, D)),
+                       "Linv": (5, (D, D)), "w": (6, (D,))}[what]
+        out = np.empty(shape, dtype=np.float64)
+        L.check(self.ctx, self.lib.ut_ssgp_read(self.ctx, code, out.ctypes.data_as(C.c_void_p), None),
+                "ut_ssgp_read")
+        return out
+
     def _shortlist(self, values: torch.Tensor, who: str) -> torch.Tensor:
         if values.dim() != 2 or values.shape[0] != self.spec.ncols:
             raise ValueError(f"{who}: values must be [{self.spec.ncols}][p]")

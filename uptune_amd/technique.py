@@ -265,13 +265,17 @@ _TPE_KW = ("gamma", "n_good_max", "prior_weight", "precision")
 _TPE_ROWS = 8192
 # SharedModel's gbt_kw: engine.gbt_fit's parameters
 _GBT_KW = ("n_rounds", "max_depth", "min_child", "eta", "reg_lambda", "gamma", "subsample", "colsample_bylevel")
+# SharedModel's ssgp_kw: features = D of engine.ssgp_fit
+_SSGP_KW = ("features",)
+# ... and the rows up to which lengthscale="auto" selects for it (gp_lml_grid factors n x n matrices)
+_SSGP_AUTO_ROWS = 4096
 # the surrogates a SharedModel refits itself
-_REFIT = ("forest", "tpe", "gbt")
+_REFIT = ("forest", "tpe", "gbt", "ssgp")
 
 
 def _surrogate_word(surrogate) -> str:
     """how the refusals name a surrogate that is not the GP"""
-    return {"tpe": "TPE", "gbt": "gbt"}.get(surrogate, "tree")
+    return {"tpe": "TPE", "gbt": "gbt", "ssgp": "ssgp"}.get(surrogate, "tree")
 
 
 class SharedModel:
@@ -293,7 +297,8 @@ class SharedModel:
                  feasibility: Union[bool, Dict[str, Any]] = False, constraints=None, prune_weighted: bool = False,
                  surrogate: Optional[str] = None, forest_kw: Optional[Dict[str, Any]] = None,
                  objectives=None, ref_point=None, forest_fit: str = "host",
-                 tpe_kw: Optional[Dict[str, Any]] = None, gbt_kw: Optional[Dict[str, Any]] = None):
+                 tpe_kw: Optional[Dict[str, Any]] = None, gbt_kw: Optional[Dict[str, Any]] = None,
+                 ssgp_kw: Optional[Dict[str, Any]] = None):
         if isinstance(lengthscale, str) and lengthscale not in ("auto", "ard"):
             raise ValueError("lengthscale: a number (or one per feature), 'auto' or 'ard'")
         self.device, self.seed, self.lengthscale, self.min_train = device, seed, lengthscale, min_train
@@ -379,8 +384,15 @@ class SharedModel:
         # (engine.forest_predict), which has no variance and takes no
         # acquisition.  gbt_kw: engine.gbt_fit's parameters, the reference's by
         # default.
+        # "ssgp" = the sparse-spectrum GP (engine.ssgp_fit, csrc/ssgp.hip): Bayesian
+        # linear regression on ssgp_kw["features"] (default 1024) random Fourier
+        # features of the GP's kernel, refitted from the same usable rows,
+        # features, y_transform and lengthscale at the same moments; O(n D^2) for
+        # up to 65,536 results, scored by EI / UCB on its own mean and variance.
+        # A numeric lengthscale is used as given; "auto" selects as for the GP
+        # while there are at most 4,096 rows; "ard" is refused.
         if surrogate not in (None,) + _REFIT:
-            raise ValueError("SharedModel surrogate: None (the GP), 'forest', 'tpe' or 'gbt'")
+            raise ValueError("SharedModel surrogate: None (the GP), 'forest', 'tpe', 'gbt' or 'ssgp'")
         if surrogate is not None and (self.feasibility is not None or self.constraints):
             raise ValueError("feasibility and constraints weight the GP's EI: not with a %s surrogate"
                              % _surrogate_word(surrogate))
@@ -400,6 +412,22 @@ class SharedModel:
             unknown = sorted(set(self.gbt_kw) - set(_GBT_KW))
             if unknown:
                 raise ValueError("gbt_kw: %s not among %s" % (unknown, sorted(_GBT_KW)))
+        self.ssgp_kw = dict(ssgp_kw or {})
+        if self.ssgp_kw:
+            if surrogate != "ssgp":
+                raise ValueError("ssgp_kw belongs to surrogate='ssgp'")
+            unknown = sorted(set(self.ssgp_kw) - set(_SSGP_KW))
+            if unknown:
+                raise ValueError("ssgp_kw: %s not among %s" % (unknown, sorted(_SSGP_KW)))
+        if surrogate == "ssgp":
+            D = self.ssgp_kw.get("features", 1024)
+            if isinstance(D, bool) or not isinstance(D, int) or not (128 <= D <= 2048 and D % 128 == 0):
+                raise ValueError("ssgp_kw features: a multiple of 128 in [128, 2048]")
+            if isinstance(lengthscale, str) and lengthscale == "ard":
+                raise ValueError("lengthscale='ard' selects on the exact GP's likelihood gradient: not with a ssgp "
+                                 "surrogate")
+            if precision != 64:
+                raise ValueError("surrogate='ssgp' is fp64 only: precision=64")
         # forest_fit: "host" = the sklearn fit above; "device" = the forest is
         # grown by the engine (engine.forest_fit, csrc/forest_fit.hip: 256-bin
         # histogram trees, bootstrap and feature draws from the context's seed
@@ -705,6 +733,36 @@ class SharedModel:
         self.fits += 1
         return True
 
+    def _fit_ssgp(self, rows, ids) -> bool:
+        """surrogate="ssgp": refit the sparse-spectrum GP iff the usable results changed"""
+        import time
+
+        key = (len(rows), ids[-1])
+        if key == self._fit_key:
+            return True
+        self._gather(rows, ids)
+        n = self._n
+        if n > 65536:
+            raise ValueError("surrogate='ssgp' takes at most 65,536 results, and there are %d" % n)
+        X, y = self._Xa[:n], self._transform(self._ya[:n])
+        ell = self.lengthscale
+        if isinstance(ell, str):   # "auto": selected where the GP would select, while gp_lml_grid can hold the rows
+            npad = -(-n // 128) * 128
+            if npad != self._ell_npad:
+                if n > _SSGP_AUTO_ROWS:
+                    raise ValueError("lengthscale='auto' factors n x n matrices: with a ssgp surrogate it is taken "
+                                     "up to %d results, and there are %d: give a number" % (_SSGP_AUTO_ROWS, n))
+                self._select_lengthscale(X, y)
+                self._ell_npad = npad
+            ell = self.lengthscale_
+        t0 = time.perf_counter()
+        self.engine.ssgp_fit(X, y, lengthscale=ell, features=self.ssgp_kw.get("features", 1024), **self.hyper)
+        self.fit_seconds += time.perf_counter() - t0
+        self.f_best = float(np.min(y))
+        self._fit_key = key
+        self.fits += 1
+        return True
+
     def _fit_forest(self, rows, ids) -> bool:
         """surrogate="forest": refit the random forest iff the usable results changed"""
         import time
@@ -752,6 +810,8 @@ class SharedModel:
             return len(rows) >= 2 and self._fit_tpe(rows, ids)
         if self.surrogate == "gbt":
             return self._fit_gbt(rows, ids)
+        if self.surrogate == "ssgp":
+            return self._fit_ssgp(rows, ids)
         if self._fit_unverified and self._fit_key is not None:
             # the previous fit ran asynchronously (no host wait when it was
             # enqueued): a kernel matrix that was not positive definite would
@@ -1045,15 +1105,16 @@ class GpuBatchTechnique(SearchTechnique):
                  forest_kw: Optional[Dict[str, Any]] = None, polish: int = 0, polish_pool: Optional[int] = None,
                  ts_features: int = 1024, objectives=None, ref_point=None, forest_fit: str = "host",
                  tpe_kw: Optional[Dict[str, Any]] = None, gbt_kw: Optional[Dict[str, Any]] = None,
-                 *pargs, **kwargs):
+                 ssgp_kw: Optional[Dict[str, Any]] = None, *pargs, **kwargs):
         super().__init__(*pargs, **kwargs)
         # surrogate="forest" (SharedModel): a random forest refitted from the
         # driver's results, scored by EI / UCB on its mean and variance over
         # trees.  A shared model carries its own setting (and forest_kw)
         # surrogate="tpe" (SharedModel): the Parzen estimator, refitted the same
         # way and ranked by log l - log g; surrogate="gbt" (SharedModel): the
-        # boosted ensemble fitted on the device, ranked by its prediction; word
-        # names the model in the refusals
+        # boosted ensemble fitted on the device, ranked by its prediction;
+        # surrogate="ssgp" (SharedModel): the sparse-spectrum GP, scored by EI /
+        # UCB on its own mean and variance; word names the model in the refusals
         refit = surrogate if isinstance(surrogate, str) and surrogate in _REFIT else None
         if shared is not None:
             if refit and shared.surrogate != refit:
@@ -1202,7 +1263,8 @@ class GpuBatchTechnique(SearchTechnique):
                                                                    surrogate=refit,
                                                                    forest_kw=forest_kw, objectives=objectives,
                                                                    ref_point=ref_point, forest_fit=forest_fit,
-                                                                   tpe_kw=tpe_kw, gbt_kw=gbt_kw)
+                                                                   tpe_kw=tpe_kw, gbt_kw=gbt_kw,
+                                                                   ssgp_kw=ssgp_kw)
         # multi-GPU: with torch.distributed initialised and
         # world > 1, rank r scores candidates [base + r*pool, base + (r+1)*pool)
         # of every round and the local top-k lists are all-gathered and merged
@@ -1298,6 +1360,8 @@ class GpuBatchTechnique(SearchTechnique):
             score = eng.tpe_score(eng.encode(vals), dup=dup)
         elif have_model and self.model.surrogate == "gbt":
             _, score = eng.forest_predict(eng.encode(vals), dup=dup)
+        elif have_model and self.model.surrogate == "ssgp":
+            _, _, score = eng.ssgp_score(vals, acq=eng.acq(self.acq_kind), dup=dup)
         elif have_model:
             if self.prune_rows > 0 and self.model.precision == 64:
                 idx, top, _ = eng.gp_topk_pruned(eng.encode(vals), self.batch, acq=eng.acq(self.acq_kind), dup=dup,
@@ -1775,7 +1839,7 @@ def _shared_model(kw) -> SharedModel:
                        and kw["surrogate"] in _REFIT else None, forest_kw=kw.get("forest_kw"),
                        objectives=kw.get("objectives"), ref_point=kw.get("ref_point"),
                        forest_fit=kw.get("forest_fit", "host"), tpe_kw=kw.get("tpe_kw"),
-                       gbt_kw=kw.get("gbt_kw"))
+                       gbt_kw=kw.get("gbt_kw"), ssgp_kw=kw.get("ssgp_kw"))
 
 
 def _tr_arm(on: bool, shared: SharedModel, kw) -> List[SearchTechniqueBase]:

@@ -42,7 +42,7 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                 forest_kw=None, polish: int = 0, polish_pool: Optional[int] = None,
                 trust_region: bool = False, cma: bool = False, acq: str = "ei", ts_features: int = 1024, objectives=None,
                 ref_point=None, driver_objective=None, forest_fit: str = "host", tpe_kw=None,
-                gbt_kw=None) -> SearchDriver:
+                gbt_kw=None, ssgp_kw=None) -> SearchDriver:
     """Run the bandit for `generations` generations; returns the driver (results,
     best_result, bandit statistics).  With torch.distributed initialised and
     world > 1 the run is SPMD: call it on every rank with the same arguments.
@@ -60,6 +60,10 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
     surrogate="gbt": the children share one gradient-boosted tree ensemble fitted
     on the device with the results and rank by its prediction (SharedModel;
     gbt_kw: engine.gbt_fit's parameters, the reference's XGBRegressor settings by default).
+    surrogate="ssgp": the children share one sparse-spectrum GP -- Bayesian linear
+    regression on ssgp_kw["features"] (default 1024) random Fourier features of
+    the GP's kernel -- refitted with up to 65,536 results and scored by EI / UCB
+    on its own mean and variance (SharedModel).
     polish=T > 0: every dense GP round refines its polish_pool best candidates
     with T gradient-ascent steps on the acquisition first (GpuBatchTechnique).
     trust_region=True: a fifth arm proposes inside a trust region around the best
@@ -91,6 +95,7 @@ def tune_bandit(manipulator, objective: Callable[[Dict[Any, Any]], float], gener
                             forest_kw=forest_kw, **({"forest_fit": forest_fit} if forest_fit != "host" else {}),
                             **({"tpe_kw": tpe_kw} if tpe_kw is not None else {}),
                             **({"gbt_kw": gbt_kw} if gbt_kw is not None else {}),
+                            **({"ssgp_kw": ssgp_kw} if ssgp_kw is not None else {}),
                             polish=polish, polish_pool=polish_pool, acq=acq,
                             **({"ts_features": ts_features} if acq == "ts" else {}),
                             **({"trust_region": True} if trust_region else {}),
