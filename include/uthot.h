@@ -695,6 +695,46 @@ int ut_ssgp_score(ut_ctx* ctx, const double* values, int64_t ld, int64_t m, cons
                   double* mu, double* var, double* score);
 int ut_ssgp_read(ut_ctx* ctx, int32_t what, double* out_host, int32_t* info);
 
+/* ut_ssgp_lml_grid: the sparse-spectrum model's own log marginal likelihood of
+ * (X, y) at g points; nothing larger than D x D is formed, whatever n is.
+ * Point z uses the lengthscales scale_host[z] * lengthscale_host[k] (the ARD
+ * shape is kept, as in ut_gp_lml_grid) and the diagonal dg_z = noise_host[z] +
+ * jitter (a NULL noise_host: hyper->sigma_n2 for every point).
+ *   Z, b, us, Zs and ys are ut_ssgp_fit's (the same draws: the features
+ *   selected on are the features the fit will use).
+ *   P[r][j] = sum_k Zs[j][k] us_rk: the projection at scale 1, in turns, without
+ *     the phase; it is computed once and shared by every point.
+ *   rs_z = 1 / scale_host[z] (rounded once);  tau = P[r][j] * rs_z + b_j, the
+ *     product and the sum NOT fused (two roundings);
+ *     phi = sqrt(2 sigma_f2 / D) cos2pi(tau - rint(tau)); padding rows are zero.
+ *     With the roundings of rs_z and of the product, A_z at scale 1 is close to
+ *     but NOT bit-identical to ut_ssgp_fit's A (the product with 1 is exact, but
+ *     the fit sums Phi's rows in another order).
+ *   A_z = Phi_z^T Phi_z + dg_z I,  c_z = Phi_z^T ys,  L_z = chol(A_z),
+ *     beta_z = L_z^-1 c_z (no inverse is formed),
+ *   lml_z = -(|ys|^2 - |beta_z|^2) / (2 dg_z) - sum_i log L_z,ii
+ *           - ((n - D) / 2) log dg_z - (n / 2) log 2 pi,
+ *     the log density of ys ~ N(0, Phi Phi^T + dg I_n) by the Woodbury identity
+ *     and the determinant lemma; n - D is negative when n < D.
+ *   lml_host[z] = NaN where A_z is not positive definite (its own slot only);
+ *   *best_host = the argmax over the finite values, ties to the smallest z, -1 if
+ *   there is none.  A_host [g][D][D] (full, symmetric) and c_host [g][D] (each
+ *   may be NULL) read A_z and c_z back, for tests.
+ * The points go through one batched chain of launches (ut_gp_lml_grid's panel
+ * loop on D x D), in batches that hold 1 GiB of matrices and 1 GiB of partial
+ * tiles at most; the rows in the units of ut_ssgp_fit, in chunks of whole
+ * units whose projection stays at or under 256 MiB.  Every sum runs in a fixed
+ * order: the bits depend on neither the launch, the chunks nor the batches, and
+ * a point's values are the same alone as inside a grid.
+ * Synchronous.  The context's ssgp fit, GP fit, a staged asynchronous fit and
+ * every scoring result stay as they are: scratch of its own.
+ * UT_EINVAL: n, D, d or the precision as for ut_ssgp_fit; g < 1; a NULL pointer
+ * (noise_host, A_host and c_host excepted); a scale that is not finite and > 0.
+ * UT_ENOMEM: the scratch could not be allocated. */
+int ut_ssgp_lml_grid(ut_ctx* ctx, const double* X_host, const double* y_host, int32_t n, int32_t d,
+                     const ut_gp_hyper* hyper, int32_t D, int32_t g, const double* scale_host,
+                     const double* noise_host, double* lml_host, int32_t* best_host, double* A_host, double* c_host);
+
 /* ---- acquisition gradient and projected-ascent polish --------------------- */
 /* The reference's default bandit carries a local-search arm, RandomNelderMead
  * (bandittechniques.py:273-278; the simplex walk itself is

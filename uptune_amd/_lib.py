@@ -206,6 +206,7 @@ SIGNATURES = {
     "ut_ssgp_fit": (C.c_int, [P, P, P, I32, I32, C.POINTER(GpHyper), I32]),
     "ut_ssgp_score": (C.c_int, [P, P, I64, I64, C.POINTER(Acq), P, P, P, P]),
     "ut_ssgp_read": (C.c_int, [P, I32, P, C.POINTER(I32)]),
+    "ut_ssgp_lml_grid": (C.c_int, [P, P, P, I32, I32, C.POINTER(GpHyper), I32, I32, P, P, P, C.POINTER(I32), P, P]),
     "ut_gp_acq_grad": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, P, P, P, I64]),
     "ut_gp_polish": (C.c_int, [P, P, I64, I32, C.POINTER(Acq), P, C.POINTER(PolishParams), P, I64, P, P, P]),
     "ut_gp_feas_set": (C.c_int, [P, P, I32, I32, C.POINTER(FeasParams)]),

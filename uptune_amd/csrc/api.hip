@@ -928,6 +928,15 @@ int ut_ssgp_read(ut_ctx* c, int32_t what, double* out_host, int32_t* info) {
   return ssgp_read_impl(c, what, out_host, info);
 }
 
+int ut_ssgp_lml_grid(ut_ctx* c, const double* X_host, const double* y_host, int32_t n, int32_t d,
+                     const ut_gp_hyper* hyper, int32_t D, int32_t g, const double* scale_host, const double* noise_host,
+                     double* lml_host, int32_t* best_host, double* A_host, double* c_host) {
+  if (!c) return UT_EINVAL;
+  UT_HIP(c, hipSetDevice(c->device));
+  return ssgp_lml_grid_impl(c, X_host, y_host, n, d, hyper, D, g, scale_host, noise_host, lml_host, best_host, A_host,
+                            c_host);
+}
+
 int ut_gp_acq_grad(ut_ctx* c, const double* values, int64_t ld, int32_t p, const ut_acq* acq, double* out_score,
                    double* out_mu, double* out_var, double* out_grad, int64_t ld_g) {
   if (!c) return UT_EINVAL;

@@ -30,8 +30,6 @@
 
 namespace ut {
 
-constexpr size_t LML_BUDGET = (size_t)1 << 30;      // bytes of K_z matrices one chunk may hold
-
 // sum over rows < n of log L_ii and of beta_i^2 -> the LML; one workgroup
 __device__ __forceinline__ double lml_reduce(const double* __restrict__ L, const double* __restrict__ beta, int32_t n,
                                              int32_t npad, double* red) {
@@ -121,7 +119,9 @@ __global__ void k_lml_rhs(const double* __restrict__ ys, int32_t npad, double* _
 
 // Panel kb, step 1, one workgroup per point: L_kk = chol(A_kk) into K_z,
 // inv(L_kk) into the point's stripe Li_z [64][npad] (columns 0 .. 63), then
-// beta_kb = inv(L_kk) r_kb in place (one wave per 16 rows, a lane per column)
+// beta_kb = inv(L_kk) r_kb in place (one wave per 16 rows, a lane per column);
+// SUBST (ut_ssgp_lml_grid's chain): beta_kb by forward substitution instead
+template <bool SUBST>
 __global__ __launch_bounds__(256) void k_lml_diag(double* __restrict__ K, double* __restrict__ Li,
                                                   double* __restrict__ rhs, int32_t npad, int32_t kb,
                                                   int32_t* __restrict__ flag) {
@@ -140,6 +140,20 @@ __global__ __launch_bounds__(256) void k_lml_diag(double* __restrict__ K, double
   chol_diag_core<true>(a, Kb, Lz, npad, 0, flag + blockIdx.x, col, nullptr, invd);
   if (t < NB) rv[t] = rz[t];
   __syncthreads();   // inv(L_kk) written by this workgroup, r_kb staged
+  if constexpr (SUBST) {
+    // by forward substitution on L_kk itself (one wave, lane r the row): backward stable, where the product with
+    // the explicit inverse carries cond(L_kk) -- |ys|^2 - |beta|^2 is divided by 2 dg (ut_ssgp_lml_grid)
+    if (g == 0) {
+      double x = rv[r];
+      for (int j = 0; j < NB; ++j) {
+        const double bj = __shfl(x, j) / Kb[(int64_t)j * npad + j];
+        if (r == j) x = bj;
+        else if (r > j) x -= Kb[(int64_t)r * npad + j] * bj;
+      }
+      rz[r] = x;
+    }
+    return;
+  }
   for (int q = 0; q < 16; ++q) {
     const int row = 16 * g + q;
     double s = Lz[(int64_t)row * npad + r] * rv[r];   // (zeros above the diagonal)
@@ -237,6 +251,22 @@ int gp_lml_impl(ut_ctx* c, double* lml_host) {
   return 0;
 }
 
+int launch_lml_chain(ut_ctx* c, double* K, double* Li, double* rhs, int32_t* flag, int32_t npad, int32_t points,
+                     bool subst) {
+  const int32_t nb = npad / NB;
+  for (int32_t kb = 0; kb < nb; ++kb) {
+    hipLaunchKernelGGL(subst ? k_lml_diag<true> : k_lml_diag<false>, dim3(points), dim3(256), 0, c->stream, K, Li, rhs,
+                       npad, kb, flag);
+    const int32_t T = nb - kb - 1;
+    if (T > 0) {
+      hipLaunchKernelGGL(k_lml_rows, dim3(T, points), dim3(256), 0, c->stream, K, Li, rhs, npad, kb);
+      hipLaunchKernelGGL(k_lml_update, dim3(T * (T + 1) / 2, points), dim3(256), 0, c->stream, K, npad, kb);
+    }
+  }
+  UT_LAUNCH_CHECK(c);
+  return 0;
+}
+
 int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
                      int32_t g, const double* scale, const double* noise, double* lml_host, int32_t* best_host) {
   UT_CHECK(c, n >= 1 && d >= 1 && g >= 1, UT_EINVAL, "gp_lml_grid: n, d and g must be at least 1");
@@ -285,17 +315,8 @@ int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int
                        h->sigma_f2, in + ohs, in + odg, z0, c->lml_k.p);
     hipLaunchKernelGGL(k_lml_rhs, dim3(grid1(npad, 256), bz), dim3(256), 0, c->stream, in + oys, (int32_t)npad,
                        c->lml_rhs.p);
-    for (int32_t kb = 0; kb < nb; ++kb) {
-      hipLaunchKernelGGL(k_lml_diag, dim3(bz), dim3(256), 0, c->stream, c->lml_k.p, c->lml_li.p, c->lml_rhs.p,
-                         (int32_t)npad, kb, c->lml_flag.p + z0);
-      const int32_t T = nb - kb - 1;
-      if (T > 0) {
-        hipLaunchKernelGGL(k_lml_rows, dim3(T, bz), dim3(256), 0, c->stream, c->lml_k.p, c->lml_li.p, c->lml_rhs.p,
-                           (int32_t)npad, kb);
-        hipLaunchKernelGGL(k_lml_update, dim3(T * (T + 1) / 2, bz), dim3(256), 0, c->stream, c->lml_k.p,
-                           (int32_t)npad, kb);
-      }
-    }
+    if ((rc = launch_lml_chain(c, c->lml_k.p, c->lml_li.p, c->lml_rhs.p, c->lml_flag.p + z0, (int32_t)npad, bz, false)))
+      return rc;
     hipLaunchKernelGGL(k_lml_points, dim3(bz), dim3(256), 0, c->stream, c->lml_k.p, c->lml_rhs.p,
                        c->lml_flag.p + z0, n, (int32_t)npad, in + olml + z0);
     UT_LAUNCH_CHECK(c);

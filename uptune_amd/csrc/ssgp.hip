@@ -34,6 +34,37 @@
 //                (kstar_colsums) reduced in tile order by the finalize.
 //   k_ssgp_finalize   var = diag |L^-1 phi|^2 (a sum of squares: nothing
 //                cancels), then gp_post.h's EI / UCB.
+//
+// ut_ssgp_lml_grid (the last section; uthot.h states the rule): the model's own
+// log marginal likelihood at g points (a common scale on the lengthscales and a
+// noise each).  A scale only divides the phase, so the projection is the same
+// for every point:
+//   k_ssgp_proj  P [rows][D] = Xs Zs^T for a chunk of rows, in turns, no phase:
+//                the fit's contraction with no epilogue, once for all points.
+//                Row-major, so that a 128-feature tile's row is 1 KiB in one
+//                piece: what one glds instruction of the Gram kernel brings in.
+//   k_ssgp_gram_grid   a workgroup owns (point, tile pair, unit).  The unit's
+//                rows go by in slices of 16: the slice's two P tiles ([16][128]
+//                each, 32 KiB, one ring stage) arrive by glds in the stage the
+//                slice before last has left, under this slice's epilogue and
+//                MFMAs; the epilogue (* rs_z + b, cos2pi, amplitude, zero past
+//                n) runs in place in LDS, a thread on one feature column with
+//                its phase in a register; then 16 MFMAs per 4 rows into the
+//                accumulators that stay in registers across the unit.  Nothing
+//                is parked and no Phi tile is held in registers, so two
+//                workgroups share a CU (64 KiB each) and one's epilogue runs
+//                under the other's MFMAs.  The point is the fastest grid
+//                dimension: the workgroups that read one P tile run together.
+//                Resources (-Rpass-analysis=kernel-resource-usage, gfx950):
+//                VGPRs 214, AGPRs 0, SGPRs 106, scratch 0, LDS 65536 B,
+//                occupancy 2 waves per SIMD.
+//   k_ssgp_gram_red_grid / k_ssgp_c_red_grid   the units' partials in unit
+//                order per point, + dg_z on the diagonal, into the batched
+//                matrices and right-hand sides that gp_lml.hip's panel chain
+//                (launch_lml_chain) factors; k_ssgp_lml_points the value.
+//   The units are the fit's (ssgp_split), the rows of a unit are summed in row
+//   order and the units in unit order: the bits depend on neither the launch,
+//   the row chunking nor the batching of the points.
 #include "gp_kstar_tile.h"
 #include "gp_post.h"
 #include "gp_tiles.h"
@@ -444,6 +475,337 @@ int ssgp_read_impl(ut_ctx* c, int32_t what, double* out_host, int32_t* info) {
   }
   UT_HIP(c, hipMemcpyAsync(out_host, src, sizeof(double) * cnt, hipMemcpyDeviceToHost, c->stream));
   UT_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// ut_ssgp_lml_grid
+// ---------------------------------------------------------------------------
+constexpr int GG_SL = 16;                    // rows of a slice: two P tiles of it are one ring stage
+constexpr int GG_TILE = GG_SL * K_BN;        // doubles of one tile's slice
+static_assert(2 * GG_TILE == K_STAGE && K_BM % (2 * GG_SL) == 0, "a slice pair is a stage; a unit has an even count");
+
+// P [rows][D] of the training rows row0 .. row0 + rows - 1 (whole 128-row steps): blockIdx.x a feature tile,
+// blockIdx.y a step of the chunk
+__global__ __launch_bounds__(K_NT, 2) void k_ssgp_proj(const double* __restrict__ xuT, int32_t npad,
+                                                       const double* __restrict__ ZT, int32_t D, int32_t dpad,
+                                                       int32_t row0, double* __restrict__ P) {
+  __shared__ __attribute__((aligned(16))) double ring[2 * K_STAGE];
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wm = w >> 1, wn = w & 1;
+  KstarOperands<double> o{};
+  o.AT = xuT, o.lda = npad, o.B = ZT, o.ldb = D, o.dpad = dpad;
+  const int32_t f0 = (int32_t)blockIdx.x * K_BN, lr0 = (int32_t)blockIdx.y * K_BM;
+  const KstarAcc<double> acc =
+      kstar_contract<double, false>(o, kstar_rows_f64(lane), row0 + lr0, (int64_t)f0, ring, w, lane, [] {});
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double* const pr = P + (int64_t)(lr0 + wm * 64 + i * 16 + (lane >> 4) + 4 * q) * D + f0 + wn * 64 + (lane & 15);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) pr[jj * 16] = acc.a[i][jj][q];
+    }
+}
+
+// slice rows r .. r + 15 (chunk-local) of feature tiles fi and (unless the pair is diagonal) fj into one stage:
+// wave w brings rows 4 w .. 4 w + 3 of each, a 1-KiB row per glds
+__device__ __forceinline__ void ssgp_p_issue(const double* __restrict__ P, int32_t D, int32_t fi, int32_t fj,
+                                             bool diagt, int64_t r, double* st, int w, int lane) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int q = 4 * w + u;
+    __builtin_amdgcn_global_load_lds(P + (r + q) * D + fi + lane * 2,
+                                     (__attribute__((address_space(3))) void*)(st + q * K_BN), 16, 0, 0);
+  }
+  if (diagt) return;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int q = 4 * w + u;
+    __builtin_amdgcn_global_load_lds(P + (r + q) * D + fj + lane * 2,
+                                     (__attribute__((address_space(3))) void*)(st + GG_TILE + q * K_BN), 16, 0, 0);
+  }
+}
+
+// the units u0 .. u1 - 1 (whole, inside the chunk that starts at row crow0) of the points z0 + blockIdx.x;
+// blockIdx.y the tile pair, blockIdx.z a run of upw units.  wsA [bz][pairs][units][128][128], wsc [bz][T][units][128]
+__global__ __launch_bounds__(K_NT, 2) void k_ssgp_gram_grid(
+    const double* __restrict__ P, int32_t crow0, int32_t n, int32_t npad, const double* __restrict__ bph, int32_t D,
+    double amp, const double* __restrict__ rs, int32_t z0, const double* __restrict__ ys, int32_t steps, int32_t units,
+    int32_t u0, int32_t u1, int32_t upw, double* __restrict__ wsA, double* __restrict__ wsc) {
+  __shared__ __attribute__((aligned(16))) double lds[2 * K_STAGE];
+  static_assert(2 * sizeof(lds) <= 160 * 1024, "two workgroups in a CU's LDS");
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wm = w >> 1, wn = w & 1;
+  int32_t ti, tj;
+  lower_tile((int32_t)blockIdx.y, ti, tj);
+  const bool diagt = ti == tj, withc = tj == 0;
+  const int32_t T = D / K_BM, pairs = (int32_t)gridDim.y, fi = ti * K_BM, fj = tj * K_BN;
+  const int col = t & (K_BN - 1), half = t >> 7;   // the epilogue's column, and which rows of a slice: half + 2 k
+  const double rsz = rs[z0 + blockIdx.x], bi = bph[fi + col], bj = bph[fj + col];
+  const int32_t nsteps = npad / K_BM;
+  const int32_t ub = u0 + (int32_t)blockIdx.z * upw, ue = min(u1, ub + upw);
+  for (int32_t u = ub; u < ue; ++u) {
+    kd4 g[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) g[i][jj] = (kd4){0.0, 0.0, 0.0, 0.0};
+    double cacc = 0.0;
+    const int32_t rbeg = u * steps * K_BM, rend = min(nsteps, (u + 1) * steps) * K_BM;
+    const int32_t nsl = (rend - rbeg) / GG_SL;   // even: the last slice's stage is 1, the next unit starts in 0
+    ssgp_p_issue(P, D, fi, fj, diagt, (int64_t)(rbeg - crow0), lds, w, lane);
+    for (int32_t it = 0; it < nsl; ++it) {
+      const int32_t r0 = rbeg + it * GG_SL;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();   // slice it has landed everywhere; slice it - 1 is fully read
+      asm volatile("" ::: "memory");
+      if (it + 1 < nsl)
+        ssgp_p_issue(P, D, fi, fj, diagt, (int64_t)(r0 + GG_SL - crow0), lds + ((it + 1) & 1) * K_STAGE, w, lane);
+      double* const Si = lds + (it & 1) * K_STAGE;
+      double* const Sj = diagt ? Si : Si + GG_TILE;
+      // the point's epilogue in place: tau = P rs + b (product and sum rounded apart)
+#pragma unroll
+      for (int k = 0; k < GG_SL / 2; ++k) {
+        const int lr = half + 2 * k;
+        const bool in = r0 + lr < n;
+        const double ta = Si[lr * K_BN + col] * rsz + bi;
+        Si[lr * K_BN + col] = in ? amp * cos2pi(ta - __builtin_rint(ta)) : 0.0;
+        if (!diagt) {
+          const double tb = Sj[lr * K_BN + col] * rsz + bj;
+          Sj[lr * K_BN + col] = in ? amp * cos2pi(tb - __builtin_rint(tb)) : 0.0;
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int ks = 0; ks < GG_SL / 4; ++ks) {
+        const int kr = ks * 4 + (lane >> 4);
+        double af[4], bf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = Si[kr * K_BN + wm * 64 + i * 16 + (lane & 15)];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) bf[jj] = Sj[kr * K_BN + wn * 64 + jj * 16 + (lane & 15)];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) g[i][jj] = kstar_mfma(af[i], bf[jj], g[i][jj]);
+      }
+      if (withc && t < K_BM) {
+#pragma unroll
+        for (int lr = 0; lr < GG_SL; ++lr) cacc += Si[lr * K_BN + t] * ys[r0 + lr];
+      }
+    }
+    __syncthreads();   // the last slice is read before the next unit's first one lands
+    double* const wt = wsA + (((int64_t)blockIdx.x * pairs + blockIdx.y) * units + u) * (K_BM * K_BN);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          wt[(wm * 64 + i * 16 + (lane >> 4) + 4 * q) * K_BN + wn * 64 + jj * 16 + (lane & 15)] = g[i][jj][q];
+    if (withc && t < K_BM) wsc[(((int64_t)blockIdx.x * T + ti) * units + u) * K_BM + t] = cacc;
+  }
+}
+
+// K [bz][D][D], whole and symmetric (the chain reads its lower 64-tiles, the read-back all of it) = the units'
+// partials in unit order, + dg_z I; a diagonal tile's upper half is its lower half mirrored
+__global__ __launch_bounds__(256) void k_ssgp_gram_red_grid(const double* __restrict__ wsA, int32_t units, int32_t D,
+                                                            const double* __restrict__ dg, int32_t z0,
+                                                            double* __restrict__ K) {
+  int32_t ti, tj;
+  lower_tile((int32_t)blockIdx.y, ti, tj);
+  const int32_t e = (int32_t)blockIdx.x * 256 + threadIdx.x;   // < 128 * 128
+  int32_t r = e >> 7, cc = e & 127;
+  if (ti == tj && cc > r) {
+    const int32_t x = r;
+    r = cc, cc = x;
+  }
+  const double* p = wsA + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * units * (K_BM * K_BN) + r * K_BN + cc;
+  double s = 0.0;
+  for (int32_t u = 0; u < units; ++u) s += p[(int64_t)u * (K_BM * K_BN)];
+  const int64_t i = (int64_t)ti * K_BM + (e >> 7), j = (int64_t)tj * K_BN + (e & 127);
+  if (i == j) s += dg[z0 + blockIdx.z];
+  double* Kz = K + (int64_t)blockIdx.z * D * D;
+  Kz[i * D + j] = s;
+  if (ti != tj) Kz[j * D + i] = s;
+}
+
+// rhs [bz][D] = c_z; blockIdx.x a feature tile, blockIdx.y the point
+__global__ __launch_bounds__(128) void k_ssgp_c_red_grid(const double* __restrict__ wsc, int32_t units, int32_t D,
+                                                         double* __restrict__ rhs) {
+  const double* p = wsc + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * units * K_BM + threadIdx.x;
+  double s = 0.0;
+  for (int32_t u = 0; u < units; ++u) s += p[(int64_t)u * K_BM];
+  rhs[(int64_t)blockIdx.y * D + (int64_t)blockIdx.x * K_BM + threadIdx.x] = s;
+}
+
+// s + t exactly as hi + lo (Knuth), and (hi, lo) += x * x or -= x * x with the product's error kept (fma)
+__device__ __forceinline__ void dd_add(double& hi, double& lo, double x, double xl) {
+  const double s = hi + x, bb = s - hi;
+  lo += ((hi - (s - bb)) + (x - bb)) + xl;
+  hi = s;
+}
+__device__ __forceinline__ void dd_add_sq(double& hi, double& lo, double x, double sign) {
+  const double p = x * x;
+  dd_add(hi, lo, sign * p, sign * __builtin_fma(x, x, -p));
+}
+
+// the values of the points z0 + blockIdx.x from their factor L (in K) and beta (in rhs); every sum by thread
+// stride, then a tree: a fixed order.  q = |ys|^2 - |beta|^2 is divided by 2 dg and both norms are near n: it is
+// one signed sum carried in two doubles, so that what is left of it is the elements' own error, not the sum's
+__global__ __launch_bounds__(256) void k_ssgp_lml_points(const double* __restrict__ K, const double* __restrict__ rhs,
+                                                         const int32_t* __restrict__ flag, const double* __restrict__ ys,
+                                                         int32_t n, int32_t D, const double* __restrict__ dg,
+                                                         int32_t z0, double* __restrict__ out) {
+  __shared__ double red[3][256];
+  const int t = threadIdx.x;
+  const double* L = K + (int64_t)blockIdx.x * D * D;
+  const double* beta = rhs + (int64_t)blockIdx.x * D;
+  double sl = 0.0, qh = 0.0, ql = 0.0;
+  for (int32_t i = t; i < D; i += 256) {
+    sl += log(L[(int64_t)i * D + i]);
+    dd_add_sq(qh, ql, beta[i], -1.0);
+  }
+  for (int32_t i = t; i < n; i += 256) dd_add_sq(qh, ql, ys[i], 1.0);
+  red[0][t] = sl, red[1][t] = qh, red[2][t] = ql;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) {
+      red[0][t] += red[0][t + h];
+      dd_add(red[1][t], red[2][t], red[1][t + h], red[2][t + h]);
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  const double d = dg[z0 + blockIdx.x];
+  const double v = -(red[1][0] + red[2][0]) / (2.0 * d) - red[0][0] - 0.5 * (double)(n - D) * log(d) -
+                   0.5 * (double)n * 1.8378770664093454836;   // log 2 pi
+  out[z0 + blockIdx.x] = flag[z0 + blockIdx.x] != 0 ? __builtin_nan("") : v;
+}
+
+int ssgp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
+                       int32_t D, int32_t g, const double* scale, const double* noise, double* lml_host,
+                       int32_t* best_host, double* A_host, double* c_host) {
+  UT_CHECK(c, X && y && h && h->lengthscale_host && scale && lml_host && best_host, UT_EINVAL,
+           "ssgp_lml_grid: NULL argument");
+  UT_CHECK(c, n >= 1 && n <= SSGP_MAX_N, UT_EINVAL,
+           "ssgp_lml_grid: n = " + std::to_string(n) + " is not in [1, 65536]");
+  UT_CHECK(c, D >= 128 && D <= SSGP_MAX_D && D % 128 == 0, UT_EINVAL,
+           "ssgp_lml_grid: D = " + std::to_string(D) + " is not a multiple of 128 in [128, 2048]");
+  UT_CHECK(c, c->has_space && d == c->space.n_feat, UT_EINVAL,
+           "ssgp_lml_grid: d = " + std::to_string(d) + " is not the space's feature count");
+  UT_CHECK(c, c->gp_prec == 64, UT_EINVAL,
+           "ssgp_lml_grid: fp64 only, and ut_gp_set_precision is " + std::to_string(c->gp_prec));
+  UT_CHECK(c, g >= 1, UT_EINVAL, "ssgp_lml_grid: g must be at least 1");
+  for (int32_t z = 0; z < g; ++z)
+    UT_CHECK(c, std::isfinite(scale[z]) && scale[z] > 0.0, UT_EINVAL, "ssgp_lml_grid: scales must be finite and > 0");
+  const int32_t npad = gp_npad(n), dpad = kstar_dpad(d), T = D / K_BM, pairs = T * (T + 1) / 2;
+  const SsgpSplit sp = ssgp_split(n, D);
+  const size_t DD = (size_t)D * D;
+  // a point's partial tiles and c's; a batch of B points holds B D^2 doubles of matrices within LML_BUDGET and
+  // its partials within as much again
+  const size_t wsz = ((size_t)pairs * K_BM * K_BN + (size_t)T * K_BM) * sp.units;
+  int64_t B = c->lml_batch > 0 ? c->lml_batch
+                               : (int64_t)std::min(LML_BUDGET / (DD * sizeof(double)), LML_BUDGET / (wsz * sizeof(double)));
+  B = std::max<int64_t>(1, std::min<int64_t>(B, g));
+  // row chunks of whole units whose P stays within the Phi* cap, at least a unit
+  const int64_t cap = (int64_t)std::max(1, c->ssgp_phi_mib) << 20;
+  const int64_t urow = (int64_t)sp.steps * K_BM;
+  const int32_t uchunk = (int32_t)std::min<int64_t>(sp.units, std::max<int64_t>(1, cap / (urow * D * 8)));
+  const int64_t prow = std::min<int64_t>(npad, (int64_t)uchunk * urow);
+  // sl_in: X | y | 1/ell | scaled rows | norms | the rows transposed | ys | stats | Z | ZT | b | 1/scale | dg | lml
+  // (every block on an even offset: the glds sources are read 16 B at a time)
+  auto up2 = [](size_t v) { return (v + 1) & ~(size_t)1; };
+  const size_t oy = up2((size_t)n * d), oinv = up2(oy + n), oXs = up2(oinv + d), oxn = up2(oXs + (size_t)npad * d);
+  const size_t oxu = up2(oxn + npad), oys = up2(oxu + (size_t)dpad * npad), ost = up2(oys + npad), oZ = ost + 4;
+  const size_t oZT = up2(oZ + (size_t)D * d), ob = up2(oZT + (size_t)dpad * D), ors = up2(ob + D), odg = ors + g;
+  const size_t olml = odg + g;
+  int rc;
+  if ((rc = ensure(c, c->sl_in, olml + g))) return rc;
+  if ((rc = ensure(c, c->sl_P, (size_t)prow * D))) return rc;
+  if ((rc = ensure(c, c->sl_ws, (size_t)B * wsz))) return rc;
+  if ((rc = ensure(c, c->lml_k, (size_t)B * DD))) return rc;
+  if ((rc = ensure(c, c->lml_li, (size_t)B * NB * D))) return rc;
+  if ((rc = ensure(c, c->lml_rhs, (size_t)B * D))) return rc;
+  if ((rc = ensure(c, c->lml_flag, (size_t)g))) return rc;
+  double* const in = c->sl_in.p;
+  std::vector<double> hp((size_t)d + 2 * g);
+  for (int32_t k = 0; k < d; ++k) hp[k] = 1.0 / h->lengthscale_host[k];
+  for (int32_t z = 0; z < g; ++z) {
+    hp[(size_t)d + z] = 1.0 / scale[z];
+    hp[(size_t)d + g + z] = (noise ? noise[z] : h->sigma_n2) + h->jitter;
+  }
+  const double amp = std::sqrt(2.0 * h->sigma_f2 / (double)D);
+  const int32_t upw = std::max(1, c->ssgp_units_per_wg);
+  hipStream_t s = c->stream;
+  auto enqueue = [&]() -> int {
+    UT_HIP(c, hipMemcpyAsync(in, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, s));
+    UT_HIP(c, hipMemcpyAsync(in + oy, y, sizeof(double) * n, hipMemcpyHostToDevice, s));
+    UT_HIP(c, hipMemcpyAsync(in + oinv, hp.data(), sizeof(double) * d, hipMemcpyHostToDevice, s));
+    UT_HIP(c, hipMemcpyAsync(in + ors, hp.data() + d, sizeof(double) * 2 * g, hipMemcpyHostToDevice, s));
+    UT_HIP(c, hipMemsetAsync(c->lml_flag.p, 0, sizeof(int32_t) * g, s));
+    hipLaunchKernelGGL(k_ssgp_draw, dim3(grid1((int64_t)dpad * D, 256)), dim3(256), 0, s, c->seed, D, d, dpad,
+                       in + oZ, in + oZT, in + ob);
+    UT_LAUNCH_CHECK(c);
+    if ((rc = launch_gp_prep_train(c, in, n, npad, d, in + oinv, in + oXs, in + oxn))) return rc;
+    if ((rc = launch_gp_ystats(c, in + oy, n, npad, in + oys, in + ost))) return rc;
+    hipLaunchKernelGGL(k_ssgp_xut, dim3(grid1((int64_t)dpad * npad, 256)), dim3(256), 0, s, in + oXs, n, npad, d, dpad,
+                       in + oxu);
+    UT_LAUNCH_CHECK(c);
+    int32_t in_P = -1;   // the chunk P holds: projected again only when another one is needed
+    for (int32_t z0 = 0; z0 < g; z0 += (int32_t)B) {
+      const int32_t bz = std::min<int32_t>((int32_t)B, g - z0);
+      double* const wsA = c->sl_ws.p;
+      double* const wsc = wsA + (size_t)bz * pairs * sp.units * K_BM * K_BN;
+      for (int32_t u0 = 0; u0 < sp.units; u0 += uchunk) {
+        const int32_t u1 = std::min(sp.units, u0 + uchunk);
+        const int32_t crow0 = (int32_t)(u0 * urow), crows = (int32_t)std::min<int64_t>(npad, u1 * urow) - crow0;
+        if (in_P != u0) {
+          hipLaunchKernelGGL(k_ssgp_proj, dim3(T, crows / K_BM), dim3(K_NT), 0, s, in + oxu, npad, in + oZT, D, dpad,
+                             crow0, c->sl_P.p);
+          in_P = u0;
+        }
+        hipLaunchKernelGGL(k_ssgp_gram_grid, dim3(bz, pairs, (u1 - u0 + upw - 1) / upw), dim3(K_NT), 0, s, c->sl_P.p,
+                           crow0, n, npad, in + ob, D, amp, in + ors, z0, in + oys, sp.steps, sp.units, u0, u1, upw,
+                           wsA, wsc);
+        UT_LAUNCH_CHECK(c);
+      }
+      hipLaunchKernelGGL(k_ssgp_gram_red_grid, dim3(K_BM * K_BN / 256, pairs, bz), dim3(256), 0, s, wsA, sp.units, D,
+                         in + odg, z0, c->lml_k.p);
+      hipLaunchKernelGGL(k_ssgp_c_red_grid, dim3(T, bz), dim3(K_BM), 0, s, wsc, sp.units, D, c->lml_rhs.p);
+      UT_LAUNCH_CHECK(c);
+      if (A_host)
+        UT_HIP(c, hipMemcpyAsync(A_host + (size_t)z0 * DD, c->lml_k.p, sizeof(double) * bz * DD,
+                                 hipMemcpyDeviceToHost, s));
+      if (c_host)
+        UT_HIP(c, hipMemcpyAsync(c_host + (size_t)z0 * D, c->lml_rhs.p, sizeof(double) * bz * D,
+                                 hipMemcpyDeviceToHost, s));
+      if ((rc = launch_lml_chain(c, c->lml_k.p, c->lml_li.p, c->lml_rhs.p, c->lml_flag.p + z0, D, bz, true)))
+        return rc;
+      hipLaunchKernelGGL(k_ssgp_lml_points, dim3(bz), dim3(256), 0, s, c->lml_k.p, c->lml_rhs.p, c->lml_flag.p,
+                         in + oys, n, D, in + odg, z0, in + olml);
+      UT_LAUNCH_CHECK(c);
+    }
+    UT_HIP(c, hipMemcpyAsync(lml_host, in + olml, sizeof(double) * g, hipMemcpyDeviceToHost, s));
+    return 0;
+  };
+  // the caller's arrays and hp are read by copies in flight: wait whatever happened
+  rc = enqueue();
+  const hipError_t es = hipStreamSynchronize(s);
+  if (rc) return rc;
+  UT_HIP(c, es);
+  int32_t best = -1;
+  for (int32_t z = 0; z < g; ++z) {
+    if (!std::isfinite(lml_host[z])) {
+      lml_host[z] = std::nan("");
+      continue;
+    }
+    if (best < 0 || lml_host[z] > lml_host[best]) best = z;
+  }
+  *best_host = best;
   return 0;
 }
 

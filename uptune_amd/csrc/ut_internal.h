@@ -684,6 +684,11 @@ struct ut_ctx {
   // debug: the units of the Gram's row split one workgroup walks (results do not depend on it), and the
   // cap on the Phi* workspace in MiB; UT_SSGP_UNITS_PER_WG, UT_SSGP_PHI_MIB
   int32_t ssgp_units_per_wg = 1, ssgp_phi_mib = 256;
+  // ut_ssgp_lml_grid's scratch (ssgp.hip); the chain's matrices, stripes, right-hand sides and flags are
+  // ut_gp_lml_grid's (lml_k, lml_li, lml_rhs, lml_flag: both calls are synchronous and keep nothing there)
+  ut::DevBuf<double> sl_in;                // staged inputs and draws, one block (ssgp_lml_grid_impl lists it)
+  ut::DevBuf<double> sl_P;                 // the projection of one row chunk [rows][D], in turns, no phase
+  ut::DevBuf<double> sl_ws;                // [B] x (partial tiles [pairs][units][128][128], c's [D / 128][units][128])
   int32_t dbg_fail_alloc = 0;             // ut_debug_fail_alloc: the next N growing ensure() / dalloc() calls fail
   int32_t dbg_fail_skip = 0;               // ut_debug_fail_alloc_after: ... once this many more have succeeded
 
@@ -835,6 +840,12 @@ int launch_gp_upper_mv(ut_ctx* c, const double* v, double* out);
 int gp_lml_impl(ut_ctx* c, double* lml_host);
 int gp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
                      int32_t g, const double* scale, const double* noise, double* lml_host, int32_t* best_host);
+// ... its panel loop over `points` matrices K [points][npad][npad] (lower 64-tiles in, L out), the stripes Li
+// [points][64][npad], the right-hand sides rhs [points][npad] (in: r, out: L^-1 r) and flag [points]
+constexpr size_t LML_BUDGET = (size_t)1 << 30;   // bytes of matrices one chunk of points may hold
+// subst: beta_kb by forward substitution on L_kk, not by the product with its explicit inverse
+int launch_lml_chain(ut_ctx* c, double* K, double* Li, double* rhs, int32_t* flag, int32_t npad, int32_t points,
+                     bool subst);
 // gp_lml_grad.hip: its gradient at the fit in place
 int gp_lml_grad_impl(ut_ctx* c, int32_t d, double* dlog_ell_host, double* dlog_sf2_host, double* dlog_sn2_host);
 // gp_fit.hip: the categorical K*'s training-side operands of rows Xs (scaled) / X (raw), as the fit builds its own
@@ -931,6 +942,10 @@ int ssgp_fit_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_
 int ssgp_score_impl(ut_ctx* c, const double* values, int64_t ld, int64_t m, const ut_acq* acq, const uint8_t* dup,
                     double* mu, double* var, double* score);
 int ssgp_read_impl(ut_ctx* c, int32_t what, double* out_host, int32_t* info);
+// ... its own log marginal likelihood over a grid of (scale, noise) points
+int ssgp_lml_grid_impl(ut_ctx* c, const double* X, const double* y, int32_t n, int32_t d, const ut_gp_hyper* h,
+                       int32_t D, int32_t g, const double* scale, const double* noise, double* lml_host,
+                       int32_t* best_host, double* A_host, double* c_host);
 // gp_fit.hip: the refit chain (Cholesky, then the explicit inverse) on a formed device matrix of npad rows, and
 // the two triangular mat-vecs on a given factor
 int launch_factor_chain(ut_ctx* c, double* K, double* Linv, double* T, int32_t* flag, int32_t npad);

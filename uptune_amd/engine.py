@@ -586,6 +586,40 @@ class BatchEngine:
                 "ut_ssgp_read")
         return out
 
+    def ssgp_lml_grid(self, X: np.ndarray, y: np.ndarray, lengthscale, scales, noises=None, features: int = 1024,
+                      sigma_f2: float = 1.0, sigma_n2: float = 1e-6, jitter: float = 0.0, parts: bool = False):
+        """ut_ssgp_lml_grid: the sparse-spectrum model's own log marginal
+        likelihood of (X, y) at the points (scales[j] * lengthscale, noises[j]
+        or sigma_n2), on the draws ssgp_fit would use; nothing larger than
+        features x features is factored.  Returns (lml [g], NaN where not
+        positive definite; the argmax over the finite values, -1 if none), and
+        with parts=True also A [g][D][D] and c [g][D].  No fit is touched."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        n, d = X.shape
+        D = int(features)
+        ell = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscale, dtype=np.float64), (d,)))
+        sc = np.ascontiguousarray(np.atleast_1d(np.asarray(scales, dtype=np.float64)))
+        g = int(sc.shape[0])
+        nz = None
+        if noises is not None:
+            nz = np.ascontiguousarray(np.atleast_1d(np.asarray(noises, dtype=np.float64)))
+            if nz.shape != sc.shape:
+                raise ValueError("ssgp_lml_grid: noises must have one entry per scale")
+        h = L.GpHyper(sigma_f2=float(sigma_f2), sigma_n2=float(sigma_n2), jitter=float(jitter),
+                      lengthscale_host=ell.ctypes.data)
+        out = np.empty(max(g, 1), dtype=np.float64)
+        keep = parts and g >= 1 and 128 <= D <= 2048
+        A = np.empty((g, D, D), dtype=np.float64) if keep else None
+        cv = np.empty((g, D), dtype=np.float64) if keep else None
+        best = C.c_int32(-1)
+        L.check(self.ctx, self.lib.ut_ssgp_lml_grid(self.ctx, X.ctypes.data, y.ctypes.data, n, d, C.byref(h), D, g,
+                                                    sc.ctypes.data, None if nz is None else nz.ctypes.data,
+                                                    out.ctypes.data, C.byref(best),
+                                                    None if A is None else A.ctypes.data,
+                                                    None if cv is None else cv.ctypes.data), "ut_ssgp_lml_grid")
+        return (out[:g], int(best.value), A, cv) if parts else (out[:g], int(best.value))
+
     def _shortlist(self, values: torch.Tensor, who: str) -> torch.Tensor:
         if values.dim() != 2 or values.shape[0] != self.spec.ncols:
             raise ValueError(f"{who}: values must be [{self.spec.ncols}][p]")

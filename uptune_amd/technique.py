@@ -265,9 +265,11 @@ _TPE_KW = ("gamma", "n_good_max", "prior_weight", "precision")
 _TPE_ROWS = 8192
 # SharedModel's gbt_kw: engine.gbt_fit's parameters
 _GBT_KW = ("n_rounds", "max_depth", "min_child", "eta", "reg_lambda", "gamma", "subsample", "colsample_bylevel")
-# SharedModel's ssgp_kw: features = D of engine.ssgp_fit
-_SSGP_KW = ("features",)
-# ... and the rows up to which lengthscale="auto" selects for it (gp_lml_grid factors n x n matrices)
+# SharedModel's ssgp_kw: features = D of engine.ssgp_fit; lml = whose likelihood lengthscale="auto" selects on:
+# "gp" (the default) the exact GP's while gp_lml_grid can hold the rows and the model's own beyond, "own" the
+# model's own (engine.ssgp_lml_grid: nothing larger than D x D) at every n
+_SSGP_KW = ("features", "lml")
+# ... and the rows up to which "gp" takes the exact GP's grid (gp_lml_grid factors n x n matrices)
 _SSGP_AUTO_ROWS = 4096
 # the surrogates a SharedModel refits itself
 _REFIT = ("forest", "tpe", "gbt", "ssgp")
@@ -389,8 +391,11 @@ class SharedModel:
         # features of the GP's kernel, refitted from the same usable rows,
         # features, y_transform and lengthscale at the same moments; O(n D^2) for
         # up to 65,536 results, scored by EI / UCB on its own mean and variance.
-        # A numeric lengthscale is used as given; "auto" selects as for the GP
-        # while there are at most 4,096 rows; "ard" is refused.
+        # A numeric lengthscale is used as given; "auto" selects on the same grid
+        # and at the same moments as for the GP: on the exact GP's likelihood
+        # while there are at most 4,096 rows and on the model's own
+        # (engine.ssgp_lml_grid) beyond, or with ssgp_kw["lml"] = "own" on the
+        # model's own at every n; "ard" is refused.
         if surrogate not in (None,) + _REFIT:
             raise ValueError("SharedModel surrogate: None (the GP), 'forest', 'tpe', 'gbt' or 'ssgp'")
         if surrogate is not None and (self.feasibility is not None or self.constraints):
@@ -423,6 +428,8 @@ class SharedModel:
             D = self.ssgp_kw.get("features", 1024)
             if isinstance(D, bool) or not isinstance(D, int) or not (128 <= D <= 2048 and D % 128 == 0):
                 raise ValueError("ssgp_kw features: a multiple of 128 in [128, 2048]")
+            if self.ssgp_kw.get("lml", "gp") not in ("gp", "own"):
+                raise ValueError("ssgp_kw lml: 'gp' or 'own'")
             if isinstance(lengthscale, str) and lengthscale == "ard":
                 raise ValueError("lengthscale='ard' selects on the exact GP's likelihood gradient: not with a ssgp "
                                  "surrogate")
@@ -746,13 +753,10 @@ class SharedModel:
             raise ValueError("surrogate='ssgp' takes at most 65,536 results, and there are %d" % n)
         X, y = self._Xa[:n], self._transform(self._ya[:n])
         ell = self.lengthscale
-        if isinstance(ell, str):   # "auto": selected where the GP would select, while gp_lml_grid can hold the rows
+        if isinstance(ell, str):   # "auto": selected where the GP would select, on the likelihood ssgp_kw["lml"] names
             npad = -(-n // 128) * 128
             if npad != self._ell_npad:
-                if n > _SSGP_AUTO_ROWS:
-                    raise ValueError("lengthscale='auto' factors n x n matrices: with a ssgp surrogate it is taken "
-                                     "up to %d results, and there are %d: give a number" % (_SSGP_AUTO_ROWS, n))
-                self._select_lengthscale(X, y)
+                self._select_lengthscale(X, y, own=self.ssgp_kw.get("lml", "gp") == "own" or n > _SSGP_AUTO_ROWS)
                 self._ell_npad = npad
             ell = self.lengthscale_
         t0 = time.perf_counter()
@@ -906,13 +910,18 @@ class SharedModel:
     def _grid(self, d: int) -> np.ndarray:
         return math.sqrt(d) * np.geomspace(0.05, 4.0, 16) if self.ell_grid is None else self.ell_grid
 
-    def _select_lengthscale(self, X, y) -> None:
+    def _select_lengthscale(self, X, y, own: bool = False) -> None:
         """lengthscale_ := the grid candidate with the largest log marginal
-        likelihood of (X, y); when no candidate is positive definite the previous
-        choice stays (the grid's median on the first fit) and the fit's jitter
-        retry takes it from there"""
+        likelihood of (X, y) -- the exact GP's, or with own the sparse-spectrum
+        model's on its own features; when no candidate is positive definite the
+        previous choice stays (the grid's median on the first fit) and the fit's
+        jitter retry takes it from there"""
         grid = self._grid(X.shape[1])
-        lml, best = self.engine.gp_lml_grid(X, y, 1.0, grid, **self.hyper)
+        if own:
+            lml, best = self.engine.ssgp_lml_grid(X, y, 1.0, grid, features=self.ssgp_kw.get("features", 1024),
+                                                  **self.hyper)
+        else:
+            lml, best = self.engine.gp_lml_grid(X, y, 1.0, grid, **self.hyper)
         if best >= 0:
             self.lengthscale_ = float(grid[best])
         elif self.lengthscale_ is None:
